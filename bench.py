@@ -22,34 +22,47 @@ N > 1: every frame is sharded by pixel rows (rank g renders rows [g*H/N, (g+1)*H
        every directed xGMI link carries one slab per N frames.  Default (--exchange compact): frames go in rounds of M*N;
        a rank queues its slab launches of a round on several streams and ONE RCCL all-to-all per round delivers the slabs
        (4-byte pixel words, expanded into records on the root).  --exchange p2p: one point-to-point gather per frame
-       (--root fixed pins the root to rank 0).  Total work is fixed as N grows ("strong").  The line also carries
+       (--root fixed pins the root to rank 0).  Total work is fixed as N grows ("strong").  With --full the line also carries
        "cpu_baseline" (rank 0, after the ranks are done) and "configs": {"C4": ...}: BASELINE config 4 (7680x4320, 1024
        spheres: at N = 8 the eight 540-row slabs of SURVEY 8(e)) through the same loop, with its own ms_per_step,
        verified_against_golden and roofline.
 
+A plain run does only what the headline figure needs: it sets up, runs the run-in and the W warm-up steps, times exactly K
+steps once, writes the outputs of the last step if --dump-outputs is given and prints the line.  Everything else below
+(repeated batches, the golden check, roofline, timing.moving_view, modes, end_to_end, cpu_baseline; for N > 1 the C4
+sub-record, the check rounds and native_group) is measured only with --full; --no-cpu-baseline, --no-verify,
+--no-moving-view and --no-side-legs leave parts of it out again.
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its last step goes to DIR/<name>.npy as float32
+(N = 1 and --native): the records of the last frame ("frame_records", one row of S bytes per pixel; when the frame is larger
+than the budget, a fixed sample of pixels drawn with seed 0, their pixel indices in "frame_records_index" as float64), or for
+--what update / update-async the minimised stream of the last Update ("update_stream", sampled the same way).  At most 64 MB
+in all.  The inputs are fixed by --config, so two builds run with the same arguments can be compared output for output.
+
 Timing (N = 1): after the run-in and the W warm-up steps, a batch of exactly K steps is timed with HIP events (recorded on
 the stream(s) the kernels are launched on: every render stream stamps the start of its first frame of the batch and the
 end of its last one; the batch took from the earliest start to the latest end) and bracketed by synchronisation on both
-sides; the batch is repeated until at least --min-timed-ms of GPU time has been measured and the MEDIAN batch is reported
-("timing" says how many repeats, their spread, and the wall-clock figure beside it).  The last frame of the last batch is
-then compared (SHA-256 of the whole 20*W*H buffer) with the committed golden value, outside the timed region:
-"verified_against_golden".  "timing.moving_view" is the same K-frame batch with a camera that turns 0.001 rad per frame
-(no two frames alike), frames in flight and one launch at a time: what the static view's learned dispatch order is worth.
+sides.  With --full the batch is repeated until at least --min-timed-ms of GPU time has been measured and the MEDIAN batch is
+reported ("timing" says how many repeats, their spread, and the wall-clock figure beside it); the last frame of the last
+batch is then compared (SHA-256 of the whole 20*W*H buffer) with the committed golden value, outside the timed region:
+"verified_against_golden" (null when nothing was compared).  "timing.moving_view" is the same K-frame batch with a camera
+that turns 0.001 rad per frame (no two frames alike), frames in flight and one launch at a time: what the static view's
+learned dispatch order is worth.
 
-Also reported (N = 1, outside the graded number): "modes": {"BIT_ASCII": ...} -- the same workload in the reference's start-up
+Also reported with --full (N = 1, outside the graded number): "modes": {"BIT_ASCII": ...} -- the same workload in the reference's start-up
 mode (RayTracingManager.h:54; 12-byte records, the integer xterm-256 mapper) with its own ms_per_step, roofline and golden check --
 and "end_to_end": the whole RayTracingManager::Update (RayTracingManager.cu:127-150: trace + GPU minimise + copy of the minimised
 stream to pinned host memory), ms per Update pipelined and blocking and the bytes that cross PCIe.
 
-Also reported: "roofline" (algorithmic HBM bytes / measured kernel time vs 8 TB/s, plus the executed-VALU utilisation from
+Also reported with --full: "roofline" (algorithmic HBM bytes / measured kernel time vs 8 TB/s, plus the executed-VALU utilisation from
 the committed rocprofv3 counters -- used only while the library sources still hash to what was profiled -- since this
 path is VALU-issue bound, not HBM bound) and "cpu_baseline" (the CPU oracle -- a structure-faithful port of the reference's
 loop -- timed on this host's cores on full frames of the same workload).
 
 --native: N GPUs driven by ONE process through a device group behind the C ABI (rtx_group_create, include/rtx.h: row slabs traced on
 N devices, gathered on the first by RCCL send/recv or peer copies, compact words expanded there) -- no launcher, no torch.distributed;
---native-devices 0,0,0,0 repeats a device (logical ranks on one GPU: the one-GPU box's walk).  The N > 1 line also carries a
-"native_group" sub-record: the same measurement made by rank 0 after the torch.distributed ranks are done.
+--native-devices 0,0,0,0 repeats a device (logical ranks on one GPU: how a single GPU walks N > 1).  With --full the N > 1 line also
+carries a "native_group" sub-record: the same measurement made by rank 0 after the torch.distributed ranks are done.
 
 --dry (tests only): the N > 1 loops over gloo with CPU tensors and the CPU oracle standing in for the HIP renderer, so that
 the launch, exchange and line-assembly code can be exercised on a machine without a GPU.  Its line says "dry": true and is
@@ -154,15 +167,40 @@ def _frame_matches_golden(frame, config, mode_name):
     return hashlib.sha256(frame.tobytes()).hexdigest() == want
 
 
+DUMP_LIMIT_BYTES = 56 << 20     # --dump-outputs: all files together stay under 64 MB
+
+
+def dump_outputs(dirname, outputs):
+    """--dump-outputs: every (n, S) uint8 array of `outputs` to dirname/<name>.npy as float32.  An array that does not fit
+    the budget is replaced by a fixed sample of its rows (seed 0, ascending), whose row indices go to <name>_index.npy as
+    float64: the same rows from run to run, so that two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(outputs))
+    for name, a in outputs.items():
+        n, S = a.shape
+        if n * S * 4 > budget:
+            keep = budget // (S * 4 + 8)
+            idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            np.save(os.path.join(dirname, name + "_index.npy"), idx.astype(np.float64))
+            a = a[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a.astype(np.float32))
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--config", default=None, help="BASELINE config name (C1..C5); the graded line uses C2 (the default; C1 with --dry)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (repeated batches, golden check, roofline, "
+                         "moving view, other modes, end_to_end, cpu_baseline; N>1: C4 sub-record, check rounds, native_group)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N=1 / --native: write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--sub-configs", default=None,
                     help="N>1: comma-separated configs that get a sub-record under \"configs\" after the main measurement "
-                         "(default: C4 when the main config is C2; none with --dry; 'none' = none)")
+                         "(default: C4 when the main config is C2 and --full is given; none with --dry; 'none' = none)")
     ap.add_argument("--mode", default="RGB_ASCII")
     ap.add_argument("--kernel", default="auto", choices=["auto", "brute", "binned"])
     ap.add_argument("--tile", type=int, default=0)
@@ -173,15 +211,15 @@ def parse_args(argv=None):
     ap.add_argument("--sorted-store", type=int, default=-1, help="staging reads a direction-sorted copy of the sphere array (RTX_OPT_SORTED_STORE): -1 auto (on), 0 off")
     ap.add_argument("--xcd-order", type=int, default=-1, help="XCD-aware dispatch order of two-level grids (RTX_OPT_XCD_ORDER): -1 auto, 0 off, 1 on")
     ap.add_argument("--tile-order", type=int, default=-2, help="heaviest-first dispatch of the macro tiles: -2 library default (auto), -1 auto, 0 off, k refresh period")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave out cpu_baseline")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--verify", action="store_true", help="(default) check the last frame against the golden hash, outside the timed region")
-    ap.add_argument("--no-verify", action="store_true", help="skip the byte check of the last frame")
+    ap.add_argument("--verify", action="store_true", help="check the last frame against the golden hash, outside the timed region (default with --full)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the byte check of the last frame")
     ap.add_argument("--no-moving-view", action="store_true", help="N=1: skip the timing.moving_view leg")
     ap.add_argument("--moving-step", type=float, default=MOVING_STEP_RAD, help="N=1: timing.moving_view's yaw step per frame in radians (default 0.001)")
     ap.add_argument("--no-side-legs", action="store_true", help="N=1: skip the secondary figures (modes.BIT_ASCII, end_to_end)")
     ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="N=1: the K-step batch is repeated until this much GPU time has been measured; the median batch is reported")
+                    help="--full: the K-step batch is repeated until this much GPU time has been measured; the median batch is reported")
     ap.add_argument("--max-repeats", type=int, default=2000)
     ap.add_argument("--root", default="rotate", choices=["rotate", "fixed"],
                     help="N>1: frame i is assembled on rank i %% N (rotate: highest throughput) or always on rank 0, in frame order "
@@ -227,6 +265,9 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.config is None:
         args.config = "C1" if args.dry else "C2"
+    # what a plain run leaves out: only --full (or --verify for the golden check) brings it back
+    args.verify = (args.full or args.verify) and not args.no_verify
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
     return args
 
 
@@ -410,6 +451,7 @@ def apply_options(R, ctx, args):
 
 def run_single(args, torch, R):
     """One GPU: returns the result line (a dict)."""
+    import numpy as np
     mode = R.MODE_NAMES.index(args.mode)
     S = R.SIZE_RGB if mode >= R.RGB_ASCII else R.SIZE_8BIT
     W, H, ns, npl, seed = R.CONFIGS[args.config]
@@ -433,11 +475,13 @@ def run_single(args, torch, R):
     frame_bytes = 20 * W * H
     F = max(1, args.frames_in_flight)
     streams, fbufs, inflight = None, None, []
+    last_update = [None, 0]     # the Update forms: the host buffer of the latest step and its minimised length
     if args.what == "update":
         F = 1
 
         def step(i):
-            ctx.update(params, mode, dt=0.016, run_physics=args.physics)
+            last_update[0] = ctx.update(params, mode, dt=0.016, run_physics=args.physics)
+            last_update[1] = len(last_update[0])
     elif args.what == "update-async":
         F = 1
         hb = [ctx.host_alloc(frame_bytes) for _ in range(2)]
@@ -446,6 +490,7 @@ def run_single(args, torch, R):
             if len(inflight) == 2:
                 ctx.update_end(inflight.pop(0))
             inflight.append(ctx.update_begin(params, mode, hb[i % 2][0]))
+            last_update[0] = hb[i % 2][1]
     elif F == 1:
         def step(i):
             ctx.render(params, mode)
@@ -468,7 +513,7 @@ def run_single(args, torch, R):
     def drain():
         if args.what == "update-async":
             while inflight:
-                ctx.update_end(inflight.pop(0))
+                last_update[1] = ctx.update_end(inflight.pop(0))   # the last one ended is the latest step's
         ctx.synchronize()
         torch.cuda.synchronize()
 
@@ -536,22 +581,35 @@ def run_single(args, torch, R):
                 break
         return evs, walls
 
-    ev_batches, wall_batches = repeat(make_timed_batch(step, F), args.min_timed_ms)
+    if args.full:
+        ev_batches, wall_batches = repeat(make_timed_batch(step, F), args.min_timed_ms)
+    else:
+        # a plain run: exactly K timed steps, one batch
+        e_ms, w_ms = make_timed_batch(step, F)()
+        ev_batches, wall_batches = [e_ms], [w_ms]
     batch_ms = median(ev_batches)
     elapsed = batch_ms * 1e-3                     # seconds per K steps, the median batch
-    timing = {"method": "HIP events on the render streams around each batch of K steps (earliest first-frame start to latest "
-                        "last-frame end), sync on both sides; median over repeated batches" if args.what == "trace" else "wall clock around each batch of K blocking steps; median",
+    how = "; median over repeated batches" if args.full else "; one batch"
+    timing = {"method": ("HIP events on the render streams around each batch of K steps (earliest first-frame start to latest "
+                         "last-frame end), sync on both sides" if args.what == "trace" else "wall clock around each batch of K blocking steps") + how,
               "repeats": len(ev_batches), "timed_ms_total": round(sum(ev_batches), 3),
               "batch_ms": {"median": round(batch_ms, 5), "min": round(min(ev_batches), 5), "max": round(max(ev_batches), 5)},
               "wall_ms_per_step_median": round(median(wall_batches) / K, 5)}
+    # what the last timed step computed, read back outside the timed region (before any other leg reuses the buffers)
     final = None
-    if not args.no_verify and args.what == "trace":
+    if args.what == "trace" and (args.verify or args.dump_outputs):
         final = ctx.read_frame(frame_bytes) if F == 1 else fbufs[(K - 1) % F].cpu().numpy()
+    if args.dump_outputs:
+        if args.what == "trace":
+            dump_outputs(args.dump_outputs, {"frame_records": final[:S * W * H].reshape(H * W, S)})
+        else:
+            dump_outputs(args.dump_outputs, {"update_stream": np.array(last_update[0][:last_update[1]]).reshape(-1, 1)})
+    kernel_ms = None
     # The dominant kernel on its own: launches one after the other on the context's stream, timed with
     # HIP events on that stream (this is what a rocprofv3 kernel trace of --frames-in-flight 1 shows).
     if args.what != "trace":
         kernel_ms = elapsed / K * 1e3
-    else:
+    elif args.full:
         Kr = max(10, min(K, 100))
         # (the context's own stream has its own dispatch order: let it settle as the render streams' did --
         # the library balances a tile grid over its first launches on a stream, and keeps refining every 64th)
@@ -570,7 +628,7 @@ def run_single(args, torch, R):
     # views, +-0.25 rad around the default pose), F frames in flight and one launch at a time.  The dispatch order the
     # library learns on a static view (rtx_balance_tiles) has nothing to learn from here; these are the rates a caller
     # whose camera never rests sees.  Outside the graded number, after the verification copy.
-    if args.what == "trace" and not args.no_moving_view:
+    if args.full and args.what == "trace" and not args.no_moving_view:
         NMV = 1000 if 1000 % F == 0 else 1200          # a multiple of the frames in flight (1200: of 1..6, 8, 10, 12)
         MS = args.moving_step
         cams = moving_cameras(R, W, H, NMV, step=MS, amplitude=NMV // 4 * MS)
@@ -625,7 +683,7 @@ def run_single(args, torch, R):
     # reference's start-up mode (RayTracingManager.h:54), 12-byte records, the integer xterm-256 mapper -- and the whole
     # RayTracingManager::Update (RayTracingManager.cu:127-150: trace + minimise + copy of the minimised stream to the host)
     side_modes, end_to_end = {}, None
-    if args.what == "trace" and not args.no_side_legs:
+    if args.full and args.what == "trace" and not args.no_side_legs:
         for mname in [m for m in ("BIT_ASCII",) if m != args.mode]:
             m2 = R.MODE_NAMES.index(mname)
             S2 = R.SIZE_RGB if m2 >= R.RGB_ASCII else R.SIZE_8BIT
@@ -646,7 +704,7 @@ def run_single(args, torch, R):
             drain()
             evs2, _ = repeat(make_timed_batch(step2, F), min(args.min_timed_ms, 25.0))
             ms2 = median(evs2) / K
-            if not args.no_verify:
+            if args.verify:
                 fin2 = ctx.read_frame(frame_bytes) if F == 1 else fbufs[(K - 1) % F].cpu().numpy()
                 rec["verified_against_golden"] = _frame_matches_golden(fin2, args.config, mname)
             for _ in range(5 if F == 1 else 300):
@@ -739,12 +797,12 @@ def run_single(args, torch, R):
     mrays = rays_per_frame * K / elapsed / 1e6
     g = golden().get("%s_%s" % (args.config, args.mode), {})
     hit_frac = (g.get("foreground_pixels") or 0) / float(rays_per_frame)
-    verified = _frame_matches_golden(final, args.config, args.mode) if final is not None else None
-    roofline = roofline_object(args.config, args.mode, kernel, W, H, S, ns, npl, H, kernel_ms, hit_frac)
+    verified = _frame_matches_golden(final, args.config, args.mode) if (args.verify and final is not None) else None
+    roofline = roofline_object(args.config, args.mode, kernel, W, H, S, ns, npl, H, kernel_ms, hit_frac) if (args.full and args.what == "trace") else None
     ctx.close()
 
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         cpu = cpu_baseline_leg(args.config, mode, args.cpu_threads)
     out = {
         "metric": BASELINE_METRIC,
@@ -763,11 +821,12 @@ def run_single(args, torch, R):
     else:
         eff_ms = elapsed / K * 1e3
         out["config"]["frames_in_flight"] = F
-        roofline["pipelined"] = {
-            "frames_in_flight": F, "effective_ms_per_frame": round(eff_ms, 5),
-            "achieved": round(roofline["bytes_per_launch"] / (eff_ms * 1e-3) / 1e9, 2), "unit": "GB/s",
-            "frac": round(roofline["bytes_per_launch"] / (eff_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-            "note": "whole-job rate with overlapping launches; 'achieved'/'frac' above are for one launch alone"}
+        if roofline is not None:
+            roofline["pipelined"] = {
+                "frames_in_flight": F, "effective_ms_per_frame": round(eff_ms, 5),
+                "achieved": round(roofline["bytes_per_launch"] / (eff_ms * 1e-3) / 1e9, 2), "unit": "GB/s",
+                "frac": round(roofline["bytes_per_launch"] / (eff_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                "note": "whole-job rate with overlapping launches; 'achieved'/'frac' above are for one launch alone"}
     if side_modes:
         out["modes"] = side_modes
     if end_to_end:
@@ -831,11 +890,15 @@ def run_native(args, torch, R, devices, config, K, Wm, prewarm_ms, update_leg=Tr
             frames(K)
             evs.append(ctx.timer_stop())
             walls.append((time.perf_counter() - tw) * 1e3)
-            if len(evs) >= min(args.max_repeats, 200) or (sum(evs) >= args.min_timed_ms and len(evs) >= 3):
-                break
+            if not args.full or len(evs) >= min(args.max_repeats, 200) or (sum(evs) >= args.min_timed_ms and len(evs) >= 3):
+                break     # (a plain run: exactly K timed frames, one batch)
         batch_ms = median(evs)
-        frame = ctx.read_frame(20 * W * H) if M == 1 else fbufs[(K - 1) % M if K % M else M - 1].cpu().numpy()
-        verified = None if args.no_verify else _frame_matches_golden(frame, config, args.mode)
+        frame = None
+        if args.verify or args.dump_outputs:
+            frame = ctx.read_frame(20 * W * H) if M == 1 else fbufs[(K - 1) % M if K % M else M - 1].cpu().numpy()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"frame_records": frame[:S * W * H].reshape(H * W, S)})
+        verified = _frame_matches_golden(frame, config, args.mode) if args.verify else None
         rays = (W - 1) * H
         rec = {"value": round(rays * K / (batch_ms * 1e-3) / 1e6, 3), "unit": "Mrays/s", "n_gpus": len(set(devices)), "logical_ranks": n,
                "steps": K, "warmup": Wm, "ms_per_step": round(batch_ms / K, 5),
@@ -846,8 +909,8 @@ def run_native(args, torch, R, devices, config, K, Wm, prewarm_ms, update_leg=Tr
                                          "sharded, slabs gathered on device %d as %s; exchange: %s"
                                          % (n, len(set(devices)), devices[0], "4-byte pixel words expanded there" if args.native_wire == "compact" else "records",
                                             ctx.exchange_note)},
-               "timing": {"method": "HIP events on the root's stream around each batch of K rtx_render calls (a frame is complete there in stream order); "
-                                    "median over repeated batches", "repeats": len(evs),
+               "timing": {"method": "HIP events on the root's stream around each batch of K rtx_render calls (a frame is complete there in stream order); " +
+                                    ("median over repeated batches" if args.full else "one batch"), "repeats": len(evs),
                           "batch_ms": {"median": round(batch_ms, 5), "min": round(min(evs), 5), "max": round(max(evs), 5)},
                           "wall_ms_per_step_median": round(median(walls) / K, 5)},
                "gather_bytes_per_frame": ctx.get_option(R.STAT_GROUP_BYTES),
@@ -1039,7 +1102,7 @@ def run_sharded(args, torch, dist, R, sharding, rank, world, local_rank, config,
 
         elapsed, q0 = sharding.timed_rounds(dist, torch, pipe, render_round, K, Wm, "cuda", torch.cuda.synchronize,
                                             prewarm=prewarm_frames,
-                                            min_total=args.min_timed_ms * 1e-3, max_repeats=min(args.max_repeats, 200))
+                                            min_total=args.min_timed_ms * 1e-3, max_repeats=min(args.max_repeats, 200) if args.full else 1)
         n_rounds = -(-K // RF)
         last_frame = (q0 + n_rounds - 1) * RF + (K - 1 - (n_rounds - 1) * RF)
         slab0 = pipe.unit(0, 0)
@@ -1070,17 +1133,17 @@ def run_sharded(args, torch, dist, R, sharding, rank, world, local_rank, config,
 
         elapsed = sharding.timed_frames(dist, torch, pipe, render, K, Wm, "cuda", torch.cuda.synchronize,
                                         prewarm=prewarm_frames,
-                                        min_total=args.min_timed_ms * 1e-3, max_repeats=min(args.max_repeats, 200))
+                                        min_total=args.min_timed_ms * 1e-3, max_repeats=min(args.max_repeats, 200) if args.full else 1)
         last_frame = K - 1
         slab0 = pipe.slabs[0] if pipe.slabs is not None else None
         exchange_note = "RCCL p2p gather per frame; frame i assembled on rank %s" % ("i % N" if args.root == "rotate" else "0")
     wins = getattr(pipe, "timed_windows", [elapsed])
-    timing = {"method": "wall clock around exactly K frames, barrier + synchronize on both sides, MAX over ranks; the window is repeated "
-                        "(each time from a drained pipeline) and the median window reported",
+    timing = {"method": "wall clock around exactly K frames, barrier + synchronize on both sides, MAX over ranks" +
+                        ("; the window is repeated (each time from a drained pipeline) and the median window reported" if args.full else "; one window"),
               "repeats": len(wins), "timed_ms_total": round(sum(wins) * 1e3, 3),
               "batch_ms": {"median": round(elapsed * 1e3, 5), "min": round(min(wins) * 1e3, 5), "max": round(max(wins) * 1e3, 5)}}
     dist_verified = None
-    if not args.no_verify:
+    if args.verify:
         # byte check of the last assembled frame, outside the timed region: its root hashes it (SHA-256 of the
         # whole 20*W*H buffer against the committed golden value); the verdict is reduced to rank 0 as a
         # tri-state: 1 = compared and equal, 0 = compared and different (or the check itself failed),
@@ -1102,7 +1165,7 @@ def run_sharded(args, torch, dist, R, sharding, rank, world, local_rank, config,
     # poison; (b) a round in which every frame has its own camera, queued launch by launch: a slab that lands in the
     # wrong frame or on the wrong root shows.  Each root compares its frames on the GPU with the whole frame it
     # renders itself for the same camera.
-    if args.exchange in ("compact", "rounds") and not args.no_verify:
+    if args.exchange in ("compact", "rounds") and args.verify:
         code = 1
         try:
             qn = q0 + n_rounds
@@ -1157,22 +1220,24 @@ def run_sharded(args, torch, dist, R, sharding, rank, world, local_rank, config,
                                           "per frame; every root compares its frames with the same frames rendered in one piece" % pipe.nbuf}
     if latency is not None:
         timing["frame_latency"] = latency
-    # per-rank kernel time, measured apart from the pipeline, for the roofline object
+    # per-rank kernel time, measured apart from the pipeline, for the roofline object (--full)
     ctx.synchronize()
     torch.cuda.synchronize()
-    n_k = max(10, min(K, 50))
-    tgt = slab0 if slab0 is not None else pipe.frames[0]
-    if isinstance(tgt, list):
-        tgt = tgt[0]
-    for _ in range(3):
-        ctx.render_rows(params, mode, row0, rows, d_out=tgt.data_ptr(), out_row_base=row0 if slab0 is not None else 0,
-                        flags=R.RENDER_COMPACT if compact else 0)
-    ctx.synchronize()
-    ctx.timer_start()
-    for _ in range(n_k):
-        ctx.render_rows(params, mode, row0, rows, d_out=tgt.data_ptr(), out_row_base=row0 if slab0 is not None else 0,
-                        flags=R.RENDER_COMPACT if compact else 0)
-    kernel_ms = ctx.timer_stop() / n_k
+    kernel_ms = None
+    if args.full:
+        n_k = max(10, min(K, 50))
+        tgt = slab0 if slab0 is not None else pipe.frames[0]
+        if isinstance(tgt, list):
+            tgt = tgt[0]
+        for _ in range(3):
+            ctx.render_rows(params, mode, row0, rows, d_out=tgt.data_ptr(), out_row_base=row0 if slab0 is not None else 0,
+                            flags=R.RENDER_COMPACT if compact else 0)
+        ctx.synchronize()
+        ctx.timer_start()
+        for _ in range(n_k):
+            ctx.render_rows(params, mode, row0, rows, d_out=tgt.data_ptr(), out_row_base=row0 if slab0 is not None else 0,
+                            flags=R.RENDER_COMPACT if compact else 0)
+        kernel_ms = ctx.timer_stop() / n_k
     kernel = ctx.last_kernel
     torch.cuda.synchronize()
     del pipe
@@ -1250,7 +1315,7 @@ def run_sharded_dry(args, torch, dist, R, sharding, rank, world, config, K, Wm):
               "timed_ms_total": round(sum(wins) * 1e3, 3),
               "batch_ms": {"median": round(elapsed * 1e3, 5), "min": round(min(wins) * 1e3, 5), "max": round(max(wins) * 1e3, 5)}}
     code = 2
-    if not args.no_verify:
+    if args.verify:
         if rank == pipe.root_of(last_frame):
             m = _frame_matches_golden(pipe.frame(last_frame).numpy(), config, args.mode)
             code = 2 if m is None else int(bool(m))
@@ -1290,6 +1355,8 @@ def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
     force_dist = os.environ.get("RTX_BENCH_FORCE_DIST") == "1"
+    if args.dump_outputs and not args.native and (args.gpus > 1 or force_dist):
+        raise SystemExit("--dump-outputs: N = 1 and --native only")
     if args.native:
         # one process drives every GPU through a device group: no launcher, no torch.distributed
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -1298,11 +1365,11 @@ def main(argv=None):
             raise SystemExit("bench.py needs a GPU: the ray-trace path has no CPU fallback")
         R = importlib.import_module(PKG)
         devices = [int(v) for v in args.native_devices.split(",")] if args.native_devices else list(range(max(1, args.gpus)))
-        rec = run_native(args, torch, R, devices, args.config, args.steps, args.warmup, args.prewarm_ms)
+        rec = run_native(args, torch, R, devices, args.config, args.steps, args.warmup, args.prewarm_ms, update_leg=args.full)
         out = {"metric": BASELINE_METRIC}
         out.update(rec)
         out.update({"higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic"})
-        if not args.no_cpu_baseline:
+        if args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_leg(args.config, R.MODE_NAMES.index(args.mode), args.cpu_threads)
             out["speedup_vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 1)
         print(json.dumps(out))
@@ -1349,7 +1416,7 @@ def main(argv=None):
         dist.init_process_group(backend="nccl", device_id=torch.device("cuda", local_rank))
     subs = args.sub_configs
     if subs is None:
-        subs = "C4" if (args.config == "C2" and not args.dry and args.exchange != "p2p") else ""
+        subs = "C4" if (args.full and args.config == "C2" and not args.dry and args.exchange != "p2p") else ""
     subs = [s for s in subs.split(",") if s and s.lower() != "none"]
     for s in subs:
         if s not in R.CONFIGS:
@@ -1377,11 +1444,11 @@ def main(argv=None):
         out["data"] = "synthetic (dry run: CPU oracle as the renderer over gloo; not a measurement)"
     # the CPU baseline of the main workload: rank 0, now that the ranks are done (it must not sit inside anyone's timed region)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.cpu_baseline:
         cpu = cpu_baseline_leg(args.config, R.MODE_NAMES.index(args.mode), args.cpu_threads)
         out["speedup_vs_cpu_baseline"] = round(out["value"] / cpu["value"], 1)
     out["cpu_baseline"] = cpu
-    if not args.dry and not args.no_native_leg:
+    if args.full and not args.dry and not args.no_native_leg:
         # the same sharded frame behind the C ABI: ONE process (this one) drives all N GPUs through a device group, now that
         # the other ranks have let go of theirs.  A sub-record beside the torch.distributed line, never the line's value.
         # In a child process with a time limit: the RCCL form of the gather between distinct GPUs has only ever run at one device
@@ -1390,7 +1457,7 @@ def main(argv=None):
             devs = list(range(n_gpus)) if torch.cuda.device_count() >= n_gpus else [0] * n_gpus
             cmd = [sys.executable, os.path.abspath(__file__), "--native", "--gpus", str(n_gpus), "--native-devices", ",".join(str(d) for d in devs),
                    "--config", args.config, "--mode", args.mode, "--steps", str(K), "--warmup", str(Wm), "--prewarm-ms", str(min(args.prewarm_ms, 50.0)),
-                   "--no-cpu-baseline", "--min-timed-ms", str(args.min_timed_ms)] + (["--no-verify"] if args.no_verify else [])
+                   "--full", "--no-cpu-baseline", "--min-timed-ms", str(args.min_timed_ms)] + (["--no-verify"] if args.no_verify else [])
             env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "ROLE_RANK")}
             proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240, env=env)
             line = next((ln for ln in proc.stdout.splitlines()[::-1] if ln.strip().startswith("{")), None)

@@ -72,3 +72,42 @@ def test_moving_view_ring_steps_by_a_constant_angle():
     for i in range(1000):
         assert abs(abs(ys[(i + 1) % 1000] - ys[i]) - b.MOVING_STEP_RAD) < 1e-9     # also across the wrap-around
     assert abs(max(ys) - math.pi - 0.25) < 1e-9 and abs(min(ys) - math.pi + 0.25) < 1e-9
+
+
+def test_full_brings_back_what_a_plain_run_leaves_out():
+    b = _bench()
+    a = b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not a.full and not a.verify and not a.cpu_baseline and a.dump_outputs is None
+    a = b.parse_args(["--full"])
+    assert a.full and a.verify and a.cpu_baseline
+    a = b.parse_args(["--full", "--no-verify", "--no-cpu-baseline"])
+    assert not a.verify and not a.cpu_baseline
+    assert b.parse_args(["--verify"]).verify
+
+
+def test_dump_outputs_writes_small_outputs_whole(tmp_path):
+    import numpy as np
+    b = _bench()
+    recs = np.random.default_rng(5).integers(0, 256, size=(320 * 180, 20), dtype=np.uint8)
+    b.dump_outputs(str(tmp_path / "out"), {"frame_records": recs})
+    got = np.load(tmp_path / "out" / "frame_records.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, recs.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame_records.npy"]
+
+
+def test_dump_outputs_samples_a_large_frame_the_same_way_every_time(tmp_path):
+    """A 1920x1080 frame of 20-byte records is larger than the budget: a fixed sample of pixels, under 64 MB in all."""
+    import numpy as np
+    b = _bench()
+    recs = np.random.default_rng(7).integers(0, 256, size=(1920 * 1080, 20), dtype=np.uint8)
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"frame_records": recs})
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 1000 * 1000
+    idx = np.load(tmp_path / "a" / "frame_records_index.npy")
+    got = np.load(tmp_path / "a" / "frame_records.npy")
+    assert idx.dtype == np.float64 and got.dtype == np.float32 and len(idx) == len(got) > 100000
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 1920 * 1080
+    assert np.array_equal(got, recs[idx.astype(np.int64)].astype(np.float32))
+    for f in ("frame_records.npy", "frame_records_index.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

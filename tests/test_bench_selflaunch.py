@@ -25,7 +25,7 @@ def _one_line(proc):
 
 
 def test_self_launch_world2_over_gloo_with_cpu_baseline_and_sub_config():
-    p = _run("--gpus", "2", "--dry", "--steps", "6", "--warmup", "1", "--sub-configs", "C1", "--cpu-threads", "2")
+    p = _run("--gpus", "2", "--dry", "--steps", "6", "--warmup", "1", "--sub-configs", "C1", "--cpu-threads", "2", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     d = _one_line(p)
     with open(os.path.join(ROOT, "BASELINE.json")) as f:
@@ -46,10 +46,27 @@ def test_self_launch_world2_over_gloo_with_cpu_baseline_and_sub_config():
 @pytest.mark.parametrize("extra", [["--exchange", "p2p", "--root", "fixed"], ["--exchange", "p2p"], ["--exchange", "rounds"],
                                    ["--exchange", "compact", "--root", "fixed", "--frames-per-root", "3"]])
 def test_self_launch_other_exchanges(extra):
-    p = _run("--gpus", "2", "--dry", "--steps", "5", "--warmup", "0", "--no-cpu-baseline", *extra)
+    p = _run("--gpus", "2", "--dry", "--steps", "5", "--warmup", "0", "--no-cpu-baseline", "--full", *extra)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _one_line(p)
     assert d["verified_against_golden"] is True and d["cpu_baseline"] is None and "configs" not in d
+
+
+def test_plain_run_times_the_steps_and_nothing_else():
+    """Without --full the line carries the headline figure only: one window of exactly K steps, no golden check, no CPU
+    baseline, no sub-record."""
+    p = _run("--gpus", "2", "--dry", "--steps", "6", "--warmup", "1")
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = _one_line(p)
+    assert d["steps"] == 6 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["unit"] == "Mrays/s"
+    assert d["timing"]["repeats"] == 1
+    assert d["verified_against_golden"] is None and d["cpu_baseline"] is None and "configs" not in d
+
+
+def test_dump_outputs_is_refused_for_several_ranks():
+    p = _run("--gpus", "2", "--dry", "--steps", "2", "--warmup", "0", "--dump-outputs", "unused")
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr
 
 
 def test_self_launch_relays_a_failing_rank_as_a_failure():

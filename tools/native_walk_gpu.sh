@@ -9,7 +9,7 @@ for d in 0 0,0 0,0,0,0 0,0,0,0,0,0,0,0; do
    for t in 1 0; do
     [ "$t" = 0 ] && [ "$m" = 16 ] && continue
     printf "threads %s  " $t
-    python bench.py --native --config $CFG --native-devices $d --native-frames $m --native-threads $t --no-cpu-baseline --steps $STEPS --warmup 32 2>/dev/null | python -c "
+    python bench.py --native --full --config $CFG --native-devices $d --native-frames $m --native-threads $t --no-cpu-baseline --steps $STEPS --warmup 32 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 e=d.get('end_to_end') or {}
