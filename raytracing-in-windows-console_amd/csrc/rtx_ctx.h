@@ -22,6 +22,25 @@ struct HostPlane {
 
 struct rtx_group; // rtx_group.cpp: the device group a context is the root of
 
+// One Minimize (rtx_post.hip): its input, a W*H frame as records or as pixel words (`lead`: how many words before `data` belong to
+// the same frame: rtx_post_kernels.inc) ...
+struct MinInput {
+    int mode = 0;
+    size_t w = 0, h = 0;
+    bool words = false; // data: pixel words, else S-byte records
+    const void* data = nullptr;
+    uint32_t lead = 0;
+};
+
+// ... and, once launched, where it writes and where its result words are.
+struct MinRun {
+    MinInput input;
+    uint8_t* out = nullptr;
+    void* d_scan = nullptr;      // the chain's scratch
+    uint64_t* d_total = nullptr; // [0] the stream's length, [1] the failure word of a fused launch
+    uint32_t epoch = 0;          // not 0: a fused launch under this epoch
+};
+
 // bit casts (the creation index of an object travels in the .w of its float4s)
 inline float bits_to_float(uint32_t u)
 {
@@ -53,10 +72,9 @@ struct rtx_ctx {
     int64_t opt_update_host_write = -1; // RTX_OPT_UPDATE_HOST_WRITE: -1 auto (frames up to 2^17 slots), 0 off, 1 on
     uint64_t stat_host_writes = 0;
     uint64_t* h_pair = nullptr;     // two pinned words: a rank's stream length and failure word (rtx_update on a group, RTX_OPT_GROUP_UPDATE)
-    uint64_t* d_look = nullptr;     // rtx_minw_fused's look-back tables (agg, grp: rtx_post.hip), zeroed when allocated
+    uint64_t* d_look = nullptr;     // rtx_min_fused's look-back tables (agg, grp: rtx_post.hip), zeroed when allocated
     size_t look_blocks = 0;         // ... sized for this many blocks
     uint32_t look_epoch = 0;        // of the last fused launch (0: none yet; never used as a tag)
-    uint32_t min_fused_epoch = 0;   // not 0: the minimise launches just queued were the fused kind, under this epoch
     int64_t opt_min_fused = -1;     // RTX_OPT_MINIMIZE_FUSED: -1 auto (on), 0 three launches, 1 on, 2 on with blocks that give up (tests)
     uint64_t stat_min_fallbacks = 0; // fused minimise launches that gave up and were redone as three launches
     uint8_t* d_grey = nullptr;
@@ -211,13 +229,9 @@ struct rtx_ctx {
         size_t bytes = 0;
         bool busy = false;
         // a small frame whose Minimize launch writes the caller's buffer itself (RTX_OPT_UPDATE_HOST_WRITE): nothing was waited for in
-        // rtx_update_begin; rtx_update_end waits for ev_ready and reads the length from h_total
+        // rtx_update_begin; rtx_update_end waits for ev_ready, reads the length from h_total and settles `run`
         bool host_write = false;
-        uint32_t hw_epoch = 0;
-        int hw_mode = 0;
-        size_t hw_w = 0, hw_h = 0;
-        const uint32_t* hw_words = nullptr;
-        uint8_t* hw_out = nullptr;
+        MinRun run; // the Minimize launch of the slot's frame
     };
     UpdateSlot upd[2];
     hipStream_t copy_stream = nullptr;

@@ -15,9 +15,14 @@
 
 namespace {
 
-int ensure_min_buffers(rtx_ctx* ctx, size_t n_blocks, bool need_out)
+uint64_t min_blocks(uint64_t n_slots) { return (n_slots + rtx::kSlotsPerBlock - 1) / rtx::kSlotsPerBlock; }
+
+// Bytes of Minimize scratch for a frame of n_slots: [total u64 x 8][offsets u64 x blocks][sums u32 x blocks]
+size_t min_scan_bytes(uint64_t n_slots) { return (size_t)min_blocks(n_slots) * (sizeof(uint32_t) + sizeof(uint64_t)) + 64; }
+
+int ensure_min_buffers(rtx_ctx* ctx, uint64_t n_slots, bool need_out)
 {
-    const size_t need = n_blocks * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
+    const size_t need = min_scan_bytes(n_slots);
     if (ctx->scan_bytes < need) {
         if (ctx->d_scan) {
             hipFree(ctx->d_scan);
@@ -39,67 +44,57 @@ int ensure_min_buffers(rtx_ctx* ctx, size_t n_blocks, bool need_out)
     return RTX_OK;
 }
 
-int launch_minimize_chain(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint8_t* d_in, uint8_t* d_out, uint64_t** d_total)
-{
-    const uint64_t n_slots = (uint64_t)w * h;
-    const size_t n_blocks = (size_t)((n_slots + rtx::kSlotsPerBlock - 1) / rtx::kSlotsPerBlock);
-    // scratch layout: [total u64][offsets u64 x n_blocks][sums u32 x n_blocks]
-    uint64_t* total = (uint64_t*)d_scan;
-    uint64_t* offsets = total + 8;
-    uint32_t* sums = (uint32_t*)(offsets + n_blocks);
-    const bool rgb = !(mode == RTX_BIT_ASCII || mode == RTX_BIT_PIXEL); // MinimizeResults, RayTracingManager.cu:167-179
-    hipStream_t st = ctx->stream;
-    if (rgb) {
-        hipLaunchKernelGGL((rtx::rtx_min_count<20>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, st, d_in, n_slots, (uint32_t)w, sums);
-    } else {
-        hipLaunchKernelGGL((rtx::rtx_min_count<12>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, st, d_in, n_slots, (uint32_t)w, sums);
-    }
-    if (rgb) {
-        hipLaunchKernelGGL((rtx::rtx_min_scatter<20>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, st, d_in, n_slots, (uint32_t)w, sums, d_out, total);
-    } else {
-        hipLaunchKernelGGL((rtx::rtx_min_scatter<12>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, st, d_in, n_slots, (uint32_t)w, sums, d_out, total);
-    }
-    RTX_HIP(ctx, hipGetLastError());
-    *d_total = total;
-    return RTX_OK;
-}
+MinInput records_input(int mode, size_t w, size_t h, const void* d_records) { return MinInput{mode, w, h, false, d_records, 0u}; }
 
-size_t words_scan_bytes(uint64_t n_slots)
-{
-    const size_t n_blocks = (size_t)((n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock);
-    return n_blocks * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
-}
+MinInput words_input(int mode, size_t w, size_t h, const void* d_words, uint32_t lead = 0) { return MinInput{mode, w, h, true, d_words, lead}; }
 
-// Minimize from W*H pixel words (every mode but SDL) on the context's stream as three launches; scratch laid out as launch_minimize's.
-int launch_minimize_words_chain(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint32_t* d_words, uint8_t* d_out, uint64_t** d_total, uint32_t lead)
+// f(Src()) with the slot source (rtx_post_kernels.inc) of `in`: the one place where a mode and an input form pick the kernels.
+template <class F>
+int with_source(rtx_ctx* ctx, const MinInput& in, F f)
 {
-    const uint64_t n_slots = (uint64_t)w * h;
-    const unsigned n_blocks = (unsigned)((n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock);
-    uint64_t* total = (uint64_t*)d_scan;
-    uint64_t* offsets = total + 8;
-    uint32_t* sums = (uint32_t*)(offsets + n_blocks);
-    hipStream_t st = ctx->stream;
-#define RTX_MINW(M)                                                                                                                        \
-    do {                                                                                                                                   \
-        hipLaunchKernelGGL((rtx::rtx_minw_count<M>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, d_words, n_slots, (uint32_t)w, sums, lead);      \
-        hipLaunchKernelGGL(rtx::rtx_min_offsets, dim3(1), dim3(rtx::kThreads), 0, st, sums, n_blocks, offsets, total);                      \
-        hipLaunchKernelGGL((rtx::rtx_minw_scatter<M>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, d_words, n_slots, (uint32_t)w, offsets, d_out, lead); \
-    } while (0)
-    switch (mode) {
-    case RTX_BIT_ASCII: RTX_MINW(RTX_K_BIT_ASCII); break;
-    case RTX_BIT_PIXEL: RTX_MINW(RTX_K_BIT_PIXEL); break;
-    case RTX_RGB_ASCII: RTX_MINW(RTX_K_RGB_ASCII); break;
-    case RTX_RGB_PIXEL: RTX_MINW(RTX_K_RGB_PIXEL); break;
-    case RTX_RGB_NORMALS: RTX_MINW(RTX_K_RGB_NORMALS); break;
+    if (!in.words) {
+        const bool rgb = !(in.mode == RTX_BIT_ASCII || in.mode == RTX_BIT_PIXEL); // MinimizeResults, RayTracingManager.cu:167-179
+        if (rgb) {
+            f(rtx::RecordSource<20>());
+        } else {
+            f(rtx::RecordSource<12>());
+        }
+        return RTX_OK;
+    }
+    switch (in.mode) {
+    case RTX_BIT_ASCII: f(rtx::WordSource<RTX_K_BIT_ASCII>()); break;
+    case RTX_BIT_PIXEL: f(rtx::WordSource<RTX_K_BIT_PIXEL>()); break;
+    case RTX_RGB_ASCII: f(rtx::WordSource<RTX_K_RGB_ASCII>()); break;
+    case RTX_RGB_PIXEL: f(rtx::WordSource<RTX_K_RGB_PIXEL>()); break;
+    case RTX_RGB_NORMALS: f(rtx::WordSource<RTX_K_RGB_NORMALS>()); break;
     default: return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "no pixel words in this mode");
     }
-#undef RTX_MINW
-    RTX_HIP(ctx, hipGetLastError());
-    *d_total = total;
     return RTX_OK;
 }
 
-// The look-back tables of rtx_minw_fused: agg (one entry per block) then 64 replicas of grp (one entry per 64 blocks); zeroed when allocated, tagged by
+// The chain of `run` on the context's stream: count, offsets, scatter; the stream's length lands at run.d_scan.
+int launch_minimize_chain(rtx_ctx* ctx, const MinRun& run)
+{
+    const MinInput& in = run.input;
+    const uint64_t n_slots = (uint64_t)in.w * in.h;
+    const unsigned n_blocks = (unsigned)min_blocks(n_slots);
+    uint64_t* total = (uint64_t*)run.d_scan;
+    uint64_t* offsets = total + 8;
+    uint32_t* sums = (uint32_t*)(offsets + n_blocks);
+    hipStream_t st = ctx->stream;
+    const int rc = with_source(ctx, in, [&](auto src) {
+        using Src = decltype(src);
+        const auto* p = (const typename Src::Elem*)in.data;
+        hipLaunchKernelGGL((rtx::rtx_min_count<Src>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, p, n_slots, (uint32_t)in.w, in.lead, sums);
+        hipLaunchKernelGGL(rtx::rtx_min_offsets, dim3(1), dim3(rtx::kThreads), 0, st, sums, n_blocks, offsets, total);
+        hipLaunchKernelGGL((rtx::rtx_min_scatter<Src>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, p, n_slots, (uint32_t)in.w, in.lead, offsets, run.out);
+    });
+    if (rc != RTX_OK) return rc;
+    RTX_HIP(ctx, hipGetLastError());
+    return RTX_OK;
+}
+
+// The look-back tables of rtx_min_fused: agg (one entry per block) then 64 replicas of grp (one entry per 64 blocks); zeroed when allocated, tagged by
 // epoch afterwards.  One set per context: every minimise launch runs on the context's stream, one after the other.
 int ensure_look_tables(rtx_ctx* ctx, size_t n_blocks)
 {
@@ -122,68 +117,17 @@ int ensure_look_tables(rtx_ctx* ctx, size_t n_blocks)
     return RTX_OK;
 }
 
-// Minimize from the records of a W*H frame on the context's stream: one launch (rtx_min_fused, RTX_OPT_MINIMIZE_FUSED) or the two of
-// launch_minimize_chain.  As for the word form: (*d_total)[0] will hold the stream's length, and after a fused launch
-// (ctx->min_fused_epoch != 0) (*d_total)[1] == that epoch says that blocks gave up -- settle_minimize redoes the frame.
-int launch_minimize(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint8_t* d_in, uint8_t* d_out, uint64_t** d_total)
-{
-    const uint64_t n_slots = (uint64_t)w * h;
-    const uint64_t n_blocks = (n_slots + rtx::kRSlotsPerBlock - 1) / rtx::kRSlotsPerBlock;
-    ctx->min_fused_epoch = 0;
-    if (ctx->opt_min_fused == 0 || n_blocks > (1u << 24)) return launch_minimize_chain(ctx, d_scan, mode, w, h, d_in, d_out, d_total);
-    int rc = ensure_look_tables(ctx, (size_t)n_blocks);
-    if (rc != RTX_OK) return rc;
-    if (++ctx->look_epoch == 0u) {
-        RTX_HIP(ctx, hipMemsetAsync(ctx->d_look, 0, 2 * ctx->look_blocks * sizeof(uint64_t), ctx->stream));
-        ctx->look_epoch = 1u;
-    }
-    const uint32_t epoch = ctx->look_epoch;
-    uint64_t* total = (uint64_t*)d_scan;
-    uint64_t* agg = ctx->d_look;
-    uint64_t* grp = agg + ctx->look_blocks;
-    const uint32_t ng = (uint32_t)(ctx->look_blocks / rtx::kLookGroup);
-    const uint32_t polls = ctx->opt_min_fused == 2 ? 0u : rtx::kLookPolls;
-    const bool rgb = !(mode == RTX_BIT_ASCII || mode == RTX_BIT_PIXEL); // MinimizeResults, RayTracingManager.cu:167-179
-    if (rgb) {
-        hipLaunchKernelGGL((rtx::rtx_min_fused<20>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, ctx->stream, d_in, n_slots, (uint32_t)w, agg, grp, ng, epoch, polls, d_out,
-                           total);
-    } else {
-        hipLaunchKernelGGL((rtx::rtx_min_fused<12>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, ctx->stream, d_in, n_slots, (uint32_t)w, agg, grp, ng, epoch, polls, d_out,
-                           total);
-    }
-    RTX_HIP(ctx, hipGetLastError());
-    ctx->min_fused_epoch = epoch;
-    *d_total = total;
-    return RTX_OK;
-}
-
-int settle_minimize(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint8_t* d_in, uint8_t* d_out, const uint64_t got[2], uint64_t* total)
-{
-    *total = got[0];
-    const uint32_t epoch = ctx->min_fused_epoch;
-    ctx->min_fused_epoch = 0;
-    if (epoch == 0u || got[1] != (uint64_t)epoch) return RTX_OK;
-    ctx->stat_min_fallbacks++;
-    uint64_t* d_total = nullptr;
-    int rc = launch_minimize_chain(ctx, d_scan, mode, w, h, d_in, d_out, &d_total);
-    if (rc != RTX_OK) return rc;
-    RTX_HIP(ctx, hipMemcpyAsync(total, d_total, sizeof *total, hipMemcpyDeviceToHost, ctx->stream));
-    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return RTX_OK;
-}
-
-// Minimize from W*H pixel words on the context's stream: one launch (rtx_minw_fused, RTX_OPT_MINIMIZE_FUSED) or the three above.
-// (*d_total)[0] will hold the stream's length; after a fused launch (ctx->min_fused_epoch != 0) (*d_total)[1] == that epoch says
-// that blocks gave up: settle_minimize_words then redoes the frame with the three launches.
+// Minimize of `in` into d_out on the context's stream (scratch d_scan: min_scan_bytes): one launch (rtx_min_fused,
+// RTX_OPT_MINIMIZE_FUSED) or the chain.  run->d_total[0] will hold the stream's length; after a fused launch (run->epoch != 0)
+// run->d_total[1] == run->epoch says that blocks gave up: settle_minimize then redoes the frame as the chain.
 // (`pair`: where the one-launch form leaves the two result words instead of at d_scan -- pinned host memory as the device addresses it,
-// for a caller that reads them after a synchronisation without a copy; the three-launch form does not take it)
-int launch_minimize_words(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint32_t* d_words, uint8_t* d_out, uint64_t** d_total, uint32_t lead = 0,
-                          uint64_t* pair = nullptr)
+// for a caller that reads them after a synchronisation without a copy; the chain does not take it)
+int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_out, MinRun* run, uint64_t* pair = nullptr)
 {
-    const uint64_t n_slots = (uint64_t)w * h;
-    const uint64_t n_blocks = (n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock;
-    ctx->min_fused_epoch = 0;
-    if (ctx->opt_min_fused == 0 || n_blocks > (1u << 24)) return launch_minimize_words_chain(ctx, d_scan, mode, w, h, d_words, d_out, d_total, lead);
+    *run = MinRun{in, d_out, d_scan, (uint64_t*)d_scan, 0u};
+    const uint64_t n_slots = (uint64_t)in.w * in.h;
+    const uint64_t n_blocks = min_blocks(n_slots);
+    if (ctx->opt_min_fused == 0 || n_blocks > (1u << 24)) return launch_minimize_chain(ctx, *run);
     int rc = ensure_look_tables(ctx, (size_t)n_blocks);
     if (rc != RTX_OK) return rc;
     if (++ctx->look_epoch == 0u) {
@@ -197,39 +141,45 @@ int launch_minimize_words(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t
     uint64_t* grp = agg + ctx->look_blocks;
     const uint32_t ng = (uint32_t)(ctx->look_blocks / rtx::kLookGroup);
     const uint32_t polls = ctx->opt_min_fused == 2 ? 0u : rtx::kLookPolls;
-    hipStream_t st = ctx->stream;
-#define RTX_MINF(M) \
-    hipLaunchKernelGGL((rtx::rtx_minw_fused<M>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, st, d_words, n_slots, (uint32_t)w, agg, grp, ng, epoch, polls, d_out, total, lead)
-    switch (mode) {
-    case RTX_BIT_ASCII: RTX_MINF(RTX_K_BIT_ASCII); break;
-    case RTX_BIT_PIXEL: RTX_MINF(RTX_K_BIT_PIXEL); break;
-    case RTX_RGB_ASCII: RTX_MINF(RTX_K_RGB_ASCII); break;
-    case RTX_RGB_PIXEL: RTX_MINF(RTX_K_RGB_PIXEL); break;
-    case RTX_RGB_NORMALS: RTX_MINF(RTX_K_RGB_NORMALS); break;
-    default: return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "no pixel words in this mode");
-    }
-#undef RTX_MINF
+    rc = with_source(ctx, in, [&](auto src) {
+        using Src = decltype(src);
+        hipLaunchKernelGGL((rtx::rtx_min_fused<Src>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, ctx->stream, (const typename Src::Elem*)in.data, n_slots,
+                           (uint32_t)in.w, in.lead, agg, grp, ng, epoch, polls, d_out, total);
+    });
+    if (rc != RTX_OK) return rc;
     RTX_HIP(ctx, hipGetLastError());
-    ctx->min_fused_epoch = epoch;
-    *d_total = total;
+    run->d_total = total;
+    run->epoch = epoch;
     return RTX_OK;
 }
 
-// got[0], got[1]: the two words at *d_total as the host read them after the launches of launch_minimize_words.  A fused launch
-// whose blocks gave up is redone here as three launches (the stream is synchronised again); *total = the stream's length.
-int settle_minimize_words(rtx_ctx* ctx, void* d_scan, int mode, size_t w, size_t h, const uint32_t* d_words, uint8_t* d_out, const uint64_t got[2], uint64_t* total,
-                          uint32_t lead = 0)
+// got[0], got[1]: the two words at run.d_total as the host read them after launch_minimize.  A fused launch whose blocks gave up
+// is redone here as the chain (the stream is synchronised again); *total = the stream's length.
+int settle_minimize(rtx_ctx* ctx, const MinRun& run, const uint64_t got[2], uint64_t* total)
 {
     *total = got[0];
-    const uint32_t epoch = ctx->min_fused_epoch;
-    ctx->min_fused_epoch = 0;
-    if (epoch == 0u || got[1] != (uint64_t)epoch) return RTX_OK;
+    if (run.epoch == 0u || got[1] != (uint64_t)run.epoch) return RTX_OK;
     ctx->stat_min_fallbacks++;
-    uint64_t* d_total = nullptr;
-    int rc = launch_minimize_words_chain(ctx, d_scan, mode, w, h, d_words, d_out, &d_total, lead);
+    int rc = launch_minimize_chain(ctx, run);
     if (rc != RTX_OK) return rc;
-    RTX_HIP(ctx, hipMemcpyAsync(total, d_total, sizeof *total, hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(total, run.d_scan, sizeof *total, hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RTX_OK;
+}
+
+// Minimize of `in` into d_out (nullptr: the context's buffer) with the context's scratch, the host waiting for the length.
+int minimize_and_wait(rtx_ctx* ctx, const MinInput& in, void* d_out, size_t* out_bytes)
+{
+    int rc = ensure_min_buffers(ctx, (uint64_t)in.w * in.h, d_out == nullptr);
+    if (rc != RTX_OK) return rc;
+    if (!d_out) d_out = ctx->d_min;
+    MinRun run;
+    if ((rc = launch_minimize(ctx, ctx->d_scan, in, (uint8_t*)d_out, &run)) != RTX_OK) return rc;
+    uint64_t got[2] = {0, 0}, total = 0;
+    RTX_HIP(ctx, hipMemcpyAsync(got, run.d_total, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = settle_minimize(ctx, run, got, &total)) != RTX_OK) return rc;
+    *out_bytes = (size_t)total;
     return RTX_OK;
 }
 
@@ -290,16 +240,15 @@ int update_host_write(rtx_ctx* ctx, const rtx_params* p, int mode, void* host_ou
     const uint32_t* d_words = nullptr;
     int rc = trace_words(ctx, p, mode, &ctx->d_words, &ctx->words_cap, &d_words);
     if (rc != RTX_OK) return rc;
-    const uint64_t n_slots = (uint64_t)W * H;
-    if ((rc = ensure_min_buffers(ctx, (size_t)((n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock), false)) != RTX_OK) return rc;
+    if ((rc = ensure_min_buffers(ctx, (uint64_t)W * H, false)) != RTX_OK) return rc;
     ctx->h_pair[0] = 0;
     ctx->h_pair[1] = 0;
-    uint64_t* d_total = nullptr;
-    if ((rc = launch_minimize_words(ctx, ctx->d_scan, mode, W, H, d_words, (uint8_t*)d_host, &d_total, 0u, (uint64_t*)d_pair)) != RTX_OK) return rc;
+    MinRun run;
+    if ((rc = launch_minimize(ctx, ctx->d_scan, words_input(mode, W, H, d_words), (uint8_t*)d_host, &run, (uint64_t*)d_pair)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t total = 0;
-    // (blocks that gave up: the three launches, into the same buffer, their length read back the usual way)
-    if ((rc = settle_minimize_words(ctx, ctx->d_scan, mode, W, H, d_words, (uint8_t*)d_host, ctx->h_pair, &total)) != RTX_OK) return rc;
+    // (blocks that gave up: the chain, into the same buffer, its length read back the usual way)
+    if ((rc = settle_minimize(ctx, run, ctx->h_pair, &total)) != RTX_OK) return rc;
     ctx->stat_host_writes++;
     *out_bytes = (size_t)total;
     *done = true;
@@ -309,7 +258,7 @@ int update_host_write(rtx_ctx* ctx, const rtx_params* p, int mode, void* host_ou
 // rtx_update on a device group WITHOUT a gather (RTX_OPT_GROUP_UPDATE): the whole Update is bound by the copy of the minimised
 // stream over one PCIe link, and a group has one link per device.  Every rank traces its rows as pixel words -- and the row above
 // them, whose last pixel is the colour its first pixel is compared with (RayTracingManager.cu:181-319 carries the last emitted colour
-// across rows) -- minimises its own rows (launch_minimize_words with `lead` = W) and, once the lengths of the ranks before it are
+// across rows) -- minimises its own rows (launch_minimize with `lead` = W) and, once the lengths of the ranks before it are
 // known on the host, copies its part of the stream to its place in host_out from its own device.  The ranks' parts, in rank
 // order, are the bytes the root would have made of the gathered frame.  false in *done: nothing was delivered, gather instead.
 int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host_out, size_t* out_bytes)
@@ -323,11 +272,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
     for (int r = 0; r < N; r++) {
         if (rtx_group_rows(root, H, r, &part[(size_t)r].row0, &part[(size_t)r].rows) != RTX_OK) return rtx_fail(root, RTX_ERR_INVALID_ARGUMENT, "rtx_group_rows failed");
     }
-    struct Queued {
-        const uint32_t* d_words = nullptr;
-        uint32_t lead = 0;
-    };
-    std::vector<Queued> queued((size_t)N);
+    std::vector<MinRun> runs((size_t)N);
     // a rank's device work: trace (its rows and the one above), minimise, the two words of the result on their way to the host
     auto queue_rows = [&](int r, rtx_ctx* m) -> int {
         Part& q = part[(size_t)r];
@@ -341,13 +286,10 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
             return rtx_fail(m, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for a rank's stream length");
         }
         if ((rc2 = rtx_render_rows(m, p, mode, q.row0 - above, q.rows + above, m->d_words, q.row0 - above, m->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc2;
-        const uint64_t n_slots = (uint64_t)W * q.rows;
-        if ((rc2 = ensure_min_buffers(m, (size_t)((n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock), true)) != RTX_OK) return rc2;
-        queued[(size_t)r].d_words = m->d_words + above * W;
-        queued[(size_t)r].lead = (uint32_t)(above * W);
-        uint64_t* d_total = nullptr;
-        if ((rc2 = launch_minimize_words(m, m->d_scan, mode, W, q.rows, queued[(size_t)r].d_words, m->d_min, &d_total, queued[(size_t)r].lead)) != RTX_OK) return rc2;
-        RTX_HIP(m, hipMemcpyAsync(m->h_pair, d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+        if ((rc2 = ensure_min_buffers(m, (uint64_t)W * q.rows, true)) != RTX_OK) return rc2;
+        MinRun& run = runs[(size_t)r];
+        if ((rc2 = launch_minimize(m, m->d_scan, words_input(mode, W, q.rows, m->d_words + above * W, (uint32_t)(above * W)), m->d_min, &run)) != RTX_OK) return rc2;
+        RTX_HIP(m, hipMemcpyAsync(m->h_pair, run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
         return RTX_OK;
     };
     auto await_rows = [&](int r, rtx_ctx* m) -> int {
@@ -356,7 +298,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         RTX_HIP(m, hipSetDevice(m->device));
         RTX_HIP(m, hipStreamSynchronize(m->stream));
         uint64_t total = 0;
-        const int rc2 = settle_minimize_words(m, m->d_scan, mode, W, q.rows, queued[(size_t)r].d_words, m->d_min, m->h_pair, &total, queued[(size_t)r].lead);
+        const int rc2 = settle_minimize(m, runs[(size_t)r], m->h_pair, &total);
         if (rc2 != RTX_OK) return rc2;
         q.bytes = (size_t)total;
         return RTX_OK;
@@ -480,21 +422,8 @@ int rtx_minimize(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_in, v
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "minimise buffers must be 16-byte aligned");
     }
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t n_slots = (uint64_t)w * h;
-    const size_t n_blocks = (size_t)((n_slots + rtx::kSlotsPerBlock - 1) / rtx::kSlotsPerBlock);
     if (!d_out && 20 * w * h > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "minimise output larger than the context's buffer");
-    int rc = ensure_min_buffers(ctx, n_blocks, d_out == nullptr);
-    if (rc != RTX_OK) return rc;
-    if (!d_out) d_out = ctx->d_min;
-    uint64_t* d_total = nullptr;
-    rc = launch_minimize(ctx, ctx->d_scan, mode, w, h, (const uint8_t*)d_in, (uint8_t*)d_out, &d_total);
-    if (rc != RTX_OK) return rc;
-    uint64_t got[2] = {0, 0}, total = 0;
-    RTX_HIP(ctx, hipMemcpyAsync(got, d_total, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
-    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = settle_minimize(ctx, ctx->d_scan, mode, w, h, (const uint8_t*)d_in, (uint8_t*)d_out, got, &total)) != RTX_OK) return rc;
-    *out_bytes = (size_t)total;
-    return RTX_OK;
+    return minimize_and_wait(ctx, records_input(mode, w, h, d_in), d_out, out_bytes);
 }
 
 int rtx_minimize_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_words, void* d_out, size_t* out_bytes)
@@ -507,19 +436,7 @@ int rtx_minimize_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d
     }
     if (!d_out && 20 * w * h > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "minimise output larger than the context's buffer");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    const uint64_t n_slots = (uint64_t)w * h;
-    const size_t n_blocks = (size_t)((n_slots + rtx::kWSlotsPerBlock - 1) / rtx::kWSlotsPerBlock);
-    int rc = ensure_min_buffers(ctx, n_blocks, d_out == nullptr);
-    if (rc != RTX_OK) return rc;
-    if (!d_out) d_out = ctx->d_min;
-    uint64_t* d_total = nullptr;
-    if ((rc = launch_minimize_words(ctx, ctx->d_scan, mode, w, h, (const uint32_t*)d_words, (uint8_t*)d_out, &d_total)) != RTX_OK) return rc;
-    uint64_t got[2] = {0, 0}, total = 0;
-    RTX_HIP(ctx, hipMemcpyAsync(got, d_total, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
-    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if ((rc = settle_minimize_words(ctx, ctx->d_scan, mode, w, h, (const uint32_t*)d_words, (uint8_t*)d_out, got, &total)) != RTX_OK) return rc;
-    *out_bytes = (size_t)total;
-    return RTX_OK;
+    return minimize_and_wait(ctx, words_input(mode, w, h, d_words), d_out, out_bytes);
 }
 
 int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, size_t* out_bytes)
@@ -626,9 +543,7 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     }
     if (!sl.ev_ready) RTX_HIP(ctx, hipEventCreateWithFlags(&sl.ev_ready, hipEventDisableTiming));
     if (!sl.ev_copied) RTX_HIP(ctx, hipEventCreateWithFlags(&sl.ev_copied, hipEventDisableTiming));
-    const uint64_t n_slots = (uint64_t)w * h;
-    const size_t n_blocks = (size_t)((n_slots + rtx::kSlotsPerBlock - 1) / rtx::kSlotsPerBlock);
-    const size_t need = n_blocks * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
+    const size_t need = min_scan_bytes((uint64_t)w * h);
     if (sl.scan_bytes < need) {
         if (sl.d_scan) hipFree(sl.d_scan);
         sl.d_scan = nullptr;
@@ -654,7 +569,6 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
         }
         (void)hipGetLastError(); // (the group gathers on its root from now on; this frame too)
     }
-    uint64_t* d_total = nullptr;
     const uint32_t* d_words = nullptr;
     sl.host_write = false;
     if (from_words && !ctx->group && ctx->opt_min_fused != 0 && ((uintptr_t)host_out & 15u) == 0 &&
@@ -666,15 +580,9 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
             if ((rc = trace_words(ctx, params, mode, &sl.d_words, &sl.words_cap, &d_words)) != RTX_OK) return rc;
             sl.h_total[0] = 0;
             sl.h_total[1] = 0;
-            if ((rc = launch_minimize_words(ctx, sl.d_scan, mode, w, h, d_words, (uint8_t*)d_host, &d_total, 0u, (uint64_t*)d_pair)) != RTX_OK) return rc;
+            if ((rc = launch_minimize(ctx, sl.d_scan, words_input(mode, w, h, d_words), (uint8_t*)d_host, &sl.run, (uint64_t*)d_pair)) != RTX_OK) return rc;
             RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
             sl.host_write = true;
-            sl.hw_epoch = ctx->min_fused_epoch;
-            sl.hw_mode = mode;
-            sl.hw_w = w;
-            sl.hw_h = h;
-            sl.hw_words = d_words;
-            sl.hw_out = (uint8_t*)d_host;
             ctx->stat_host_writes++;
             sl.busy = true;
             *ticket = (int)si;
@@ -686,7 +594,7 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     if (from_words) {
         // pixel words into the slot's own buffer (a group: into the group's, gathered), minimised from there
         if ((rc = trace_words(ctx, params, mode, &sl.d_words, &sl.words_cap, &d_words)) != RTX_OK) return rc;
-        if ((rc = launch_minimize_words(ctx, sl.d_scan, mode, w, h, d_words, sl.d_min, &d_total)) != RTX_OK) return rc;
+        if ((rc = launch_minimize(ctx, sl.d_scan, words_input(mode, w, h, d_words), sl.d_min, &sl.run)) != RTX_OK) return rc;
     } else {
     // the slot's frame buffer is caller-style memory for rtx_render_rows: whole frame, with the zero
     // semantics of the per-frame memset (the buffer starts zeroed; SDL frames write nothing, so clear)
@@ -699,21 +607,16 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     } else if ((rc = rtx_render_rows(ctx, params, mode, 0, h, sl.d_frame, 0, ctx->stream, rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) {
         return rc;
     }
-    if ((rc = launch_minimize(ctx, sl.d_scan, mode, w, h, sl.d_frame, sl.d_min, &d_total)) != RTX_OK) return rc;
+    if ((rc = launch_minimize(ctx, sl.d_scan, records_input(mode, w, h, sl.d_frame), sl.d_min, &sl.run)) != RTX_OK) return rc;
     }
-    RTX_HIP(ctx, hipMemcpyAsync(sl.h_total, d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(sl.h_total, sl.run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
     // the length is needed on the host to size the copy: wait for this frame's kernels (the previous frame's
     // copy keeps running on the copy stream meanwhile)
     RTX_HIP(ctx, hipEventSynchronize(sl.ev_ready));
     {
         uint64_t total = 0;
-        if (from_words) {
-            rc = settle_minimize_words(ctx, sl.d_scan, mode, w, h, d_words, sl.d_min, sl.h_total, &total);
-        } else {
-            rc = settle_minimize(ctx, sl.d_scan, mode, w, h, sl.d_frame, sl.d_min, sl.h_total, &total);
-        }
-        if (rc != RTX_OK) return rc;
+        if ((rc = settle_minimize(ctx, sl.run, sl.h_total, &total)) != RTX_OK) return rc;
         sl.h_total[0] = total;
     }
     sl.bytes = (size_t)*sl.h_total;
@@ -738,8 +641,7 @@ int rtx_update_end(rtx_ctx* ctx, int ticket, size_t* out_bytes)
         sl.host_write = false;
         sl.busy = false;
         uint64_t total = 0;
-        ctx->min_fused_epoch = sl.hw_epoch;
-        const int rc = settle_minimize_words(ctx, sl.d_scan, sl.hw_mode, sl.hw_w, sl.hw_h, sl.hw_words, sl.hw_out, sl.h_total, &total);
+        const int rc = settle_minimize(ctx, sl.run, sl.h_total, &total);
         if (rc != RTX_OK) return rc;
         *out_bytes = (size_t)total;
         return RTX_OK;

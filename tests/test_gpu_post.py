@@ -497,7 +497,7 @@ def test_update_from_words_and_from_records_hand_over_the_same_stream(R):
         assert bytes(c.update(p, R.SDL)) == b"\n" * H
 
 
-# ---- the one-launch form of Minimize from words (rtx_minw_fused, RTX_OPT_MINIMIZE_FUSED)
+# ---- the one-launch form of Minimize from words (rtx_min_fused<WordSource>, RTX_OPT_MINIMIZE_FUSED)
 
 @pytest.mark.parametrize("res", [(1024, 1), (1024, 63), (1024, 64), (1024, 65), (1024, 129), (1920, 1080), (3840, 2160), (977, 331), (5, 3)])
 def test_fused_minimize_is_the_three_launch_minimize(R, ctx, res):
@@ -598,7 +598,7 @@ def test_fused_minimize_beside_other_launches(R):
         assert c.get_option(R.STAT_MINIMIZE_FALLBACKS) == 0
 
 
-# ---- the record form of Minimize as one launch (rtx_min_fused)
+# ---- the record form of Minimize as one launch (rtx_min_fused<RecordSource>)
 
 @pytest.mark.parametrize("res", [(1024, 1), (1024, 64), (1024, 65), (1920, 1080), (977, 331), (5, 3), (1, 7)])
 def test_fused_record_minimize_is_the_two_launch_minimize(R, ctx, res):
