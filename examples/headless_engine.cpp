@@ -4,6 +4,7 @@
 //   headless_engine <W> <H> <frames> <mode 0..4> <dt> <out_file>
 // Renders `frames` frames of the reference's start scene and writes the last minimised frame (what
 // the reference's printer thread would fwrite to stdout, PrintMachine.cpp:289-290) to out_file.
+// RTX_SHADOWS=1 in the environment turns hard shadows on (no reference counterpart; read like RTX_DEVICES).
 #include "rtx_compat.hpp"
 
 #include <cstdio>
@@ -30,6 +31,8 @@ int main(int argc, char** argv)
         camera->Update();
         scene->Init();
         rayTracingManager->SetRenderingMode(mode);
+        const char* shadows = std::getenv("RTX_SHADOWS");
+        if (shadows && std::atoi(shadows) == 1) rayTracingManager->SetShadows(true);
 
         for (int f = 0; f < frames; f++) {
             // Engine3D::Render

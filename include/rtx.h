@@ -151,6 +151,19 @@ enum rtx_option {
                                * way.  -1 auto: 1 where the list names two or more distinct devices.  A HIP error on the direct path makes the group
                                * fall back to 0 for good (RTX_STAT_GROUP_DIRECT_UPDATES counts the direct ones) */
     RTX_OPT_GROUP_WIRE = 13,  /* device groups: enum rtx_group_wire -- what travels: compact pixel words (default) or records */
+    RTX_OPT_SHADOWS = 20,     /* hard shadows from the light (rtx_scene_set_light): 0 off (default), 1 on.  A pixel whose hit point faces
+                               * away from the light, or whose segment to the light meets another object, is shaded with the light's two
+                               * powers at 0 (ambient only; glyph and every other field unchanged).  The character modes only: RGB_NORMALS and
+                               * SDL are unaffected.  With shadows off and the reference's light the frame loop launches exactly what it
+                               * launches without this option; any other state traces the closest hit first and shades in a second launch,
+                               * which culls occluders per 16 x 16 tile against the cone from the light through the tile's hit points.
+                               * The closest hits go through a hit buffer of 8 bytes per pixel, one per render stream (at most 64 streams),
+                               * allocated at the first such launch on it; a recorded graph keeps the buffer of the stream it was recorded
+                               * on, so replays of it must not overlap launches on that stream or one another.
+                               * No reference counterpart (RayTracing.cu:132 "#todo: INTRODUCE REAL LIGHTS!", :143-157) */
+    RTX_OPT_SHADOW_CHECK = 21, /* for checks, not for the frame loop: 0 normal (default); 1 every shadow ray tests every object, no culling (the
+                               * brute reference of the culled path); 2 the two-launch path with no occlusion and no self-shadow test, so that
+                               * every pixel is lit.  No reference counterpart */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -174,6 +187,13 @@ enum rtx_stat {
     RTX_STAT_GROUP_EXCHANGE = 111,  /* the exchange the last sharded frame used: RTX_EXCHANGE_PEER_COPY or RTX_EXCHANGE_RCCL (0: none yet) */
     RTX_STAT_GROUP_GATHERS = 112,   /* sharded frames gathered so far */
     RTX_STAT_GROUP_BYTES = 113,     /* bytes the last gather moved between devices */
+    RTX_STAT_SHADOW_FRAMES = 118,   /* launch pairs queued on the light / shadow path (RTX_OPT_SHADOWS, rtx_scene_set_light): one per
+                                     * rtx_render_rows call, so one per slab of a sliced frame; a recorded launch counts once, when it is
+                                     * recorded, not at each replay */
+    RTX_STAT_SHADOW_LONGEST_LIST = 119, /* the most occluder candidates one shading workgroup kept after culling (summed over the refills of its
+                                     * 1024-entry LDS list; every sphere under RTX_OPT_SHADOW_CHECK 1) in the launch pair queued last.  One
+                                     * word per context: with launch pairs in flight on several streams it holds one of theirs.  Reading it
+                                     * waits for the device */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -265,6 +285,24 @@ int rtx_scene_clear(rtx_ctx* ctx);
 int rtx_scene_add_sphere(rtx_ctx* ctx, const float pos[3], float radius, const float rgb[3]);
 int rtx_scene_add_plane(rtx_ctx* ctx, const float pos[3], const float normal[3], const float rgb[3],
                         float width, float height);
+/* The point light of the Blinn-Phong shading, context state like the scene (rtx_scene_clear leaves it alone).  The reference
+ * has one light, constant at its call site (RayTracing.cu:132,143-157): position (1, 50, 0), diffuse and specular colour
+ * (1, 1, 1), diffuse power 2000, specular power 3000 -- the default here.  Shading keeps the reference's operation order with
+ * these values in place of the constants (per component ((colour * intensity) * power) * divDistance).  44 bytes.
+ * No reference counterpart. */
+typedef struct rtx_light {
+    float pos[3];
+    float diffuse_rgb[3];
+    float diffuse_power;
+    float specular_rgb[3];
+    float specular_power;
+} rtx_light;
+/* Sets the light (NULL: the reference's light again).  RTX_ERR_INVALID_ARGUMENT for a non-finite value, a negative power or a
+ * negative colour component.  On a device group every rank's replica.  Takes effect for launches queued afterwards; a recorded
+ * graph keeps the light (and RTX_OPT_SHADOWS) it was recorded with.  No reference counterpart (RayTracing.cu:132,143-157). */
+int rtx_scene_set_light(rtx_ctx* ctx, const rtx_light* light);
+/* The light in use.  No reference counterpart (RayTracing.cu:132,143-157). */
+int rtx_scene_get_light(const rtx_ctx* ctx, rtx_light* out);
 /* Bulk append: n records of 7 floats (cx cy cz r R G B). */
 int rtx_scene_add_spheres(rtx_ctx* ctx, size_t n, const float* xyzr_rgb);
 unsigned rtx_scene_count(const rtx_ctx* ctx);

@@ -32,6 +32,8 @@ OPT_MINIMIZE_FUSED = 17
 OPT_GROUP_UPDATE = 18
 OPT_UPDATE_HOST_WRITE = 19
 STAT_UPDATE_HOST_WRITES = 117
+OPT_SHADOWS, OPT_SHADOW_CHECK = 20, 21
+STAT_SHADOW_FRAMES, STAT_SHADOW_LONGEST_LIST = 118, 119
 STAT_GROUP_DIRECT_UPDATES = 116
 STAT_MINIMIZE_FALLBACKS = 115
 STAT_GROUP_SIZE, STAT_GROUP_EXCHANGE, STAT_GROUP_GATHERS, STAT_GROUP_BYTES = 110, 111, 112, 113
@@ -60,6 +62,17 @@ class Params(C.Structure):
                 ("x", C.c_uint64), ("y", C.c_uint64)]
 
 
+class Light(C.Structure):
+    """struct rtx_light: the point light of the shading (the reference's constant light, RayTracing.cu:143-157, by default)."""
+    _fields_ = [("pos", C.c_float * 3), ("diffuse_rgb", C.c_float * 3), ("diffuse_power", C.c_float),
+                ("specular_rgb", C.c_float * 3), ("specular_power", C.c_float)]
+
+
+def make_light(pos=(1.0, 50.0, 0.0), diffuse_rgb=(1.0, 1.0, 1.0), diffuse_power=2000.0, specular_rgb=(1.0, 1.0, 1.0), specular_power=3000.0):
+    """A Light; the defaults are the reference's light."""
+    return Light((C.c_float * 3)(*pos), (C.c_float * 3)(*diffuse_rgb), diffuse_power, (C.c_float * 3)(*specular_rgb), specular_power)
+
+
 # every symbol include/rtx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = [
@@ -81,6 +94,8 @@ _SIGNATURES = [
     ("rtx_scene_count", C.c_uint, [_P]),
     ("rtx_scene_set_sphere_motion", C.c_int, [_P, C.c_uint, C.c_int, C.c_float]),
     ("rtx_scene_get_object", C.c_int, [_P, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    ("rtx_scene_set_light", C.c_int, [_P, C.POINTER(Light)]),
+    ("rtx_scene_get_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_render", C.c_int, [_P, C.POINTER(Params), C.c_int]),
     ("rtx_render_rows", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, C.c_uint]),
     ("rtx_submit_frames", C.c_int, [_P, C.c_size_t, C.POINTER(Params), C.c_int, C.POINTER(_P), C.POINTER(_P)]),
@@ -321,6 +336,15 @@ class Context:
         out = (C.c_float * 11)()
         self._check(lib().rtx_scene_get_object(self._h, index, C.byref(t), out))
         return t.value, np.array(out[:], dtype=np.float32)
+
+    def set_light(self, light=None):
+        """rtx_scene_set_light (None: the reference's light)."""
+        self._check(lib().rtx_scene_set_light(self._h, C.byref(light) if light is not None else None))
+
+    def get_light(self):
+        out = Light()
+        self._check(lib().rtx_scene_get_light(self._h, C.byref(out)))
+        return out
 
     # -- render
     def render(self, params, mode):

@@ -20,6 +20,19 @@ struct HostPlane {
     float4 a, b, c, od;
 };
 
+// RayTracing.cu:143-157: the one light of the reference, a constant at the BlinnPhongShading call site
+inline rtx_light rtx_reference_light()
+{
+    rtx_light l;
+    l.pos[0] = 1.0f;
+    l.pos[1] = 50.0f;
+    l.pos[2] = 0.0f;
+    for (int k = 0; k < 3; k++) l.diffuse_rgb[k] = l.specular_rgb[k] = 1.0f;
+    l.diffuse_power = 2000.0f;
+    l.specular_power = 3000.0f;
+    return l;
+}
+
 struct rtx_group; // rtx_group.cpp: the device group a context is the root of
 
 // One Minimize (rtx_post.hip): its input, a W*H frame as records or as pixel words (`lead`: how many words before `data` belong to
@@ -236,6 +249,26 @@ struct rtx_ctx {
     UpdateSlot upd[2];
     hipStream_t copy_stream = nullptr;
     unsigned upd_next = 0;
+
+    // light and hard shadows (RTX_OPT_SHADOWS, rtx_scene_set_light): with shadows off and the reference's light every launch is
+    // today's one-pass trace; otherwise rtx_render_rows traces the closest hit into a hit buffer (8 bytes per pixel) and
+    // rtx_shadow_shade shades from it.  One hit buffer per render stream (launches on one stream are ordered; frames on two
+    // streams never share one), allocated at the first two-pass launch on that stream, for at most kMaxHitStreams streams; an
+    // outgrown buffer is freed, or kept until the context is destroyed if a recorded graph may still read it.
+    rtx_light light = rtx_reference_light();
+    int64_t opt_shadows = 0;
+    int64_t opt_shadow_check = 0;
+    uint64_t stat_shadow_frames = 0;
+    uint32_t* d_shadow_longest = nullptr; // the longest occluder list of the last two-pass launch (one word)
+    static constexpr int kMaxHitStreams = 64;
+    struct HitScratch {
+        hipStream_t stream = nullptr;
+        void* p = nullptr;
+        size_t bytes = 0;
+        bool recorded = false; // a launch recorded into a graph reads this buffer
+    };
+    std::vector<HitScratch> hit_scratch;
+    std::vector<void*> hit_retired;
 
     std::string error;
     const char* last_kernel = "";

@@ -246,6 +246,42 @@ __device__ __forceinline__ V3 shade(const Ray& r, float distance, V3 normal, V3 
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 
+// shade() with a light in place of the call-site constants (rtx_scene_set_light): the same operations in the same order, the
+// light's values where shade() has the reference's literals -- 1.0f * x and x * 1.0f are exact, so for the reference's light
+// the result is shade()'s bit for bit.  A shadowed pixel is this with both powers 0.
+// (LightT: KLight of rtx_kernels.h -- position px py pz, diffuse colour dr dg db, specular colour sr sg sb)
+template <class LightT>
+__device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 normal, V3 od, const LightT& L, float dpow, float spow)
+{
+    const V3 point = add(r.o, mulf(r.d, distance));
+    const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
+
+    V3 lightDir = sub(v3(L.px, L.py, L.pz), point);
+    float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
+    dist = dist * dist;
+    const float divDistance = rcp_cr(dist);
+    lightDir = normalize_gpu(lightDir);
+
+    const V3 nn = normalize_gpu(normal);
+    const V3 nv = normalize_gpu(viewDir);
+
+    const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
+    const V3 diffuse = v3(((L.dr * diffuseIntensity) * dpow) * divDistance, ((L.dg * diffuseIntensity) * dpow) * divDistance,
+                          ((L.db * diffuseIntensity) * dpow) * divDistance);
+
+    const V3 h = normalize_gpu(add(lightDir, nv));
+    const float specularIntensity = pow32(clampf(dot(nn, h), 0.0f, 1.0f));
+    const V3 specular = v3(((L.sr * specularIntensity) * spow) * divDistance, ((L.sg * specularIntensity) * spow) * divDistance,
+                           ((L.sb * specularIntensity) * spow) * divDistance);
+
+    V3 res;
+    res.x = 0.2f * od.x + diffuse.x * od.x + specular.x * 1.0f;
+    res.y = 0.2f * od.y + diffuse.y * od.y + specular.y * 1.0f;
+    res.z = 0.2f * od.z + diffuse.z * od.z + specular.z * 1.0f;
+    res = mulf(res, 255.0f);
+    return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
+}
+
 // GetASCIICharacter's index, RayTracing.cu:26-39.  The reference clamps to 68, one past its
 // 68-entry table; the build resolves that to the last glyph.
 __device__ __forceinline__ int ramp_index(float shadingValue)

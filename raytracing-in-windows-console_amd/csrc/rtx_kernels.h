@@ -116,6 +116,20 @@ struct KBatch {
     KFrame f[kMaxBatch];
 };
 
+// The light / shadow path's second launch (rtx_shadow_shade): the light of rtx_scene_set_light and what to test.
+struct KLight {
+    float px, py, pz;
+    float dr, dg, db, dpow;
+    float sr, sg, sb, spow;
+};
+struct ShadowArgs {
+    const uint2* hits;  // the first launch's closest hits (kOutHit), row row0 of the launch at hits[0]
+    KLight light;
+    uint32_t test;      // 1: shadow rays (RTX_OPT_SHADOWS on, RTX_OPT_SHADOW_CHECK != 2); 0: every pixel lit
+    uint32_t brute;     // 1: no culling, every sphere tested (RTX_OPT_SHADOW_CHECK 1)
+    uint32_t* longest;  // atomicMax of the longest occluder list a workgroup held, or nullptr
+};
+
 // Arguments of rtx_expand_words (compact pixel words -> records), by value.
 constexpr int kMaxExpandSeg = 16;
 constexpr int kExpandPixels = 1024;             // pixels per workgroup
@@ -137,6 +151,9 @@ int rtx_k_launch_expand(const ExpandArgs* e, int mode, unsigned blocks, void* st
 const char* rtx_k_launch_trace(const KArgs* a, int mode, int cull, void* stream, int* hip_error);
 // The batched form (culling kernels without per-wave refinement, records or compact words): a->batch_n frames of kb in one launch.
 const char* rtx_k_launch_trace_batch(const KArgs* a, const KBatch* kb, int mode, void* stream, int* hip_error);
+// a->compact == 3 asks rtx_k_launch_trace for the closest hits alone (8 bytes per pixel into a->out, whatever the mode); this
+// shades them into a->out as `mode`'s records / words / values (a->compact 0 / 1 / 2).  Character modes only.
+const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* s, int mode, void* stream, int* hip_error);
 int rtx_k_launch_bin_cells(const KArgs* a, unsigned splits, void* stream);
 int rtx_k_launch_zero(void* p, size_t bytes, void* stream);
 // tile_cost[n_tiles] (grid gx wide) -> tile_order[n_tiles], heaviest first, dealt over n_cu compute units so that the

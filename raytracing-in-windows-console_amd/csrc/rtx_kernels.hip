@@ -18,6 +18,7 @@
 #include "rtx_device.hpp"
 #include "rtx_kernels.h"
 #include "rtx_records.hpp"
+#include "rtx_shadow.hpp"
 
 // The experiment build's hooks (ABL, STAMP, RTX_X_*): empty / constant false in the product build.
 #define RTX_X_SECTION_DEVICE
@@ -258,7 +259,9 @@ __device__ __forceinline__ Fields pixel_fields(const KArgs& a, const uint8_t* s_
 
 // OUT: what a pixel's result is stored as -- a kernel per form, so that the frame loop's kernel carries no
 // trace of the other two.
-enum { kOutRecords = 0, kOutCompact = 1, kOutValues = 2 };
+// kOutHit: the first launch of the light / shadow path -- the closest hit alone (t, and which object), 8 bytes per pixel, for
+// rtx_shadow_shade (rtx_shadow_kernels.inc); no shading, nothing encoded.
+enum { kOutRecords = 0, kOutCompact = 1, kOutValues = 2, kOutHit = 3 };
 
 template <int MODE, int OUT>
 __device__ __forceinline__ void encode_and_store(const KArgs& a, const Camera& cam, const uint32_t* s_digits, const uint8_t* s_ramp, bool in_frame, bool is_newline_col,
@@ -1182,6 +1185,8 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
     }
 }
 
+#include "rtx_shadow_kernels.inc"
+
 } // namespace rtx
 
 extern "C" int rtx_k_launch_expand(const ExpandArgs* e, int mode, unsigned blocks, void* stream_v)
@@ -1218,6 +1223,22 @@ extern "C" const char* rtx_k_launch_trace(const KArgs* a, int mode, int cull, vo
     dim3 grid((a->W + mw - 1u) / mw, (rows + mh - 1u) / mh, 1), block(kThreads, 1, 1);
     const char* name = nullptr;
     const unsigned lds_pad = rtx_x_lds_pad(); // 0 in the product build
+    if (a->compact == 3u) {
+        // the closest hits alone (the light / shadow path): one kernel per (CULL, REFINE), the mode does not enter
+        if (mode < RTX_K_BIT_ASCII || mode > RTX_K_RGB_PIXEL) return nullptr;
+        if (cull && a->refine) {
+            hipLaunchKernelGGL((rtx_trace<RTX_K_RGB_PIXEL, true, kOutHit, true>), grid, block, lds_pad, stream, *a);
+            name = "rtx_trace<hits,true,refine>";
+        } else if (cull) {
+            hipLaunchKernelGGL((rtx_trace<RTX_K_RGB_PIXEL, true, kOutHit, false>), grid, block, lds_pad, stream, *a);
+            name = "rtx_trace<hits,true>";
+        } else {
+            hipLaunchKernelGGL((rtx_trace<RTX_K_RGB_PIXEL, false, kOutHit, false>), grid, block, lds_pad, stream, *a);
+            name = "rtx_trace<hits,false>";
+        }
+        *hip_error = (int)hipGetLastError();
+        return name;
+    }
 #define RTX_LAUNCH(M, C, O, SUFFIX)                                                          \
     do {                                                                                     \
         if (C && a->refine) {                                                                \
@@ -1309,6 +1330,40 @@ extern "C" const char* rtx_k_launch_trace_batch(const KArgs* a, const KBatch* kb
     default: return nullptr;
     }
 #undef RTX_LAUNCH_BATCH
+    *hip_error = (int)hipGetLastError();
+    return name;
+}
+
+extern "C" const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* sh, int mode, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u || a->compact > 2u) return nullptr;
+    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
+    const char* name = nullptr;
+#define RTX_LAUNCH_SHADOW(M)                                                                           \
+    do {                                                                                               \
+        if (a->compact == 0u) {                                                                        \
+            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutRecords>), grid, block, 0, stream, *a, *sh);   \
+            name = "rtx_shadow_shade<" #M ">";                                                         \
+        } else if (a->compact == 1u) {                                                                 \
+            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutCompact>), grid, block, 0, stream, *a, *sh);   \
+            name = "rtx_shadow_shade<" #M ",compact>";                                                 \
+        } else {                                                                                       \
+            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutValues>), grid, block, 0, stream, *a, *sh);    \
+            name = "rtx_shadow_shade<" #M ",values>";                                                  \
+        }                                                                                              \
+    } while (0)
+    switch (mode) {
+    case RTX_K_BIT_ASCII: RTX_LAUNCH_SHADOW(RTX_K_BIT_ASCII); break;
+    case RTX_K_BIT_PIXEL: RTX_LAUNCH_SHADOW(RTX_K_BIT_PIXEL); break;
+    case RTX_K_RGB_ASCII: RTX_LAUNCH_SHADOW(RTX_K_RGB_ASCII); break;
+    case RTX_K_RGB_PIXEL: RTX_LAUNCH_SHADOW(RTX_K_RGB_PIXEL); break;
+    default: return nullptr;
+    }
+#undef RTX_LAUNCH_SHADOW
     *hip_error = (int)hipGetLastError();
     return name;
 }

@@ -566,6 +566,90 @@ rtx_ctx::TileOrder* tile_order_set(rtx_ctx* ctx, hipStream_t stream, const uint6
     return to;
 }
 
+// ---- the light / shadow path (RTX_OPT_SHADOWS, rtx_scene_set_light)
+
+// Does a launch of `mode` take the two-launch path?  Not in the state the reference has (shadows off, its light): there every
+// launch is today's.  Never for RGB_NORMALS and SDL, which do not shade.
+bool shadow_path(const rtx_ctx* ctx, int mode)
+{
+    if (mode < RTX_BIT_ASCII || mode > RTX_RGB_PIXEL) return false;
+    const rtx_light ref = rtx_reference_light();
+    return ctx->opt_shadows != 0 || std::memcmp(&ctx->light, &ref, sizeof ref) != 0;
+}
+
+// The hit buffer of `stream` with room for `bytes` (rtx_ctx::HitScratch).  At most kMaxHitStreams distinct streams (as
+// rtx_submit_slabs' join events).  An outgrown buffer is freed (hipFree waits for the device, so no queued launch still reads it),
+// unless a recorded graph may read it: then it is kept until rtx_destroy.
+int hit_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, bool capturing, void** out)
+{
+    rtx_ctx::HitScratch* hs = nullptr;
+    for (auto& h : ctx->hit_scratch) {
+        if (h.stream == stream) hs = &h;
+    }
+    if (!hs) {
+        if (ctx->hit_scratch.size() >= (size_t)rtx_ctx::kMaxHitStreams) {
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "light / shadow path: more than 64 distinct render streams");
+        }
+        ctx->hit_scratch.push_back(rtx_ctx::HitScratch());
+        hs = &ctx->hit_scratch.back();
+        hs->stream = stream;
+    }
+    if (hs->bytes < bytes) {
+        if (capturing) {
+            // (hipFree is not allowed while a stream captures; a buffer that grows here is kept)
+            if (hs->p) ctx->hit_retired.push_back(hs->p);
+        } else if (hs->p) {
+            if (hs->recorded) {
+                ctx->hit_retired.push_back(hs->p);
+            } else {
+                RTX_HIP(ctx, hipFree(hs->p));
+            }
+        }
+        hs->p = nullptr;
+        hs->bytes = 0;
+        hs->recorded = false;
+        RTX_HIP(ctx, hipMalloc(&hs->p, bytes));
+        hs->bytes = bytes;
+    }
+    if (capturing) hs->recorded = true;
+    *out = hs->p;
+    return RTX_OK;
+}
+
+// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade).
+int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
+{
+    const size_t rows = a.row_end - a.row0;
+    void* hits = nullptr;
+    int rc = hit_buffer(ctx, stream, (size_t)a.W * rows * 8u, capturing, &hits);
+    if (rc != RTX_OK) return rc;
+    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
+    KArgs h = a;
+    h.out = (uint8_t*)hits;
+    h.out_row_base = a.row0;
+    h.compact = 3u;
+    int herr = 0;
+    const char* name = rtx_k_launch_trace(&h, mode, cull, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch (closest hits)");
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
+    ShadowArgs sa;
+    std::memset(&sa, 0, sizeof sa);
+    sa.hits = (const uint2*)hits;
+    const rtx_light& l = ctx->light;
+    sa.light = KLight{l.pos[0], l.pos[1], l.pos[2], l.diffuse_rgb[0], l.diffuse_rgb[1], l.diffuse_rgb[2], l.diffuse_power,
+                      l.specular_rgb[0], l.specular_rgb[1], l.specular_rgb[2], l.specular_power};
+    sa.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
+    sa.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
+    sa.longest = ctx->d_shadow_longest;
+    name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow pass: invalid rendering mode or output form");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow shading kernel launch");
+    ctx->last_kernel = name;
+    ctx->stat_shadow_frames++;
+    return RTX_OK;
+}
+
 // ---- the pieces of rtx_render_rows
 
 struct RenderCall { // what the arguments of a call come to
@@ -850,6 +934,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
                  hipStream_t stream, unsigned flags, bool* done)
 {
     *done = false;
+    if (shadow_path(ctx, mode)) return RTX_OK; // (two launches per slab)
     if (n < 2 || n > (size_t)kMaxBatch || mode < RTX_BIT_ASCII || mode >= RTX_SDL || (flags & ~(unsigned)RTX_RENDER_COMPACT) != 0u) return RTX_OK;
     if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt_refine == 1) return RTX_OK;
     for (size_t i = 0; i < n; i++) {
@@ -1030,11 +1115,15 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     rtxplan::DispatchOrder::Decision od;
     if (cull && (rc = dispatch_order_args(ctx, stream, p, c, shape, capturing, static_order, a, &to, &od)) != RTX_OK) return rc;
     if (adapt && (rc = density_feedback_args(ctx, stream, q.view_dense, a)) != RTX_OK) return rc;
-    int herr = 0;
-    const char* name = rtx_k_launch_trace(&a, mode, cull, stream, &herr);
-    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
-    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch");
-    ctx->last_kernel = name;
+    if (shadow_path(ctx, mode)) {
+        if ((rc = launch_shadow_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
+    } else {
+        int herr = 0;
+        const char* name = rtx_k_launch_trace(&a, mode, cull, stream, &herr);
+        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
+        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch");
+        ctx->last_kernel = name;
+    }
     if (adapt && (rc = density_feedback_collect(ctx, stream)) != RTX_OK) return rc;
     if (to && (rc = dispatch_order_derive(ctx, stream, shape, a, to, od)) != RTX_OK) return rc;
     return RTX_OK;

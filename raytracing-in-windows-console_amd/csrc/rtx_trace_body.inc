@@ -23,6 +23,7 @@
     __shared__ uint16_t s_wlist[REFINE ? 4 : 1][REFINE ? kWaveListCap : 1]; // REFINE: a wave's own candidates (list positions)
     __shared__ uint32_t s_cost[3];               // this tile's work estimate, summed over the waves; waves done; start time
     __shared__ uint32_t s_nplanes;               // planes of the LDS table this macro tile can see
+    __shared__ uint32_t s_plmap[OUT == kOutHit ? kPlaneTable : 1]; // kOutHit: table entry -> plane index
     // What only the rare paths of the pass loop need (the overflow fallback: the item list and the pyramid; planes
     // beyond the table: the plane arrays) is parked here and read back inside those paths, so that it does not
     // occupy scalar registers -- or spill slots that every pass reloads -- for the whole loop.
@@ -242,6 +243,7 @@
             s_plane[3 * at + 0] = make_float4(n.x, n.y, n.z, num);
             s_plane[3 * at + 1] = bounds;
             s_plane[3 * at + 2] = pld;
+            if (OUT == kOutHit) s_plmap[at] = tid;
         }
         if (tid == 0u) {
             s_nplanes = (uint32_t)__popcll(m);
@@ -420,6 +422,8 @@
         V3 normal = ray.d, colour = ray.d;
         if (ABL(32u)) {
             distance = b.t; shadingValue = ray.d.x;
+        } else if (OUT == kOutHit) {
+            distance = b.t; // the shadow path's first launch: the winner only; rtx_shadow_shade shades it
         } else if (plane_q != 0xffffffffu || b.k != 0xffffffffu) {
             V3 n0, od;
             if (plane_q != 0xffffffffu) {
@@ -448,7 +452,20 @@
             }
         }
 
-        if (MODE != RTX_K_SDL && !ABL(64u)) {
+        if (OUT == kOutHit) {
+            if (in_frame) {
+                // 8 bytes per pixel: t and the winner (sphere position, or plane index | bit 31); 0xffffffff: no hit, or column W-1
+                uint32_t id = 0xffffffffu;
+                if (!newline_col) {
+                    if (plane_q != 0xffffffffu) {
+                        id = 0x80000000u | (plane_q < np_tab ? s_plmap[plane_q] : plane_q);
+                    } else if (b.k != 0xffffffffu) {
+                        id = b.k;
+                    }
+                }
+                reinterpret_cast<uint2*>(a.out)[(size_t)(row - a.out_row_base) * a.W + col] = make_uint2(__float_as_uint(b.t), id);
+            }
+        } else if (MODE != RTX_K_SDL && !ABL(64u)) {
             encode_and_store<MODE, OUT>(a, cam, s_digits, s_ramp, in_frame, newline_col, row, col, distance, normal, colour, shadingValue);
         }
         // per wave and pass: ray generation, planes and encoding; the exact test per candidate; winner normal, shading
