@@ -95,6 +95,28 @@ __device__ __forceinline__ float rcp_sqrt_cr(float x)
     return r;
 }
 
+__device__ __attribute__((noinline)) float div_generic(float num, float den) { return num / den; }
+
+// num / den correctly rounded (Markstein): r = RN(1/den) from rcp_fast, q = RN(num * r), rem = num - q*den (exact, one FMA),
+// result RN(q + rem*r).  Proof obligation: Markstein's theorem gives RN(num/den) when r = RN(1/den), q is within one ulp of
+// num/den and nothing overflows or underflows.  With |num|, |den| in [2^-60, 2^60] every intermediate is normal (the
+// quotient lies in [2^-120, 2^120]; rem, when not zero, is at least 2^-107), so each step commutes with scaling both operands
+// by powers of two and with their signs, and the result is fixed by the pair of significands.  All 2^46 pairs are checked
+// against num / den on the GPU (tests/gpu_checks/div_check.hip, tests/test_gpu_div.py): that test is the proof.  Outside the
+// range the wave falls back to the generic expansion for the lanes concerned, as rcp_cr does.
+__device__ __forceinline__ float div_cr(float num, float den)
+{
+    const float r = rcp_fast(den);
+    const float q = num * r;
+    const float rem = __builtin_fmaf(-q, den, num);
+    float t = __builtin_fmaf(rem, r, q);
+    const bool odd = !in_safe_range(fabsf(num)) || !in_safe_range(fabsf(den));
+    if (__builtin_expect(__ballot(odd) != 0ull, 0)) {
+        if (odd) t = div_generic(num, den);
+    }
+    return t;
+}
+
 // MyMath.h:139-145: one reciprocal, three multiplies, no zero check
 __device__ __forceinline__ V3 normalize_gpu(V3 a)
 {
@@ -212,10 +234,12 @@ __device__ __forceinline__ bool plane_hit(const Ray& r, V3 p, V3 n, float width,
     return true;
 }
 
-// BlinnPhongShading with the call-site constants, RayTracing.cu:41-79 and :143-157.
+// BlinnPhongShading with the call-site constants, RayTracing.cu:41-79 and :143-157, given nn = normalize_gpu(normal): a
+// plane's comes ready-made from the trace kernel's per-workgroup table, a sphere's is computed by the caller.  Every other
+// operation is the reference's, in its order.
 // od in: object colour / 255.0f (RayTracing.cu:144; the division is done once per object at upload,
 // the same IEEE operation on the same operands); out: shaded colour clamped to <= 255.
-__device__ __forceinline__ V3 shade(const Ray& r, float distance, V3 normal, V3 od)
+__device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 od)
 {
     const V3 point = add(r.o, mulf(r.d, distance));
     const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
@@ -226,7 +250,6 @@ __device__ __forceinline__ V3 shade(const Ray& r, float distance, V3 normal, V3 
     const float divDistance = rcp_cr(dist);
     lightDir = normalize_gpu(lightDir);
 
-    const V3 nn = normalize_gpu(normal);
     const V3 nv = normalize_gpu(viewDir);
 
     const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
@@ -246,9 +269,9 @@ __device__ __forceinline__ V3 shade(const Ray& r, float distance, V3 normal, V3 
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 
-// shade() with a light in place of the call-site constants (rtx_scene_set_light): the same operations in the same order, the
-// light's values where shade() has the reference's literals -- 1.0f * x and x * 1.0f are exact, so for the reference's light
-// the result is shade()'s bit for bit.  A shadowed pixel is this with both powers 0.
+// shade_nn() with a light in place of the call-site constants (rtx_scene_set_light) and nn computed here: the same operations
+// in the same order, the light's values where shade_nn() has the reference's literals -- 1.0f * x and x * 1.0f are exact, so
+// for the reference's light the result is shade_nn(normalize_gpu(normal))'s bit for bit.  A shadowed pixel is this with both powers 0.
 // (LightT: KLight of rtx_kernels.h -- position px py pz, diffuse colour dr dg db, specular colour sr sg sb)
 template <class LightT>
 __device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 normal, V3 od, const LightT& L, float dpow, float spow)

@@ -378,6 +378,7 @@ constexpr int kMaxMacro = 128;    // macro tile is at most 128 x 128 pixels
 constexpr int kMaxMacroRefine = 64; // ... 64 x 64 for the REFINE kernels
 constexpr int kChunk = 2 * kThreads; // spheres staged per barrier: two per thread
 constexpr int kPlaneTable = 16;   // planes hoisted into LDS; further planes take the direct path
+constexpr uint32_t kPlaneRow = 5; // float4s per plane in that table (rtx_trace_body.inc: s_plane)
 
 constexpr uint32_t kStageFull = 0xffffffffu; // stage_chunk: the step's survivors would not fit the list (nothing was written)
 

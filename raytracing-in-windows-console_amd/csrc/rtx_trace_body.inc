@@ -13,7 +13,8 @@
     __shared__ uint32_t s_idx[kListCap];
     __shared__ float4 s_col[kTable];             // per column: (m0, m4, m8) * vx
     __shared__ float4 s_row[kTable];             // per row:    (m1, m5, m9) * vy
-    __shared__ float4 s_plane[3 * kPlaneTable];  // per plane: {n, num} {xlo, xhi, zlo, zhi} {od, gidx}
+    // per plane: {n, num} {xlo, xhi, zlo, zhi} {od, gidx} {normalize_gpu(n), its shadingValue} {shade_nn()'s nn, 0}
+    __shared__ float4 s_plane[kPlaneRow * kPlaneTable];
     __shared__ uint32_t s_digits[256];           // three decimal digits of 0..255, NUL padded
     __shared__ __attribute__((aligned(4))) uint8_t s_ramp[68]; // the glyph ramp (RayTracing.h:97-115)
     __shared__ uint32_t s_wcnt[2][8];            // survivors per wave and half of the current step, double-buffered
@@ -240,9 +241,15 @@
         const unsigned long long m = __ballot(listed);
         if (listed) {
             const uint32_t at = (uint32_t)__popcll(m & ((1ull << tid) - 1ull));
-            s_plane[3 * at + 0] = make_float4(n.x, n.y, n.z, num);
-            s_plane[3 * at + 1] = bounds;
-            s_plane[3 * at + 2] = pld;
+            s_plane[kPlaneRow * at + 0] = make_float4(n.x, n.y, n.z, num);
+            s_plane[kPlaneRow * at + 1] = bounds;
+            s_plane[kPlaneRow * at + 2] = pld;
+            // what shading a pixel this plane wins needs of the plane alone: normal = normalize_gpu(n) and its Dot with (1,0,0)
+            // (RayTracing.cu:129, 133), and shade's nn = normalize_gpu(normal) -- the operations the pass loop used to run per pixel
+            const V3 nrm = normalize_gpu(n);
+            const V3 nn = normalize_gpu(nrm);
+            s_plane[kPlaneRow * at + 3] = make_float4(nrm.x, nrm.y, nrm.z, nrm.x * 1.0f + nrm.y * 0.0f + nrm.z * 0.0f);
+            s_plane[kPlaneRow * at + 4] = make_float4(nn.x, nn.y, nn.z, 0.0f);
             if (OUT == kOutHit) s_plmap[at] = tid;
         }
         if (tid == 0u) {
@@ -376,21 +383,21 @@
         // ---- planes: hoisted form from LDS (wave-uniform index: broadcast reads), Plane.cu:38-72
         uint32_t plane_q = 0xffffffffu; // winning plane, if a plane beats the best sphere
         for (uint32_t q = 0; q < np_vis; q++) {
-            const float4 pn = s_plane[3 * q + 0];
+            const float4 pn = s_plane[kPlaneRow * q + 0];
             const float dn = ray.d.x * pn.x + ray.d.y * pn.y + ray.d.z * pn.z;
             if (dn > 0.0f || fabsf(dn - 0.0f) < 1.1920928955078125e-7f) {
                 continue;
             }
-            const float t1 = pn.w / dn;
+            const float t1 = div_cr(pn.w, dn); // = pn.w / dn, bit for bit
             if (t1 <= 0.0f) {
                 continue;
             }
-            const float4 bd = s_plane[3 * q + 1];
+            const float4 bd = s_plane[kPlaneRow * q + 1];
             const float hx = ray.o.x + ray.d.x * t1, hz = ray.o.z + ray.d.z * t1;
             if ((hx <= bd.x || hx >= bd.y) || (hz <= bd.z || hz >= bd.w)) {
                 continue;
             }
-            const uint32_t gi = __float_as_uint(s_plane[3 * q + 2].w);
+            const uint32_t gi = __float_as_uint(s_plane[kPlaneRow * q + 2].w);
             if (t1 < b.t || (t1 == b.t && gi < (plane_q != 0xffffffffu ? best_gidx : (sphere_hit_any ? __float_as_uint(wod.w) : 0xffffffffu)))) {
                 b.t = t1;
                 best_gidx = gi;
@@ -425,30 +432,37 @@
         } else if (OUT == kOutHit) {
             distance = b.t; // the shadow path's first launch: the winner only; rtx_shadow_shade shades it
         } else if (plane_q != 0xffffffffu || b.k != 0xffffffffu) {
-            V3 n0, od;
-            if (plane_q != 0xffffffffu) {
-                // the plane's normal and colour: from the LDS table when it is there (the same values)
-                float4 pb, pd;
-                if (plane_q < np_tab) {
-                    pb = s_plane[3u * plane_q + 0u];
-                    pd = s_plane[3u * plane_q + 2u];
-                } else {
-                    asm volatile("" ::: "memory");
-                    pb = reinterpret_cast<const float4*>((uintptr_t)s_rare_ptr[2])[plane_q];
-                    pd = reinterpret_cast<const float4*>((uintptr_t)s_rare_ptr[3])[plane_q];
-                }
-                n0 = v3(pb.x, pb.y, pb.z);
+            V3 nn, od;
+            if (plane_q < np_tab) {
+                // a plane of the LDS table: normal, shadingValue and nn depend on the plane alone and are in the table (the
+                // same operations on the same values), so a wave of such pixels skips two normalisations
+                const float4 pm = s_plane[kPlaneRow * plane_q + 3u], pnn = s_plane[kPlaneRow * plane_q + 4u];
+                const float4 pd = s_plane[kPlaneRow * plane_q + 2u];
+                normal = v3(pm.x, pm.y, pm.z);
+                shadingValue = pm.w;
+                nn = v3(pnn.x, pnn.y, pnn.z);
                 od = v3(pd.x, pd.y, pd.z);
             } else {
-                // Sphere.cu:67: (origin + direction * t1 - spherePos).Normalize_GPU()
-                n0 = normalize_gpu(sub(add(ray.o, mulf(ray.d, b.t)), v3(wgeom.x, wgeom.y, wgeom.z)));
-                od = v3(wod.x, wod.y, wod.z);
+                V3 n0;
+                if (plane_q != 0xffffffffu) {
+                    // a plane beyond the table: its normal and colour from the arrays
+                    asm volatile("" ::: "memory");
+                    const float4 pb = reinterpret_cast<const float4*>((uintptr_t)s_rare_ptr[2])[plane_q];
+                    const float4 pd = reinterpret_cast<const float4*>((uintptr_t)s_rare_ptr[3])[plane_q];
+                    n0 = v3(pb.x, pb.y, pb.z);
+                    od = v3(pd.x, pd.y, pd.z);
+                } else {
+                    // Sphere.cu:67: (origin + direction * t1 - spherePos).Normalize_GPU()
+                    n0 = normalize_gpu(sub(add(ray.o, mulf(ray.d, b.t)), v3(wgeom.x, wgeom.y, wgeom.z)));
+                    od = v3(wod.x, wod.y, wod.z);
+                }
+                normal = normalize_gpu(n0);                                         // RayTracing.cu:129
+                shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // Dot(normal, (1,0,0)), :133
+                nn = normalize_gpu(normal);                                         // BlinnPhongShading, RayTracing.cu:52
             }
             distance = b.t;
-            normal = normalize_gpu(n0);                                         // RayTracing.cu:129
-            shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // Dot(normal, (1,0,0)), :133
             if (MODE != RTX_K_RGB_NORMALS && MODE != RTX_K_SDL) {
-                colour = ABL(16u) ? mulf(od, 255.0f) : shade(ray, distance, normal, od);
+                colour = ABL(16u) ? mulf(od, 255.0f) : shade_nn(ray, distance, nn, od);
             }
         }
 

@@ -85,7 +85,7 @@ def main():
 
     dev = function_ranges(os.path.join(PKG, "csrc", "rtx_device.hpp"),
                           ["rcp_generic", "sqrt_generic", "rcp_fast", "sqrt_fast", "in_safe_range", "rcp_cr", "sqrt_cr", "rcp_sqrt_cr", "normalize_gpu", "clampf",
-                           "minf", "pow32", "u8_sat", "sphere_reject", "sphere_hit", "plane_hit", "shade", "ramp_index", "ansi_distance", "cube_level",
+                           "minf", "pow32", "u8_sat", "sphere_reject", "sphere_hit", "plane_hit", "shade_nn", "div_cr", "ramp_index", "ansi_distance", "cube_level",
                            "cube_value", "palette_grey_value", "ansi256_from_rgb", "dot", "sub", "add", "mulf", "v3"])
     ker = function_ranges(os.path.join(PKG, "csrc", "rtx_kernels.hip"),
                           ["tile_culls", "tile_plane", "plane_invisible", "comes_first", "pixel_fields", "encode_and_store", "test_candidate", "scan_candidates",
@@ -147,7 +147,8 @@ def main():
             stage = body_stage(line)
         elif f == "rtx_device.hpp":
             if in_range(dev, ["pow32"], line): stage = "pow32"
-            elif in_range(dev, ["shade", "clampf", "minf"], line): stage = "normal + shade"
+            elif in_range(dev, ["shade_nn", "clampf", "minf"], line): stage = "normal + shade"
+            elif in_range(dev, ["div_cr"], line): stage = "planes"
             elif in_range(dev, ["sphere_reject"], line): stage = "candidate loop"
             elif in_range(dev, ["sphere_hit"], line): stage = "exact test (sphere_hit)"
             elif in_range(dev, ["ansi_distance", "cube_level", "cube_value", "palette_grey_value", "ansi256_from_rgb", "u8_sat", "ramp_index"], line): stage = "encode + store"
