@@ -51,7 +51,7 @@ struct Terminal { // raw input mode for the lifetime of the object; output proce
     }
 };
 
-enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS };
+enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS, K_MIRRORS };
 
 // Bytes from stdin -> key events.  Escape sequences: CSI A/B/C/D arrows; SS3 P/Q/R/S and CSI 11~..15~ for F1..F5.
 struct KeyReader {
@@ -125,6 +125,7 @@ struct KeyReader {
         case '4': return K_MODE3;
         case '5': return K_MODE4;
         case 'h': case 'H': return K_SHADOWS; // (no reference counterpart: hard shadows on / off, RTX_OPT_SHADOWS)
+        case 'm': case 'M': return K_MIRRORS; // (no reference counterpart: every plane a half mirror or not, rtx_scene_set_reflectivity)
         case 'x': case 'X': case 3 /* ^C in raw mode */: return K_QUIT;
         default: return K_OTHER;
         }
@@ -164,7 +165,7 @@ int main(int argc, char** argv)
     }
     if (keys_only) {
         static const char* const names[] = {"none", "w", "a", "s", "d", "space", "shift", "up", "down", "left", "right", "mode0", "mode1", "mode2", "mode3",
-                                            "mode4", "quit", "eof", "other", "shadows"};
+                                            "mode4", "quit", "eof", "other", "shadows", "mirrors"};
         Terminal term;
         KeyReader keys;
         std::printf("raw %d\n", term.active ? 1 : 0);
@@ -194,7 +195,7 @@ int main(int argc, char** argv)
         scene->Init();
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
         int mode = mode0;
-        bool shadows = false;
+        bool shadows = false, mirrors = false;
         const char hide[] = "\x1b[?25l\x1b[2J"; // hide the cursor, clear (PrintMachine.cpp:120)
         if (write(STDOUT_FILENO, hide, sizeof hide - 1) < 0) return 1;
         PrintMachine::StartPrinter(STDOUT_FILENO, status);
@@ -233,6 +234,10 @@ int main(int argc, char** argv)
                 case K_SHADOWS:
                     shadows = !shadows;
                     rayTracingManager->SetShadows(shadows);
+                    break;
+                case K_MIRRORS:
+                    mirrors = !mirrors;
+                    scene->SetPlaneReflectivity(mirrors ? 0.5f : 0.0f);
                     break;
                 case K_QUIT: case K_EOF: quit = true; break;
                 default: break;

@@ -5,6 +5,7 @@
 // Renders `frames` frames of the reference's start scene and writes the last minimised frame (what
 // the reference's printer thread would fwrite to stdout, PrintMachine.cpp:289-290) to out_file.
 // RTX_SHADOWS=1 in the environment turns hard shadows on (no reference counterpart; read like RTX_DEVICES).
+// RTX_REFLECT=<k> gives every plane reflectivity k (one-bounce mirrors; no reference counterpart; read like RTX_SHADOWS).
 #include "rtx_compat.hpp"
 
 #include <cstdio>
@@ -33,6 +34,8 @@ int main(int argc, char** argv)
         rayTracingManager->SetRenderingMode(mode);
         const char* shadows = std::getenv("RTX_SHADOWS");
         if (shadows && std::atoi(shadows) == 1) rayTracingManager->SetShadows(true);
+        const char* reflect = std::getenv("RTX_REFLECT");
+        if (reflect) scene->SetPlaneReflectivity(std::strtof(reflect, nullptr));
 
         for (int f = 0; f < frames; f++) {
             // Engine3D::Render

@@ -164,6 +164,10 @@ enum rtx_option {
     RTX_OPT_SHADOW_CHECK = 21, /* for checks, not for the frame loop: 0 normal (default); 1 every shadow ray tests every object, no culling (the
                                * brute reference of the culled path); 2 the two-launch path with no occlusion and no self-shadow test, so that
                                * every pixel is lit.  No reference counterpart */
+    RTX_OPT_REFLECT_CHECK = 22, /* for checks, not for the frame loop: 0 normal (default); 1 every secondary ray of the mirror path
+                               * (rtx_scene_set_reflectivity) tests every sphere, no culling (the brute reference of the culled pass); 2 the
+                               * reflection launches even where no object reflects (they then give the bytes of the launches they replace).
+                               * No reference counterpart */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -194,6 +198,10 @@ enum rtx_stat {
                                      * 1024-entry LDS list; every sphere under RTX_OPT_SHADOW_CHECK 1) in the launch pair queued last.  One
                                      * word per context: with launch pairs in flight on several streams it holds one of theirs.  Reading it
                                      * waits for the device */
+    RTX_STAT_REFLECT_FRAMES = 120,  /* launch sets queued on the mirror path (rtx_scene_set_reflectivity): as RTX_STAT_SHADOW_FRAMES */
+    RTX_STAT_REFLECT_LONGEST_LIST = 121, /* the most sphere candidates one workgroup kept for its secondary rays after culling (summed over
+                                     * the refills of its 1024-entry LDS list; every sphere under RTX_OPT_REFLECT_CHECK 1) in the launch set
+                                     * queued last.  One word per context, as RTX_STAT_SHADOW_LONGEST_LIST.  Reading it waits for the device */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -303,6 +311,23 @@ typedef struct rtx_light {
 int rtx_scene_set_light(rtx_ctx* ctx, const rtx_light* light);
 /* The light in use.  No reference counterpart (RayTracing.cu:132,143-157). */
 int rtx_scene_get_light(const rtx_ctx* ctx, rtx_light* out);
+/* One-bounce mirror reflections: the reflectivity k in [0, 1] of objects first .. first+n-1 (creation indices, spheres and planes
+ * alike: what the add calls return).  Every new object has k = 0; rtx_scene_clear forgets them.  A shaded pixel (the character
+ * modes; RGB_NORMALS and SDL are unaffected) whose closest object has k > 0 traces one secondary ray, the view ray mirrored
+ * about its normal, from its hit point; its colour becomes minf(255, local * (1 - k) + reflected * k) per component, where
+ * `reflected` is the Blinn-Phong colour of the secondary ray's closest hit (the object itself excluded; no shadow test and no
+ * further bounce there; black when it hits nothing).  Distance, glyph and normal stay the primary's, so k = 0 gives today's
+ * bytes.  While no object has k > 0 every launch is what it is without this call.  All or nothing: a non-finite k, k < 0,
+ * k > 1 or a range past rtx_scene_count changes nothing and returns RTX_ERR_INVALID_ARGUMENT (on a device group: validated
+ * before any rank is touched, then applied to every rank).  Geometry is unchanged, so sorted copies and cell lists stay valid;
+ * a graph recorded before the call is refused by rtx_graph_launch (re-capture).  The device copies are uploaded by the next
+ * launch that takes the mirror path, which first waits for the whole device (every stream, every logical rank on it): a change,
+ * a scene edit or a new direction sort costs one such wait.  A graph capture cannot do that upload, so recording right after
+ * such a change fails with RTX_ERR_INVALID_ARGUMENT ("render once before capturing").  No reference counterpart
+ * (RayTracing.cu:635 plans a recursive RayTrace). */
+int rtx_scene_set_reflectivity(rtx_ctx* ctx, unsigned first, size_t n, const float* k);
+/* The reflectivity of object `index`.  No reference counterpart. */
+int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);
 /* Bulk append: n records of 7 floats (cx cy cz r R G B). */
 int rtx_scene_add_spheres(rtx_ctx* ctx, size_t n, const float* xyzr_rgb);
 unsigned rtx_scene_count(const rtx_ctx* ctx);

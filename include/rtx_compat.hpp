@@ -361,6 +361,7 @@ public:
     {
         ctx();
         check(rtx_scene_clear(ctx()), "rtx_scene_clear");
+        m_planes.clear();
         // the reference's start scene, Scene3D.cpp:28-33
         CreateSphere(7.0f, MyMath::Vector3(0.0f, 10.0f, 20.0f), MyMath::Vector3(255.0f, 1.0f, 1.0f));
         CreateSphere(6.0f, MyMath::Vector3(5.0f, 10.0f, 20.0f), MyMath::Vector3(1.0f, 255.0f, 1.0f));
@@ -370,7 +371,11 @@ public:
         CreatePlane(MyMath::Vector3(0.0f, -3.0f, 30.0f), MyMath::Vector3(0.0f, 1.0f, 0.0f), MyMath::Vector3(100.0f, 100.0f, 100.0f), 10, 20);
     }
     void Update(const long double) {} // the GPU updates objects (Scene3D.cpp:89-92)
-    void CleanUp() { check(rtx_scene_clear(ctx()), "rtx_scene_clear"); }
+    void CleanUp()
+    {
+        check(rtx_scene_clear(ctx()), "rtx_scene_clear");
+        m_planes.clear();
+    }
 
     void CreatePlane(const MyMath::Vector3& middlePos, const MyMath::Vector3& normal, const MyMath::Vector3& color,
                      const float width, const float height)
@@ -378,12 +383,26 @@ public:
         const float p[3] = {middlePos.x, middlePos.y, middlePos.z}, n[3] = {normal.x, normal.y, normal.z}, c[3] = {color.x, color.y, color.z};
         const int idx = rtx_scene_add_plane(ctx(), p, n, c, width, height);
         if (idx < 0) check(-idx, "rtx_scene_add_plane");
+        m_planes.push_back((unsigned)idx); // (creation indices only grow)
     }
     void CreateSphere(const float radius, const MyMath::Vector3& middlePos, const MyMath::Vector3& color)
     {
         const float p[3] = {middlePos.x, middlePos.y, middlePos.z}, c[3] = {color.x, color.y, color.z};
         const int idx = rtx_scene_add_sphere(ctx(), p, radius, c);
         if (idx < 0) check(-idx, "rtx_scene_add_sphere");
+    }
+    // Extensions, no reference counterpart (RayTracing.cu:635 plans a recursive RayTrace): one-bounce mirrors, k in [0, 1] for the
+    // object of creation index `index` (rtx_scene_set_reflectivity), or for every plane this scene created -- one call over the
+    // range they span, the values of the objects between them read back from the host copy (rtx_scene_get_reflectivity).
+    void SetReflectivity(const unsigned index, const float k) { check(rtx_scene_set_reflectivity(ctx(), index, 1, &k), "rtx_scene_set_reflectivity"); }
+    void SetPlaneReflectivity(const float k)
+    {
+        if (m_planes.empty()) return;
+        const unsigned first = m_planes.front(), last = m_planes.back();
+        std::vector<float> v(last - first + 1);
+        for (unsigned i = first; i <= last; i++) check(rtx_scene_get_reflectivity(ctx(), i, &v[i - first]), "rtx_scene_get_reflectivity");
+        for (const unsigned i : m_planes) v[i - first] = k;
+        check(rtx_scene_set_reflectivity(ctx(), first, v.size(), v.data()), "rtx_scene_set_reflectivity");
     }
     DeviceObjectArray<Object3D*> GetObjects()
     {
@@ -397,6 +416,7 @@ public:
 private:
     static rtx_ctx* ctx() { return rtx_compat::Device::get(PrintMachine::GetWidth(), PrintMachine::GetHeight()); }
     static void check(int status, const char* what) { rtx_compat::check(ctx(), status, what); }
+    std::vector<unsigned> m_planes; // creation indices of the planes CreatePlane added since the last clear
 };
 
 // ---------------------------------------------------------------------------------------------

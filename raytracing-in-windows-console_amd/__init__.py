@@ -34,6 +34,8 @@ OPT_UPDATE_HOST_WRITE = 19
 STAT_UPDATE_HOST_WRITES = 117
 OPT_SHADOWS, OPT_SHADOW_CHECK = 20, 21
 STAT_SHADOW_FRAMES, STAT_SHADOW_LONGEST_LIST = 118, 119
+OPT_REFLECT_CHECK = 22
+STAT_REFLECT_FRAMES, STAT_REFLECT_LONGEST_LIST = 120, 121
 STAT_GROUP_DIRECT_UPDATES = 116
 STAT_MINIMIZE_FALLBACKS = 115
 STAT_GROUP_SIZE, STAT_GROUP_EXCHANGE, STAT_GROUP_GATHERS, STAT_GROUP_BYTES = 110, 111, 112, 113
@@ -96,6 +98,8 @@ _SIGNATURES = [
     ("rtx_scene_get_object", C.c_int, [_P, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     ("rtx_scene_set_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_get_light", C.c_int, [_P, C.POINTER(Light)]),
+    ("rtx_scene_set_reflectivity", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
+    ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
     ("rtx_render", C.c_int, [_P, C.POINTER(Params), C.c_int]),
     ("rtx_render_rows", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, C.c_uint]),
     ("rtx_submit_frames", C.c_int, [_P, C.c_size_t, C.POINTER(Params), C.c_int, C.POINTER(_P), C.POINTER(_P)]),
@@ -345,6 +349,16 @@ class Context:
         out = Light()
         self._check(lib().rtx_scene_get_light(self._h, C.byref(out)))
         return out
+
+    def set_reflectivity(self, first, k):
+        """rtx_scene_set_reflectivity: k (a number or a sequence) for objects first, first+1, ... (creation indices)."""
+        v = np.ascontiguousarray(np.atleast_1d(np.asarray(k, dtype=np.float32)))
+        self._check(lib().rtx_scene_set_reflectivity(self._h, first, v.size, v.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def get_reflectivity(self, index):
+        out = C.c_float()
+        self._check(lib().rtx_scene_get_reflectivity(self._h, index, C.byref(out)))
+        return out.value
 
     # -- render
     def render(self, params, mode):

@@ -270,6 +270,21 @@ struct rtx_ctx {
     std::vector<HitScratch> hit_scratch;
     std::vector<void*> hit_retired;
 
+    // one-bounce mirrors (rtx_scene_set_reflectivity): k by creation index, and how many objects have k > 0 (the path is taken
+    // while that is not 0, or under RTX_OPT_REFLECT_CHECK 2).  Then rtx_render_rows traces the closest hits, rtx_reflect_hit the
+    // secondary hits of the reflective pixels and rtx_reflect_shade shades and blends: 16 bytes per pixel of the stream's hit
+    // buffer.  The device copies -- spheres by index and by sorted position (rtx_sort_scene keeps h_sorted_idx), planes by index
+    // -- are uploaded at the next launch on the path after a change (refl_dirty); refl_gen tells recorded graphs they are stale.
+    std::vector<float> refl;
+    uint32_t n_reflective = 0;
+    bool refl_dirty = true;
+    uint64_t refl_gen = 0;
+    DeviceArray d_refl_sph, d_refl_sorted, d_refl_pl;
+    std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
+    int64_t opt_reflect_check = 0;
+    uint64_t stat_reflect_frames = 0;
+    uint32_t* d_reflect_longest = nullptr; // the longest candidate list of the last launch set on the path (one word)
+
     std::string error;
     const char* last_kernel = "";
 };

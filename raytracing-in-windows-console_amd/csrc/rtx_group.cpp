@@ -487,6 +487,16 @@ int scene_set_light(rtx_ctx* root, const rtx_light* light)
     return RTX_OK;
 }
 
+int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k)
+{
+    rtx_group* g = root->group;
+    for (int r = 1; r < g->n; r++) {
+        const int rc = rtx_scene_set_reflectivity(g->member[(size_t)r], first, n, k);
+        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    return RTX_OK;
+}
+
 int set_option(rtx_ctx* root, int option, int64_t value)
 {
     rtx_group* g = root->group;

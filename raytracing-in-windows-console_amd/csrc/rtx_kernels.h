@@ -130,6 +130,18 @@ struct ShadowArgs {
     uint32_t* longest;  // atomicMax of the longest occluder list a workgroup held, or nullptr
 };
 
+// The mirror path (rtx_scene_set_reflectivity): its second launch (rtx_reflect_hit) traces one secondary ray per reflective pixel
+// from the first launch's closest hits and writes its closest hit; its third (rtx_reflect_shade) shades as rtx_shadow_shade and
+// blends the secondary hit's colour in.
+struct ReflectArgs {
+    const uint2* hits;   // the first launch's closest hits (kOutHit), row row0 of the launch at hits[0]
+    uint2* hits2;        // (t, object) of each reflective pixel's secondary ray, laid out as `hits`; other pixels' entries are not written
+    const float* k_sph;  // reflectivity of the spheres, by the position the trace kernels index them by (KArgs::sph_geom's order)
+    const float* k_pl;   // ... of the planes, by plane index
+    uint32_t brute;      // 1: no culling, every sphere tested (RTX_OPT_REFLECT_CHECK 1)
+    uint32_t* longest;   // atomicMax of the longest candidate list a workgroup held, or nullptr
+};
+
 // Arguments of rtx_expand_words (compact pixel words -> records), by value.
 constexpr int kMaxExpandSeg = 16;
 constexpr int kExpandPixels = 1024;             // pixels per workgroup
@@ -154,6 +166,10 @@ const char* rtx_k_launch_trace_batch(const KArgs* a, const KBatch* kb, int mode,
 // a->compact == 3 asks rtx_k_launch_trace for the closest hits alone (8 bytes per pixel into a->out, whatever the mode); this
 // shades them into a->out as `mode`'s records / words / values (a->compact 0 / 1 / 2).  Character modes only.
 const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* s, int mode, void* stream, int* hip_error);
+// The mirror path's second and third launches: secondary hits of every reflective pixel into r->hits2, then the shading (with
+// s's shadow test) and the blend into a->out as for rtx_k_launch_shadow.  Character modes only.
+const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream, int* hip_error);
+const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* s, const ReflectArgs* r, int mode, void* stream, int* hip_error);
 int rtx_k_launch_bin_cells(const KArgs* a, unsigned splits, void* stream);
 int rtx_k_launch_zero(void* p, size_t bytes, void* stream);
 // tile_cost[n_tiles] (grid gx wide) -> tile_order[n_tiles], heaviest first, dealt over n_cu compute units so that the

@@ -18,6 +18,7 @@
 #include "rtx_device.hpp"
 #include "rtx_kernels.h"
 #include "rtx_records.hpp"
+#include "rtx_reflect.hpp"
 #include "rtx_shadow.hpp"
 
 // The experiment build's hooks (ABL, STAMP, RTX_X_*): empty / constant false in the product build.
@@ -1186,6 +1187,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
     }
 }
 
+#include "rtx_reflect_kernels.inc"
 #include "rtx_shadow_kernels.inc"
 
 } // namespace rtx
@@ -1365,6 +1367,53 @@ extern "C" const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* sh,
     default: return nullptr;
     }
 #undef RTX_LAUNCH_SHADOW
+    *hip_error = (int)hipGetLastError();
+    return name;
+}
+
+extern "C" const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u) return nullptr;
+    const dim3 grid((a->W + kReflectTile - 1u) / kReflectTile, (rows + kReflectTile - 1u) / kReflectTile, 1), block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_reflect_hit, grid, block, 0, stream, *a, *r);
+    *hip_error = (int)hipGetLastError();
+    return "rtx_reflect_hit";
+}
+
+extern "C" const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* sh, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u || a->compact > 2u) return nullptr;
+    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
+    const char* name = nullptr;
+#define RTX_LAUNCH_REFLECT(M)                                                                               \
+    do {                                                                                                    \
+        if (a->compact == 0u) {                                                                             \
+            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutRecords>), grid, block, 0, stream, *a, *sh, *r);   \
+            name = "rtx_reflect_shade<" #M ">";                                                             \
+        } else if (a->compact == 1u) {                                                                      \
+            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutCompact>), grid, block, 0, stream, *a, *sh, *r);   \
+            name = "rtx_reflect_shade<" #M ",compact>";                                                     \
+        } else {                                                                                            \
+            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutValues>), grid, block, 0, stream, *a, *sh, *r);    \
+            name = "rtx_reflect_shade<" #M ",values>";                                                      \
+        }                                                                                                   \
+    } while (0)
+    switch (mode) {
+    case RTX_K_BIT_ASCII: RTX_LAUNCH_REFLECT(RTX_K_BIT_ASCII); break;
+    case RTX_K_BIT_PIXEL: RTX_LAUNCH_REFLECT(RTX_K_BIT_PIXEL); break;
+    case RTX_K_RGB_ASCII: RTX_LAUNCH_REFLECT(RTX_K_RGB_ASCII); break;
+    case RTX_K_RGB_PIXEL: RTX_LAUNCH_REFLECT(RTX_K_RGB_PIXEL); break;
+    default: return nullptr;
+    }
+#undef RTX_LAUNCH_REFLECT
     *hip_error = (int)hipGetLastError();
     return name;
 }

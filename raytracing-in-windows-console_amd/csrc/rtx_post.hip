@@ -691,5 +691,7 @@ int rtx_sort_scene(rtx_ctx* ctx, const float origin[3])
     RTX_HIP(ctx, hipGetLastError());
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the staging vectors go out of scope; other streams may render next)
     ctx->sorted_gen = ctx->scene_gen;
+    ctx->h_sorted_idx.swap(order); // the reflectivities by sorted position follow this order (rtx_render.cpp, upload_reflectivity)
+    ctx->refl_dirty = true;
     return RTX_OK;
 }

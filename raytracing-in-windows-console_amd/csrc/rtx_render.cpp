@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -616,14 +617,9 @@ int hit_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, bool capturing, v
     return RTX_OK;
 }
 
-// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade).
-int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
+// The first launch of the light / shadow and mirror paths: the closest hits of `a` into `hits` (8 bytes per pixel, kOutHit).
+int trace_hits(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, void* hits)
 {
-    const size_t rows = a.row_end - a.row0;
-    void* hits = nullptr;
-    int rc = hit_buffer(ctx, stream, (size_t)a.W * rows * 8u, capturing, &hits);
-    if (rc != RTX_OK) return rc;
-    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     KArgs h = a;
     h.out = (uint8_t*)hits;
     h.out_row_base = a.row0;
@@ -632,7 +628,12 @@ int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStre
     const char* name = rtx_k_launch_trace(&h, mode, cull, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch (closest hits)");
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
+    return RTX_OK;
+}
+
+// What the shading launch of either path reads of the light and the shadow options.
+ShadowArgs shadow_args(const rtx_ctx* ctx, const void* hits)
+{
     ShadowArgs sa;
     std::memset(&sa, 0, sizeof sa);
     sa.hits = (const uint2*)hits;
@@ -642,11 +643,104 @@ int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStre
     sa.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
     sa.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
     sa.longest = ctx->d_shadow_longest;
-    name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
+    return sa;
+}
+
+// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade).
+int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
+{
+    const size_t rows = a.row_end - a.row0;
+    void* hits = nullptr;
+    int rc = hit_buffer(ctx, stream, (size_t)a.W * rows * 8u, capturing, &hits);
+    if (rc != RTX_OK) return rc;
+    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
+    if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
+    const ShadowArgs sa = shadow_args(ctx, hits);
+    int herr = 0;
+    const char* name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow pass: invalid rendering mode or output form");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow shading kernel launch");
     ctx->last_kernel = name;
     ctx->stat_shadow_frames++;
+    return RTX_OK;
+}
+
+// ---- the mirror path (rtx_scene_set_reflectivity)
+
+// Does a launch of `mode` take the three-launch mirror path?  Only while some object reflects (an O(1) count), or under
+// RTX_OPT_REFLECT_CHECK 2; it takes precedence over shadow_path and runs the shadow test itself.  The character modes only.
+bool reflect_path(const rtx_ctx* ctx, int mode)
+{
+    if (mode < RTX_BIT_ASCII || mode > RTX_RGB_PIXEL) return false;
+    return ctx->n_reflective != 0 || ctx->opt_reflect_check == 2;
+}
+
+// The device copies of the reflectivities after a change, a scene edit or a new sort: spheres by index and by sorted position,
+// planes by index (at least one entry each, so that the kernels always get an array).  Waits for the frames in flight first.
+int upload_reflectivity(rtx_ctx* ctx)
+{
+    const size_t ns = ctx->ns, np = ctx->np;
+    std::vector<float> ks(ns > 0 ? ns : 1, 0.0f), kso(ks.size(), 0.0f), kp(np > 0 ? np : 1, 0.0f);
+    for (size_t g = 0; g < ctx->refl.size(); g++) {
+        (ctx->kind_of[g] == 2 ? ks : kp)[ctx->local_of[g]] = ctx->refl[g];
+    }
+    const bool sorted = ctx->h_sorted_idx.size() == ns && ns > 0;
+    for (size_t p = 0; sorted && p < ns; p++) kso[p] = ks[ctx->h_sorted_idx[p]];
+    RTX_HIP(ctx, hipDeviceSynchronize());
+    for (const auto& pr : {std::make_pair(&ctx->d_refl_sph, &ks), std::make_pair(&ctx->d_refl_sorted, &kso), std::make_pair(&ctx->d_refl_pl, &kp)}) {
+        DeviceArray& d = *pr.first;
+        const std::vector<float>& h = *pr.second;
+        if (d.cap < h.size()) {
+            if (d.p) RTX_HIP(ctx, hipFree(d.p));
+            d.p = nullptr;
+            d.cap = 0;
+            RTX_HIP(ctx, hipMalloc(&d.p, h.size() * sizeof(float)));
+            d.cap = h.size();
+        }
+        RTX_HIP(ctx, hipMemcpy(d.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    ctx->refl_dirty = false;
+    return RTX_OK;
+}
+
+// Closest hits (rtx_trace, kOutHit), the secondary hits of the reflective pixels (rtx_reflect_hit), then shading with the shadow
+// test and the blend into a.out (rtx_reflect_shade).  The stream's hit buffer holds both hit arrays: 16 bytes per pixel.
+int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
+{
+    int rc;
+    if (ctx->refl_dirty) {
+        if (capturing) {
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: the reflectivities are not uploaded yet (render once before capturing)");
+        }
+        if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
+    }
+    const size_t px = (size_t)a.W * (a.row_end - a.row0);
+    void* hits = nullptr;
+    if ((rc = hit_buffer(ctx, stream, px * 16u, capturing, &hits)) != RTX_OK) return rc;
+    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
+    if (!ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
+    if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
+    ReflectArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.hits = (const uint2*)hits;
+    ra.hits2 = (uint2*)hits + px;
+    ra.k_sph = (const float*)(a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.p : ctx->d_refl_sph.p);
+    ra.k_pl = (const float*)ctx->d_refl_pl.p;
+    ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
+    ra.longest = ctx->d_reflect_longest;
+    int herr = 0;
+    const char* name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "secondary hit kernel launch");
+    const ShadowArgs sa = shadow_args(ctx, hits);
+    name = rtx_k_launch_reflect_shade(&a, &sa, &ra, mode, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "mirror shading kernel launch");
+    ctx->last_kernel = name;
+    ctx->stat_reflect_frames++;
     return RTX_OK;
 }
 
@@ -934,7 +1028,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
                  hipStream_t stream, unsigned flags, bool* done)
 {
     *done = false;
-    if (shadow_path(ctx, mode)) return RTX_OK; // (two launches per slab)
+    if (shadow_path(ctx, mode) || reflect_path(ctx, mode)) return RTX_OK; // (two or three launches per slab)
     if (n < 2 || n > (size_t)kMaxBatch || mode < RTX_BIT_ASCII || mode >= RTX_SDL || (flags & ~(unsigned)RTX_RENDER_COMPACT) != 0u) return RTX_OK;
     if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt_refine == 1) return RTX_OK;
     for (size_t i = 0; i < n; i++) {
@@ -1115,7 +1209,9 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     rtxplan::DispatchOrder::Decision od;
     if (cull && (rc = dispatch_order_args(ctx, stream, p, c, shape, capturing, static_order, a, &to, &od)) != RTX_OK) return rc;
     if (adapt && (rc = density_feedback_args(ctx, stream, q.view_dense, a)) != RTX_OK) return rc;
-    if (shadow_path(ctx, mode)) {
+    if (reflect_path(ctx, mode)) {
+        if ((rc = launch_reflect_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
+    } else if (shadow_path(ctx, mode)) {
         if ((rc = launch_shadow_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
     } else {
         int herr = 0;
@@ -1292,6 +1388,7 @@ void release_frozen_orders(rtx_ctx* ctx, const std::vector<uint64_t>& ids)
 struct rtx_graph_handle {
     hipGraphExec_t exec = nullptr;
     uint64_t scene_gen = 0;
+    uint64_t refl_gen = 0; // ... and the reflectivities (the mirror path's launches read their device copies)
     std::vector<uint64_t> frozen; // dispatch-order sets its launches read (released by rtx_graph_destroy)
 };
 
@@ -1325,6 +1422,7 @@ int rtx_graph_end(rtx_ctx* ctx, void* stream_v, void** graph_out)
     }
     h->exec = exec;
     h->scene_gen = ctx->scene_gen;
+    h->refl_gen = ctx->refl_gen;
     h->frozen.swap(frozen);
     *graph_out = h;
     return RTX_OK;
@@ -1337,6 +1435,10 @@ int rtx_graph_launch(rtx_ctx* ctx, void* graph, void* stream_v)
     if (h->scene_gen != ctx->scene_gen) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the scene was edited after this graph was recorded (its launches keep the old object "
                                                        "counts and array addresses): re-capture after a scene edit");
+    }
+    if (h->refl_gen != ctx->refl_gen) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the reflectivities changed after this graph was recorded (its launches read "
+                                                       "the device copies, which the next launch replaces): re-capture");
     }
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     RTX_HIP(ctx, hipGraphLaunch(h->exec, stream_v ? (hipStream_t)stream_v : ctx->stream));
