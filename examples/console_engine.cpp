@@ -11,6 +11,7 @@
 //   space, z       m_Keys.Space (up), m_Keys.Shift (down)           (:155-171; a terminal cannot see Shift alone)
 //   arrow keys     Camera3D::AddRot by 25 mouse counts = 0.05 rad   (:209-239)
 //   1..5, F1..F5   RayTracingManager::SetRenderingMode(BIT_ASCII .. RGB_NORMALS)   (:178-197)
+//   p              rtx_pick on the centre cell: object index and distance on a line under the FPS lines (no reference counterpart)
 //   Esc, x         quit                                             (:173-176)
 // Once per second of engine time a random sphere is created, as Engine3D::Run does (Engine3D.cpp:60-69; rand() is
 // never seeded there either).  --lockstep: exactly one key event is consumed per frame (blocking; end of input
@@ -51,7 +52,7 @@ struct Terminal { // raw input mode for the lifetime of the object; output proce
     }
 };
 
-enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS, K_MIRRORS };
+enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS, K_MIRRORS, K_PICK };
 
 // Bytes from stdin -> key events.  Escape sequences: CSI A/B/C/D arrows; SS3 P/Q/R/S and CSI 11~..15~ for F1..F5.
 struct KeyReader {
@@ -126,6 +127,7 @@ struct KeyReader {
         case '5': return K_MODE4;
         case 'h': case 'H': return K_SHADOWS; // (no reference counterpart: hard shadows on / off, RTX_OPT_SHADOWS)
         case 'm': case 'M': return K_MIRRORS; // (no reference counterpart: every plane a half mirror or not, rtx_scene_set_reflectivity)
+        case 'p': case 'P': return K_PICK;    // (no reference counterpart: which object is under the centre cell, rtx_pick)
         case 'x': case 'X': case 3 /* ^C in raw mode */: return K_QUIT;
         default: return K_OTHER;
         }
@@ -165,7 +167,7 @@ int main(int argc, char** argv)
     }
     if (keys_only) {
         static const char* const names[] = {"none", "w", "a", "s", "d", "space", "shift", "up", "down", "left", "right", "mode0", "mode1", "mode2", "mode3",
-                                            "mode4", "quit", "eof", "other", "shadows", "mirrors"};
+                                            "mode4", "quit", "eof", "other", "shadows", "mirrors", "pick"};
         Terminal term;
         KeyReader keys;
         std::printf("raw %d\n", term.active ? 1 : 0);
@@ -195,7 +197,7 @@ int main(int argc, char** argv)
         scene->Init();
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
         int mode = mode0;
-        bool shadows = false, mirrors = false;
+        bool shadows = false, mirrors = false, pick = false;
         const char hide[] = "\x1b[?25l\x1b[2J"; // hide the cursor, clear (PrintMachine.cpp:120)
         if (write(STDOUT_FILENO, hide, sizeof hide - 1) < 0) return 1;
         PrintMachine::StartPrinter(STDOUT_FILENO, status);
@@ -239,6 +241,7 @@ int main(int argc, char** argv)
                     mirrors = !mirrors;
                     scene->SetPlaneReflectivity(mirrors ? 0.5f : 0.0f);
                     break;
+                case K_PICK: pick = true; break;
                 case K_QUIT: case K_EOF: quit = true; break;
                 default: break;
                 }
@@ -279,6 +282,26 @@ int main(int argc, char** argv)
                 std::fflush(trace);
             }
             if (lockstep) PrintMachine::WaitPrinted();
+            if (pick) { // the object under the centre cell and its distance, on a status line of its own below the two FPS lines
+                pick = false;
+                const rtx_params rp = rtx_compat::to_rtx_params(params);
+                {
+                    rtx_ray_hit hit;
+                    rtx_ctx* ctx = rtx_compat::Device::get(PrintMachine::GetWidth(), PrintMachine::GetHeight());
+                    char line[160];
+                    int n;
+                    if (rtx_pick(ctx, &rp, (params.x - 1) / 2, params.y / 2, &hit) != RTX_OK) {
+                        n = std::snprintf(line, sizeof line, "\x1b[%zu;1H\x1b[mPick: %s\x1b[K", (size_t)params.y + 3, rtx_last_error(ctx));
+                    } else if (hit.index == RTX_NO_OBJECT) {
+                        n = std::snprintf(line, sizeof line, "\x1b[%zu;1H\x1b[mPick: nothing under the centre cell\x1b[K", (size_t)params.y + 3);
+                    } else {
+                        n = std::snprintf(line, sizeof line, "\x1b[%zu;1H\x1b[mPick: object %u at distance %g\x1b[K", (size_t)params.y + 3, hit.index, (double)hit.t);
+                    }
+                    if (n >= (int)sizeof line) n = (int)sizeof line - 1;
+                    PrintMachine::WaitPrinted(); // (the printer thread owns the terminal while a frame is going out)
+                    if (n > 0 && write(STDOUT_FILENO, line, (size_t)n) < 0) return 1;
+                }
+            }
 
             if (fpsTimer >= 1.0) { // Engine3D.cpp:60-69
                 if (spawn) {

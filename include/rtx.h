@@ -168,6 +168,11 @@ enum rtx_option {
                                * (rtx_scene_set_reflectivity) tests every sphere, no culling (the brute reference of the culled pass); 2 the
                                * reflection launches even where no object reflects (they then give the bytes of the launches they replace).
                                * No reference counterpart */
+    RTX_OPT_QUERY_CHECK = 23, /* for checks, not for production: 0 normal (default): rtx_query_rays walks the world grid; 1 every ray tests
+                               * every object (the brute kernel the grid is checked against).  The same bytes either way.
+                               * No reference counterpart (RayTracingManager.cu:21,46-51) */
+    RTX_OPT_QUERY_LOAD = 24,  /* spheres per cell the world grid of the ray queries aims at, in sixteenths (16 = 1 per cell); 0 = the
+                               * default.  Speed only; takes effect at the next build.  No reference counterpart */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -202,6 +207,20 @@ enum rtx_stat {
     RTX_STAT_REFLECT_LONGEST_LIST = 121, /* the most sphere candidates one workgroup kept for its secondary rays after culling (summed over
                                      * the refills of its 1024-entry LDS list; every sphere under RTX_OPT_REFLECT_CHECK 1) in the launch set
                                      * queued last.  One word per context, as RTX_STAT_SHADOW_LONGEST_LIST.  Reading it waits for the device */
+    RTX_STAT_QUERY_GRID_BUILDS = 122, /* builds of the ray queries' world grid so far: one by the first query after rtx_scene_add_*,
+                                     * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD; none by a query on an unchanged scene */
+    RTX_STAT_QUERY_FALLBACK_RAYS = 123, /* rays of the last rtx_query_rays / rtx_query_rays_host / rtx_pick call that the grid kernel answered by
+                                     * testing every object because they cannot be walked (see rtx_query_rays).  0 after a call under
+                                     * RTX_OPT_QUERY_CHECK 1.  Reading it waits for the device */
+    RTX_STAT_QUERY_LARGE_SPHERES = 124, /* spheres the last build kept outside the cells, in the list every ray tests: those whose box covers
+                                     * more than 64 cells or is not finite */
+    RTX_STAT_QUERY_GRID_CELLS = 125, /* cells of the last build (0: no grid) */
+    RTX_STAT_QUERY_GRID_PAIRS = 126, /* (sphere, cell) pairs the last build listed */
+    RTX_STAT_QUERY_BRUTE = 127,     /* 1 while queries are answered by the brute kernel because the last build found no usable grid: more
+                                     * than 256 large spheres, no finite sphere, or coordinates beyond 2^50 or below 2^-50 */
+    RTX_STAT_QUERY_GRID_GEOMETRY = 128, /* 128 .. 136: the last build's grid, for checks that aim rays at cell faces and corners: the fp32 bits of
+                                     * the low corner x y z, of the cell size x y z, then the cells per axis x y z.  Boundary i of an axis
+                                     * is low + (float)i * size, each operation rounded to fp32 */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -399,6 +418,56 @@ int rtx_graph_begin(rtx_ctx* ctx, void* stream);
 int rtx_graph_end(rtx_ctx* ctx, void* stream, void** graph_out);
 int rtx_graph_launch(rtx_ctx* ctx, void* graph, void* stream);
 void rtx_graph_destroy(rtx_ctx* ctx, void* graph);
+
+/* ---- ray queries: rays of the caller against the scene.  No reference counterpart (RayTracingManager.cu:21 "Do culling, oct-tree,
+ * occlusion" and the empty Culling kernel, :46-51; the reference keeps the mouse's cell, Camera3D.cpp:189-198, and asks nothing with it).
+ *
+ * A ray is o + t d for t >= 0: d is not normalised and t is in units of d, as everywhere in this path (a = Dot(d, d),
+ * RayTracing.cu:90-92).  It is tested with the reference's sphere and plane tests for a ray with its own origin (Sphere.cu:30-68,
+ * so a ray that starts inside a sphere misses it; Plane.cu:38-72).  A hit counts iff t <= tmax: INFINITY means no limit, a NaN
+ * tmax accepts nothing.  `skip` is a creation index (what the rtx_scene_add_* calls return) that is never reported, or
+ * RTX_NO_OBJECT.  32 bytes. */
+typedef struct rtx_ray {
+    float o[3];
+    float tmax;
+    float d[3];
+    unsigned skip;
+} rtx_ray;
+/* The answer.  RTX_QUERY_CLOSEST: the lexicographic minimum of (t, creation index) over the objects hit, index = the creation
+ * index; nothing hit: t = 99999999.f (RayTracing.h:21), index = RTX_NO_OBJECT.  RTX_QUERY_ANY (occlusion): t = 0 and index =
+ * RTX_SOME_OBJECT if any object is hit within tmax, else the no-hit pair; which object stopped the ray is not reported, so the
+ * answer does not depend on any order.  8 bytes. */
+typedef struct rtx_ray_hit {
+    float t;
+    unsigned index;
+} rtx_ray_hit;
+#define RTX_NO_OBJECT 0xffffffffu
+#define RTX_SOME_OBJECT 0xfffffffeu
+enum rtx_query_flags {
+    RTX_QUERY_CLOSEST = 0,
+    RTX_QUERY_ANY = 1
+};
+/* n rays at d_rays -> n answers at d_hits (device memory of the caller, 16- and 8-byte aligned), on `stream` (a hipStream_t; NULL =
+ * the context's), ordered after earlier work on that stream; asynchronous.  Rays walk a uniform grid over the spheres' bounding box,
+ * built on the GPU by the first query after a scene edit or rtx_update_objects (on the context's stream, which it waits for twice;
+ * the caller's stream is made to wait for the build), and test only the spheres listed in the cells they visit, the planes and the
+ * few spheres too large for the cells.  The answer is byte for byte the one of testing every object (RTX_OPT_QUERY_CHECK 1): the
+ * lists are conservative by a proved bound (csrc/rtx_grid.hpp).  Rays the walk is not proved for -- origin or direction not finite,
+ * Dot(d, d) outside [2^-40, 2^40], an origin further from the centre of the spheres' box than three times its largest half-extent
+ * on some axis -- are not an error: they test every object (RTX_STAT_QUERY_FALLBACK_RAYS) and get whatever the tests give for them.
+ * Must not race with scene edits or physics steps, like frames in flight (rtx_submit_frames).  n = 0: RTX_OK, nothing is launched.
+ * NULL pointers with n > 0 or unknown flag bits: RTX_ERR_INVALID_ARGUMENT.  Inside rtx_graph_begin / rtx_graph_end (on the stream
+ * given): refused with RTX_ERR_INVALID_ARGUMENT, because a build allocates and waits.  On a device group the scene is replicated:
+ * the call runs on the root's device alone, not sharded.  No reference counterpart (RayTracingManager.cu:21,46-51). */
+int rtx_query_rays(rtx_ctx* ctx, size_t n, const rtx_ray* d_rays, rtx_ray_hit* d_hits, unsigned flags, void* stream);
+/* The same with host memory: copies the rays in, queries on the context's stream, copies the answers out.  Blocking.
+ * No reference counterpart (RayTracingManager.cu:21,46-51). */
+int rtx_query_rays_host(rtx_ctx* ctx, size_t n, const rtx_ray* rays, rtx_ray_hit* hits, unsigned flags);
+/* Which object is under console cell (col, row) of the frame `params` describes: the primary ray of that cell, formed on the
+ * device by the very expressions the trace kernels use (RayTracing.cu:12-23), queried with tmax = cam_far and RTX_QUERY_CLOSEST.
+ * col >= x - 1 (the newline column) or row >= y: RTX_ERR_INVALID_ARGUMENT.  Blocking.
+ * No reference counterpart (Camera3D.cpp:189-198, Engine3D.cpp:199-239 keep the mouse's cell and do nothing with it). */
+int rtx_pick(rtx_ctx* ctx, const rtx_params* params, size_t col, size_t row, rtx_ray_hit* hit);
 
 int rtx_synchronize(rtx_ctx* ctx);
 

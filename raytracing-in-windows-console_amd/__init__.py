@@ -36,6 +36,13 @@ OPT_SHADOWS, OPT_SHADOW_CHECK = 20, 21
 STAT_SHADOW_FRAMES, STAT_SHADOW_LONGEST_LIST = 118, 119
 OPT_REFLECT_CHECK = 22
 STAT_REFLECT_FRAMES, STAT_REFLECT_LONGEST_LIST = 120, 121
+OPT_QUERY_CHECK, OPT_QUERY_LOAD = 23, 24
+STAT_QUERY_GRID_BUILDS, STAT_QUERY_FALLBACK_RAYS, STAT_QUERY_LARGE_SPHERES = 122, 123, 124
+STAT_QUERY_GRID_CELLS, STAT_QUERY_GRID_PAIRS, STAT_QUERY_BRUTE = 125, 126, 127
+STAT_QUERY_GRID_GEOMETRY = 128
+QUERY_CLOSEST, QUERY_ANY = 0, 1
+NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
+NO_HIT = 99999999.0  # the t of a ray that hits nothing (RayTracing.h:21)
 STAT_GROUP_DIRECT_UPDATES = 116
 STAT_MINIMIZE_FALLBACKS = 115
 STAT_GROUP_SIZE, STAT_GROUP_EXCHANGE, STAT_GROUP_GATHERS, STAT_GROUP_BYTES = 110, 111, 112, 113
@@ -68,6 +75,27 @@ class Light(C.Structure):
     """struct rtx_light: the point light of the shading (the reference's constant light, RayTracing.cu:143-157, by default)."""
     _fields_ = [("pos", C.c_float * 3), ("diffuse_rgb", C.c_float * 3), ("diffuse_power", C.c_float),
                 ("specular_rgb", C.c_float * 3), ("specular_power", C.c_float)]
+
+
+# struct rtx_ray (32 bytes) and struct rtx_ray_hit (8 bytes) as numpy structured types: what Context.query_rays takes and returns
+RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("skip", np.uint32)])
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.uint32)])
+
+
+class RayHit(C.Structure):
+    """struct rtx_ray_hit."""
+    _fields_ = [("t", C.c_float), ("index", C.c_uint)]
+
+
+def make_rays(origins, directions, tmax=np.inf, skip=NO_OBJECT):
+    """An array of RAY_DTYPE from (n, 3) origins and directions; tmax and skip are scalars or length-n sequences."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    rays = np.zeros(o.shape[0], dtype=RAY_DTYPE)
+    rays["o"] = o
+    rays["d"] = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+    rays["tmax"] = tmax
+    rays["skip"] = skip
+    return rays
 
 
 def make_light(pos=(1.0, 50.0, 0.0), diffuse_rgb=(1.0, 1.0, 1.0), diffuse_power=2000.0, specular_rgb=(1.0, 1.0, 1.0), specular_power=3000.0):
@@ -110,6 +138,9 @@ _SIGNATURES = [
     ("rtx_graph_end", C.c_int, [_P, _P, C.POINTER(_P)]),
     ("rtx_graph_launch", C.c_int, [_P, _P, _P]),
     ("rtx_graph_destroy", None, [_P, _P]),
+    ("rtx_query_rays", C.c_int, [_P, C.c_size_t, _P, _P, C.c_uint, _P]),
+    ("rtx_query_rays_host", C.c_int, [_P, C.c_size_t, _P, _P, C.c_uint]),
+    ("rtx_pick", C.c_int, [_P, C.POINTER(Params), C.c_size_t, C.c_size_t, C.POINTER(RayHit)]),
     ("rtx_synchronize", C.c_int, [_P]),
     ("rtx_frame_device_ptr", _P, [_P]),
     ("rtx_frame_capacity", C.c_size_t, [_P]),
@@ -359,6 +390,25 @@ class Context:
         out = C.c_float()
         self._check(lib().rtx_scene_get_reflectivity(self._h, index, C.byref(out)))
         return out.value
+
+    # -- ray queries
+    def query_rays(self, rays, flags=QUERY_CLOSEST):
+        """rtx_query_rays_host: an array of RAY_DTYPE (make_rays) -> an array of RAY_HIT_DTYPE.  Blocking."""
+        r = np.ascontiguousarray(rays, dtype=RAY_DTYPE)
+        hits = np.empty(r.shape[0], dtype=RAY_HIT_DTYPE)
+        self._check(lib().rtx_query_rays_host(self._h, r.shape[0], r.ctypes.data if r.shape[0] else None,
+                                              hits.ctypes.data if r.shape[0] else None, flags))
+        return hits
+
+    def query_rays_device(self, n, d_rays, d_hits, flags=QUERY_CLOSEST, stream=None):
+        """rtx_query_rays: device pointers (e.g. torch tensors' data_ptr(): n x 32 bytes of rays, n x 8 bytes of answers).  Asynchronous."""
+        self._check(lib().rtx_query_rays(self._h, n, d_rays, d_hits, flags, stream))
+
+    def pick(self, params, col, row):
+        """rtx_pick: (t, creation index) of the object under console cell (col, row); index NO_OBJECT on the background."""
+        out = RayHit()
+        self._check(lib().rtx_pick(self._h, C.byref(params), col, row, C.byref(out)))
+        return out.t, out.index
 
     # -- render
     def render(self, params, mode):

@@ -285,6 +285,26 @@ struct rtx_ctx {
     uint64_t stat_reflect_frames = 0;
     uint32_t* d_reflect_longest = nullptr; // the longest candidate list of the last launch set on the path (one word)
 
+    // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
+    // context's stream by the first query after a scene edit or a physics step (qgrid.dirty); queries on other streams wait for
+    // ev_built, and a rebuild waits for the last query (ev_done).
+    struct QueryGrid {
+        rtxgrid::Grid plan;
+        bool dirty = true;            // the scene changed since the last build
+        bool brute = false;           // the last build gave up (more than kLargeCap large spheres): queries test every sphere
+        uint32_t n_cells = 0, n_large = 0, pairs = 0;
+        DeviceArray cell_count, cell_fill, is_large, pair_tmp, list_geom, list_gidx; // (elements: words / bytes / float4)
+        uint32_t* d_large = nullptr;  // kLargeCap sphere indices
+        uint32_t* d_words = nullptr;  // [0] pairs, [1] large spheres, [2] fallback rays of the last call, [4..10] bounds
+        void* d_ray = nullptr;        // rtx_pick's ray and hit (48 bytes)
+        hipEvent_t ev_built = nullptr, ev_done = nullptr;
+        bool query_pending = false;   // ev_done has been recorded since the last build
+    };
+    QueryGrid qgrid;
+    int64_t opt_query_check = 0;
+    int64_t opt_query_load = 0;       // RTX_OPT_QUERY_LOAD: spheres per cell the grid aims at, in 1/16 (0: rtxgrid::kDefaultLoad)
+    uint64_t stat_query_builds = 0;
+
     std::string error;
     const char* last_kernel = "";
 };
@@ -296,6 +316,8 @@ int rtx_hip_fail(rtx_ctx* ctx, hipError_t e, const char* what);
 int rtx_sync_scene(rtx_ctx* ctx);
 void rtx_scene_edited(rtx_ctx* ctx);
 int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip
+void rtx_query_release(rtx_ctx* ctx);                    // rtx_query.cpp: frees the grid (rtx_destroy)
+bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status); // rtx_query.cpp: the RTX_STAT_QUERY_* values
 // the zero-fill bookkeeping of the context's own frame buffer for a frame of `mode` whose records something other than
 // rtx_render_rows is about to write there (a group's gathered slabs, its expanded words), on the context's stream
 extern "C" int rtx_frame_zero_semantics(rtx_ctx* ctx, int mode, uint64_t W, uint64_t H, unsigned flags); // (hidden: not part of the ABI)

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rtx_grid.hpp"
+
 // Kernel-side mode numbers = enum RenderingMode (RayTracingManager.h:21).
 enum {
     RTX_K_BIT_ASCII = 0,
@@ -142,6 +144,47 @@ struct ReflectArgs {
     uint32_t* longest;   // atomicMax of the longest candidate list a workgroup held, or nullptr
 };
 
+// Ray queries (rtx_query_rays): n rays of the caller against the scene arrays in creation order (spheres are known by sphere
+// index here, not by the direction-sorted position the trace kernels use), through the world grid or against every sphere.
+struct QueryArgs {
+    const float4* rays;       // two float4 per ray: o.xyz tmax | d.xyz skip
+    uint2* hits;              // t bits, creation index
+    uint32_t n;
+    uint32_t any;             // RTX_QUERY_ANY
+    const float4* sph_geom;   // cx cy cz r, by sphere index
+    const float4* sph_od;     // .w: creation index
+    const float4* pl_a;
+    const float4* pl_b;
+    const float4* pl_od;
+    uint32_t ns, np;
+    rtxgrid::Grid grid;
+    const uint32_t* cell_start; // cells + 1 offsets into the two arrays below
+    const float4* list_geom;    // per (cell, sphere) pair, grouped by cell, ascending sphere index within a cell: the sphere's geometry ...
+    const uint32_t* list_gidx;  // ... and its creation index
+    const uint32_t* large;      // sphere indices every ray tests (ascending)
+    uint32_t n_large;
+    uint32_t* fallback;         // rays of the launch that tested every sphere because they could not be walked (atomicAdd)
+};
+
+// The grid's build (rtx_grid_* kernels), in launch order: bounds -> [host: rtxgrid::plan_grid] -> count -> scan -> [host: allocate the
+// pair arrays] -> scatter -> sort.
+struct GridBuildArgs {
+    const float4* sph_geom;
+    const float4* sph_od;
+    uint32_t ns;
+    rtxgrid::Grid grid;
+    uint32_t n_cells;
+    float* bounds;            // out of bounds: lo xyz, hi xyz of the finite spheres' boxes, then (as uint bits) how many are finite
+    uint32_t* cell_count;     // cells + 1 words: counts, then (scan) exclusive offsets with the pair total in the last word
+    uint32_t* cell_fill;      // cells words, zeroed: scatter's cursors
+    uint8_t* is_large;        // ns flags (count)
+    uint32_t* large;          // kLargeCap sphere indices, ascending (scan)
+    uint32_t* totals;         // [0] pairs, [1] large spheres (scan)
+    uint32_t* pair_tmp;       // scatter: sphere index per pair, any order within a cell
+    float4* list_geom;        // sort
+    uint32_t* list_gidx;
+};
+
 // Arguments of rtx_expand_words (compact pixel words -> records), by value.
 constexpr int kMaxExpandSeg = 16;
 constexpr int kExpandPixels = 1024;             // pixels per workgroup
@@ -170,6 +213,12 @@ const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* s, int mode, v
 // s's shadow test) and the blend into a->out as for rtx_k_launch_shadow.  Character modes only.
 const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream, int* hip_error);
 const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* s, const ReflectArgs* r, int mode, void* stream, int* hip_error);
+// kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
+int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
+// step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort
+int rtx_k_launch_grid_build(const GridBuildArgs* b, int step, void* stream);
+// the primary ray of cell (col, row) of the frame a describes, as the trace kernels form it, with tmax = a->far and no skip: one rtx_ray at d_ray
+int rtx_k_launch_pick_ray(const KArgs* a, uint32_t col, uint32_t row, void* d_ray, void* stream);
 int rtx_k_launch_bin_cells(const KArgs* a, unsigned splits, void* stream);
 int rtx_k_launch_zero(void* p, size_t bytes, void* stream);
 // tile_cost[n_tiles] (grid gx wide) -> tile_order[n_tiles], heaviest first, dealt over n_cu compute units so that the

@@ -1189,6 +1189,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 
 #include "rtx_reflect_kernels.inc"
 #include "rtx_shadow_kernels.inc"
+#include "rtx_query_kernels.inc"
 
 } // namespace rtx
 
@@ -1416,6 +1417,44 @@ extern "C" const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowAr
 #undef RTX_LAUNCH_REFLECT
     *hip_error = (int)hipGetLastError();
     return name;
+}
+
+extern "C" int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream_v)
+{
+    if (q->n == 0u) return 0;
+    const dim3 grid((q->n + (uint32_t)rtx::kThreads - 1u) / (uint32_t)rtx::kThreads), block(rtx::kThreads);
+    if (kind == 0) {
+        hipLaunchKernelGGL(rtx::rtx_query_grid, grid, block, 0, (hipStream_t)stream_v, *q);
+    } else {
+        hipLaunchKernelGGL(rtx::rtx_query_brute, grid, block, 0, (hipStream_t)stream_v, *q);
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int rtx_k_launch_grid_build(const GridBuildArgs* b, int step, void* stream_v)
+{
+    hipStream_t stream = (hipStream_t)stream_v;
+    const dim3 per_sphere((b->ns + (uint32_t)rtx::kThreads - 1u) / (uint32_t)rtx::kThreads), block(rtx::kThreads);
+    switch (step) {
+    case 0: hipLaunchKernelGGL(rtx::rtx_grid_bounds, dim3(1), block, 0, stream, *b); break;
+    case 1: hipLaunchKernelGGL(rtx::rtx_grid_count, per_sphere, block, 0, stream, *b); break;
+    case 2: hipLaunchKernelGGL(rtx::rtx_grid_scan, dim3(1), dim3(rtx::kScanThreads), 0, stream, *b); break;
+    case 3: hipLaunchKernelGGL(rtx::rtx_grid_scatter, per_sphere, block, 0, stream, *b); break;
+    case 4: {
+        uint32_t blocks = (b->n_cells + 3u) / 4u;
+        if (blocks > 4096u) blocks = 4096u;
+        hipLaunchKernelGGL(rtx::rtx_grid_sort, dim3(blocks), block, 0, stream, *b);
+        break;
+    }
+    default: return (int)hipErrorInvalidValue;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int rtx_k_launch_pick_ray(const KArgs* a, uint32_t col, uint32_t row, void* d_ray, void* stream_v)
+{
+    hipLaunchKernelGGL(rtx::rtx_pick_ray, dim3(1), dim3(1), 0, (hipStream_t)stream_v, *a, col, row, (float4*)d_ray);
+    return (int)hipGetLastError();
 }
 
 extern "C" int rtx_k_launch_bin_cells(const KArgs* a, unsigned splits, void* stream_v)
