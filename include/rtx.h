@@ -173,6 +173,10 @@ enum rtx_option {
                                * No reference counterpart (RayTracingManager.cu:21,46-51) */
     RTX_OPT_QUERY_LOAD = 24,  /* spheres per cell the world grid of the ray queries aims at, in sixteenths (16 = 1 per cell); 0 = the
                                * default.  Speed only; takes effect at the next build.  No reference counterpart */
+    RTX_OPT_LIGHTS_CHECK = 25, /* for checks, not for the frame loop: 0 normal (default): a set of one light (rtx_scene_set_lights) launches
+                               * exactly what rtx_scene_set_light launches; 1 the several-lights kernels (rtx_lights_shade,
+                               * rtx_lights_reflect_shade) are launched even for a set of one light (they then give the bytes of the
+                               * launches they replace).  No reference counterpart (RayTracing.cu:132,143-157) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -221,6 +225,8 @@ enum rtx_stat {
     RTX_STAT_QUERY_GRID_GEOMETRY = 128, /* 128 .. 136: the last build's grid, for checks that aim rays at cell faces and corners: the fp32 bits of
                                      * the low corner x y z, of the cell size x y z, then the cells per axis x y z.  Boundary i of an axis
                                      * is low + (float)i * size, each operation rounded to fp32 */
+    RTX_STAT_LIGHTS = 137,          /* lights in the set (rtx_scene_set_lights): 1 .. RTX_MAX_LIGHTS.  No reference counterpart
+                                     * (RayTracing.cu:132,143-157) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -330,6 +336,25 @@ typedef struct rtx_light {
 int rtx_scene_set_light(rtx_ctx* ctx, const rtx_light* light);
 /* The light in use.  No reference counterpart (RayTracing.cu:132,143-157). */
 int rtx_scene_get_light(const rtx_ctx* ctx, rtx_light* out);
+/* Several point lights.  rtx_scene_set_lights replaces the whole set with the n lights given, n in [1, RTX_MAX_LIGHTS], each
+ * validated as rtx_scene_set_light validates its one.  All or nothing: n == 0, n > RTX_MAX_LIGHTS, lights == NULL or one bad
+ * light changes nothing and returns RTX_ERR_INVALID_ARGUMENT (on a device group: validated before any rank is touched, then
+ * applied to every rank).  The colour of a visible pixel (the character modes; RGB_NORMALS and SDL are unaffected) is the
+ * reference's expression with the per-light terms summed in the order given: res = 0.2f * od; for each light
+ * res = (res + diffuse_i * od) + specular_i * 1.0f; then res * 255.0f and minf(255.0f, .), every operation rounded to fp32 -- for
+ * one light the expression of rtx_scene_set_light, operation for operation.  With RTX_OPT_SHADOWS each light gets the shadow test
+ * on its own (a light the pixel is shadowed from enters with both powers 0), and one walk of the sphere array per 16 x 16 tile
+ * serves all lights.  Mirrors shade their secondary hit with all lights.  Distance, glyph and normal do not depend on lights.  A set
+ * of one light launches exactly what rtx_scene_set_light launches; a set of two or more takes the closest-hit launch and then
+ * rtx_lights_shade (rtx_lights_reflect_shade on the mirror path), which receives the set by value in its arguments: a recorded
+ * graph keeps the set it was recorded with, launches queued afterwards see a change.  rtx_scene_set_light(ctx, L) means
+ * rtx_scene_set_lights(ctx, 1, L), and rtx_scene_get_light returns light 0.  Context state like the one light: rtx_scene_clear
+ * leaves the set alone.  No reference counterpart (RayTracing.cu:132,143-157). */
+#define RTX_MAX_LIGHTS 8
+int rtx_scene_set_lights(rtx_ctx* ctx, size_t n, const rtx_light* lights);
+/* The set in use: writes min(capacity, n) lights to out (which may be NULL when capacity is 0) and always *n_out = n.
+ * No reference counterpart (RayTracing.cu:132,143-157). */
+int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, size_t* n_out);
 /* One-bounce mirror reflections: the reflectivity k in [0, 1] of objects first .. first+n-1 (creation indices, spheres and planes
  * alike: what the add calls return).  Every new object has k = 0; rtx_scene_clear forgets them.  A shaded pixel (the character
  * modes; RGB_NORMALS and SDL are unaffected) whose closest object has k > 0 traces one secondary ray, the view ray mirrored

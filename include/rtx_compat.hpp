@@ -548,6 +548,7 @@ public:
     // Extensions, no reference counterpart (its light is a constant, RayTracing.cu:132,143-157): the point light (nullptr: the
     // reference's) and hard shadows (RTX_OPT_SHADOWS).
     void SetLight(const rtx_light* light) { rtx_compat::check(m_ctx, rtx_scene_set_light(m_ctx, light), "rtx_scene_set_light"); }
+    void SetLights(const rtx_light* lights, const size_t n) { rtx_compat::check(m_ctx, rtx_scene_set_lights(m_ctx, n, lights), "rtx_scene_set_lights"); }
     void SetShadows(const bool on) { rtx_compat::check(m_ctx, rtx_set_option(m_ctx, RTX_OPT_SHADOWS, on ? 1 : 0), "rtx_set_option(RTX_OPT_SHADOWS)"); }
 
 private:

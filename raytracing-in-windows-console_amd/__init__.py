@@ -40,6 +40,9 @@ OPT_QUERY_CHECK, OPT_QUERY_LOAD = 23, 24
 STAT_QUERY_GRID_BUILDS, STAT_QUERY_FALLBACK_RAYS, STAT_QUERY_LARGE_SPHERES = 122, 123, 124
 STAT_QUERY_GRID_CELLS, STAT_QUERY_GRID_PAIRS, STAT_QUERY_BRUTE = 125, 126, 127
 STAT_QUERY_GRID_GEOMETRY = 128
+OPT_LIGHTS_CHECK = 25
+STAT_LIGHTS = 137
+MAX_LIGHTS = 8
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
 NO_HIT = 99999999.0  # the t of a ray that hits nothing (RayTracing.h:21)
@@ -126,6 +129,8 @@ _SIGNATURES = [
     ("rtx_scene_get_object", C.c_int, [_P, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
     ("rtx_scene_set_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_get_light", C.c_int, [_P, C.POINTER(Light)]),
+    ("rtx_scene_set_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light)]),
+    ("rtx_scene_get_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_reflectivity", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
     ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
     ("rtx_render", C.c_int, [_P, C.POINTER(Params), C.c_int]),
@@ -379,6 +384,26 @@ class Context:
     def get_light(self):
         out = Light()
         self._check(lib().rtx_scene_get_light(self._h, C.byref(out)))
+        return out
+
+    def set_lights(self, lights):
+        """rtx_scene_set_lights: the whole set, 1 .. MAX_LIGHTS Light values, in the order they are summed in."""
+        lights = list(lights)
+        arr = (Light * max(len(lights), 1))()
+        for i, l in enumerate(lights):
+            C.memmove(C.byref(arr[i]), C.byref(l), C.sizeof(Light))
+        self._check(lib().rtx_scene_set_lights(self._h, len(lights), arr))
+
+    def get_lights(self):
+        """rtx_scene_get_lights: the set in use, as a list of Light."""
+        arr = (Light * MAX_LIGHTS)()
+        n = C.c_size_t()
+        self._check(lib().rtx_scene_get_lights(self._h, MAX_LIGHTS, arr, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            l = Light()
+            C.memmove(C.byref(l), C.byref(arr[i]), C.sizeof(Light))
+            out.append(l)
         return out
 
     def set_reflectivity(self, first, k):

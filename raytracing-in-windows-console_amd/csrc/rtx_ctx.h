@@ -255,7 +255,11 @@ struct rtx_ctx {
     // rtx_shadow_shade shades from it.  One hit buffer per render stream (launches on one stream are ordered; frames on two
     // streams never share one), allocated at the first two-pass launch on that stream, for at most kMaxHitStreams streams; an
     // outgrown buffer is freed, or kept until the context is destroyed if a recorded graph may still read it.
-    rtx_light light = rtx_reference_light();
+    // the lights (rtx_scene_set_lights; rtx_scene_set_light sets a set of one).  A set of one launches what it always has; two or
+    // more (or RTX_OPT_LIGHTS_CHECK 1) shade with rtx_lights_shade / rtx_lights_reflect_shade, which get the set by value.
+    rtx_light lights[RTX_MAX_LIGHTS] = {rtx_reference_light()};
+    size_t n_lights = 1;
+    int64_t opt_lights_check = 0;
     int64_t opt_shadows = 0;
     int64_t opt_shadow_check = 0;
     uint64_t stat_shadow_frames = 0;

@@ -477,11 +477,11 @@ int scene_set_sphere_motion(rtx_ctx* root, unsigned index, int mover, float spee
     return RTX_OK;
 }
 
-int scene_set_light(rtx_ctx* root, const rtx_light* light)
+int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights)
 {
     rtx_group* g = root->group;
     for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_light(g->member[(size_t)r], light);
+        const int rc = rtx_scene_set_lights(g->member[(size_t)r], n, lights);
         if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
     }
     return RTX_OK;

@@ -26,7 +26,7 @@ int scene_clear(rtx_ctx* root);
 int scene_add_sphere(rtx_ctx* root, const float pos[3], float radius, const float rgb[3]);
 int scene_add_plane(rtx_ctx* root, const float pos[3], const float normal[3], const float rgb[3], float width, float height);
 int scene_set_sphere_motion(rtx_ctx* root, unsigned index, int mover, float speed);
-int scene_set_light(rtx_ctx* root, const rtx_light* light);
+int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights);
 int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k); // (the root has validated and applied it)
 int set_option(rtx_ctx* root, int option, int64_t value);
 int update_objects(rtx_ctx* root, double dt); // every member steps its own replica (the same arithmetic on the same values)

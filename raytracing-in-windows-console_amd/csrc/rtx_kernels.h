@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rtx_grid.hpp"
+#include "rtx_lights.hpp"
 
 // Kernel-side mode numbers = enum RenderingMode (RayTracingManager.h:21).
 enum {
@@ -132,6 +133,16 @@ struct ShadowArgs {
     uint32_t* longest;  // atomicMax of the longest occluder list a workgroup held, or nullptr
 };
 
+// The shading launch for a set of several lights (rtx_lights_shade, rtx_lights_reflect_shade): the set of rtx_scene_set_lights by
+// value (a recorded graph keeps it, nothing is uploaded) and what to test, as ShadowArgs.
+struct LightsArgs {
+    const uint2* hits;       // the first launch's closest hits (kOutHit), row row0 of the launch at hits[0]
+    rtxlights::Block lights; // the count and the lights, in the order given
+    uint32_t test;           // 1: shadow rays to every light; 0: every pixel lit by every light
+    uint32_t brute;          // 1: no culling, every sphere a candidate for every live light (RTX_OPT_SHADOW_CHECK 1)
+    uint32_t* longest;       // atomicMax of the most list entries a workgroup held, or nullptr
+};
+
 // The mirror path (rtx_scene_set_reflectivity): its second launch (rtx_reflect_hit) traces one secondary ray per reflective pixel
 // from the first launch's closest hits and writes its closest hit; its third (rtx_reflect_shade) shades as rtx_shadow_shade and
 // blends the secondary hit's colour in.
@@ -213,6 +224,8 @@ const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* s, int mode, v
 // s's shadow test) and the blend into a->out as for rtx_k_launch_shadow.  Character modes only.
 const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream, int* hip_error);
 const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* s, const ReflectArgs* r, int mode, void* stream, int* hip_error);
+// The same two shading launches for a set of several lights (rtx_scene_set_lights; r == NULL: no mirror).
+const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream, int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

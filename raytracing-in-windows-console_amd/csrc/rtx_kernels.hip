@@ -1189,6 +1189,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 
 #include "rtx_reflect_kernels.inc"
 #include "rtx_shadow_kernels.inc"
+#include "rtx_lights_kernels.inc"
 #include "rtx_query_kernels.inc"
 
 } // namespace rtx
@@ -1415,6 +1416,48 @@ extern "C" const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowAr
     default: return nullptr;
     }
 #undef RTX_LAUNCH_REFLECT
+    *hip_error = (int)hipGetLastError();
+    return name;
+}
+
+extern "C" const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u || a->compact > 2u || l->lights.n == 0u || l->lights.n > (uint32_t)rtxlights::kMaxLights) return nullptr;
+    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
+    const char* name = nullptr;
+#define RTX_LAUNCH_LIGHTS_OUT(M, O, SUFFIX)                                                                      \
+    do {                                                                                                         \
+        if (r != nullptr) {                                                                                      \
+            hipLaunchKernelGGL((rtx_lights_reflect_shade<M, O>), grid, block, 0, stream, *a, *l, *r);            \
+            name = "rtx_lights_reflect_shade<" #M SUFFIX ">";                                                    \
+        } else {                                                                                                 \
+            hipLaunchKernelGGL((rtx_lights_shade<M, O>), grid, block, 0, stream, *a, *l);                        \
+            name = "rtx_lights_shade<" #M SUFFIX ">";                                                            \
+        }                                                                                                        \
+    } while (0)
+#define RTX_LAUNCH_LIGHTS(M)                                        \
+    do {                                                            \
+        if (a->compact == 0u) {                                     \
+            RTX_LAUNCH_LIGHTS_OUT(M, kOutRecords, "");              \
+        } else if (a->compact == 1u) {                              \
+            RTX_LAUNCH_LIGHTS_OUT(M, kOutCompact, ",compact");      \
+        } else {                                                    \
+            RTX_LAUNCH_LIGHTS_OUT(M, kOutValues, ",values");        \
+        }                                                           \
+    } while (0)
+    switch (mode) {
+    case RTX_K_BIT_ASCII: RTX_LAUNCH_LIGHTS(RTX_K_BIT_ASCII); break;
+    case RTX_K_BIT_PIXEL: RTX_LAUNCH_LIGHTS(RTX_K_BIT_PIXEL); break;
+    case RTX_K_RGB_ASCII: RTX_LAUNCH_LIGHTS(RTX_K_RGB_ASCII); break;
+    case RTX_K_RGB_PIXEL: RTX_LAUNCH_LIGHTS(RTX_K_RGB_PIXEL); break;
+    default: return nullptr;
+    }
+#undef RTX_LAUNCH_LIGHTS
+#undef RTX_LAUNCH_LIGHTS_OUT
     *hip_error = (int)hipGetLastError();
     return name;
 }

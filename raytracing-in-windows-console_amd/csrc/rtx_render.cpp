@@ -575,8 +575,11 @@ bool shadow_path(const rtx_ctx* ctx, int mode)
 {
     if (mode < RTX_BIT_ASCII || mode > RTX_RGB_PIXEL) return false;
     const rtx_light ref = rtx_reference_light();
-    return ctx->opt_shadows != 0 || std::memcmp(&ctx->light, &ref, sizeof ref) != 0;
+    return ctx->opt_shadows != 0 || ctx->n_lights != 1 || ctx->opt_lights_check != 0 || std::memcmp(&ctx->lights[0], &ref, sizeof ref) != 0;
 }
+
+// Is the shading launch of either path the several-lights kernel?  A set of one light keeps rtx_shadow_shade / rtx_reflect_shade.
+bool lights_kernels(const rtx_ctx* ctx) { return ctx->n_lights >= 2 || ctx->opt_lights_check != 0; }
 
 // The hit buffer of `stream` with room for `bytes` (rtx_ctx::HitScratch).  At most kMaxHitStreams distinct streams (as
 // rtx_submit_slabs' join events).  An outgrown buffer is freed (hipFree waits for the device, so no queued launch still reads it),
@@ -637,7 +640,7 @@ ShadowArgs shadow_args(const rtx_ctx* ctx, const void* hits)
     ShadowArgs sa;
     std::memset(&sa, 0, sizeof sa);
     sa.hits = (const uint2*)hits;
-    const rtx_light& l = ctx->light;
+    const rtx_light& l = ctx->lights[0];
     sa.light = KLight{l.pos[0], l.pos[1], l.pos[2], l.diffuse_rgb[0], l.diffuse_rgb[1], l.diffuse_rgb[2], l.diffuse_power,
                       l.specular_rgb[0], l.specular_rgb[1], l.specular_rgb[2], l.specular_power};
     sa.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
@@ -646,7 +649,21 @@ ShadowArgs shadow_args(const rtx_ctx* ctx, const void* hits)
     return sa;
 }
 
-// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade).
+// The same for the several-lights kernels: the whole set, packed by value (rtx_lights.hpp).
+LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
+{
+    LightsArgs la;
+    std::memset(&la, 0, sizeof la);
+    la.hits = (const uint2*)hits;
+    rtxlights::pack(ctx->n_lights, ctx->lights, &la.lights); // (the set was validated when it was stored)
+    la.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
+    la.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
+    la.longest = ctx->d_shadow_longest;
+    return la;
+}
+
+// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade, or rtx_lights_shade
+// for a set of several lights).
 int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
 {
     const size_t rows = a.row_end - a.row0;
@@ -656,9 +673,15 @@ int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStre
     if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
-    const ShadowArgs sa = shadow_args(ctx, hits);
     int herr = 0;
-    const char* name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
+    const char* name = nullptr;
+    if (lights_kernels(ctx)) {
+        const LightsArgs la = lights_args(ctx, hits);
+        name = rtx_k_launch_lights_shade(&a, &la, nullptr, mode, stream, &herr);
+    } else {
+        const ShadowArgs sa = shadow_args(ctx, hits);
+        name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
+    }
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow pass: invalid rendering mode or output form");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow shading kernel launch");
     ctx->last_kernel = name;
@@ -735,8 +758,13 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
     const char* name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "secondary hit kernel launch");
-    const ShadowArgs sa = shadow_args(ctx, hits);
-    name = rtx_k_launch_reflect_shade(&a, &sa, &ra, mode, stream, &herr);
+    if (lights_kernels(ctx)) {
+        const LightsArgs la = lights_args(ctx, hits);
+        name = rtx_k_launch_lights_shade(&a, &la, &ra, mode, stream, &herr);
+    } else {
+        const ShadowArgs sa = shadow_args(ctx, hits);
+        name = rtx_k_launch_reflect_shade(&a, &sa, &ra, mode, stream, &herr);
+    }
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "mirror shading kernel launch");
     ctx->last_kernel = name;
