@@ -11,6 +11,7 @@
 //   space, z       m_Keys.Space (up), m_Keys.Shift (down)           (:155-171; a terminal cannot see Shift alone)
 //   arrow keys     Camera3D::AddRot by 25 mouse counts = 0.05 rad   (:209-239)
 //   1..5, F1..F5   RayTracingManager::SetRenderingMode(BIT_ASCII .. RGB_NORMALS)   (:178-197)
+//   b              mirrors see mirrors: reflection depth 1 -> 2 -> 3 -> 4 -> 1, RTX_OPT_REFLECT_DEPTH (no reference counterpart)
 //   p              rtx_pick on the centre cell: object index and distance on a line under the FPS lines (no reference counterpart)
 //   Esc, x         quit                                             (:173-176)
 // Once per second of engine time a random sphere is created, as Engine3D::Run does (Engine3D.cpp:60-69; rand() is
@@ -52,7 +53,7 @@ struct Terminal { // raw input mode for the lifetime of the object; output proce
     }
 };
 
-enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS, K_MIRRORS, K_PICK };
+enum Key { K_NONE, K_W, K_A, K_S, K_D, K_SPACE, K_SHIFT, K_UP, K_DOWN, K_LEFT, K_RIGHT, K_MODE0, K_MODE1, K_MODE2, K_MODE3, K_MODE4, K_QUIT, K_EOF, K_OTHER, K_SHADOWS, K_MIRRORS, K_PICK, K_BOUNCES };
 
 // Bytes from stdin -> key events.  Escape sequences: CSI A/B/C/D arrows; SS3 P/Q/R/S and CSI 11~..15~ for F1..F5.
 struct KeyReader {
@@ -127,6 +128,7 @@ struct KeyReader {
         case '5': return K_MODE4;
         case 'h': case 'H': return K_SHADOWS; // (no reference counterpart: hard shadows on / off, RTX_OPT_SHADOWS)
         case 'm': case 'M': return K_MIRRORS; // (no reference counterpart: every plane a half mirror or not, rtx_scene_set_reflectivity)
+        case 'b': case 'B': return K_BOUNCES; // (no reference counterpart: reflection depth 1 -> 2 -> 3 -> 4 -> 1, RTX_OPT_REFLECT_DEPTH)
         case 'p': case 'P': return K_PICK;    // (no reference counterpart: which object is under the centre cell, rtx_pick)
         case 'x': case 'X': case 3 /* ^C in raw mode */: return K_QUIT;
         default: return K_OTHER;
@@ -167,7 +169,7 @@ int main(int argc, char** argv)
     }
     if (keys_only) {
         static const char* const names[] = {"none", "w", "a", "s", "d", "space", "shift", "up", "down", "left", "right", "mode0", "mode1", "mode2", "mode3",
-                                            "mode4", "quit", "eof", "other", "shadows", "mirrors", "pick"};
+                                            "mode4", "quit", "eof", "other", "shadows", "mirrors", "pick", "bounces"};
         Terminal term;
         KeyReader keys;
         std::printf("raw %d\n", term.active ? 1 : 0);
@@ -198,6 +200,7 @@ int main(int argc, char** argv)
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;
+        int bounces = 1;
         const char hide[] = "\x1b[?25l\x1b[2J"; // hide the cursor, clear (PrintMachine.cpp:120)
         if (write(STDOUT_FILENO, hide, sizeof hide - 1) < 0) return 1;
         PrintMachine::StartPrinter(STDOUT_FILENO, status);
@@ -240,6 +243,10 @@ int main(int argc, char** argv)
                 case K_MIRRORS:
                     mirrors = !mirrors;
                     scene->SetPlaneReflectivity(mirrors ? 0.5f : 0.0f);
+                    break;
+                case K_BOUNCES:
+                    bounces = bounces % RTX_MAX_REFLECT_DEPTH + 1;
+                    scene->SetReflectDepth(bounces);
                     break;
                 case K_PICK: pick = true; break;
                 case K_QUIT: case K_EOF: quit = true; break;

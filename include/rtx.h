@@ -177,6 +177,17 @@ enum rtx_option {
                                * exactly what rtx_scene_set_light launches; 1 the several-lights kernels (rtx_lights_shade,
                                * rtx_lights_reflect_shade) are launched even for a set of one light (they then give the bytes of the
                                * launches they replace).  No reference counterpart (RayTracing.cu:132,143-157) */
+    RTX_OPT_REFLECT_DEPTH = 26, /* mirrors that see mirrors: how many levels of secondary rays a reflective pixel may trace, 1 (default:
+                               * today's one bounce) .. RTX_MAX_REFLECT_DEPTH; the rule is at rtx_scene_set_reflectivity.  Anything else
+                               * returns RTX_ERR_INVALID_ARGUMENT and changes nothing.  Takes effect for launches queued afterwards; a
+                               * recorded graph keeps the depth it was recorded with (the depth travels in the kernel arguments, as the
+                               * light set does).  At depth 1 every launch is what it is without this option; deeper, the mirror path's
+                               * second and third launches are rtx_reflect_chain (every level in one launch) and rtx_lights_chain_shade,
+                               * and the hit buffer holds 8 (depth + 1) bytes per pixel.
+                               * No reference counterpart (RayTracing.cu:635) */
+    RTX_OPT_REFLECT_DEPTH_CHECK = 27, /* for checks, not for the frame loop: 0 normal (default); 1 the chain kernels (rtx_reflect_chain,
+                               * rtx_lights_chain_shade) are launched even at depth 1 (they then give the bytes of the launches they
+                               * replace).  No reference counterpart (RayTracing.cu:635) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -210,7 +221,13 @@ enum rtx_stat {
     RTX_STAT_REFLECT_FRAMES = 120,  /* launch sets queued on the mirror path (rtx_scene_set_reflectivity): as RTX_STAT_SHADOW_FRAMES */
     RTX_STAT_REFLECT_LONGEST_LIST = 121, /* the most sphere candidates one workgroup kept for its secondary rays after culling (summed over
                                      * the refills of its 1024-entry LDS list; every sphere under RTX_OPT_REFLECT_CHECK 1) in the launch set
-                                     * queued last.  One word per context, as RTX_STAT_SHADOW_LONGEST_LIST.  Reading it waits for the device */
+                                     * queued last; with RTX_OPT_REFLECT_DEPTH > 1 the maximum over the levels.  One word per context, as
+                                     * RTX_STAT_SHADOW_LONGEST_LIST.  Reading it waits for the device */
+    RTX_STAT_REFLECT_RAYS = 138,    /* 138 .. 141: the secondary rays of level 1 .. RTX_MAX_REFLECT_DEPTH that the launch set queued last on
+                                     * the chain kernels (RTX_OPT_REFLECT_DEPTH > 1, or RTX_OPT_REFLECT_DEPTH_CHECK 1) traced; all 0 after a
+                                     * set that took the one-bounce kernels.  One 4-word device array per context, as
+                                     * RTX_STAT_REFLECT_LONGEST_LIST.  Reading it waits for the device.
+                                     * No reference counterpart (RayTracing.cu:635) */
     RTX_STAT_QUERY_GRID_BUILDS = 122, /* builds of the ray queries' world grid so far: one by the first query after rtx_scene_add_*,
                                      * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD; none by a query on an unchanged scene */
     RTX_STAT_QUERY_FALLBACK_RAYS = 123, /* rays of the last rtx_query_rays / rtx_query_rays_host / rtx_pick call that the grid kernel answered by
@@ -355,20 +372,32 @@ int rtx_scene_set_lights(rtx_ctx* ctx, size_t n, const rtx_light* lights);
 /* The set in use: writes min(capacity, n) lights to out (which may be NULL when capacity is 0) and always *n_out = n.
  * No reference counterpart (RayTracing.cu:132,143-157). */
 int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, size_t* n_out);
-/* One-bounce mirror reflections: the reflectivity k in [0, 1] of objects first .. first+n-1 (creation indices, spheres and planes
+/* The most levels of secondary rays RTX_OPT_REFLECT_DEPTH takes.  No reference counterpart (RayTracing.cu:635). */
+#define RTX_MAX_REFLECT_DEPTH 4
+/* Mirror reflections: the reflectivity k in [0, 1] of objects first .. first+n-1 (creation indices, spheres and planes
  * alike: what the add calls return).  Every new object has k = 0; rtx_scene_clear forgets them.  A shaded pixel (the character
  * modes; RGB_NORMALS and SDL are unaffected) whose closest object has k > 0 traces one secondary ray, the view ray mirrored
  * about its normal, from its hit point; its colour becomes minf(255, local * (1 - k) + reflected * k) per component, where
  * `reflected` is the Blinn-Phong colour of the secondary ray's closest hit (the object itself excluded; no shadow test and no
- * further bounce there; black when it hits nothing).  Distance, glyph and normal stay the primary's, so k = 0 gives today's
+ * further bounce there at the default depth; black when it hits nothing).  Distance, glyph and normal stay the primary's, so k = 0 gives today's
  * bytes.  While no object has k > 0 every launch is what it is without this call.  All or nothing: a non-finite k, k < 0,
  * k > 1 or a range past rtx_scene_count changes nothing and returns RTX_ERR_INVALID_ARGUMENT (on a device group: validated
  * before any rank is touched, then applied to every rank).  Geometry is unchanged, so sorted copies and cell lists stay valid;
  * a graph recorded before the call is refused by rtx_graph_launch (re-capture).  The device copies are uploaded by the next
  * launch that takes the mirror path, which first waits for the whole device (every stream, every logical rank on it): a change,
  * a scene edit or a new direction sort costs one such wait.  A graph capture cannot do that upload, so recording right after
- * such a change fails with RTX_ERR_INVALID_ARGUMENT ("render once before capturing").  No reference counterpart
- * (RayTracing.cu:635 plans a recursive RayTrace). */
+ * such a change fails with RTX_ERR_INVALID_ARGUMENT ("render once before capturing").
+ * The rule for any RTX_OPT_REFLECT_DEPTH (the above is depth 1, operation for operation).  Level 0 is the primary ray r_0, its hit
+ * (t_0, o_0) and its local colour local_0: today's, with the shadow tests of RTX_OPT_SHADOWS and every light of the set.  A pixel
+ * has a chain when it is visible and k(o_0) > 0.  For j >= 0: level j+1 exists iff j+1 <= depth, level j hit an object and
+ * k(o_j) > 0; r_{j+1} = the mirror of r_j at t_j about normal_j (sphere: normalize(normalize(P - C)), plane: normalize(n), with
+ * the library's normalize), tested against every object but o_j with the reference's tests for a ray of its own origin and no far
+ * limit, the winner the lexicographic minimum of (t, creation index).  For j >= 1 local_j is the Blinn-Phong colour of r_j at t_j
+ * with full powers for every light of the set, in order (no shadow test there), black when level j hit nothing.  Colours are
+ * folded from the deepest level inwards: C_j = local_j when level j+1 does not exist, otherwise
+ * C_j = minf(255.0f, local_j * (1.0f - k_j) + C_{j+1} * k_j) per component, each operation rounded to fp32, no contraction.  The
+ * pixel's colour is C_0; distance, glyph and normal stay the primary's.
+ * No reference counterpart (RayTracing.cu:635 plans a recursive RayTrace). */
 int rtx_scene_set_reflectivity(rtx_ctx* ctx, unsigned first, size_t n, const float* k);
 /* The reflectivity of object `index`.  No reference counterpart. */
 int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);

@@ -404,6 +404,15 @@ public:
         for (const unsigned i : m_planes) v[i - first] = k;
         check(rtx_scene_set_reflectivity(ctx(), first, v.size(), v.data()), "rtx_scene_set_reflectivity");
     }
+    // Mirrors that see mirrors: levels of secondary rays, 1 .. RTX_MAX_REFLECT_DEPTH (RTX_OPT_REFLECT_DEPTH).
+    // No reference counterpart (RayTracing.cu:635).
+    void SetReflectDepth(const int depth) { check(rtx_set_option(ctx(), RTX_OPT_REFLECT_DEPTH, depth), "RTX_OPT_REFLECT_DEPTH"); }
+    int GetReflectDepth()
+    {
+        int64_t v = 1;
+        check(rtx_get_option(ctx(), RTX_OPT_REFLECT_DEPTH, &v), "RTX_OPT_REFLECT_DEPTH");
+        return (int)v;
+    }
     DeviceObjectArray<Object3D*> GetObjects()
     {
         DeviceObjectArray<Object3D*> a;

@@ -43,6 +43,9 @@ STAT_QUERY_GRID_GEOMETRY = 128
 OPT_LIGHTS_CHECK = 25
 STAT_LIGHTS = 137
 MAX_LIGHTS = 8
+OPT_REFLECT_DEPTH, OPT_REFLECT_DEPTH_CHECK = 26, 27
+STAT_REFLECT_RAYS = 138  # 138 .. 141: level 1 .. MAX_REFLECT_DEPTH
+MAX_REFLECT_DEPTH = 4
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
 NO_HIT = 99999999.0  # the t of a ray that hits nothing (RayTracing.h:21)

@@ -288,6 +288,13 @@ struct rtx_ctx {
     int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;
     uint32_t* d_reflect_longest = nullptr; // the longest candidate list of the last launch set on the path (one word)
+    // mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): at depth 1 with the check option 0 every launch is the one-bounce path's;
+    // otherwise rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade folds the chain, through 8 (depth + 1)
+    // bytes per pixel of the stream's hit buffer.  The depth travels in the kernel arguments.
+    int64_t opt_reflect_depth = 1;
+    int64_t opt_reflect_depth_check = 0;
+    uint32_t* d_reflect_rays = nullptr; // secondary rays per level of the last launch set on the chain kernels (RTX_MAX_REFLECT_DEPTH words)
+    bool reflect_rays_valid = false;    // the launch set queued last took the chain kernels (else RTX_STAT_REFLECT_RAYS reads 0)
 
     // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
     // context's stream by the first query after a scene edit or a physics step (qgrid.dirty); queries on other streams wait for

@@ -155,6 +155,16 @@ struct ReflectArgs {
     uint32_t* longest;   // atomicMax of the longest candidate list a workgroup held, or nullptr
 };
 
+// Mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade
+// folds the chain.  The hit buffer holds depth + 1 hit arrays of px entries: level j's at ReflectArgs::hits + j * px (hits2 is
+// level 1's).  By value, so a recorded graph keeps its depth.
+constexpr int kMaxReflectDepth = 4; // = RTX_MAX_REFLECT_DEPTH
+struct ChainArgs {
+    uint32_t depth;  // levels of secondary rays, 1 .. kMaxReflectDepth
+    uint32_t px;     // pixels of the launch (W * rows): the stride between the levels' hit arrays
+    uint32_t* rays;  // kMaxReflectDepth words: the secondary rays traced per level (one atomicAdd per workgroup and level), or nullptr
+};
+
 // Ray queries (rtx_query_rays): n rays of the caller against the scene arrays in creation order (spheres are known by sphere
 // index here, not by the direction-sorted position the trace kernels use), through the world grid or against every sphere.
 struct QueryArgs {
@@ -226,6 +236,10 @@ const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void*
 const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* s, const ReflectArgs* r, int mode, void* stream, int* hip_error);
 // The same two shading launches for a set of several lights (rtx_scene_set_lights; r == NULL: no mirror).
 const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream, int* hip_error);
+// The mirror path's second and third launches for a chain of c->depth levels (any set of lights).
+const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream, int* hip_error);
+const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream,
+                                            int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

@@ -1188,8 +1188,10 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 }
 
 #include "rtx_reflect_kernels.inc"
+#include "rtx_reflect_chain_kernels.inc"
 #include "rtx_shadow_kernels.inc"
 #include "rtx_lights_kernels.inc"
+#include "rtx_lights_chain_kernels.inc"
 #include "rtx_query_kernels.inc"
 
 } // namespace rtx
@@ -1458,6 +1460,57 @@ extern "C" const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArg
     }
 #undef RTX_LAUNCH_LIGHTS
 #undef RTX_LAUNCH_LIGHTS_OUT
+    *hip_error = (int)hipGetLastError();
+    return name;
+}
+
+extern "C" const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u || c->depth == 0u || c->depth > (uint32_t)kMaxReflectDepth || c->px != a->W * rows) return nullptr;
+    const dim3 grid((a->W + kReflectTile - 1u) / kReflectTile, (rows + kReflectTile - 1u) / kReflectTile, 1), block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, stream, *a, *r, *c);
+    *hip_error = (int)hipGetLastError();
+    return "rtx_reflect_chain";
+}
+
+extern "C" const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream_v,
+                                                       int* hip_error)
+{
+    using namespace rtx;
+    hipStream_t stream = (hipStream_t)stream_v;
+    *hip_error = 0;
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u || a->compact > 2u || l->lights.n == 0u || l->lights.n > (uint32_t)rtxlights::kMaxLights || c->depth == 0u ||
+        c->depth > (uint32_t)kMaxReflectDepth || c->px != a->W * rows) {
+        return nullptr;
+    }
+    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
+    const char* name = nullptr;
+#define RTX_LAUNCH_CHAIN(M)                                                                                          \
+    do {                                                                                                             \
+        if (a->compact == 0u) {                                                                                      \
+            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutRecords>), grid, block, 0, stream, *a, *l, *r, *c);    \
+            name = "rtx_lights_chain_shade<" #M ">";                                                                 \
+        } else if (a->compact == 1u) {                                                                               \
+            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutCompact>), grid, block, 0, stream, *a, *l, *r, *c);    \
+            name = "rtx_lights_chain_shade<" #M ",compact>";                                                         \
+        } else {                                                                                                     \
+            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutValues>), grid, block, 0, stream, *a, *l, *r, *c);     \
+            name = "rtx_lights_chain_shade<" #M ",values>";                                                          \
+        }                                                                                                            \
+    } while (0)
+    switch (mode) {
+    case RTX_K_BIT_ASCII: RTX_LAUNCH_CHAIN(RTX_K_BIT_ASCII); break;
+    case RTX_K_BIT_PIXEL: RTX_LAUNCH_CHAIN(RTX_K_BIT_PIXEL); break;
+    case RTX_K_RGB_ASCII: RTX_LAUNCH_CHAIN(RTX_K_RGB_ASCII); break;
+    case RTX_K_RGB_PIXEL: RTX_LAUNCH_CHAIN(RTX_K_RGB_PIXEL); break;
+    default: return nullptr;
+    }
+#undef RTX_LAUNCH_CHAIN
     *hip_error = (int)hipGetLastError();
     return name;
 }

@@ -94,8 +94,14 @@ __device__ __forceinline__ V3 lights_reflect_blend(const KArgs& a, const LightsA
     return v3(minf(255.0f, cl.x * w + cr.x * k), minf(255.0f, cl.y * w + cr.y * k), minf(255.0f, cl.z * w + cr.z * k));
 }
 
-template <int MODE, int OUT, bool REFLECT>
-__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra)
+// (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels)
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
+                                                 float distance, V3 normal, uint32_t id, V3 cl, size_t at);
+
+// REFLECT 0: no mirror; 1: one bounce (ra.hits2, lights_reflect_blend); 2: a chain (ca, lights_chain_blend).  What a value does
+// not use is not compiled.
+template <int MODE, int OUT, int REFLECT>
+__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca)
 {
     __shared__ LightsShared s;
 
@@ -328,8 +334,10 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
     // ---- shade with every light (both powers 0 for the lights the pixel is shadowed from) and encode
     if (any_hit) {
         colour = shade_lights(ray, distance, normal, od, la.lights, dark);
-        if constexpr (REFLECT) {
+        if constexpr (REFLECT == 1) {
             if (distance <= cam.far) colour = lights_reflect_blend(a, la, ra, ray, distance, normal, id, colour, (size_t)(row - a.row0) * a.W + col);
+        } else if constexpr (REFLECT == 2) {
+            if (distance <= cam.far) colour = lights_chain_blend(a, la, ra, ca, ray, distance, normal, id, colour, (size_t)(row - a.row0) * a.W + col);
         }
     }
     encode_and_store<MODE, OUT>(a, cam, s.digits, s.ramp, in_frame, newline_col, row, col, distance, normal, colour, shadingValue);
@@ -339,12 +347,14 @@ template <int MODE, int OUT>
 __global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgs la)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
-    lights_shade_body<MODE, OUT, false>(a, la, ra);
+    const ChainArgs ca = {};
+    lights_shade_body<MODE, OUT, 0>(a, la, ra, ca);
 }
 
 // The mirror path's third launch for a set of several lights: rtx_lights_shade's shading, then the blend.
 template <int MODE, int OUT>
 __global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra)
 {
-    lights_shade_body<MODE, OUT, true>(a, la, ra);
+    const ChainArgs ca = {}; // (read only by the chain's blend, which is not compiled here)
+    lights_shade_body<MODE, OUT, 1>(a, la, ra, ca);
 }

@@ -727,8 +727,13 @@ int upload_reflectivity(rtx_ctx* ctx)
     return RTX_OK;
 }
 
+// Do the mirror path's second and third launches go through the chain kernels?  Not at depth 1 unless the check option asks.
+bool chain_kernels(const rtx_ctx* ctx) { return ctx->opt_reflect_depth > 1 || ctx->opt_reflect_depth_check != 0; }
+
 // Closest hits (rtx_trace, kOutHit), the secondary hits of the reflective pixels (rtx_reflect_hit), then shading with the shadow
 // test and the blend into a.out (rtx_reflect_shade).  The stream's hit buffer holds both hit arrays: 16 bytes per pixel.
+// With RTX_OPT_REFLECT_DEPTH > 1 (or RTX_OPT_REFLECT_DEPTH_CHECK 1): closest hits, rtx_reflect_chain (every level in one launch),
+// rtx_lights_chain_shade; the hit buffer holds depth + 1 hit arrays.
 int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
 {
     int rc;
@@ -738,11 +743,14 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
         }
         if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
     }
+    const bool chain = chain_kernels(ctx);
+    const size_t depth = (size_t)ctx->opt_reflect_depth;
     const size_t px = (size_t)a.W * (a.row_end - a.row0);
     void* hits = nullptr;
-    if ((rc = hit_buffer(ctx, stream, px * 16u, capturing, &hits)) != RTX_OK) return rc;
+    if ((rc = hit_buffer(ctx, stream, chain ? px * 8u * (depth + 1u) : px * 16u, capturing, &hits)) != RTX_OK) return rc;
     if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     if (!ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
+    if (chain && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
@@ -755,7 +763,27 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
     ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
     ra.longest = ctx->d_reflect_longest;
     int herr = 0;
-    const char* name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
+    const char* name = nullptr;
+    ctx->reflect_rays_valid = chain;
+    if (chain) {
+        RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
+        ChainArgs ca;
+        std::memset(&ca, 0, sizeof ca);
+        ca.depth = (uint32_t)depth;
+        ca.px = (uint32_t)px;
+        ca.rays = ctx->d_reflect_rays;
+        name = rtx_k_launch_reflect_chain(&a, &ra, &ca, stream, &herr);
+        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry or depth");
+        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "reflection chain kernel launch");
+        const LightsArgs la = lights_args(ctx, hits);
+        name = rtx_k_launch_lights_chain_shade(&a, &la, &ra, &ca, mode, stream, &herr);
+        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
+        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "chain shading kernel launch");
+        ctx->last_kernel = name;
+        ctx->stat_reflect_frames++;
+        return RTX_OK;
+    }
+    name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "secondary hit kernel launch");
     if (lights_kernels(ctx)) {
