@@ -289,3 +289,88 @@ def paths_case(R, torch, seed, sizes=PATH_SIZES, oracle_rows=0, max_spheres=1200
     finally:
         c.close()
     return found
+
+
+CHAIN_SIZES = [(640, 360), (333, 77), (400, 150), (97, 301)]
+
+
+def chain_inputs(seed, max_spheres=700, max_pixels=8000):
+    """The inputs of one seed of the mirror-chain fuzzer, without a GPU: the construction of
+    tests/test_gpu_reflect.py::test_culled_equals_brute_fuzz_cases (a general camera matrix, a field of view from half to twice
+    the reference's, one of scene()'s kinds with random k and at least one mirror) plus 1-3 random lights within 80 of the camera
+    on every axis, and a sample of at most `max_pixels` pixels that holds the first and the last row.
+    Returns (oracle params, spheres, planes, k per object, lights as restate.Light, pixels)."""
+    import restate as RS
+    g = np.random.default_rng(9000 + seed)
+    W, H = CHAIN_SIZES[seed % 4]
+    pos = [float(v) for v in g.uniform(-30, 30, 3)]
+    p = O.camera_params(W, H, pos, (0.0, float(np.pi), 0.0))
+    M = general_matrix(g)
+    fov = float(g.choice([1.0, 0.5, 2.0]))
+    p.element1 = float(p.element1) * fov
+    p.element2 = float(p.element2) * fov
+    for i in range(3):
+        for j in range(3):
+            p.inv_v[i][j] = float(M[i, j])
+    M = np.array([[p.inv_v[i][j] for j in range(3)] for i in range(3)], dtype=np.float64)  # (as stored: float32)
+    sph, pl = scene(g, p, M, pos, W, H, max_spheres=max_spheres)
+    n = len(sph) + len(pl)
+    k = (g.uniform(0, 1, n) * (g.uniform(0, 1, n) < 0.5)).astype(np.float32)
+    k[int(g.integers(0, n))] = 0.75  # (at least one mirror: small scenes could draw none)
+    nl = int(g.integers(1, 4))
+    cam = np.array(pos, dtype=np.float64)
+    lights = [RS.Light(tuple(float(v) for v in cam + g.uniform(-80, 80, 3)), tuple(float(v) for v in g.uniform(0.2, 1.0, 3)),
+                       float(g.uniform(300, 1500)), tuple(float(v) for v in g.uniform(0.2, 1.0, 3)), float(g.uniform(500, 2500)))
+              for _ in range(nl)]
+    if W * H <= max_pixels:
+        pix = np.arange(W * H)
+    else:
+        edge = np.concatenate([np.arange(W), np.arange((H - 1) * W, H * W)])
+        rest = g.choice(np.arange(W, (H - 1) * W), size=max_pixels - len(edge), replace=False)
+        pix = np.sort(np.concatenate([edge, rest]))
+    return p, sph, pl, k, lights, pix
+
+
+def chain_case(R, torch, ctx, seed, max_spheres=700, stats=None):
+    """One seed of the mirror-chain fuzzer on the context `ctx` (at least 640 x 360): the frame of chain_inputs(seed) at depth 4,
+    shadows off, as RTX_RENDER_VALUES against the numpy restatement (tests/restate.py), all eight floats of every sampled pixel
+    bit for bit; where the restatement's float is a NaN the kernel's must be one, the payload is free.  A pixel without a hit
+    is compared on its distance, column W-1 on being all zero.  Returns a list of findings (empty = the case agreed)."""
+    import restate as RS
+    p, sph, pl, k, lights, pix = chain_inputs(seed, max_spheres)
+    W, H = int(p.x), int(p.y)
+    pp = U.product_params(np.array(p.inv_v, dtype=np.float32), p.cam_pos[:], W, H, p.element1, p.element2, p.cam_far)
+    ctx.set_scene(sph, pl)
+    ctx.set_reflectivity(0, k)
+    ctx.set_lights([R.make_light(*RS.light_tuple(l)) for l in lights])
+    ctx.set_option(R.OPT_SHADOWS, 0)
+    ctx.set_option(R.OPT_REFLECT_DEPTH, 4)
+    buf = torch.full((W * H * 32,), 0xEE, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    ctx.render_rows(pp, R.RGB_ASCII, 0, H, d_out=buf.data_ptr(), out_row_base=0, flags=R.RENDER_VALUES)
+    ctx.synchronize()
+    got = buf.cpu().numpy().view(np.float32).reshape(-1, 8)[pix]
+    kernel = ctx.last_kernel
+    trace = RS.trace_chain(p, sph, pl, k, pix)
+    want = RS.values8(trace, RS.shade_chain(trace, lights)[4])
+    same = RS.same_floats(got, want)
+    same[~trace["hit"], 1:] = True  # (normal and colour are defined for pixels with a hit only)
+    same[pix % W == W - 1] = (got[pix % W == W - 1].view(np.uint32) == 0)
+    if stats is not None:
+        stats["pixels"] = stats.get("pixels", 0) + len(pix)
+        stats["visible"] = stats.get("visible", 0) + int(trace["vis"].sum())
+        stats["nan"] = stats.get("nan", 0) + int(np.isnan(want[trace["vis"]]).any(axis=1).sum())
+        for j, r in enumerate(trace["rays"]):
+            stats["rays%d" % (j + 1)] = stats.get("rays%d" % (j + 1), 0) + r
+        stats.setdefault("kernels", {})
+        stats["kernels"][kernel] = stats["kernels"].get(kernel, 0) + 1
+    found = []
+    if not kernel.startswith("rtx_lights_chain_shade<"):
+        found.append("seed %d: the last kernel is %s, not rtx_lights_chain_shade" % (seed, kernel))
+    bad = np.nonzero(~same.all(axis=1))[0]
+    if bad.size:
+        i = int(bad[0])
+        found.append("seed %d: %d of %d sampled pixels differ from the restatement, %dx%d, %d spheres %d planes, %d lights (%s); first pixel %d "
+                     "(row %d col %d) fields %s: got %r want %r" % (seed, bad.size, len(pix), W, H, len(sph), len(pl), len(lights), kernel, int(pix[i]),
+                                                                   int(pix[i]) // W, int(pix[i]) % W, np.nonzero(~same[i])[0].tolist(), got[i], want[i]))
+    return found

@@ -14,6 +14,7 @@ import pytest
 
 import oracle as O
 import util as U
+from restate import _pow32, _shade_lights  # (moved to tests/restate.py)
 from test_gpu_reflect import _closest, _dot, _normal, _nrm, _scene_k, _set_k, _clear_k
 from test_gpu_shadows import _check_lit_or_dark, _fuzz_case, _fuzz_seeds, _rays64, directed_params, directed_scene
 
@@ -231,41 +232,6 @@ def test_lights_kernels_with_one_light_on_the_mirror_path(R, ctx):
 
 
 # ---------------------------------------------------------------- 3. the sum, bit for bit
-
-def _pow32(x):
-    d = x.astype(np.float64)
-    for _ in range(5):
-        d = d * d
-    return d.astype(np.float32)
-
-
-def _shade_lights(O3, D, t, normal, od, lights):
-    """The colour of the issue: res = 0.2f * od; per light, in order, res = (res + diffuse_i * od) + specular_i * 1.0f;
-    res * 255.0f; minf(255.0f, res).  One numpy float32 operation per IEEE operation of the kernel."""
-    point = tuple(O3[k] + D[k] * t for k in range(3))
-    view = _nrm(*(D[k] * f32(-1.0) for k in range(3)))
-    nn = _nrm(*normal)
-    nv = _nrm(*view)
-    res = [f32(0.2) * od[k] for k in range(3)]
-    for l in lights:
-        ld = tuple(f32(l.pos[k]) - point[k] for k in range(3))
-        dist = np.sqrt((ld[0] * ld[0] + ld[1] * ld[1]) + ld[2] * ld[2])
-        dist = dist * dist
-        divd = f32(1.0) / dist
-        ld = _nrm(*ld)
-        di = np.clip(_dot(nn, ld), f32(0.0), f32(1.0))
-        h = _nrm(ld[0] + nv[0], ld[1] + nv[1], ld[2] + nv[2])
-        si = _pow32(np.clip(_dot(nn, h), f32(0.0), f32(1.0)))
-        for k in range(3):
-            diffuse = ((f32(l.diffuse_rgb[k]) * di) * f32(l.diffuse_power)) * divd
-            spec = ((f32(l.specular_rgb[k]) * si) * f32(l.specular_power)) * divd
-            res[k] = (res[k] + diffuse * od[k]) + spec * f32(1.0)
-    out = []
-    for k in range(3):
-        r = res[k] * f32(255.0)
-        out.append(np.where(f32(255.0) < r, f32(255.0), r).astype(np.float32))
-    return out
-
 
 def restate(p, sph, pl, lights, pix, ks=None):
     """The primary hit and the colour of the pixels `pix` (flat indices) under `lights`, shadows off; with ks ({creation index: k})

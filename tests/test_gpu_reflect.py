@@ -13,11 +13,11 @@ import pytest
 
 import oracle as O
 import util as U
+from restate import _closest, _dot, _normal, _nrm, _scene_k, _shade, f32  # (the restatement's helpers live in tests/restate.py)
 
 pytestmark = pytest.mark.gpu
 
 MODES = [O.BIT_ASCII, O.BIT_PIXEL, O.RGB_ASCII, O.RGB_PIXEL]
-f32 = np.float32
 
 
 @pytest.fixture(scope="module")
@@ -73,26 +73,6 @@ def _set_k(c, ks):
 
 def _clear_k(c, n):
     c.set_reflectivity(0, np.zeros(n, dtype=np.float32))
-
-
-def _scene_k(name, sph, pl, variant):
-    """The reflective objects of the issue's scenes: creation indices (spheres first, then planes) -> k."""
-    ns, npl = len(sph), len(pl)
-    ks = {}
-    if variant in ("floor", "floor+quarter"):
-        ks[ns] = 0.5
-    if variant == "floor+quarter":
-        rng = np.random.default_rng(11)
-        for i in rng.choice(ns, size=ns // 4, replace=False):
-            ks[int(i)] = float(rng.uniform(0.05, 1.0))
-    if variant == "room":
-        for q in range(npl):
-            ks[ns + q] = 0.7
-    if variant == "quarter":
-        rng = np.random.default_rng(12)
-        for i in rng.choice(ns, size=max(1, ns // 4), replace=False):
-            ks[int(i)] = float(rng.uniform(0.05, 1.0))
-    return ks
 
 
 # ---------------------------------------------------------------- 1. default state: today's kernels
@@ -254,92 +234,6 @@ def test_culled_equals_brute_fuzz_cases(R, ctx):
 
 
 # ---------------------------------------------------------------- 4. exact against a numpy float32 restatement
-
-def _nrm(x, y, z):
-    inv = f32(1.0) / np.sqrt((x * x + y * y) + z * z)
-    return x * inv, y * inv, z * inv
-
-
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def _closest(O3, D, sph, pl, a, fourA, divTwoA, exclude=None):
-    """Lexicographic minimum of (t, creation index) over every sphere and plane (spheres first), from kNoHit; `exclude` the
-    creation index per ray to skip, or None.  Returns (t, creation index or -1)."""
-    n = D[0].shape[0]
-    bt = np.full(n, f32(99999999.0), dtype=np.float32)
-    bid = np.full(n, -1, dtype=np.int64)
-    for j, s in enumerate(sph.astype(np.float32)):
-        ox, oy, oz = O3[0] - s[0], O3[1] - s[1], O3[2] - s[2]
-        cc = ((ox * ox + oy * oy) + oz * oz) - s[3] * s[3]
-        sd = (D[0] * ox + D[1] * oy) + D[2] * oz
-        q = sd * sd - a * cc
-        b = f32(2.0) * sd
-        disc = b * b - fourA * cc
-        with np.errstate(invalid="ignore"):
-            t2 = (-b - np.sqrt(np.maximum(disc, f32(0.0)))) * divTwoA
-        hit = ~(q < f32(-1e-30)) & ~(disc < f32(0.0)) & ~(t2 < f32(0.0)) & ~np.isnan(t2)
-        if exclude is not None:
-            hit &= exclude != j
-        take = hit & ((t2 < bt) | ((t2 == bt) & ((bid < 0) | (j < bid))))
-        bt = np.where(take, t2, bt)
-        bid = np.where(take, j, bid)
-    ns = len(sph)
-    for q, P in enumerate(pl.astype(np.float32)):
-        gi = ns + q
-        nn = (P[3], P[4], P[5])
-        dn = _dot(D, nn)
-        num = (((P[0] - O3[0]) * nn[0] + (P[1] - O3[1]) * nn[1]) + (P[2] - O3[2]) * nn[2])
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t1 = num / dn
-        hx, hz = O3[0] + D[0] * t1, O3[2] + D[2] * t1
-        hw, hh = P[9] * f32(0.5), P[10] * f32(0.5)
-        hit = ~((dn > f32(0.0)) | (np.abs(dn - f32(0.0)) < f32(1.1920928955078125e-7))) & ~(t1 <= f32(0.0)) & ~np.isnan(t1)
-        hit &= ~(((hx <= P[0] - hw) | (hx >= P[0] + hw)) | ((hz <= P[2] - hh) | (hz >= P[2] + hh)))
-        if exclude is not None:
-            hit &= exclude != gi
-        take = hit & ((t1 < bt) | ((t1 == bt) & ((bid < 0) | (gi < bid))))
-        bt = np.where(take, t1, bt)
-        bid = np.where(take, gi, bid)
-    return bt, bid
-
-
-def _normal(P3, sph, pl, gid):
-    """normalize_gpu of the winner's normal (RayTracing.cu:129): sphere normalize(normalize(P - C)), plane normalize(n)."""
-    ns = len(sph)
-    C = np.concatenate([sph[:, :3], pl[:, :3]]).astype(np.float32)[np.maximum(gid, 0)]
-    Np = np.concatenate([np.zeros((ns, 3), np.float32), pl[:, 3:6].astype(np.float32)])[np.maximum(gid, 0)]
-    s = _nrm(P3[0] - C[:, 0], P3[1] - C[:, 1], P3[2] - C[:, 2])
-    is_pl = gid >= ns
-    n0 = tuple(np.where(is_pl, Np[:, k], s[k]) for k in range(3))
-    return _nrm(*n0)
-
-
-def _shade(O3, D, t, normal, od):
-    """shade_light with the reference's light and both powers on (RayTracing.cu:41-79)."""
-    point = tuple(O3[k] + D[k] * t for k in range(3))
-    view = _nrm(*(D[k] * f32(-1.0) for k in range(3)))
-    ld = (f32(1.0) - point[0], f32(50.0) - point[1], f32(0.0) - point[2])
-    dist = np.sqrt((ld[0] * ld[0] + ld[1] * ld[1]) + ld[2] * ld[2])
-    dist = dist * dist
-    divd = f32(1.0) / dist
-    ld = _nrm(*ld)
-    nn = _nrm(*normal)
-    nv = _nrm(*view)
-    di = np.clip(_dot(nn, ld), f32(0.0), f32(1.0))
-    h = _nrm(ld[0] + nv[0], ld[1] + nv[1], ld[2] + nv[2])
-    si = np.clip(_dot(nn, h), f32(0.0), f32(1.0)).astype(np.float64) ** 32
-    si = si.astype(np.float32)
-    out = []
-    for k in range(3):
-        diffuse = ((f32(1.0) * di) * f32(2000.0)) * divd
-        spec = ((f32(1.0) * si) * f32(3000.0)) * divd
-        r = (f32(0.2) * od[k] + diffuse * od[k]) + spec * f32(1.0)
-        r = r * f32(255.0)
-        out.append(np.where(f32(255.0) < r, f32(255.0), r).astype(np.float32))
-    return out
-
 
 def restate(p, sph, pl, ks, pix):
     """Steps 1-6 for the pixels `pix` (flat indices): the primary t and the blended colour (the local colour without shadows)."""
