@@ -15,6 +15,10 @@
 // Closest hit = lexicographic minimum of (t, creation order): the same object the reference's in-order scan with strict '<'
 // keeps (RayTracing.cu:123).  Spheres are known by their position in the arrays the kernel reads (KArgs::sph_geom: the
 // direction-sorted copies when there are some); the creation order is looked up only in an exact tie (comes_first).
+#include <stdio.h>
+
+#include <type_traits>
+
 #include "rtx_device.hpp"
 #include "rtx_kernels.h"
 #include "rtx_records.hpp"
@@ -1187,6 +1191,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
     }
 }
 
+#include "rtx_tile_pass.inc"
 #include "rtx_reflect_kernels.inc"
 #include "rtx_reflect_chain_kernels.inc"
 #include "rtx_shadow_kernels.inc"
@@ -1341,138 +1346,113 @@ extern "C" const char* rtx_k_launch_trace_batch(const KArgs* a, const KBatch* kb
     return name;
 }
 
-extern "C" const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* sh, int mode, void* stream_v, int* hip_error)
+// The shade launches of the tile passes (rtx_tile_pass.inc): one workgroup per 16 x 16 tile of the launch's rows, a kernel family
+// instantiated over the four character modes and the three output forms (a->compact 0 / 1 / 2).  launch(MODE, OUT, grid, block)
+// -- two std::integral_constants and the grid -- launches the family's instantiation.  Returns the kernel's name as
+// "family<RTX_K_mode>", "family<RTX_K_mode,compact>" or "family<RTX_K_mode,values>", or nullptr when the launch is refused.
+struct ShadeNames {
+    char s[4][3][64];
+    explicit ShadeNames(const char* family)
+    {
+        static const char* const kMode[4] = {"RTX_K_BIT_ASCII", "RTX_K_BIT_PIXEL", "RTX_K_RGB_ASCII", "RTX_K_RGB_PIXEL"};
+        static const char* const kSuffix[3] = {"", ",compact", ",values"};
+        for (int m = 0; m < 4; m++) {
+            for (int o = 0; o < 3; o++) snprintf(s[m][o], sizeof s[m][o], "%s<%s%s>", family, kMode[m], kSuffix[o]);
+        }
+    }
+};
+
+// The grid of a tile pass over the launch's rows; false: nothing to launch.
+static bool tile_grid(const KArgs* a, dim3& grid)
+{
+    const uint32_t rows = a->row_end - a->row0;
+    if (a->W == 0u || rows == 0u) return false;
+    grid = dim3((a->W + rtx::kTile - 1u) / rtx::kTile, (rows + rtx::kTile - 1u) / rtx::kTile, 1);
+    return true;
+}
+
+template <class Launch>
+static const char* launch_shade(const KArgs* a, int mode, const ShadeNames& names, int* hip_error, Launch launch)
 {
     using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
+    static_assert(RTX_K_BIT_ASCII == 0 && RTX_K_RGB_PIXEL == 3 && kOutRecords == 0 && kOutCompact == 1 && kOutValues == 2, "names are indexed by mode and form");
     *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u || a->compact > 2u) return nullptr;
-    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
-    const char* name = nullptr;
-#define RTX_LAUNCH_SHADOW(M)                                                                           \
-    do {                                                                                               \
-        if (a->compact == 0u) {                                                                        \
-            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutRecords>), grid, block, 0, stream, *a, *sh);   \
-            name = "rtx_shadow_shade<" #M ">";                                                         \
-        } else if (a->compact == 1u) {                                                                 \
-            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutCompact>), grid, block, 0, stream, *a, *sh);   \
-            name = "rtx_shadow_shade<" #M ",compact>";                                                 \
-        } else {                                                                                       \
-            hipLaunchKernelGGL((rtx_shadow_shade<M, kOutValues>), grid, block, 0, stream, *a, *sh);    \
-            name = "rtx_shadow_shade<" #M ",values>";                                                  \
-        }                                                                                              \
-    } while (0)
+    dim3 grid;
+    if (!tile_grid(a, grid) || a->compact > 2u || mode < RTX_K_BIT_ASCII || mode > RTX_K_RGB_PIXEL) return nullptr;
+    const dim3 block(kThreads, 1, 1);
+    const auto with_out = [&](auto m) {
+        switch (a->compact) {
+        case 0u: launch(m, std::integral_constant<int, kOutRecords>{}, grid, block); break;
+        case 1u: launch(m, std::integral_constant<int, kOutCompact>{}, grid, block); break;
+        default: launch(m, std::integral_constant<int, kOutValues>{}, grid, block); break;
+        }
+    };
     switch (mode) {
-    case RTX_K_BIT_ASCII: RTX_LAUNCH_SHADOW(RTX_K_BIT_ASCII); break;
-    case RTX_K_BIT_PIXEL: RTX_LAUNCH_SHADOW(RTX_K_BIT_PIXEL); break;
-    case RTX_K_RGB_ASCII: RTX_LAUNCH_SHADOW(RTX_K_RGB_ASCII); break;
-    case RTX_K_RGB_PIXEL: RTX_LAUNCH_SHADOW(RTX_K_RGB_PIXEL); break;
-    default: return nullptr;
+    case RTX_K_BIT_ASCII: with_out(std::integral_constant<int, RTX_K_BIT_ASCII>{}); break;
+    case RTX_K_BIT_PIXEL: with_out(std::integral_constant<int, RTX_K_BIT_PIXEL>{}); break;
+    case RTX_K_RGB_ASCII: with_out(std::integral_constant<int, RTX_K_RGB_ASCII>{}); break;
+    default: with_out(std::integral_constant<int, RTX_K_RGB_PIXEL>{}); break;
     }
-#undef RTX_LAUNCH_SHADOW
     *hip_error = (int)hipGetLastError();
-    return name;
+    return names.s[mode][a->compact];
+}
+
+static bool lights_ok(const LightsArgs* l) { return l->lights.n != 0u && l->lights.n <= (uint32_t)rtxlights::kMaxLights; }
+static bool chain_ok(const KArgs* a, const ChainArgs* c)
+{
+    return c->depth != 0u && c->depth <= (uint32_t)kMaxReflectDepth && c->px == a->W * (a->row_end - a->row0);
+}
+
+extern "C" const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* sh, int mode, void* stream_v, int* hip_error)
+{
+    static const ShadeNames names("rtx_shadow_shade");
+    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((rtx::rtx_shadow_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *sh);
+    });
 }
 
 extern "C" const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream_v, int* hip_error)
 {
     using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
     *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u) return nullptr;
-    const dim3 grid((a->W + kReflectTile - 1u) / kReflectTile, (rows + kReflectTile - 1u) / kReflectTile, 1), block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_reflect_hit, grid, block, 0, stream, *a, *r);
+    dim3 grid;
+    if (!tile_grid(a, grid)) return nullptr;
+    const dim3 block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_reflect_hit, grid, block, 0, (hipStream_t)stream_v, *a, *r);
     *hip_error = (int)hipGetLastError();
     return "rtx_reflect_hit";
 }
 
 extern "C" const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* sh, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
 {
-    using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
-    *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u || a->compact > 2u) return nullptr;
-    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
-    const char* name = nullptr;
-#define RTX_LAUNCH_REFLECT(M)                                                                               \
-    do {                                                                                                    \
-        if (a->compact == 0u) {                                                                             \
-            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutRecords>), grid, block, 0, stream, *a, *sh, *r);   \
-            name = "rtx_reflect_shade<" #M ">";                                                             \
-        } else if (a->compact == 1u) {                                                                      \
-            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutCompact>), grid, block, 0, stream, *a, *sh, *r);   \
-            name = "rtx_reflect_shade<" #M ",compact>";                                                     \
-        } else {                                                                                            \
-            hipLaunchKernelGGL((rtx_reflect_shade<M, kOutValues>), grid, block, 0, stream, *a, *sh, *r);    \
-            name = "rtx_reflect_shade<" #M ",values>";                                                      \
-        }                                                                                                   \
-    } while (0)
-    switch (mode) {
-    case RTX_K_BIT_ASCII: RTX_LAUNCH_REFLECT(RTX_K_BIT_ASCII); break;
-    case RTX_K_BIT_PIXEL: RTX_LAUNCH_REFLECT(RTX_K_BIT_PIXEL); break;
-    case RTX_K_RGB_ASCII: RTX_LAUNCH_REFLECT(RTX_K_RGB_ASCII); break;
-    case RTX_K_RGB_PIXEL: RTX_LAUNCH_REFLECT(RTX_K_RGB_PIXEL); break;
-    default: return nullptr;
-    }
-#undef RTX_LAUNCH_REFLECT
-    *hip_error = (int)hipGetLastError();
-    return name;
+    static const ShadeNames names("rtx_reflect_shade");
+    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((rtx::rtx_reflect_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *sh, *r);
+    });
 }
 
 extern "C" const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
 {
-    using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
+    static const ShadeNames plain("rtx_lights_shade"), mirror("rtx_lights_reflect_shade");
     *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u || a->compact > 2u || l->lights.n == 0u || l->lights.n > (uint32_t)rtxlights::kMaxLights) return nullptr;
-    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
-    const char* name = nullptr;
-#define RTX_LAUNCH_LIGHTS_OUT(M, O, SUFFIX)                                                                      \
-    do {                                                                                                         \
-        if (r != nullptr) {                                                                                      \
-            hipLaunchKernelGGL((rtx_lights_reflect_shade<M, O>), grid, block, 0, stream, *a, *l, *r);            \
-            name = "rtx_lights_reflect_shade<" #M SUFFIX ">";                                                    \
-        } else {                                                                                                 \
-            hipLaunchKernelGGL((rtx_lights_shade<M, O>), grid, block, 0, stream, *a, *l);                        \
-            name = "rtx_lights_shade<" #M SUFFIX ">";                                                            \
-        }                                                                                                        \
-    } while (0)
-#define RTX_LAUNCH_LIGHTS(M)                                        \
-    do {                                                            \
-        if (a->compact == 0u) {                                     \
-            RTX_LAUNCH_LIGHTS_OUT(M, kOutRecords, "");              \
-        } else if (a->compact == 1u) {                              \
-            RTX_LAUNCH_LIGHTS_OUT(M, kOutCompact, ",compact");      \
-        } else {                                                    \
-            RTX_LAUNCH_LIGHTS_OUT(M, kOutValues, ",values");        \
-        }                                                           \
-    } while (0)
-    switch (mode) {
-    case RTX_K_BIT_ASCII: RTX_LAUNCH_LIGHTS(RTX_K_BIT_ASCII); break;
-    case RTX_K_BIT_PIXEL: RTX_LAUNCH_LIGHTS(RTX_K_BIT_PIXEL); break;
-    case RTX_K_RGB_ASCII: RTX_LAUNCH_LIGHTS(RTX_K_RGB_ASCII); break;
-    case RTX_K_RGB_PIXEL: RTX_LAUNCH_LIGHTS(RTX_K_RGB_PIXEL); break;
-    default: return nullptr;
-    }
-#undef RTX_LAUNCH_LIGHTS
-#undef RTX_LAUNCH_LIGHTS_OUT
-    *hip_error = (int)hipGetLastError();
-    return name;
+    if (!lights_ok(l)) return nullptr;
+    return launch_shade(a, mode, r != nullptr ? mirror : plain, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        if (r != nullptr) {
+            hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r);
+        } else {
+            hipLaunchKernelGGL((rtx::rtx_lights_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l);
+        }
+    });
 }
 
 extern "C" const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream_v, int* hip_error)
 {
     using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
     *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u || c->depth == 0u || c->depth > (uint32_t)kMaxReflectDepth || c->px != a->W * rows) return nullptr;
-    const dim3 grid((a->W + kReflectTile - 1u) / kReflectTile, (rows + kReflectTile - 1u) / kReflectTile, 1), block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, stream, *a, *r, *c);
+    dim3 grid;
+    if (!tile_grid(a, grid) || !chain_ok(a, c)) return nullptr;
+    const dim3 block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, (hipStream_t)stream_v, *a, *r, *c);
     *hip_error = (int)hipGetLastError();
     return "rtx_reflect_chain";
 }
@@ -1480,39 +1460,12 @@ extern "C" const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectA
 extern "C" const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream_v,
                                                        int* hip_error)
 {
-    using namespace rtx;
-    hipStream_t stream = (hipStream_t)stream_v;
+    static const ShadeNames names("rtx_lights_chain_shade");
     *hip_error = 0;
-    const uint32_t rows = a->row_end - a->row0;
-    if (a->W == 0u || rows == 0u || a->compact > 2u || l->lights.n == 0u || l->lights.n > (uint32_t)rtxlights::kMaxLights || c->depth == 0u ||
-        c->depth > (uint32_t)kMaxReflectDepth || c->px != a->W * rows) {
-        return nullptr;
-    }
-    const dim3 grid((a->W + kShadowTile - 1u) / kShadowTile, (rows + kShadowTile - 1u) / kShadowTile, 1), block(kThreads, 1, 1);
-    const char* name = nullptr;
-#define RTX_LAUNCH_CHAIN(M)                                                                                          \
-    do {                                                                                                             \
-        if (a->compact == 0u) {                                                                                      \
-            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutRecords>), grid, block, 0, stream, *a, *l, *r, *c);    \
-            name = "rtx_lights_chain_shade<" #M ">";                                                                 \
-        } else if (a->compact == 1u) {                                                                               \
-            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutCompact>), grid, block, 0, stream, *a, *l, *r, *c);    \
-            name = "rtx_lights_chain_shade<" #M ",compact>";                                                         \
-        } else {                                                                                                     \
-            hipLaunchKernelGGL((rtx_lights_chain_shade<M, kOutValues>), grid, block, 0, stream, *a, *l, *r, *c);     \
-            name = "rtx_lights_chain_shade<" #M ",values>";                                                          \
-        }                                                                                                            \
-    } while (0)
-    switch (mode) {
-    case RTX_K_BIT_ASCII: RTX_LAUNCH_CHAIN(RTX_K_BIT_ASCII); break;
-    case RTX_K_BIT_PIXEL: RTX_LAUNCH_CHAIN(RTX_K_BIT_PIXEL); break;
-    case RTX_K_RGB_ASCII: RTX_LAUNCH_CHAIN(RTX_K_RGB_ASCII); break;
-    case RTX_K_RGB_PIXEL: RTX_LAUNCH_CHAIN(RTX_K_RGB_PIXEL); break;
-    default: return nullptr;
-    }
-#undef RTX_LAUNCH_CHAIN
-    *hip_error = (int)hipGetLastError();
-    return name;
+    if (!lights_ok(l) || !chain_ok(a, c)) return nullptr;
+    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c);
+    });
 }
 
 extern "C" int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream_v)

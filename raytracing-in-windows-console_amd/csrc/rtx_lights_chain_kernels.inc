@@ -1,7 +1,8 @@
 // rtx_lights_chain_kernels.inc -- the mirror path's third launch when mirrors see mirrors (RTX_OPT_REFLECT_DEPTH > 1, or
-// RTX_OPT_REFLECT_DEPTH_CHECK 1), included into namespace rtx of rtx_kernels.hip after rtx_lights_kernels.inc.  ONE shade family
-// for any set of 1 .. 8 lights (the set by value, as rtx_lights_reflect_shade gets it; DESIGN.md 4.9: +6-8 % for one light, on a
-// path nobody takes by default, for half the instantiations).
+// RTX_OPT_REFLECT_DEPTH_CHECK 1), included into namespace rtx of rtx_kernels.hip after rtx_lights_kernels.inc, whose
+// lights_shade_body and shade_lights it uses (the device functions the tile passes share: rtx_tile_pass.inc).  ONE shade family for
+// any set of 1 .. 8 lights (the set by value, as rtx_lights_reflect_shade gets it; DESIGN.md 4.9: +6-8 % for one light, on a path
+// nobody takes by default, for half the instantiations).
 //
 // Level 0 is lights_shade_body's work: the shadow test per light, one walk of the scene, local_0 = shade_lights with the pixel's
 // dark lights at powers 0.  lights_chain_blend then walks the chain forward from the hits rtx_reflect_chain stored (level j at
@@ -9,7 +10,7 @@
 // light, in order, no shadow test, black when level j hit nothing.  It keeps local_j and k_j for the at most 5 levels in
 // registers (loops unrolled: no indexed array, no scratch), then folds from the deepest level inwards:
 // C_j = local_j where level j + 1 does not exist, else minf(255.0f, local_j * (1.0f - k_j) + C_{j+1} * k_j) per component --
-// reflect_blend's expression in its operation order.  With depth 1 this is lights_reflect_blend operation for operation.
+// reflect_blend's expression in its operation order.  With depth 1 this is reflect_blend over shade_lights operation for operation.
 
 __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
                                                  float distance, V3 normal, uint32_t id, V3 cl, size_t at)
@@ -39,19 +40,9 @@ __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArg
                 if (alive) {
                     t = __uint_as_float(h.x);
                     o = h.y;
-                    V3 n0, od;
-                    if (h.y & 0x80000000u) {
-                        const uint32_t q = h.y & 0x7fffffffu;
-                        const float4 pb = a.pl_b[q], pd = a.pl_od[q];
-                        n0 = v3(pb.x, pb.y, pb.z);
-                        od = v3(pd.x, pd.y, pd.z);
-                    } else {
-                        const float4 g = a.sph_geom[h.y], d4 = a.sph_od[h.y];
-                        n0 = normalize_gpu(sub(add(r.o, mulf(r.d, t)), v3(g.x, g.y, g.z)));
-                        od = v3(d4.x, d4.y, d4.z);
-                    }
-                    n = normalize_gpu(n0);
-                    local[j + 1] = shade_lights(r, t, n, od, la.lights, 0u);
+                    const Surface sf = surface_of(a, h.y, add(r.o, mulf(r.d, t)));
+                    n = sf.normal;
+                    local[j + 1] = shade_lights(r, t, n, sf.od, la.lights, 0u);
                 }
             }
         }

@@ -1,5 +1,5 @@
 // rtx_query_kernels.inc -- ray queries (rtx_query_rays, rtx_pick), included into namespace rtx of rtx_kernels.hip after
-// rtx_reflect_kernels.inc, whose secondary_sphere_hit (and rtx_device.hpp's plane_hit) test every ray here: rays of the caller,
+// rtx_tile_pass.inc, whose secondary_sphere_hit (and rtx_device.hpp's plane_hit) test every ray here: rays of the caller,
 // each with its own origin, an unnormalised direction, a far limit tmax and a creation index to skip.
 //
 // One ray per lane, 256-thread workgroups; a ray is two 16-byte loads, a hit one 8-byte store.  Spheres are known by sphere index
