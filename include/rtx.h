@@ -188,6 +188,24 @@ enum rtx_option {
     RTX_OPT_REFLECT_DEPTH_CHECK = 27, /* for checks, not for the frame loop: 0 normal (default); 1 the chain kernels (rtx_reflect_chain,
                                * rtx_lights_chain_shade) are launched even at depth 1 (they then give the bytes of the launches they
                                * replace).  No reference counterpart (RayTracing.cu:635) */
+    RTX_OPT_REFLECT_SHADOWS = 28, /* shadows seen in mirrors: 0 (default: every launch, byte for byte, what it is without this option) or
+                               * 1: the shadow test of RTX_OPT_SHADOWS at every reflected hit as well.  Anything else returns
+                               * RTX_ERR_INVALID_ARGUMENT and changes nothing.  It has an effect only while RTX_OPT_SHADOWS is 1 and some
+                               * object reflects (rtx_scene_set_reflectivity); otherwise every launch is what it is without it.  The
+                               * rule, in the terms of rtx_scene_set_reflectivity: for every level j in 1 .. depth at which the chain
+                               * exists and hit an object o_j, the hit point P_j = r_j.o + r_j.d * t_j with the normal n_j of o_j there
+                               * gets level 0's test for every light i of the set, on its own.  Light i is dark at level j iff
+                               * dot(n_j, L_i - P_j) <= 0, or the open segment from P_j to L_i crosses a plane other than o_j (inside
+                               * its bounds, level 0's expressions), or comes closer than r to the centre of a sphere other than o_j.
+                               * Levels j >= 1 have no far limit (level 0 keeps its distance <= cam_far condition).  local_j is then
+                               * the Blinn-Phong colour with the dark lights at both powers 0; the fold, distance, glyph and normal are
+                               * unchanged.  RTX_OPT_SHADOW_CHECK applies to these tests exactly as to level 0's: 1 makes every sphere a
+                               * candidate, 2 applies no test, so every level is lit.  While in effect the mirror path takes the chain
+                               * kernels at any depth: closest hits, rtx_reflect_chain, rtx_chain_shadow (the tests, per 16 x 16 tile
+                               * and level), rtx_lights_chain_shadow_shade; the hit buffer holds 8 (depth + 1) + 4 bytes per pixel.
+                               * The value travels to the launches by value: a recorded graph keeps what it was recorded with.
+                               * Replicated over a device group like every option.  RTX_STAT_SHADOW_LONGEST_LIST then covers the
+                               * deeper levels' lists too.  No reference counterpart (RayTracing.cu:132,635) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -228,6 +246,11 @@ enum rtx_stat {
                                      * set that took the one-bounce kernels.  One 4-word device array per context, as
                                      * RTX_STAT_REFLECT_LONGEST_LIST.  Reading it waits for the device.
                                      * No reference counterpart (RayTracing.cu:635) */
+    RTX_STAT_REFLECT_SHADOW_POINTS = 142, /* 142 .. 145: the hit points of level 1 .. RTX_MAX_REFLECT_DEPTH that the launch set queued last
+                                     * shadow-tested under RTX_OPT_REFLECT_SHADOWS (every point of the level that hit an object; none
+                                     * under RTX_OPT_SHADOW_CHECK 2, which tests nothing); all 0 after a set the option had no effect
+                                     * on.  One 4-word device array per context, as RTX_STAT_REFLECT_RAYS.  Reading it waits for the
+                                     * device.  No reference counterpart (RayTracing.cu:132,635) */
     RTX_STAT_QUERY_GRID_BUILDS = 122, /* builds of the ray queries' world grid so far: one by the first query after rtx_scene_add_*,
                                      * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD; none by a query on an unchanged scene */
     RTX_STAT_QUERY_FALLBACK_RAYS = 123, /* rays of the last rtx_query_rays / rtx_query_rays_host / rtx_pick call that the grid kernel answered by
@@ -378,8 +401,8 @@ int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, si
  * alike: what the add calls return).  Every new object has k = 0; rtx_scene_clear forgets them.  A shaded pixel (the character
  * modes; RGB_NORMALS and SDL are unaffected) whose closest object has k > 0 traces one secondary ray, the view ray mirrored
  * about its normal, from its hit point; its colour becomes minf(255, local * (1 - k) + reflected * k) per component, where
- * `reflected` is the Blinn-Phong colour of the secondary ray's closest hit (the object itself excluded; no shadow test and no
- * further bounce there at the default depth; black when it hits nothing).  Distance, glyph and normal stay the primary's, so k = 0 gives today's
+ * `reflected` is the Blinn-Phong colour of the secondary ray's closest hit (the object itself excluded; no shadow test -- deeper
+ * levels: see RTX_OPT_REFLECT_SHADOWS -- and no further bounce there at the default depth; black when it hits nothing).  Distance, glyph and normal stay the primary's, so k = 0 gives today's
  * bytes.  While no object has k > 0 every launch is what it is without this call.  All or nothing: a non-finite k, k < 0,
  * k > 1 or a range past rtx_scene_count changes nothing and returns RTX_ERR_INVALID_ARGUMENT (on a device group: validated
  * before any rank is touched, then applied to every rank).  Geometry is unchanged, so sorted copies and cell lists stay valid;
@@ -393,7 +416,8 @@ int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, si
  * k(o_j) > 0; r_{j+1} = the mirror of r_j at t_j about normal_j (sphere: normalize(normalize(P - C)), plane: normalize(n), with
  * the library's normalize), tested against every object but o_j with the reference's tests for a ray of its own origin and no far
  * limit, the winner the lexicographic minimum of (t, creation index).  For j >= 1 local_j is the Blinn-Phong colour of r_j at t_j
- * with full powers for every light of the set, in order (no shadow test there), black when level j hit nothing.  Colours are
+ * with full powers for every light of the set, in order (no shadow test there unless RTX_OPT_REFLECT_SHADOWS asks for one),
+ * black when level j hit nothing.  Colours are
  * folded from the deepest level inwards: C_j = local_j when level j+1 does not exist, otherwise
  * C_j = minf(255.0f, local_j * (1.0f - k_j) + C_{j+1} * k_j) per component, each operation rounded to fp32, no contraction.  The
  * pixel's colour is C_0; distance, glyph and normal stay the primary's.

@@ -295,6 +295,11 @@ struct rtx_ctx {
     int64_t opt_reflect_depth_check = 0;
     uint32_t* d_reflect_rays = nullptr; // secondary rays per level of the last launch set on the chain kernels (RTX_MAX_REFLECT_DEPTH words)
     bool reflect_rays_valid = false;    // the launch set queued last took the chain kernels (else RTX_STAT_REFLECT_RAYS reads 0)
+    // shadows seen in mirrors (RTX_OPT_REFLECT_SHADOWS): in effect while RTX_OPT_SHADOWS is 1 and the mirror path is taken; then the
+    // chain kernels at any depth, rtx_chain_shadow between them, and 4 more bytes per pixel of the hit buffer (the dark words)
+    int64_t opt_reflect_shadows = 0;
+    uint32_t* d_reflect_shadow_points = nullptr; // hit points tested per level by the last launch set (RTX_MAX_REFLECT_DEPTH words)
+    bool reflect_shadow_points_valid = false;    // the launch set queued last ran rtx_chain_shadow (else the counters read 0)
 
     // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
     // context's stream by the first query after a scene edit or a physics step (qgrid.dirty); queries on other streams wait for

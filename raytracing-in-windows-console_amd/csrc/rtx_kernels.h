@@ -165,6 +165,14 @@ struct ChainArgs {
     uint32_t* rays;  // kMaxReflectDepth words: the secondary rays traced per level (one atomicAdd per workgroup and level), or nullptr
 };
 
+// Shadows seen in mirrors (RTX_OPT_REFLECT_SHADOWS): rtx_chain_shadow, between rtx_reflect_chain and the shade launch, runs the
+// shadow test at every deeper level's hit point and leaves one word per pixel, which rtx_lights_chain_shadow_shade reads.  The
+// words follow the depth + 1 hit arrays in the hit buffer: 8 (depth + 1) + 4 bytes per pixel.
+struct ChainShadowArgs {
+    uint32_t* dark;    // px words, laid out as the hits: bit 8 (j - 1) + i: light i is dark at level j
+    uint32_t* points;  // kMaxReflectDepth words: the hit points tested per level (one atomicAdd per workgroup and level), or nullptr
+};
+
 // Ray queries (rtx_query_rays): n rays of the caller against the scene arrays in creation order (spheres are known by sphere
 // index here, not by the direction-sorted position the trace kernels use), through the world grid or against every sphere.
 struct QueryArgs {
@@ -240,6 +248,12 @@ const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const
 const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream, int* hip_error);
 const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream,
                                             int* hip_error);
+// The chain under RTX_OPT_REFLECT_SHADOWS: the shadow tests of the deeper levels (after rtx_k_launch_reflect_chain), and the shade
+// launch that reads their result.
+const char* rtx_k_launch_chain_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs, void* stream,
+                                      int* hip_error);
+const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                                   int mode, void* stream, int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

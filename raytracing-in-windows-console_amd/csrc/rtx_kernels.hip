@@ -1197,6 +1197,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 #include "rtx_shadow_kernels.inc"
 #include "rtx_lights_kernels.inc"
 #include "rtx_lights_chain_kernels.inc"
+#include "rtx_chain_shadow_kernels.inc"
 #include "rtx_query_kernels.inc"
 
 } // namespace rtx
@@ -1465,6 +1466,31 @@ extern "C" const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const Lig
     if (!lights_ok(l) || !chain_ok(a, c)) return nullptr;
     return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
         hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c);
+    });
+}
+
+extern "C" const char* rtx_k_launch_chain_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                                 void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    *hip_error = 0;
+    dim3 grid;
+    if (!tile_grid(a, grid) || !lights_ok(l) || !chain_ok(a, c) || cs->dark == nullptr) return nullptr;
+    const dim3 block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_chain_shadow, grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c, *cs);
+    *hip_error = (int)hipGetLastError();
+    return "rtx_chain_shadow";
+}
+
+extern "C" const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c,
+                                                              const ChainShadowArgs* cs, int mode, void* stream_v, int* hip_error)
+{
+    static const ShadeNames names("rtx_lights_chain_shadow_shade");
+    *hip_error = 0;
+    if (!lights_ok(l) || !chain_ok(a, c) || cs->dark == nullptr) return nullptr;
+    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c,
+                           *cs);
     });
 }
 

@@ -7,13 +7,19 @@
 // Level 0 is lights_shade_body's work: the shadow test per light, one walk of the scene, local_0 = shade_lights with the pixel's
 // dark lights at powers 0.  lights_chain_blend then walks the chain forward from the hits rtx_reflect_chain stored (level j at
 // ra.hits + j * ca.px), rebuilding r_j with mirror_ray; local_j (j >= 1) = shade_lights of r_j at t_j with full powers for every
-// light, in order, no shadow test, black when level j hit nothing.  It keeps local_j and k_j for the at most 5 levels in
+// light, in order, no shadow test (under RTX_OPT_REFLECT_SHADOWS: see below), black when level j hit nothing.  It keeps local_j and k_j for the at most 5 levels in
 // registers (loops unrolled: no indexed array, no scratch), then folds from the deepest level inwards:
 // C_j = local_j where level j + 1 does not exist, else minf(255.0f, local_j * (1.0f - k_j) + C_{j+1} * k_j) per component --
 // reflect_blend's expression in its operation order.  With depth 1 this is reflect_blend over shade_lights operation for operation.
 
-__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
-                                                 float distance, V3 normal, uint32_t id, V3 cl, size_t at)
+//
+// RTX_OPT_REFLECT_SHADOWS: the blend takes a word per pixel, byte j - 1 the lights level j is shadowed from (rtx_chain_shadow's
+// output), and local_j is shade_lights with those lights at powers 0.  It is written once: lights_chain_blend is the blend with the
+// constant word 0 (the compiler folds the mask away: rtx_lights_chain_shade's code is what it was), rtx_lights_chain_shadow_shade
+// the same body with the pixel's word.
+
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
+                                                      float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark)
 {
     V3 local[kMaxReflectDepth + 1];
     float kk[kMaxReflectDepth];
@@ -42,7 +48,7 @@ __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArg
                     o = h.y;
                     const Surface sf = surface_of(a, h.y, add(r.o, mulf(r.d, t)));
                     n = sf.normal;
-                    local[j + 1] = shade_lights(r, t, n, sf.od, la.lights, 0u);
+                    local[j + 1] = shade_lights(r, t, n, sf.od, la.lights, (deep_dark >> (8 * j)) & 0xffu);
                 }
             }
         }
@@ -61,8 +67,22 @@ __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArg
     return C;
 }
 
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
+                                                 float distance, V3 normal, uint32_t id, V3 cl, size_t at)
+{
+    return lights_chain_blend_dark(a, la, ra, ca, ray, distance, normal, id, cl, at, 0u);
+}
+
 template <int MODE, int OUT>
 __global__ __launch_bounds__(kThreads) void rtx_lights_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca)
 {
     lights_shade_body<MODE, OUT, 2>(a, la, ra, ca);
+}
+
+// The chain's shade launch under RTX_OPT_REFLECT_SHADOWS: rtx_lights_chain_shade with the deeper levels' dark lights (cs.dark).
+template <int MODE, int OUT>
+__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shadow_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca,
+                                                                          const ChainShadowArgs cs)
+{
+    lights_shade_body<MODE, OUT, 3>(a, la, ra, ca, cs.dark);
 }

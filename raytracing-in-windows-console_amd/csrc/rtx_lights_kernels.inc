@@ -10,12 +10,13 @@
 // direction, nn) is formed once.  A light the pixel is shadowed from enters with both powers 0.
 //
 // The shadow test per light is the one-light pass's: self-shadow, the planes per pixel (shadowed_before_spheres), then the spheres.
-// Every thread keeps a bit mask of the lights still open for its pixel.  Per light the workgroup reduces its open hit points to a
-// cone from that light (light_cone), kept in LDS; a light with no open pixel in the workgroup has no cone.  The sphere array is
-// then walked ONCE for all lights (walk_spheres): each staged sphere is tested against every live cone and, if kept for at least
-// one light, appended once to the LDS list with the 8-bit mask of the lights it was kept for.  At a flush every wave goes through
-// the lights some lane of it is still open for; per light the segment (toL, 1 / len2) is formed once and the list entries whose
-// mask names the light (four mask bytes a word) are tested by the lanes open for it (segment_hits_sphere).
+// It is lights_dark_set (rtx_tile_pass.inc), which rtx_chain_shadow (rtx_chain_shadow_kernels.inc) runs over the deeper levels'
+// hit points: every thread keeps a bit mask of the lights still open for its pixel.  Per light the workgroup reduces its open hit
+// points to a cone from that light (light_cone), kept in LDS; a light with no open pixel in the workgroup has no cone.  The sphere
+// array is then walked ONCE for all lights (walk_spheres): each staged sphere is tested against every live cone and, if kept for at
+// least one light, appended once to the LDS list with the 8-bit mask of the lights it was kept for.  At a flush every wave goes
+// through the lights some lane of it is still open for; per light the segment (toL, 1 / len2) is formed once and the list entries
+// whose mask names the light (four mask bytes a word) are tested by the lanes open for it (segment_hits_sphere).
 
 struct LightsShared {
     float4 occ[kTileList];
@@ -67,14 +68,19 @@ __device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 norm
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 
-// (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels)
+// (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels; deep_dark: byte j - 1 the lights
+// level j is shadowed from)
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
+                                                      float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark);
 __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
                                                  float distance, V3 normal, uint32_t id, V3 cl, size_t at);
 
 // REFLECT 0: no mirror; 1: one bounce (ra.hits2, reflect_blend with every light at full powers); 2: a chain (ca,
-// lights_chain_blend).  What a value does not use is not compiled.
+// lights_chain_blend); 3: a chain whose deeper levels were shadow-tested (RTX_OPT_REFLECT_SHADOWS: deep_dark, the words
+// rtx_chain_shadow left, laid out as the hits).  What a value does not use is not compiled.
 template <int MODE, int OUT, int REFLECT>
-__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca)
+__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca,
+                                                  const uint32_t* deep_dark = nullptr)
 {
     __shared__ LightsShared s;
 
@@ -104,72 +110,10 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
         shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // RayTracing.cu:133
     }
 
-    // ---- the shadow test, per light: self-shadow and planes per pixel, and the workgroup's cone from that light
-    const uint32_t nl = la.lights.n;
+    // ---- the shadow test: per light self-shadow, planes and the workgroup's cone, then one walk of the scene for all lights
     const V3 P = add(ray.o, mulf(ray.d, distance)); // the point shade() lights
-    const float Pf[3] = {P.x, P.y, P.z};
     const bool testable = la.test != 0u && any_hit && distance <= cam.far;
-    const uint32_t own_plane = (id & 0x80000000u) ? (id & 0x7fffffffu) : 0xffffffffu;
-    uint32_t open = 0u; // lights this pixel's segment is still to be tested for
-    uint32_t dark = 0u; // lights this pixel is shadowed from
-    uint32_t live = 0u; // lights with a cone: some pixel of the workgroup is open for them (workgroup-uniform)
-    for (uint32_t i = 0; i < nl; i++) { // (every wave meets the same barriers: the trip count is the set's size)
-        const rtxlights::PackedLight& Lt = la.lights.light[i];
-        const V3 L = v3(Lt.px, Lt.py, Lt.pz);
-        bool pending = testable;
-        if (shadowed_before_spheres(a, P, normal, L, sub(L, P), own_plane, pending)) dark |= 1u << i;
-        if (pending) open |= 1u << i;
-
-        const float Lf[3] = {L.x, L.y, L.z};
-        rtxshadow::Cone cone;
-        if (light_cone(Lf, Pf, pending, la.brute != 0u, a.ns, lane, wave, s.red, cone)) {
-            if (tid == 0u) s.cone[i] = cone;
-            live |= 1u << i;
-        }
-        lds_barrier(); // everyone is done with this light's sums before the next light's are written; the cone is visible
-    }
-    live = __builtin_amdgcn_readfirstlane(live);
-
-    // ---- spheres: one walk of the scene for all lights
-    if (live != 0u) {
-        const uint32_t own_sphere = (id & 0x80000000u) ? 0xffffffffu : id;
-        walk_spheres<kTileList>(
-            a, tid, lane, s.occ, s.occ_pos, reinterpret_cast<uint8_t*>(s.occ_mask), &s.cnt, la.longest,
-            [&](bool in0, float4 c0, bool in1, float4 c1, uint32_t& km0, uint32_t& km1) { // the lights each of the two spheres may occlude
-                for (uint32_t m = live; m != 0u; m &= m - 1u) {
-                    const uint32_t i = (uint32_t)__builtin_ctz(m);
-                    const rtxshadow::Cone cone = s.cone[i];
-                    const float Lf[3] = {la.lights.light[i].px, la.lights.light[i].py, la.lights.light[i].pz};
-                    if (in0 && rtxshadow::may_occlude(cone, Lf, c0.x, c0.y, c0.z, c0.w)) km0 |= 1u << i;
-                    if (in1 && rtxshadow::may_occlude(cone, Lf, c1.x, c1.y, c1.z, c1.w)) km1 |= 1u << i;
-                }
-            },
-            [&](uint32_t cnt) {
-                for (uint32_t m = live; m != 0u; m &= m - 1u) {
-                    const uint32_t i = (uint32_t)__builtin_ctz(m), bit = 1u << i;
-                    bool pending = (open & bit) != 0u;
-                    if (__ballot(pending) == 0ull) continue; // no lane of this wave is open for the light
-                    const V3 toL = sub(v3(la.lights.light[i].px, la.lights.light[i].py, la.lights.light[i].pz), P);
-                    const float len2 = dot(toL, toL);
-                    const float inv_len2 = len2 > 0.0f ? 1.0f / len2 : 0.0f;
-                    const uint32_t sel = 0x01010101u << i;
-                    for (uint32_t j4 = 0; j4 < cnt && __ballot(pending) != 0ull; j4 += 4u) {
-                        // four entries' masks a word; entries at or past cnt are leftovers
-                        for (uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.occ_mask[j4 >> 2]) & sel; w != 0u; w &= w - 1u) {
-                            const uint32_t j = j4 + ((uint32_t)__builtin_ctz(w) >> 3);
-                            if (j >= cnt) break;
-                            const float4 sp = s.occ[j];
-                            if (pending && s.occ_pos[j] != own_sphere) {
-                                const bool hit = segment_hits_sphere(P, toL, inv_len2, sp);
-                                dark |= hit ? bit : 0u;
-                                pending = !hit;
-                            }
-                        }
-                    }
-                    if (!pending) open &= ~bit;
-                }
-            });
-    }
+    const uint32_t dark = lights_dark_set(a, la, s, tid, lane, wave, P, normal, id, testable); // lights this pixel is shadowed from
 
     // ---- shade with every light (both powers 0 for the lights the pixel is shadowed from) and encode
     if (any_hit) {
@@ -181,6 +125,8 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
             }
         } else if constexpr (REFLECT == 2) {
             if (distance <= cam.far) colour = lights_chain_blend(a, la, ra, ca, ray, distance, normal, id, colour, px.at(a));
+        } else if constexpr (REFLECT == 3) {
+            if (distance <= cam.far) colour = lights_chain_blend_dark(a, la, ra, ca, ray, distance, normal, id, colour, px.at(a), deep_dark[px.at(a)]);
         }
     }
     encode_and_store<MODE, OUT>(a, cam, s.digits, s.ramp, px.in_frame, px.newline_col, px.row, px.col, distance, normal, colour, shadingValue);

@@ -727,13 +727,19 @@ int upload_reflectivity(rtx_ctx* ctx)
     return RTX_OK;
 }
 
-// Do the mirror path's second and third launches go through the chain kernels?  Not at depth 1 unless the check option asks.
-bool chain_kernels(const rtx_ctx* ctx) { return ctx->opt_reflect_depth > 1 || ctx->opt_reflect_depth_check != 0; }
+// Are the deeper levels shadow-tested (RTX_OPT_REFLECT_SHADOWS)?  Only with shadows on and while some object reflects.
+bool reflect_shadows(const rtx_ctx* ctx) { return ctx->opt_reflect_shadows != 0 && ctx->opt_shadows != 0 && ctx->n_reflective != 0; }
+
+// Do the mirror path's second and third launches go through the chain kernels?  Not at depth 1 unless the check option asks, or the
+// deeper levels are shadow-tested.
+bool chain_kernels(const rtx_ctx* ctx) { return ctx->opt_reflect_depth > 1 || ctx->opt_reflect_depth_check != 0 || reflect_shadows(ctx); }
 
 // Closest hits (rtx_trace, kOutHit), the secondary hits of the reflective pixels (rtx_reflect_hit), then shading with the shadow
 // test and the blend into a.out (rtx_reflect_shade).  The stream's hit buffer holds both hit arrays: 16 bytes per pixel.
 // With RTX_OPT_REFLECT_DEPTH > 1 (or RTX_OPT_REFLECT_DEPTH_CHECK 1): closest hits, rtx_reflect_chain (every level in one launch),
-// rtx_lights_chain_shade; the hit buffer holds depth + 1 hit arrays.
+// rtx_lights_chain_shade; the hit buffer holds depth + 1 hit arrays.  With RTX_OPT_REFLECT_SHADOWS in effect: the chain kernels at
+// any depth, rtx_chain_shadow after rtx_reflect_chain (the deeper levels' dark lights, a word per pixel behind the hit arrays) and
+// rtx_lights_chain_shadow_shade, which reads them.
 int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
 {
     int rc;
@@ -744,13 +750,17 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
         if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
     }
     const bool chain = chain_kernels(ctx);
+    const bool deep_shadows = reflect_shadows(ctx);
     const size_t depth = (size_t)ctx->opt_reflect_depth;
     const size_t px = (size_t)a.W * (a.row_end - a.row0);
     void* hits = nullptr;
-    if ((rc = hit_buffer(ctx, stream, chain ? px * 8u * (depth + 1u) : px * 16u, capturing, &hits)) != RTX_OK) return rc;
+    if ((rc = hit_buffer(ctx, stream, chain ? px * (8u * (depth + 1u) + (deep_shadows ? 4u : 0u)) : px * 16u, capturing, &hits)) != RTX_OK) return rc;
     if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     if (!ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
     if (chain && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
+    if (deep_shadows && !ctx->d_reflect_shadow_points) {
+        RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_shadow_points, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
+    }
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
@@ -765,6 +775,7 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
     int herr = 0;
     const char* name = nullptr;
     ctx->reflect_rays_valid = chain;
+    ctx->reflect_shadow_points_valid = deep_shadows;
     if (chain) {
         RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
         ChainArgs ca;
@@ -776,7 +787,19 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
         if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry or depth");
         if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "reflection chain kernel launch");
         const LightsArgs la = lights_args(ctx, hits);
-        name = rtx_k_launch_lights_chain_shade(&a, &la, &ra, &ca, mode, stream, &herr);
+        if (deep_shadows) {
+            RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
+            ChainShadowArgs cs;
+            std::memset(&cs, 0, sizeof cs);
+            cs.dark = (uint32_t*)((uint2*)hits + px * (depth + 1u));
+            cs.points = ctx->d_reflect_shadow_points;
+            name = rtx_k_launch_chain_shadow(&a, &la, &ra, &ca, &cs, stream, &herr);
+            if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry, depth or light set");
+            if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "chain shadow kernel launch");
+            name = rtx_k_launch_lights_chain_shadow_shade(&a, &la, &ra, &ca, &cs, mode, stream, &herr);
+        } else {
+            name = rtx_k_launch_lights_chain_shade(&a, &la, &ra, &ca, mode, stream, &herr);
+        }
         if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
         if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "chain shading kernel launch");
         ctx->last_kernel = name;
@@ -1179,6 +1202,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "batched trace kernel launch");
     ctx->last_kernel = name;
+    ctx->reflect_shadow_points_valid = false; // (batched launches are never the mirror path's)
     ctx->stat_batched_launches++;
     if (to && (rc = dispatch_order_derive(ctx, stream, shape, a, to, od)) != RTX_OK) return rc;
     *done = true;
@@ -1268,8 +1292,10 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     if (reflect_path(ctx, mode)) {
         if ((rc = launch_reflect_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
     } else if (shadow_path(ctx, mode)) {
+        ctx->reflect_shadow_points_valid = false; // (not the mirror path: RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
         if ((rc = launch_shadow_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
     } else {
+        ctx->reflect_shadow_points_valid = false;
         int herr = 0;
         const char* name = rtx_k_launch_trace(&a, mode, cull, stream, &herr);
         if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");

@@ -1,7 +1,7 @@
 // rtx_tile_pass.inc -- the device code the tile passes share, included into namespace rtx of rtx_kernels.hip before the kernel
 // files that use it (rtx_reflect_kernels.inc, rtx_reflect_chain_kernels.inc, rtx_shadow_kernels.inc, rtx_lights_kernels.inc,
-// rtx_lights_chain_kernels.inc).  A tile pass is a launch that follows the trace kernel in its kOutHit form (every pixel's closest
-// hit, 8 bytes: t, object): a 256-thread workgroup owns a 16 x 16 tile, every thread rebuilds its pixel's primary ray and its
+// rtx_lights_chain_kernels.inc, rtx_chain_shadow_kernels.inc).  A tile pass is a launch that follows the trace kernel in its
+// kOutHit form (every pixel's closest hit, 8 bytes: t, object): a 256-thread workgroup owns a 16 x 16 tile, every thread rebuilds its pixel's primary ray and its
 // winner's surface exactly as the trace body does, the workgroup culls the scene's spheres against a bound of its pixels' rays
 // (a cone of shadow segments, rtx_shadow.hpp; bundles of mirrored rays, rtx_reflect.hpp) into a list in LDS, and every thread
 // runs its exact test over that list.  Each block below exists once; no floating-point operation of any of them may be added,
@@ -236,6 +236,86 @@ __device__ __forceinline__ bool segment_hits_sphere(V3 P, V3 toL, float inv_len2
     return dot(e, e) < sp.w * sp.w;
 }
 
+// ---------------------------------------------------------------- the shadow test of a set of lights
+
+// The lights (bit i: light i of la.lights) that the point P -- normal `normal`, on object `id` (sphere position, or plane index |
+// bit 31) -- is shadowed from; 0 for a pixel that is not `testable`.  Per light: self-shadow and the planes per pixel
+// (shadowed_before_spheres) and the workgroup's cone from that light over its open points (light_cone), kept in s.cone; a light
+// with no open pixel in the workgroup has no cone.  Then ONE walk of the scene for all lights (walk_spheres): each staged sphere is
+// tested against every live cone and listed once with the 8-bit mask of the lights it was kept for; at a flush every wave goes
+// through the lights some lane of it is still open for, the segment (toL, 1 / len2) formed once per light.  Called by every
+// thread of the workgroup (the trip counts are workgroup-uniform; every wave meets the same barriers, at least one per light).
+// `s` holds occ, occ_pos, occ_mask (one byte per entry), red, cone and cnt, which is 0 on entry and 0 again on return.
+template <class Shared>
+__device__ __forceinline__ uint32_t lights_dark_set(const KArgs& a, const LightsArgs& la, Shared& s, uint32_t tid, uint32_t lane, uint32_t wave, V3 P, V3 normal,
+                                                    uint32_t id, bool testable)
+{
+    const uint32_t nl = la.lights.n;
+    const float Pf[3] = {P.x, P.y, P.z};
+    const uint32_t own_plane = (id & 0x80000000u) ? (id & 0x7fffffffu) : 0xffffffffu;
+    uint32_t open = 0u; // lights this pixel's segment is still to be tested for
+    uint32_t dark = 0u; // lights this pixel is shadowed from
+    uint32_t live = 0u; // lights with a cone: some pixel of the workgroup is open for them (workgroup-uniform)
+    for (uint32_t i = 0; i < nl; i++) { // (every wave meets the same barriers: the trip count is the set's size)
+        const rtxlights::PackedLight& Lt = la.lights.light[i];
+        const V3 L = v3(Lt.px, Lt.py, Lt.pz);
+        bool pending = testable;
+        if (shadowed_before_spheres(a, P, normal, L, sub(L, P), own_plane, pending)) dark |= 1u << i;
+        if (pending) open |= 1u << i;
+
+        const float Lf[3] = {L.x, L.y, L.z};
+        rtxshadow::Cone cone;
+        if (light_cone(Lf, Pf, pending, la.brute != 0u, a.ns, lane, wave, s.red, cone)) {
+            if (tid == 0u) s.cone[i] = cone;
+            live |= 1u << i;
+        }
+        lds_barrier(); // everyone is done with this light's sums before the next light's are written; the cone is visible
+    }
+    live = __builtin_amdgcn_readfirstlane(live);
+
+    // ---- spheres: one walk of the scene for all lights
+    if (live != 0u) {
+        const uint32_t own_sphere = (id & 0x80000000u) ? 0xffffffffu : id;
+        walk_spheres<kTileList>(
+            a, tid, lane, s.occ, s.occ_pos, reinterpret_cast<uint8_t*>(s.occ_mask), &s.cnt, la.longest,
+            [&](bool in0, float4 c0, bool in1, float4 c1, uint32_t& km0, uint32_t& km1) { // the lights each of the two spheres may occlude
+                for (uint32_t m = live; m != 0u; m &= m - 1u) {
+                    const uint32_t i = (uint32_t)__builtin_ctz(m);
+                    const rtxshadow::Cone cone = s.cone[i];
+                    const float Lf[3] = {la.lights.light[i].px, la.lights.light[i].py, la.lights.light[i].pz};
+                    if (in0 && rtxshadow::may_occlude(cone, Lf, c0.x, c0.y, c0.z, c0.w)) km0 |= 1u << i;
+                    if (in1 && rtxshadow::may_occlude(cone, Lf, c1.x, c1.y, c1.z, c1.w)) km1 |= 1u << i;
+                }
+            },
+            [&](uint32_t cnt) {
+                for (uint32_t m = live; m != 0u; m &= m - 1u) {
+                    const uint32_t i = (uint32_t)__builtin_ctz(m), bit = 1u << i;
+                    bool pending = (open & bit) != 0u;
+                    if (__ballot(pending) == 0ull) continue; // no lane of this wave is open for the light
+                    const V3 toL = sub(v3(la.lights.light[i].px, la.lights.light[i].py, la.lights.light[i].pz), P);
+                    const float len2 = dot(toL, toL);
+                    const float inv_len2 = len2 > 0.0f ? 1.0f / len2 : 0.0f;
+                    const uint32_t sel = 0x01010101u << i;
+                    for (uint32_t j4 = 0; j4 < cnt && __ballot(pending) != 0ull; j4 += 4u) {
+                        // four entries' masks a word; entries at or past cnt are leftovers
+                        for (uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)s.occ_mask[j4 >> 2]) & sel; w != 0u; w &= w - 1u) {
+                            const uint32_t j = j4 + ((uint32_t)__builtin_ctz(w) >> 3);
+                            if (j >= cnt) break;
+                            const float4 sp = s.occ[j];
+                            if (pending && s.occ_pos[j] != own_sphere) {
+                                const bool hit = segment_hits_sphere(P, toL, inv_len2, sp);
+                                dark |= hit ? bit : 0u;
+                                pending = !hit;
+                            }
+                        }
+                    }
+                    if (!pending) open &= ~bit;
+                }
+            });
+    }
+    return dark;
+}
+
 // ---------------------------------------------------------------- the mirror's secondary rays
 
 // The reflectivity of a winner (sphere position, or plane index | bit 31), by the order the trace kernels index spheres by.
@@ -417,8 +497,8 @@ struct MayMeetBundles {
 };
 
 // Steps 4-6 for one pixel of the mirror path's shading launch: the secondary hit (ra.hits2[at]) shaded by shade(r2, t2, normal,
-// od) -- the light or lights at full powers, no shadow test there, no further bounce; black without a hit -- and blended with the
-// local colour cl.  Pixels whose winner does not reflect keep cl.
+// od) -- the light or lights at full powers, no shadow test there (the chain's launches have one: RTX_OPT_REFLECT_SHADOWS), no
+// further bounce; black without a hit -- and blended with the local colour cl.  Pixels whose winner does not reflect keep cl.
 template <class Shade>
 __device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& ra, const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at,
                                             Shade shade)
