@@ -206,6 +206,34 @@ enum rtx_option {
                                * The value travels to the launches by value: a recorded graph keeps what it was recorded with.
                                * Replicated over a device group like every option.  RTX_STAT_SHADOW_LONGEST_LIST then covers the
                                * deeper levels' lists too.  No reference counterpart (RayTracing.cu:132,635) */
+    RTX_OPT_SHADOW_GRID = 29, /* shadow tests through the world grid of the ray queries: 0 (default: every launch, byte for byte and
+                               * kernel for kernel, what it is without this option) or 1.  Anything else returns
+                               * RTX_ERR_INVALID_ARGUMENT and changes nothing.  The rule: the test itself is unchanged -- self-shadow,
+                               * the planes, and for every sphere other than the point's own the closest point of the segment to its
+                               * centre, at every level RTX_OPT_SHADOWS and RTX_OPT_REFLECT_SHADOWS test -- only WHICH spheres a segment
+                               * is tested against changes: those listed in the cells the segment P + k (L - P), k in [0, 1], passes
+                               * through (and the grid's large spheres) instead of those a cone over the 16 x 16 tile keeps.  No sphere
+                               * the test would report is left out (a proved bound), so the frames are byte for byte those of
+                               * the existing path.  It has an effect only while RTX_OPT_SHADOWS is 1, RTX_OPT_SHADOW_CHECK is 0
+                               * (checks 1 and 2 keep today's launches: they are the brute reference), the scene has at least one
+                               * sphere, and the grid is usable (RTX_STAT_QUERY_BRUTE reads 0 after the build); otherwise every launch
+                               * is what it is without it.  The launches, while in effect: closest hits (and on the mirror path
+                               * rtx_reflect_hit or rtx_reflect_chain, unchanged), rtx_grid_shadow -- one pixel per thread, no list in
+                               * LDS: level 0's dark lights, and in place of rtx_chain_shadow the deeper levels' -- then
+                               * rtx_grid_shade / rtx_grid_reflect_shade / rtx_grid_chain_shade / rtx_grid_chain_shadow_shade, which
+                               * read them, for any light set, a set of one included.  The hit buffer holds 4 more bytes per pixel
+                               * (level 0's word): 12 on the shadow path, 20 for one bounce, 8 (depth + 1) + 4 (+ 4 under
+                               * RTX_OPT_REFLECT_SHADOWS) on the chain.  The grid is the queries' own (one object, one
+                               * RTX_STAT_QUERY_GRID_BUILDS): the first frame after rtx_scene_add_*, rtx_scene_clear or
+                               * rtx_update_objects rebuilds it, which blocks as a query's build does -- a physics step per frame
+                               * means a build per frame.  A segment that cannot be walked -- its point further from the spheres' box
+                               * than three times the box's largest half-extent (a far floor), the light at the point itself, a length
+                               * outside [2^-20, 2^20] -- tests every sphere (RTX_STAT_SHADOW_GRID_FALLBACK_POINTS).  A launch on this
+                               * path is refused inside a graph capture with RTX_ERR_INVALID_ARGUMENT (the lists change with physics,
+                               * and the build allocates and waits); rtx_submit_slabs queues its slabs one by one, as on the shadow
+                               * path.  Replicated over a device group like every option; every member builds its own grid on its own
+                               * device.  RTX_STAT_SHADOW_LONGEST_LIST reads 0 after such a set.  Off by default: where most segments
+                               * fall back it is slower.  No reference counterpart (RayTracing.cu:132) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -251,8 +279,14 @@ enum rtx_stat {
                                      * under RTX_OPT_SHADOW_CHECK 2, which tests nothing); all 0 after a set the option had no effect
                                      * on.  One 4-word device array per context, as RTX_STAT_REFLECT_RAYS.  Reading it waits for the
                                      * device.  No reference counterpart (RayTracing.cu:132,635) */
+    RTX_STAT_SHADOW_GRID_FRAMES = 146, /* launch sets queued with the shadow tests through the world grid (RTX_OPT_SHADOW_GRID in effect):
+                                     * counted as RTX_STAT_SHADOW_FRAMES counts, on either path */
+    RTX_STAT_SHADOW_GRID_FALLBACK_POINTS = 147, /* the (point, light) segments of the last such launch set that could not be walked and
+                                     * tested every sphere instead, over all levels.  One word per context, as RTX_STAT_SHADOW_LONGEST_LIST.
+                                     * Reading it waits for the device, as RTX_STAT_QUERY_FALLBACK_RAYS does */
     RTX_STAT_QUERY_GRID_BUILDS = 122, /* builds of the ray queries' world grid so far: one by the first query after rtx_scene_add_*,
-                                     * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD; none by a query on an unchanged scene */
+                                     * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD (or by the first frame after one, under
+                                     * RTX_OPT_SHADOW_GRID: the grid is shared); none by a query or a frame on an unchanged scene */
     RTX_STAT_QUERY_FALLBACK_RAYS = 123, /* rays of the last rtx_query_rays / rtx_query_rays_host / rtx_pick call that the grid kernel answered by
                                      * testing every object because they cannot be walked (see rtx_query_rays).  0 after a call under
                                      * RTX_OPT_QUERY_CHECK 1.  Reading it waits for the device */

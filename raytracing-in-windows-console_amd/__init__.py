@@ -47,6 +47,9 @@ OPT_REFLECT_DEPTH, OPT_REFLECT_DEPTH_CHECK = 26, 27
 STAT_REFLECT_RAYS = 138  # 138 .. 141: level 1 .. MAX_REFLECT_DEPTH
 MAX_REFLECT_DEPTH = 4
 OPT_REFLECT_SHADOWS = 28
+OPT_SHADOW_GRID = 29
+STAT_SHADOW_GRID_FRAMES = 146
+STAT_SHADOW_GRID_FALLBACK_POINTS = 147
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE

@@ -315,11 +315,26 @@ struct rtx_ctx {
         void* d_ray = nullptr;        // rtx_pick's ray and hit (48 bytes)
         hipEvent_t ev_built = nullptr, ev_done = nullptr;
         bool query_pending = false;   // ev_done has been recorded since the last build
+        // render launches that read the lists (RTX_OPT_SHADOW_GRID): an event per render stream, recorded behind the stream's last
+        // such launch; a rebuild waits for those marked pending
+        struct Reader {
+            hipStream_t stream = nullptr;
+            hipEvent_t ev = nullptr;
+            bool pending = false;
+        };
+        std::vector<Reader> readers;
     };
     QueryGrid qgrid;
     int64_t opt_query_check = 0;
     int64_t opt_query_load = 0;       // RTX_OPT_QUERY_LOAD: spheres per cell the grid aims at, in 1/16 (0: rtxgrid::kDefaultLoad)
     uint64_t stat_query_builds = 0;
+
+    // shadow tests through that grid (RTX_OPT_SHADOW_GRID): in effect while RTX_OPT_SHADOWS is 1, RTX_OPT_SHADOW_CHECK 0, the scene has
+    // a sphere and the build found a usable grid; then rtx_grid_shadow decides every level's dark lights per pixel and the
+    // rtx_grid_*shade family shades from its words: 4 more bytes per pixel of the stream's hit buffer
+    int64_t opt_shadow_grid = 0;
+    uint64_t stat_shadow_grid_frames = 0;
+    uint32_t* d_shadow_grid_fallback = nullptr; // segments of the last launch set on the path that tested every sphere (one word)
 
     std::string error;
     const char* last_kernel = "";
@@ -333,6 +348,11 @@ int rtx_sync_scene(rtx_ctx* ctx);
 void rtx_scene_edited(rtx_ctx* ctx);
 int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip
 void rtx_query_release(rtx_ctx* ctx);                    // rtx_query.cpp: frees the grid (rtx_destroy)
+// rtx_query.cpp: the world grid for a launch on `stream` that reads its lists -- the one grid object the queries use, brought up to date
+// if the scene changed since its last build (a build blocks, as a query's does, and counts in RTX_STAT_QUERY_GRID_BUILDS); `stream` is
+// ordered after the build.  Not inside a graph capture.  Then rtx_grid_read, behind the launches: a later rebuild waits for them.
+int rtx_grid_ensure(rtx_ctx* ctx, hipStream_t stream);
+int rtx_grid_read(rtx_ctx* ctx, hipStream_t stream);
 bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status); // rtx_query.cpp: the RTX_STAT_QUERY_* values
 // the zero-fill bookkeeping of the context's own frame buffer for a frame of `mode` whose records something other than
 // rtx_render_rows is about to write there (a group's gathered slabs, its expanded words), on the context's stream

@@ -30,6 +30,27 @@
 //    Hence the walk may stop as soon as the best t so far is below t_out of the cell just tested: no margin in t is needed,
 //    because t_out and the reported t are compared as the fp32 numbers they are.
 //
+// 4. The shadow test (RTX_OPT_SHADOW_GRID).  Shadow segments are tested by another fp32 test, segment_hits_sphere
+//    (rtx_tile_pass.inc): for the segment P + k toL, k in [0, 1], w = fl(c - P), k = the clamped fl(fl(w . toL) * inv_len2),
+//    e = fl(w - fl(toL k)), hit iff fl(e . e) < fl(r r).  Claim: when it reports a hit for a walkable segment (P within `reach` of
+//    the box centre on every axis, a = fl(toL . toL) in [2^-40, 2^40], everything finite), the exact point X = P + k toL, at the
+//    fp32 value k the test formed and with the fp32 vectors P and toL taken as exact, lies within step 1's R of c.  Nothing is
+//    assumed about how k was arrived at, only that it is an fp32 number in [0, 1] (a NaN k reports no hit).
+//    Write w* = c - P and e* = w* - k toL = c - X for the exact vectors.  Per component e_i = ((w*_i (1 + d1)) - (toL_i k)(1 + d2))
+//    (1 + d3) with |d| <= u, so |e - e*| <= u |w*| + u k |toL| + 1.01u |e| in norm.  A reported hit has fl(e . e) < fl(r r):
+//    three non-negative products and two additions give fl(e . e) >= |e|^2 (1 - u)^3, and fl(r r) <= r^2 (1 + u), hence
+//    |e| < r (1 + 3.01u).  From e* = w* - k toL, k |toL| <= |w*| + |e*|.  With E = |e*| and D >= |w*|:
+//    E <= |e| (1 + 1.01u) + u (2 D + E), so E <= r (1 + 5.2u) + 2.01u D -- the point lies within r (1 + 5.2u) + eps D of the centre
+//    with eps = 2.01u = 1.2e-7.  Squared, with 2 r eps D <= eps (r^2 + D^2): E^2 <= r^2 (1 + 10.5u + 1.3e-7) + 1.3e-7 D^2 <=
+//    r^2 (1 + kappa) + kappa D^2 for the kappa = 2e-6 the lists are built with (10.5u + 1.3e-7 = 7.6e-7): X lies within R of c
+//    and the listed boxes suffice as they are -- the grid is not rebuilt with another bound.  (Underflow is gradual on host and
+//    device, denormals are not flushed: a product is off by at most 2^-149 absolutely, which moves E by less than 2^-73, against a
+//    margin of at least 2^-66.)  By steps 2 and 3, read with o = P, d = toL -- the fp32 vector the test itself uses -- and t = k,
+//    the sphere is listed in the cell whose walk interval holds k, or is in the large list.  k <= 1, so the walk runs with
+//    tmax = 1 and may end once t_out of the cell just tested is past 1; there is no hit to report a t for, so it ends at the
+//    first hit as well.  segment_walkable() is the classification, for the kernel (rtx_grid_shadow) and the host check alike;
+//    tests/host/test_grid_shadow_bound.cpp checks the claim and the walk against float64.
+//
 // Rays that are not walkable (origin or direction not finite, a = d . d outside [2^-40, 2^40], origin further than `reach` from
 // the box centre on some axis) test every sphere instead.  tests/host/test_grid_bound.cpp checks all of this against float64.
 #pragma once
@@ -185,6 +206,14 @@ RTX_GRID_HD inline bool walkable(const Grid& g, const float o[3], float a)
         ok = ok && fabsf(o[k] - g.ctr[k]) <= g.reach; // (false for NaN and infinities)
     }
     return ok;
+}
+
+// May the shadow segment (P, P + toL) be walked (d = toL, tmax = 1)?  a is formed as the shadow test forms len2.  A segment of no
+// length (the light at the point itself) is not: a = 0.
+RTX_GRID_HD inline bool segment_walkable(const Grid& g, const float P[3], const float toL[3])
+{
+    const float a = toL[0] * toL[0] + toL[1] * toL[1] + toL[2] * toL[2];
+    return walkable(g, P, a);
 }
 
 struct Axis {

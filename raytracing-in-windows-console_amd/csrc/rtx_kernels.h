@@ -173,6 +173,24 @@ struct ChainShadowArgs {
     uint32_t* points;  // kMaxReflectDepth words: the hit points tested per level (one atomicAdd per workgroup and level), or nullptr
 };
 
+// Shadow tests through the world grid (RTX_OPT_SHADOW_GRID): rtx_grid_shadow, after the hits are known (the trace launch, and on
+// the mirror path rtx_reflect_hit / rtx_reflect_chain) and before the shade launch, walks every pixel's segments through the ray
+// queries' grid and leaves level 0's dark lights a word per pixel (dark0, behind everything else in the hit buffer: 4 more bytes
+// per pixel), and with `deep` the deeper levels' in ChainShadowArgs::dark as rtx_chain_shadow does.  The shade launch reads both.
+struct GridShadowArgs {
+    rtxgrid::Grid grid;
+    const uint32_t* cell_start; // the build's lists, as QueryArgs has them
+    const float4* list_geom;
+    const uint32_t* list_gidx;
+    const float4* scene_geom;   // the scene arrays in creation order, which the large list indexes
+    const float4* scene_od;
+    const uint32_t* large;
+    uint32_t n_large;
+    uint32_t deep;              // 1: the levels 1 .. ChainArgs::depth are tested too (RTX_OPT_REFLECT_SHADOWS in effect)
+    uint32_t* dark0;            // px words, laid out as the hits: bit i: light i is dark at level 0
+    uint32_t* fallback;         // the (point, light) segments that tested every sphere because they cannot be walked (atomicAdd)
+};
+
 // Ray queries (rtx_query_rays): n rays of the caller against the scene arrays in creation order (spheres are known by sphere
 // index here, not by the direction-sorted position the trace kernels use), through the world grid or against every sphere.
 struct QueryArgs {
@@ -254,6 +272,12 @@ const char* rtx_k_launch_chain_shadow(const KArgs* a, const LightsArgs* l, const
                                       int* hip_error);
 const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
                                                    int mode, void* stream, int* hip_error);
+// The grid path's launches (RTX_OPT_SHADOW_GRID): the tests (r, c, cs are read only with gs->deep), and the shade launch that reads
+// their result: r == NULL no mirror, c == NULL one bounce, cs == NULL a chain without the deeper levels' words.
+const char* rtx_k_launch_grid_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                     const GridShadowArgs* gs, void* stream, int* hip_error);
+const char* rtx_k_launch_grid_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                    const uint32_t* dark0, int mode, void* stream, int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

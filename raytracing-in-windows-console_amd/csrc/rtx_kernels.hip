@@ -1198,6 +1198,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 #include "rtx_lights_kernels.inc"
 #include "rtx_lights_chain_kernels.inc"
 #include "rtx_chain_shadow_kernels.inc"
+#include "rtx_grid_shadow_kernels.inc"
 #include "rtx_query_kernels.inc"
 
 } // namespace rtx
@@ -1491,6 +1492,44 @@ extern "C" const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, co
     return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
         hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c,
                            *cs);
+    });
+}
+
+extern "C" const char* rtx_k_launch_grid_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                                const GridShadowArgs* gs, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    *hip_error = 0;
+    dim3 grid;
+    if (!tile_grid(a, grid) || !lights_ok(l) || gs->dark0 == nullptr || gs->fallback == nullptr || gs->grid.ok == 0u || a->ns == 0u) return nullptr;
+    if (gs->deep != 0u && (!chain_ok(a, c) || cs->dark == nullptr)) return nullptr;
+    const dim3 block(kThreads, 1, 1);
+    hipLaunchKernelGGL(rtx_grid_shadow, grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c, *cs, *gs);
+    *hip_error = (int)hipGetLastError();
+    return "rtx_grid_shadow";
+}
+
+extern "C" const char* rtx_k_launch_grid_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
+                                               const uint32_t* dark0, int mode, void* stream_v, int* hip_error)
+{
+    static const ShadeNames plain("rtx_grid_shade"), mirror("rtx_grid_reflect_shade"), chain("rtx_grid_chain_shade"), deep("rtx_grid_chain_shadow_shade");
+    *hip_error = 0;
+    if (!lights_ok(l) || dark0 == nullptr) return nullptr;
+    if (c != nullptr && (r == nullptr || !chain_ok(a, c))) return nullptr;
+    if (cs != nullptr && (c == nullptr || cs->dark == nullptr)) return nullptr;
+    const ShadeNames& names = cs != nullptr ? deep : (c != nullptr ? chain : (r != nullptr ? mirror : plain));
+    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        constexpr int M = decltype(m)::value, O = decltype(o)::value;
+        hipStream_t st = (hipStream_t)stream_v;
+        if (cs != nullptr) {
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *a, *l, *r, *c, *cs, dark0);
+        } else if (c != nullptr) {
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *a, *l, *r, *c, dark0);
+        } else if (r != nullptr) {
+            hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *a, *l, *r, dark0);
+        } else {
+            hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *a, *l, dark0);
+        }
     });
 }
 

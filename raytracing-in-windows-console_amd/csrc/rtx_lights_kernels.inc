@@ -75,14 +75,22 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
 __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
                                                  float distance, V3 normal, uint32_t id, V3 cl, size_t at);
 
+// What the shade family of the grid path keeps of LightsShared (RTX_OPT_SHADOW_GRID, rtx_grid_shadow_kernels.inc): the encoder's tables.
+struct ShadeTablesShared {
+    uint32_t digits[256];
+    __attribute__((aligned(4))) uint8_t ramp[68];
+};
+
 // REFLECT 0: no mirror; 1: one bounce (ra.hits2, reflect_blend with every light at full powers); 2: a chain (ca,
 // lights_chain_blend); 3: a chain whose deeper levels were shadow-tested (RTX_OPT_REFLECT_SHADOWS: deep_dark, the words
-// rtx_chain_shadow left, laid out as the hits).  What a value does not use is not compiled.
-template <int MODE, int OUT, int REFLECT>
+// rtx_chain_shadow left, laid out as the hits).  DARK0: level 0's dark set is read from dark0 (a word per pixel, laid out as the
+// hits: rtx_grid_shadow's output) instead of computed here -- no cone, no walk, no list in LDS.  What a value does not use is not
+// compiled.
+template <int MODE, int OUT, int REFLECT, bool DARK0 = false>
 __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca,
-                                                  const uint32_t* deep_dark = nullptr)
+                                                  const uint32_t* deep_dark = nullptr, const uint32_t* dark0 = nullptr)
 {
-    __shared__ LightsShared s;
+    __shared__ std::conditional_t<DARK0, ShadeTablesShared, LightsShared> s;
 
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
@@ -91,7 +99,9 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
     if (tid < 17u) {
         reinterpret_cast<uint32_t*>(s.ramp)[tid] = reinterpret_cast<const uint32_t*>(kRamp)[tid];
     }
-    if (tid == 0u) s.cnt = 0u; // (these three: visible behind the first light's first barrier)
+    if constexpr (!DARK0) {
+        if (tid == 0u) s.cnt = 0u; // (these three: visible behind the first light's first barrier)
+    }
 
     const Camera cam = tile_camera(a);
     const TilePixel px = tile_pixel(a, cam, la.hits, tid);
@@ -113,7 +123,13 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
     // ---- the shadow test: per light self-shadow, planes and the workgroup's cone, then one walk of the scene for all lights
     const V3 P = add(ray.o, mulf(ray.d, distance)); // the point shade() lights
     const bool testable = la.test != 0u && any_hit && distance <= cam.far;
-    const uint32_t dark = lights_dark_set(a, la, s, tid, lane, wave, P, normal, id, testable); // lights this pixel is shadowed from
+    uint32_t dark; // lights this pixel is shadowed from
+    if constexpr (DARK0) {
+        dark = testable ? dark0[px.at(a)] : 0u;
+        lds_barrier(); // the encoder's tables are visible
+    } else {
+        dark = lights_dark_set(a, la, s, tid, lane, wave, P, normal, id, testable);
+    }
 
     // ---- shade with every light (both powers 0 for the lights the pixel is shadowed from) and encode
     if (any_hit) {

@@ -42,6 +42,11 @@ int build_grid(rtx_ctx* ctx)
     // the lists may still be read by the last query, on whatever stream it ran
     if (q.query_pending) RTX_HIP(ctx, hipStreamWaitEvent(st, q.ev_done, 0));
     q.query_pending = false;
+    // ... or by render launches (RTX_OPT_SHADOW_GRID), on their streams
+    for (auto& r : q.readers) {
+        if (r.pending && r.stream != st) RTX_HIP(ctx, hipStreamWaitEvent(st, r.ev, 0));
+        r.pending = false;
+    }
     q.brute = false;
     q.n_cells = q.n_large = q.pairs = 0;
     q.plan = rtxgrid::plan_grid(nullptr, nullptr, 0, 0.0f);
@@ -123,14 +128,7 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
     if (rc != RTX_OK) return rc;
     rtx_ctx::QueryGrid& g = ctx->qgrid;
     const bool brute = ctx->opt_query_check == 1;
-    if (g.dirty || !g.d_words) {
-        if ((rc = build_grid(ctx)) != RTX_OK) {
-            g.dirty = true;
-            return rc;
-        }
-    }
-    // the caller's stream is ordered after the build (and after the uploads and physics steps queued on the context's stream before it)
-    if (stream != ctx->stream) RTX_HIP(ctx, hipStreamWaitEvent(stream, g.ev_built, 0));
+    if ((rc = rtx_grid_ensure(ctx, stream)) != RTX_OK) return rc;
     QueryArgs a;
     std::memset(&a, 0, sizeof a);
     a.rays = (const float4*)d_rays;
@@ -164,9 +162,49 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
 
 } // namespace
 
+// The grid up to date, `stream` ordered after its build: what a query and a render launch on the grid path (RTX_OPT_SHADOW_GRID) share.
+int rtx_grid_ensure(rtx_ctx* ctx, hipStream_t stream)
+{
+    rtx_ctx::QueryGrid& g = ctx->qgrid;
+    if (g.dirty || !g.d_words) {
+        const int rc = build_grid(ctx);
+        if (rc != RTX_OK) {
+            g.dirty = true;
+            return rc;
+        }
+    }
+    // the caller's stream is ordered after the build (and after the uploads and physics steps queued on the context's stream before it)
+    if (stream != ctx->stream) RTX_HIP(ctx, hipStreamWaitEvent(stream, g.ev_built, 0));
+    return RTX_OK;
+}
+
+// Launches that read the lists have been queued on `stream`: the next rebuild waits for them.
+int rtx_grid_read(rtx_ctx* ctx, hipStream_t stream)
+{
+    rtx_ctx::QueryGrid& g = ctx->qgrid;
+    rtx_ctx::QueryGrid::Reader* rd = nullptr;
+    for (auto& r : g.readers) {
+        if (r.stream == stream) rd = &r;
+    }
+    if (!rd) {
+        if (g.readers.size() >= (size_t)rtx_ctx::kMaxHitStreams) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "shadow grid: more than 64 distinct render streams");
+        rtx_ctx::QueryGrid::Reader fresh;
+        fresh.stream = stream;
+        RTX_HIP(ctx, hipEventCreateWithFlags(&fresh.ev, hipEventDisableTiming));
+        g.readers.push_back(fresh);
+        rd = &g.readers.back();
+    }
+    RTX_HIP(ctx, hipEventRecord(rd->ev, stream));
+    rd->pending = true;
+    return RTX_OK;
+}
+
 void rtx_query_release(rtx_ctx* ctx)
 {
     rtx_ctx::QueryGrid& q = ctx->qgrid;
+    for (auto& r : q.readers) {
+        if (r.ev) hipEventDestroy(r.ev);
+    }
     for (DeviceArray* a : {&q.cell_count, &q.cell_fill, &q.is_large, &q.pair_tmp, &q.list_geom, &q.list_gidx}) {
         if (a->p) hipFree(a->p);
         a->p = nullptr;

@@ -581,6 +581,47 @@ bool shadow_path(const rtx_ctx* ctx, int mode)
 // Is the shading launch of either path the several-lights kernel?  A set of one light keeps rtx_shadow_shade / rtx_reflect_shade.
 bool lights_kernels(const rtx_ctx* ctx) { return ctx->n_lights >= 2 || ctx->opt_lights_check != 0; }
 
+// Is the shadow test asked to go through the world grid (RTX_OPT_SHADOW_GRID)?  By the options and the scene alone: whether the
+// grid is usable is known after its build (grid_shadow_args).  Checks 1 and 2 keep today's launches: they are the brute reference.
+bool grid_shadows_wanted(const rtx_ctx* ctx) { return ctx->opt_shadow_grid != 0 && ctx->opt_shadows != 0 && ctx->opt_shadow_check == 0 && ctx->ns != 0; }
+
+// The grid up to date for a launch set on `stream` (rtx_grid_ensure: a build blocks) and what rtx_grid_shadow reads of it.
+// *in_effect = false: no usable grid (RTX_STAT_QUERY_BRUTE), every launch is today's.
+int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool* in_effect)
+{
+    *in_effect = false;
+    std::memset(gs, 0, sizeof *gs);
+    int rc = rtx_grid_ensure(ctx, stream);
+    if (rc != RTX_OK) return rc;
+    const rtx_ctx::QueryGrid& g = ctx->qgrid;
+    if (g.brute || g.plan.ok == 0u || g.n_cells == 0u) return RTX_OK;
+    if (!ctx->d_shadow_grid_fallback) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_grid_fallback, sizeof(uint32_t)));
+    gs->grid = g.plan;
+    gs->cell_start = (const uint32_t*)g.cell_count.p;
+    gs->list_geom = (const float4*)g.list_geom.p;
+    gs->list_gidx = (const uint32_t*)g.list_gidx.p;
+    gs->scene_geom = (const float4*)ctx->d_sph_geom.p;
+    gs->scene_od = (const float4*)ctx->d_sph_od.p;
+    gs->large = g.d_large;
+    gs->n_large = g.n_large;
+    gs->fallback = ctx->d_shadow_grid_fallback;
+    *in_effect = true;
+    return RTX_OK;
+}
+
+// rtx_grid_shadow on `stream`, behind the launches that left the hits: level 0's words into gs->dark0, the deeper levels' into
+// cs->dark when gs->deep is set.
+int launch_grid_shadow(rtx_ctx* ctx, const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const ChainShadowArgs& cs,
+                       const GridShadowArgs& gs, hipStream_t stream)
+{
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback, 0, sizeof(uint32_t), stream));
+    int herr = 0;
+    const char* name = rtx_k_launch_grid_shadow(&a, &la, &ra, &ca, &cs, &gs, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow grid pass: invalid frame geometry, depth or light set");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow grid kernel launch");
+    return RTX_OK;
+}
+
 // The hit buffer of `stream` with room for `bytes` (rtx_ctx::HitScratch).  At most kMaxHitStreams distinct streams (as
 // rtx_submit_slabs' join events).  An outgrown buffer is freed (hipFree waits for the device, so no queued launch still reads it),
 // unless a recorded graph may read it: then it is kept until rtx_destroy.
@@ -667,15 +708,33 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
 int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
 {
     const size_t rows = a.row_end - a.row0;
+    const size_t px = (size_t)a.W * rows;
     void* hits = nullptr;
-    int rc = hit_buffer(ctx, stream, (size_t)a.W * rows * 8u, capturing, &hits);
-    if (rc != RTX_OK) return rc;
+    int rc;
+    GridShadowArgs gs;
+    bool grid = false; // (never while capturing: rtx_render_rows has refused)
+    if (grid_shadows_wanted(ctx) && (rc = grid_shadow_args(ctx, stream, &gs, &grid)) != RTX_OK) return rc;
+    if ((rc = hit_buffer(ctx, stream, px * (grid ? 12u : 8u), capturing, &hits)) != RTX_OK) return rc;
     if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
     int herr = 0;
     const char* name = nullptr;
-    if (lights_kernels(ctx)) {
+    if (grid) {
+        // the tests through the world grid, then the shade family that reads their words: any light set, a set of one included
+        const LightsArgs la = lights_args(ctx, hits);
+        ReflectArgs ra;
+        ChainArgs ca;
+        ChainShadowArgs cs;
+        std::memset(&ra, 0, sizeof ra);
+        std::memset(&ca, 0, sizeof ca);
+        std::memset(&cs, 0, sizeof cs);
+        gs.dark0 = (uint32_t*)((uint2*)hits + px);
+        if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
+        name = rtx_k_launch_grid_shade(&a, &la, nullptr, nullptr, nullptr, gs.dark0, mode, stream, &herr);
+        if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
+        if (name && herr == 0) ctx->stat_shadow_grid_frames++;
+    } else if (lights_kernels(ctx)) {
         const LightsArgs la = lights_args(ctx, hits);
         name = rtx_k_launch_lights_shade(&a, &la, nullptr, mode, stream, &herr);
     } else {
@@ -754,7 +813,13 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
     const size_t depth = (size_t)ctx->opt_reflect_depth;
     const size_t px = (size_t)a.W * (a.row_end - a.row0);
     void* hits = nullptr;
-    if ((rc = hit_buffer(ctx, stream, chain ? px * (8u * (depth + 1u) + (deep_shadows ? 4u : 0u)) : px * 16u, capturing, &hits)) != RTX_OK) return rc;
+    GridShadowArgs gs;
+    bool grid = false; // (never while capturing: rtx_render_rows has refused)
+    if (grid_shadows_wanted(ctx) && (rc = grid_shadow_args(ctx, stream, &gs, &grid)) != RTX_OK) return rc;
+    // (the grid path's level-0 words follow everything else: 4 more bytes per pixel)
+    const size_t hit_bytes = chain ? px * (8u * (depth + 1u) + (deep_shadows ? 4u : 0u)) : px * 16u;
+    if ((rc = hit_buffer(ctx, stream, hit_bytes + (grid ? px * 4u : 0u), capturing, &hits)) != RTX_OK) return rc;
+    gs.dark0 = grid ? (uint32_t*)((char*)hits + hit_bytes) : nullptr;
     if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
     if (!ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
     if (chain && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
@@ -787,7 +852,21 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
         if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry or depth");
         if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "reflection chain kernel launch");
         const LightsArgs la = lights_args(ctx, hits);
-        if (deep_shadows) {
+        if (grid) {
+            // rtx_grid_shadow decides level 0 and, in place of rtx_chain_shadow, the deeper levels; the grid family shades
+            ChainShadowArgs cs;
+            std::memset(&cs, 0, sizeof cs);
+            if (deep_shadows) {
+                RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
+                cs.dark = (uint32_t*)((uint2*)hits + px * (depth + 1u));
+                cs.points = ctx->d_reflect_shadow_points;
+            }
+            gs.deep = deep_shadows ? 1u : 0u;
+            if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
+            name = rtx_k_launch_grid_shade(&a, &la, &ra, &ca, deep_shadows ? &cs : nullptr, gs.dark0, mode, stream, &herr);
+            if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
+            if (name && herr == 0) ctx->stat_shadow_grid_frames++;
+        } else if (deep_shadows) {
             RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
             ChainShadowArgs cs;
             std::memset(&cs, 0, sizeof cs);
@@ -809,7 +888,17 @@ int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStr
     name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "secondary hit kernel launch");
-    if (lights_kernels(ctx)) {
+    if (grid) {
+        const LightsArgs la = lights_args(ctx, hits);
+        ChainArgs ca;
+        ChainShadowArgs cs;
+        std::memset(&ca, 0, sizeof ca);
+        std::memset(&cs, 0, sizeof cs);
+        if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
+        name = rtx_k_launch_grid_shade(&a, &la, &ra, nullptr, nullptr, gs.dark0, mode, stream, &herr);
+        if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
+        if (name && herr == 0) ctx->stat_shadow_grid_frames++;
+    } else if (lights_kernels(ctx)) {
         const LightsArgs la = lights_args(ctx, hits);
         name = rtx_k_launch_lights_shade(&a, &la, &ra, mode, stream, &herr);
     } else {
@@ -1228,6 +1317,10 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
     bool capturing = false;
     if ((rc = check_recordable(ctx, stream, &capturing)) != RTX_OK) return rc;
+    if (capturing && grid_shadows_wanted(ctx) && (shadow_path(ctx, mode) || reflect_path(ctx, mode))) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID: "
+                                                       "the lists change with physics, and their build allocates and waits)");
+    }
     if (capturing && c.own) {
         // the zero-fill of the context's buffer is decided from what earlier launches left in it (dirty_hi): a recorded
         // launch would replay that decision whatever the replays in between have written
@@ -1338,6 +1431,9 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
         bool capturing = false;
         const int rc = check_recordable(ctx, join, &capturing);
         if (rc != RTX_OK) return rc;
+        if (capturing && grid_shadows_wanted(ctx) && (shadow_path(ctx, mode) || reflect_path(ctx, mode))) {
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID)");
+        }
     }
     // distinct render streams of this call, each with its event
     std::vector<rtx_ctx::JoinEvent*> used;
