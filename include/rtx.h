@@ -301,6 +301,13 @@ enum rtx_stat {
                                      * is low + (float)i * size, each operation rounded to fp32 */
     RTX_STAT_LIGHTS = 137,          /* lights in the set (rtx_scene_set_lights): 1 .. RTX_MAX_LIGHTS.  No reference counterpart
                                      * (RayTracing.cu:132,143-157) */
+    RTX_STAT_SCENE_EDITS = 148,     /* rtx_scene_set_spheres, rtx_scene_set_spheres_device and rtx_scene_set_plane calls that changed something
+                                     * (not the refused ones, not n == 0); every member of a device group counts its own, alike.
+                                     * No reference counterpart beyond Object3D.cu:34 */
+    RTX_STAT_SCENE_EDIT_MOVE = 149, /* the fp32 bits of the displacement bound of the last sphere edit: no centre moved further (formed
+                                     * in double on the device, rounded up); 0x7f800000 (+inf) when that edit counted as a full change of
+                                     * geometry (a radius changed, or a move that is no finite float); 0 after a colour-only edit.
+                                     * No reference counterpart beyond Object3D.cu:34 */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -386,7 +393,8 @@ int rtx_set_option(rtx_ctx* ctx, int option, int64_t value);
 int rtx_get_option(const rtx_ctx* ctx, int option, int64_t* value);
 
 /* ---- scene: Scene3D::CreateSphere / CreatePlane / GetObjects (Scene3D.h:15-25, Scene3D.cpp:36-105).
- * Append-only; creation order is the closest-hit tie-break order (RayTracing.cu:100-136).
+ * Objects are appended, never removed one by one (rtx_scene_set_spheres / rtx_scene_set_plane edit them in place); creation order is
+ * the closest-hit tie-break order (RayTracing.cu:100-136).
  * No 5 MB arena cap (Scene3D.h:6).  The add calls return the new object's index (>= 0) or -status. */
 int rtx_scene_clear(rtx_ctx* ctx);
 int rtx_scene_add_sphere(rtx_ctx* ctx, const float pos[3], float radius, const float rgb[3]);
@@ -469,6 +477,40 @@ int rtx_scene_set_sphere_motion(rtx_ctx* ctx, unsigned index, int mover, float s
 /* Reads object `index` back from the device store: type (1 plane, 2 sphere, Object3D.h:14) and
  * 11 floats (sphere: cx cy cz r R G B mover speed 0 0; plane: px py pz nx ny nz R G B w h). */
 int rtx_scene_get_object(rtx_ctx* ctx, unsigned index, int* type, float out[11]);
+/* Edits spheres in place: objects first .. first+n-1 (creation indices, as the add calls return them; every one a sphere) take the
+ * centre, radius and colour of their row of 7 floats (cx cy cz r R G B, the rows of rtx_scene_add_spheres; any float is accepted,
+ * as the add calls accept any).  The state afterwards is that of a context built by the same add calls in the same order with
+ * these values -- od = rgb / 255.0f by the same IEEE division -- and every later launch on every path gives that context's bytes.
+ * Unchanged: the creation index (the tie-break), mover and speed, the reflectivity, the light set, every option, the object
+ * counts and the array addresses -- recorded graphs stay valid and replay with the new values, as after rtx_update_objects.
+ * All or nothing: a range past rtx_scene_count or an index in it that is a plane changes nothing and returns
+ * RTX_ERR_INVALID_ARGUMENT (rtx_last_error names the first index that is not a sphere); so does a NULL pointer with n > 0, and
+ * a call inside a graph capture on the context's stream (the call waits).  n == 0: RTX_OK, nothing is launched.
+ * The call uploads pending appends, makes the context's stream wait for cell-list builds in flight, runs rtx_write_spheres on
+ * the context's stream and returns when the edit has been applied; it waits for the device once.  Like every scene change it
+ * must not race with frames in flight on other streams.  What it costs later launches: the world grid is rebuilt (as after
+ * rtx_update_objects); cell lists and dispatch orders see the largest displacement of a centre exactly as they see a physics
+ * step of that size (RTX_STAT_SCENE_EDIT_MOVE; a colour-only edit costs nothing), unless a radius changed or a move is no finite
+ * float: then the cell lists are rebuilt and the orders start over.  A new cy outside [-10, 10] makes the next physics step count
+ * as the first after an edit (it may pull the sphere onto +-10 from anywhere).  On a device group: validated on the root before
+ * any rank is touched, then applied to every rank.  No reference counterpart beyond Object3D.cu:34 (Object3D::SetMiddlePos,
+ * Object3D.h:55, which the reference never calls after upload). */
+int rtx_scene_set_spheres(rtx_ctx* ctx, unsigned first, size_t n, const float* xyzr_rgb);
+/* The same with the rows in device memory of the caller (4-byte aligned, on the context's device; a group's root's), for
+ * positions that come out of the caller's own kernels.  `stream` is a hipStream_t (NULL = the context's stream): the edit is
+ * ordered after everything queued on it so far, runs on the context's stream and has been applied when the call returns; a
+ * capture on either stream is refused.  The rows never come to the host, so the next direction sort (RTX_OPT_SORTED_STORE)
+ * still orders by the centres the spheres were created or last edited from the host with: a speed matter only.  On a device
+ * group the rows are copied to every other rank (hipMemcpyPeerAsync), behind `stream`.  No reference counterpart beyond
+ * Object3D.cu:34. */
+int rtx_scene_set_spheres_device(rtx_ctx* ctx, unsigned first, size_t n, const float* d_xyzr_rgb, void* stream);
+/* Replaces every field of plane `index` (a creation index that is a plane; anything else: RTX_ERR_INVALID_ARGUMENT, nothing
+ * changes) with what rtx_scene_add_plane would have stored for these arguments: the same safe normalise, the same od, the
+ * creation index kept.  Blocking (four 16-byte uploads on the context's stream); not inside a graph capture.  Cell lists and the
+ * world grid hold spheres only and stay valid; dispatch orders start over.  Reflectivity and everything else that
+ * rtx_scene_set_spheres leaves alone stays.  No reference counterpart beyond Object3D.cu:34. */
+int rtx_scene_set_plane(rtx_ctx* ctx, unsigned index, const float pos[3], const float normal[3],
+                        const float rgb[3], float width, float height);
 
 /* ---- render: RayTracing::RayTrace (RayTracing.h:31-38, RayTracing.cu:797-867) together with the
  * zero-fill that precedes it in RayTracingManager::Update (RayTracingManager.cu:86).

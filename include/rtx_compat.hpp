@@ -413,6 +413,22 @@ public:
         check(rtx_get_option(ctx(), RTX_OPT_REFLECT_DEPTH, &v), "RTX_OPT_REFLECT_DEPTH");
         return (int)v;
     }
+    // Objects edited in place, by creation index.  The reference has the seam -- Object3D::SetMiddlePos (Object3D.h:55,
+    // Object3D.cu:34) -- and never calls it after upload; here a sphere takes a new centre, radius and colour (rtx_scene_set_spheres:
+    // rows of cx cy cz r R G B for first .. first+n-1), a plane all its fields (rtx_scene_set_plane).  Mover, speed, reflectivity
+    // and the creation order stay.
+    void SetSphere(const unsigned index, const float radius, const MyMath::Vector3& middlePos, const MyMath::Vector3& color)
+    {
+        const float row[7] = {middlePos.x, middlePos.y, middlePos.z, radius, color.x, color.y, color.z};
+        check(rtx_scene_set_spheres(ctx(), index, 1, row), "rtx_scene_set_spheres");
+    }
+    void SetSpheres(const unsigned first, const size_t n, const float* xyzr_rgb) { check(rtx_scene_set_spheres(ctx(), first, n, xyzr_rgb), "rtx_scene_set_spheres"); }
+    void SetPlane(const unsigned index, const MyMath::Vector3& middlePos, const MyMath::Vector3& normal, const MyMath::Vector3& color,
+                  const float width, const float height)
+    {
+        const float p[3] = {middlePos.x, middlePos.y, middlePos.z}, n[3] = {normal.x, normal.y, normal.z}, c[3] = {color.x, color.y, color.z};
+        check(rtx_scene_set_plane(ctx(), index, p, n, c, width, height), "rtx_scene_set_plane");
+    }
     DeviceObjectArray<Object3D*> GetObjects()
     {
         DeviceObjectArray<Object3D*> a;

@@ -50,6 +50,7 @@ OPT_REFLECT_SHADOWS = 28
 OPT_SHADOW_GRID = 29
 STAT_SHADOW_GRID_FRAMES = 146
 STAT_SHADOW_GRID_FALLBACK_POINTS = 147
+STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
@@ -135,6 +136,9 @@ _SIGNATURES = [
     ("rtx_scene_count", C.c_uint, [_P]),
     ("rtx_scene_set_sphere_motion", C.c_int, [_P, C.c_uint, C.c_int, C.c_float]),
     ("rtx_scene_get_object", C.c_int, [_P, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    ("rtx_scene_set_spheres", C.c_int, [_P, C.c_uint, C.c_size_t, _P]),
+    ("rtx_scene_set_spheres_device", C.c_int, [_P, C.c_uint, C.c_size_t, _P, _P]),
+    ("rtx_scene_set_plane", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]),
     ("rtx_scene_set_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_get_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_set_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light)]),
@@ -384,6 +388,21 @@ class Context:
         out = (C.c_float * 11)()
         self._check(lib().rtx_scene_get_object(self._h, index, C.byref(t), out))
         return t.value, np.array(out[:], dtype=np.float32)
+
+    def set_spheres(self, first, arr):
+        """rtx_scene_set_spheres: rows of 7 floats (cx cy cz r R G B) for spheres first, first+1, ... (creation indices), in place."""
+        arr = np.ascontiguousarray(arr, dtype=np.float32).reshape(-1, 7)
+        self._check(lib().rtx_scene_set_spheres(self._h, first, arr.shape[0], arr.ctypes.data if arr.shape[0] else None))
+
+    def set_spheres_device(self, first, n, d_ptr, stream=None):
+        """rtx_scene_set_spheres_device: the same from n rows in device memory (e.g. a float32 torch tensor's data_ptr()), ordered
+        after what `stream` (a hipStream_t; None: the context's) holds.  Blocking."""
+        self._check(lib().rtx_scene_set_spheres_device(self._h, first, n, d_ptr, stream))
+
+    def set_plane(self, index, pos, normal, color, width, height):
+        """rtx_scene_set_plane: every field of plane `index`, as add_plane would have stored it."""
+        self._check(lib().rtx_scene_set_plane(self._h, index, (C.c_float * 3)(*pos), (C.c_float * 3)(*normal),
+                                              (C.c_float * 3)(*color), width, height))
 
     def set_light(self, light=None):
         """rtx_scene_set_light (None: the reference's light)."""

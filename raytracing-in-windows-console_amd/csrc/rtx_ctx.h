@@ -211,7 +211,8 @@ struct rtx_ctx {
 
     hipStream_t aux_stream = nullptr; // the balancing passes' stream (created with the first pass)
     double scene_drift = 0.0;        // how far any sphere can have moved since the context was created (rtx_update_objects:
-                                     // |dt| x the largest |speed x mover|; scene edits add 1e3): dispatch orders go stale with it
+                                     // |dt| x the largest |speed x mover|; rtx_scene_set_spheres: the largest move; other scene edits add 1e3):
+                                     // dispatch orders go stale with it
     float max_speed = 0.0f;          // largest |speed * mover| any sphere was given: what a physics step moves it by per unit of dt
     int64_t opt_batch = -1;         // -1 auto (on), 0 off: rtx_submit_slabs renders consecutive slabs of one stream with one launch
     uint64_t stat_batched_launches = 0;
@@ -336,6 +337,16 @@ struct rtx_ctx {
     uint64_t stat_shadow_grid_frames = 0;
     uint32_t* d_shadow_grid_fallback = nullptr; // segments of the last launch set on the path that tested every sphere (one word)
 
+    // objects edited in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane; rtx_post.hip): rows that
+    // come from the host, or from another member of a device group, are staged in d_edit_rows (floats; grown by doubling);
+    // rtx_write_spheres leaves its two result words in d_edit_result, which the call copies to the pinned pair and waits for
+    DeviceArray d_edit_rows;
+    uint32_t* d_edit_result = nullptr;
+    uint32_t* h_edit_result = nullptr;
+    hipEvent_t ev_edit = nullptr;       // orders a device-form edit after what the caller's stream holds
+    uint64_t stat_scene_edits = 0;      // edit calls that changed something
+    uint32_t stat_edit_move_bits = 0;   // RTX_STAT_SCENE_EDIT_MOVE
+
     std::string error;
     const char* last_kernel = "";
 };
@@ -347,6 +358,11 @@ int rtx_hip_fail(rtx_ctx* ctx, hipError_t e, const char* what);
 int rtx_sync_scene(rtx_ctx* ctx);
 void rtx_scene_edited(rtx_ctx* ctx);
 int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip
+// rtx_post.hip: the rows of an edit in place -> spheres first .. first+n-1 of THIS context alone (a validated range of creation
+// indices, n > 0, not inside a capture), blocking.  `rows` is host memory (src_device < 0; h_centres follows) or device memory of
+// src_device: read in place, or copied into the context's scratch first (`stage`: a group member's copy of the root's rows).
+// `after`, if not null, is an event the edit is ordered behind.
+int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* rows, int src_device, bool stage, hipEvent_t after);
 void rtx_query_release(rtx_ctx* ctx);                    // rtx_query.cpp: frees the grid (rtx_destroy)
 // rtx_query.cpp: the world grid for a launch on `stream` that reads its lists -- the one grid object the queries use, brought up to date
 // if the scene changed since its last build (a build blocks, as a query's does, and counts in RTX_STAT_QUERY_GRID_BUILDS); `stream` is

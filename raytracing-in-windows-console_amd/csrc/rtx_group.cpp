@@ -497,6 +497,40 @@ int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float*
     return RTX_OK;
 }
 
+int scene_set_spheres(rtx_ctx* root, unsigned first, size_t n, const float* rows)
+{
+    rtx_group* g = root->group;
+    for (int r = 1; r < g->n; r++) {
+        const int rc = rtx_scene_set_spheres(g->member[(size_t)r], first, n, rows);
+        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return RTX_OK;
+}
+
+int scene_set_spheres_device(rtx_ctx* root, unsigned first, size_t n, const float* d_rows, hipEvent_t after)
+{
+    rtx_group* g = root->group;
+    // every member keeps its own books from its own result words: the same values, so the same decisions
+    for (int r = 1; r < g->n; r++) {
+        const int rc = rtx_edit_spheres_here(g->member[(size_t)r], first, n, d_rows, root->device, true, after);
+        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return RTX_OK;
+}
+
+int scene_set_plane(rtx_ctx* root, unsigned index, const float pos[3], const float normal[3], const float rgb[3], float width, float height)
+{
+    rtx_group* g = root->group;
+    for (int r = 1; r < g->n; r++) {
+        const int rc = rtx_scene_set_plane(g->member[(size_t)r], index, pos, normal, rgb, width, height);
+        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return RTX_OK;
+}
+
 int set_option(rtx_ctx* root, int option, int64_t value)
 {
     rtx_group* g = root->group;

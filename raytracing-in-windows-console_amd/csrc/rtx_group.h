@@ -28,6 +28,12 @@ int scene_add_plane(rtx_ctx* root, const float pos[3], const float normal[3], co
 int scene_set_sphere_motion(rtx_ctx* root, unsigned index, int mover, float speed);
 int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights);
 int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k); // (the root has validated and applied it)
+// edits in place (the root has validated the range and applied the edit to itself): the host form calls every member; the device
+// form copies the rows from the root's device into every other member's scratch, behind `after` (an event on the caller's stream),
+// and runs the kernel there -- logical ranks on the root's own GPU take the same path
+int scene_set_spheres(rtx_ctx* root, unsigned first, size_t n, const float* rows);
+int scene_set_spheres_device(rtx_ctx* root, unsigned first, size_t n, const float* d_rows, hipEvent_t after);
+int scene_set_plane(rtx_ctx* root, unsigned index, const float pos[3], const float normal[3], const float rgb[3], float width, float height);
 int set_option(rtx_ctx* root, int option, int64_t value);
 int update_objects(rtx_ctx* root, double dt); // every member steps its own replica (the same arithmetic on the same values)
 

@@ -894,4 +894,29 @@ private:
     int still_frames_ = 0;
 };
 
+// ------------------------------------------------------------------------------------------------ scene edits in place
+
+// What an edit of spheres in place (rtx_scene_set_spheres) means for the state above, from the two words rtx_write_spheres leaves:
+// `move`, an upper bound on how far any centre went, and `flags` (bit 0 a radius changed, bit 1 a move that is no finite number,
+// bit 2 a new cy outside [-10, 10]).  A move alone is motion: the cell lists' delta and the dispatch orders see it exactly as
+// they see a physics step of that size (drift_add; a colour-only edit adds 0).  A changed radius is NOT motion -- the lists'
+// position budget is margin(r, .) of the r they were built with (the soundness note above) -- and neither is a move without a
+// bound: then the lists are invalid and the drift grows as by any scene edit.  A sphere put outside [-10, 10] may be pulled
+// onto +-10 from anywhere by the next physics step (Sphere.cu:18-22), which therefore counts as the first step after an edit.
+struct EditEffect {
+    double drift_add = 0.0;
+    bool invalidate_lists = false;
+    bool unsettle_physics = false;
+};
+
+inline EditEffect edit_effect(float move, unsigned flags)
+{
+    EditEffect e;
+    const bool bounded = std::isfinite(move) && move >= 0.0f;
+    e.invalidate_lists = (flags & 3u) != 0u || !bounded;
+    e.drift_add = e.invalidate_lists ? 1.0e3 : (double)move;
+    e.unsettle_physics = (flags & 4u) != 0u;
+    return e;
+}
+
 } // namespace rtxplan

@@ -1,6 +1,8 @@
 // rtx_post.hip -- what RayTracingManager::Update runs around the trace kernel, on the GPU:
 // UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319),
 // plus rtx_update, the whole of Update in one call.
+// Also the edits of scene objects in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane): their kernel sits
+// beside the physics step's, which moves the same arrays.
 #include "rtx_ctx.h"
 #include "rtx_group.h"
 #include "rtx_device.hpp"
@@ -9,6 +11,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "rtx_post_kernels.inc" // namespace rtx: the kernels launched below
@@ -355,9 +358,175 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
     return RTX_OK;
 }
 
+// rtx_scene_set_spheres*: is [first, first + n) a run of spheres?  (Then it is a run of consecutive sphere indices too.)
+int check_sphere_range(rtx_ctx* ctx, const char* who, unsigned first, size_t n)
+{
+    if (first > ctx->next_gidx || n > (size_t)(ctx->next_gidx - first)) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": the range goes past rtx_scene_count");
+    }
+    for (size_t i = 0; i < n; i++) {
+        if (ctx->kind_of[first + i] != 2) {
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": object " + std::to_string(first + i) + " is not a sphere");
+        }
+    }
+    return RTX_OK;
+}
+
+// an edit waits for its result: not inside a graph capture, on either stream
+int check_not_capturing(rtx_ctx* ctx, const char* who, hipStream_t other)
+{
+    for (hipStream_t s : {ctx->stream, other}) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        RTX_HIP(ctx, hipStreamIsCapturing(s, &cs));
+        if (cs != hipStreamCaptureStatusNone) {
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, std::string(who) + ": not inside a graph capture (the call waits for the edit)");
+        }
+    }
+    return RTX_OK;
+}
+
 } // namespace
 
+int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* rows, int src_device, bool stage, hipEvent_t after)
+{
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = rtx_sync_scene(ctx);
+    if (rc != RTX_OK) return rc;
+    // cell lists being built ahead of time on the side stream read the spheres: the edit waits for them (as a physics step does)
+    for (auto& sl : ctx->cell_cache) {
+        if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
+    }
+    if (after) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, after, 0));
+    if (!ctx->d_edit_result) {
+        RTX_HIP(ctx, hipMalloc((void**)&ctx->d_edit_result, 2 * sizeof(uint32_t)));
+        RTX_HIP(ctx, hipHostMalloc((void**)&ctx->h_edit_result, 2 * sizeof(uint32_t), hipHostMallocDefault));
+    }
+    const float* d_rows = rows;
+    if (src_device < 0 || stage) {
+        const size_t need = 7 * n;
+        if (ctx->d_edit_rows.cap < need) {
+            // (every earlier edit has been waited for: nothing reads the old scratch)
+            size_t cap = ctx->d_edit_rows.cap ? ctx->d_edit_rows.cap : 7 * 1024;
+            while (cap < need) cap *= 2;
+            void* p = nullptr;
+            if (hipMalloc(&p, cap * sizeof(float)) != hipSuccess) {
+                (void)hipGetLastError();
+                return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the scene edit scratch");
+            }
+            if (ctx->d_edit_rows.p) hipFree(ctx->d_edit_rows.p);
+            ctx->d_edit_rows.p = p;
+            ctx->d_edit_rows.cap = cap;
+        }
+        if (src_device < 0) {
+            RTX_HIP(ctx, hipMemcpyAsync(ctx->d_edit_rows.p, rows, need * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            RTX_HIP(ctx, hipMemcpyPeerAsync(ctx->d_edit_rows.p, ctx->device, rows, src_device, need * sizeof(float), ctx->stream));
+        }
+        d_rows = (const float*)ctx->d_edit_rows.p;
+    }
+    const uint32_t k0 = ctx->local_of[first];
+    const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.p != nullptr;
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_edit_result, 0, 2 * sizeof(uint32_t), ctx->stream));
+    const unsigned blocks = (unsigned)((n + rtx::kThreads - 1) / rtx::kThreads);
+    hipLaunchKernelGGL(rtx::rtx_write_spheres, dim3(blocks), dim3(rtx::kThreads), 0, ctx->stream, d_rows, k0, (uint32_t)n,
+                       (float4*)ctx->d_sph_geom.p, (float4*)ctx->d_sph_color.p, (float4*)ctx->d_sph_od.p,
+                       sorted ? (float4*)ctx->d_sorted_geom.p : nullptr, sorted ? (float4*)ctx->d_sorted_od.p : nullptr,
+                       sorted ? (const uint32_t*)ctx->d_pos_of.p : nullptr, ctx->d_edit_result);
+    RTX_HIP(ctx, hipGetLastError());
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_edit_result, ctx->d_edit_result, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the one wait: the edit is applied, the rows are free, the words are here
+    const uint32_t flags = ctx->h_edit_result[1];
+    const rtxplan::EditEffect eff = rtxplan::edit_effect(bits_to_float(ctx->h_edit_result[0]), flags);
+    ctx->qgrid.dirty = true; // (the world grid lists spheres where they were)
+    ctx->ns_moved_since_build = true;
+    ctx->stat_scene_edits++;
+    if (eff.invalidate_lists) {
+        // the branch rtx_update_objects takes for its first step after an edit; scene_gen stays: object counts and array addresses
+        // are what they were, recorded graphs stay valid and replay with the new values
+        ctx->lists_gen++;
+        ctx->cell_policy.invalidate();
+        ctx->stat_edit_move_bits = 0x7f800000u;
+    } else {
+        ctx->stat_edit_move_bits = ctx->h_edit_result[0];
+    }
+    ctx->scene_drift += eff.drift_add;
+    if (eff.unsettle_physics) ctx->physics_settled = false;
+    if (src_device < 0) {
+        // the sort's input at the next re-sort.  The device form leaves h_centres as they are: the order is a speed matter only
+        // (ties are broken by creation index in any order), and the rows never come to the host
+        for (size_t i = 0; i < n && (size_t)k0 + i < ctx->h_centres.size(); i++) {
+            ctx->h_centres[(size_t)k0 + i] = make_float4(rows[7 * i], rows[7 * i + 1], rows[7 * i + 2], rows[7 * i + 3]);
+        }
+    }
+    return RTX_OK;
+}
+
 extern "C" {
+
+int rtx_scene_set_spheres(rtx_ctx* ctx, unsigned first, size_t n, const float* xyzr_rgb)
+{
+    if (!ctx || (n && !xyzr_rgb)) return ctx ? rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_spheres: the rows are NULL") : RTX_ERR_INVALID_ARGUMENT;
+    // all or nothing: the range is checked before anything is touched (and, on a group, before any rank is)
+    int rc = check_sphere_range(ctx, "rtx_scene_set_spheres", first, n);
+    if (rc != RTX_OK || n == 0) return rc;
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_not_capturing(ctx, "rtx_scene_set_spheres", ctx->stream)) != RTX_OK) return rc;
+    if ((rc = rtx_edit_spheres_here(ctx, first, n, xyzr_rgb, -1, false, nullptr)) != RTX_OK) return rc;
+    return ctx->group ? rtxgroup::scene_set_spheres(ctx, first, n, xyzr_rgb) : RTX_OK;
+}
+
+int rtx_scene_set_spheres_device(rtx_ctx* ctx, unsigned first, size_t n, const float* d_xyzr_rgb, void* stream_v)
+{
+    if (!ctx || (n && !d_xyzr_rgb)) return ctx ? rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_spheres_device: the rows are NULL") : RTX_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)d_xyzr_rgb & 3u) != 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_spheres_device: the rows must be 4-byte aligned");
+    int rc = check_sphere_range(ctx, "rtx_scene_set_spheres_device", first, n);
+    if (rc != RTX_OK || n == 0) return rc;
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
+    if ((rc = check_not_capturing(ctx, "rtx_scene_set_spheres_device", st)) != RTX_OK) return rc;
+    // after everything queued so far on the caller's stream (the kernel that wrote the rows); a group's members wait for it too
+    hipEvent_t after = nullptr;
+    if (st != ctx->stream || ctx->group) {
+        if (!ctx->ev_edit) RTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_edit, hipEventDisableTiming));
+        RTX_HIP(ctx, hipEventRecord(ctx->ev_edit, st));
+        after = ctx->ev_edit;
+    }
+    if ((rc = rtx_edit_spheres_here(ctx, first, n, d_xyzr_rgb, ctx->device, false, st != ctx->stream ? after : nullptr)) != RTX_OK) return rc;
+    return ctx->group ? rtxgroup::scene_set_spheres_device(ctx, first, n, d_xyzr_rgb, after) : RTX_OK;
+}
+
+int rtx_scene_set_plane(rtx_ctx* ctx, unsigned index, const float pos[3], const float normal[3], const float rgb[3], float width, float height)
+{
+    if (!ctx) return RTX_ERR_INVALID_ARGUMENT;
+    if (!pos || !normal || !rgb) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_plane: a NULL argument");
+    if (index >= ctx->next_gidx || ctx->kind_of[index] != 1) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_set_plane: object " + std::to_string(index) + " is not a plane");
+    }
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = check_not_capturing(ctx, "rtx_scene_set_plane", ctx->stream);
+    if (rc != RTX_OK) return rc;
+    if ((rc = rtx_sync_scene(ctx)) != RTX_OK) return rc;
+    // what rtx_scene_add_plane stores: the safe host normalise of Plane::Plane (Plane.cu:6-12, MyMath.h:117-123), od by the same
+    // IEEE division, the creation index kept in the .w words
+    const float length = std::sqrt(normal[0] * normal[0] + normal[1] * normal[1] + normal[2] * normal[2]);
+    const float divider = length < 0.000001f ? 0.0f : 1.0f / length;
+    const float4 a = make_float4(pos[0], pos[1], pos[2], width);
+    const float4 b = make_float4(normal[0] * divider, normal[1] * divider, normal[2] * divider, height);
+    const float4 c = make_float4(rgb[0], rgb[1], rgb[2], bits_to_float(index));
+    const float4 od = make_float4(rgb[0] / 255.0f, rgb[1] / 255.0f, rgb[2] / 255.0f, bits_to_float(index));
+    const uint32_t k = ctx->local_of[index];
+    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_a.p + k, &a, sizeof a, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_b.p + k, &b, sizeof b, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_c.p + k, &c, sizeof c, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_od.p + k, &od, sizeof od, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // Cell lists hold spheres only and stay valid; the dispatch orders' estimates are stale.  qgrid.dirty is left as it is: the
+    // world grid (rtx_grid.hpp, the build in rtx_query.cpp) lists spheres and takes its bounds from spheres alone -- the query and
+    // shadow kernels read the plane arrays themselves at every launch, so nothing of a plane is cached in it.
+    ctx->scene_drift += 1.0e3;
+    ctx->stat_scene_edits++;
+    return ctx->group ? rtxgroup::scene_set_plane(ctx, index, pos, normal, rgb, width, height) : RTX_OK;
+}
 
 int rtx_update_objects(rtx_ctx* ctx, double dt)
 {

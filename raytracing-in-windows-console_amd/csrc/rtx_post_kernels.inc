@@ -36,6 +36,80 @@ __global__ __launch_bounds__(kThreads) void rtx_update_spheres(float4* geom, flo
     }
 }
 
+// ---------------------------------------------------------------- rtx_scene_set_spheres
+// Object3D::SetMiddlePos (Object3D.cu:34), which the reference never calls after upload, for a run of spheres: sphere first + j
+// takes centre, radius and colour of row j of `rows` (7 floats, cx cy cz r R G B; 4-byte aligned device memory).  One sphere per
+// thread; a block's rows are loaded as consecutive dwords into LDS first (a lane's own seven are 28 bytes apart in memory; in LDS
+// the stride of 7 dwords is odd against 64 banks: no conflicts).  The .w words of color / od (the creation index) stay; od is the
+// IEEE division rtx_scene_add_sphere does on the host (-fno-fast-math: the compiler's `/`, tests/test_gpu_div.py).
+// The old geometry lives only here (physics moves it), so the bound on how far anything moved is formed here as well:
+// result[0] = the bits of the largest |new centre - old centre|, formed in double and rounded UP to float (atomicMax on the bits:
+// order-preserving for floats >= 0), result[1] = flags ORed over the spheres: bit 0 a radius changed (NaN counts), bit 1 a move
+// that is no finite float (it then adds 0 to the maximum), bit 2 a new cy outside [-10, 10] (NaN counts).  Both zeroed by the host.
+__global__ __launch_bounds__(kThreads) void rtx_write_spheres(const float* rows, uint32_t first, uint32_t n, float4* geom, float4* color, float4* od,
+                                                              float4* sorted_geom, float4* sorted_od, const uint32_t* pos_of, uint32_t* result)
+{
+    __shared__ float s_rows[kThreads * 7];
+    const uint32_t base = blockIdx.x * kThreads;
+    const uint32_t here = n - base < (uint32_t)kThreads ? n - base : (uint32_t)kThreads; // (the tail block)
+    const float* src = rows + (size_t)base * 7u;
+    for (uint32_t k = threadIdx.x; k < here * 7u; k += kThreads) {
+        s_rows[k] = src[k];
+    }
+    __syncthreads();
+    uint32_t move_bits = 0u, flags = 0u;
+    if (threadIdx.x < here) {
+        const uint32_t i = first + base + threadIdx.x;
+        const float* v = s_rows + threadIdx.x * 7u;
+        const float4 g = make_float4(v[0], v[1], v[2], v[3]);
+        const float4 old = geom[i];
+        const double dx = (double)g.x - (double)old.x, dy = (double)g.y - (double)old.y, dz = (double)g.z - (double)old.z;
+        // a few double ulps up, so that whatever the last bit of the device's sqrt, the float below is no less than the true length
+        const double move = sqrt(dx * dx + dy * dy + dz * dz) * (1.0 + 0x1p-50);
+        float up = (float)move;
+        if ((double)up < move) {
+            up = __uint_as_float(__float_as_uint(up) + 1u); // (up >= 0: the next float up; the largest float goes to +inf)
+        }
+        if (!(move == move) || !(up < __uint_as_float(0x7f800000u))) {
+            flags |= 2u;
+        } else {
+            move_bits = __float_as_uint(up);
+        }
+        flags |= (g.w != old.w) ? 1u : 0u;
+        flags |= (g.y >= -10.0f && g.y <= 10.0f) ? 0u : 4u;
+        float4 c = color[i], o = od[i];
+        c.x = v[4];
+        c.y = v[5];
+        c.z = v[6];
+        o.x = v[4] / 255.0f;
+        o.y = v[5] / 255.0f;
+        o.z = v[6] / 255.0f;
+        geom[i] = g;
+        color[i] = c;
+        od[i] = o;
+        if (sorted_geom != nullptr) {
+            const uint32_t p = pos_of[i];
+            float4 so = sorted_od[p];
+            so.x = o.x;
+            so.y = o.y;
+            so.z = o.z;
+            sorted_geom[p] = g; // the direction-sorted copy staging reads (rtx_sort_scene) takes the edit too
+            sorted_od[p] = so;
+        }
+    }
+    // one atomic pair per wave (wave64: kThreads is a multiple of 64 and no lane has left)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) {
+        const uint32_t m = (uint32_t)__shfl_xor((int)move_bits, s);
+        flags |= (uint32_t)__shfl_xor((int)flags, s);
+        move_bits = m > move_bits ? m : move_bits;
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+        if (move_bits != 0u) atomicMax(&result[0], move_bits);
+        if (flags != 0u) atomicOr(&result[1], flags);
+    }
+}
+
 // sorted[p] = geom[order[p]]: the direction-sorted copy of the sphere array, from the live one.
 __global__ __launch_bounds__(kThreads) void rtx_gather_spheres(const float4* geom, const float4* od, const uint32_t* order, float4* sorted_geom,
                                                                float4* sorted_od, uint32_t ns)
