@@ -308,6 +308,9 @@ enum rtx_stat {
                                      * in double on the device, rounded up); 0x7f800000 (+inf) when that edit counted as a full change of
                                      * geometry (a radius changed, or a move that is no finite float); 0 after a colour-only edit.
                                      * No reference counterpart beyond Object3D.cu:34 */
+    RTX_STAT_SCENE_REMOVED = 150,   /* objects removed so far by rtx_scene_remove_objects / rtx_scene_remove_marked_device calls that succeeded
+                                     * (|R| per call); every member of a device group counts its own, alike.  No reference
+                                     * counterpart (Scene3D.h:15-25 creates objects, Scene3D::CleanUp frees all of them at once) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -393,8 +396,9 @@ int rtx_set_option(rtx_ctx* ctx, int option, int64_t value);
 int rtx_get_option(const rtx_ctx* ctx, int option, int64_t* value);
 
 /* ---- scene: Scene3D::CreateSphere / CreatePlane / GetObjects (Scene3D.h:15-25, Scene3D.cpp:36-105).
- * Objects are appended, never removed one by one (rtx_scene_set_spheres / rtx_scene_set_plane edit them in place); creation order is
- * the closest-hit tie-break order (RayTracing.cu:100-136).
+ * Objects are appended (here), edited in place (rtx_scene_set_spheres / rtx_scene_set_plane) and removed one by one or in sets
+ * (rtx_scene_remove_objects, which renumbers the survivors); creation order is the closest-hit tie-break order
+ * (RayTracing.cu:100-136).
  * No 5 MB arena cap (Scene3D.h:6).  The add calls return the new object's index (>= 0) or -status. */
 int rtx_scene_clear(rtx_ctx* ctx);
 int rtx_scene_add_sphere(rtx_ctx* ctx, const float pos[3], float radius, const float rgb[3]);
@@ -511,6 +515,39 @@ int rtx_scene_set_spheres_device(rtx_ctx* ctx, unsigned first, size_t n, const f
  * rtx_scene_set_spheres leaves alone stays.  No reference counterpart beyond Object3D.cu:34. */
 int rtx_scene_set_plane(rtx_ctx* ctx, unsigned index, const float pos[3], const float normal[3],
                         const float rgb[3], float width, float height);
+/* Removes objects: the n objects whose creation indices are listed (spheres and planes mixed, in any order; the set R).
+ * THE RULE: afterwards the context is in the state of a context to which the surviving objects were added, in their order, with
+ * their CURRENT values -- geometry and colour as rtx_scene_get_object reports them just before the call (physics steps and edits
+ * included), the od words bit for bit, mover, speed and reflectivity as they are -- and a surviving object of old index i has the
+ * new index  i - |{r in R : r < i}|.  Callers renumber the indices they hold by this rule.  rtx_scene_count drops by |R|, the
+ * tie-break order among the survivors is unchanged, and every later launch on every path gives that fresh context's bytes.
+ * Removing every object is legal and leaves what rtx_scene_clear leaves (the bound on the spheres' speed may stay as it was: an
+ * upper bound).  Unchanged: the light set, every option, the hit buffers.
+ * All or nothing: R is checked before anything is touched (on a device group: before any rank is).  An index >= rtx_scene_count,
+ * an index listed twice, or indices == NULL with n > 0 changes nothing and returns RTX_ERR_INVALID_ARGUMENT; rtx_last_error names
+ * the first offending index.  So does a call inside a graph capture on the context's stream (the call waits).  n == 0: RTX_OK,
+ * nothing is launched, RTX_STAT_SCENE_REMOVED is unchanged.
+ * The arrays never come to the host: the call uploads pending appends, makes the context's stream wait for cell-list builds in
+ * flight, uploads R (4 bytes per removed object, twice) and runs rtx_compact_objects on the context's stream, which moves the
+ * survivors into a second set of arrays that then becomes the scene; it returns when that is done, having waited for the device
+ * once.  Like every scene change it must not race with frames or queries in flight on other streams.
+ * What it costs later launches: object counts and array addresses change, so graphs recorded before are refused by
+ * rtx_graph_launch exactly as after rtx_scene_add_*; cell lists, the world grid and the direction-sorted copy are rebuilt;
+ * dispatch orders start over; the next physics step counts as the first after an edit.  On a device group: validated on the root,
+ * then every member allocates what it needs, and only then does every member compact its own replica (pure moves: the replicas
+ * stay identical) -- RTX_ERR_OUT_OF_MEMORY leaves every rank as it was; an RTX_ERR_HIP from a launch or a wait after that point
+ * (a lost device) may leave the members with different scenes: destroy the group.
+ * No reference counterpart: Scene3D.h:15-25 creates objects and Scene3D::CleanUp frees all of them at once. */
+int rtx_scene_remove_objects(rtx_ctx* ctx, size_t n, const unsigned* indices);
+/* The same for callers whose own kernels decide what dies (the companion of rtx_scene_set_spheres_device): d_marks is
+ * rtx_scene_count bytes of device memory on the context's device (a group's root's), one byte per creation index, non-zero =
+ * remove.  `stream` is a hipStream_t (NULL = the context's stream): the marks are read after everything queued on it so far; a
+ * capture on either stream is refused.  The call copies the marks to pinned host memory and waits, builds the ascending list
+ * of marked indices and takes exactly the path of rtx_scene_remove_objects (a device group sees a host list), so the rule
+ * above holds, and it waits for the device once more.  *n_removed (may be NULL) receives |R|.  All marks zero (or an empty
+ * scene): RTX_OK, nothing further is launched.  d_marks == NULL with objects in the scene: RTX_ERR_INVALID_ARGUMENT.
+ * No reference counterpart: Scene3D.h:15-25 creates objects and Scene3D::CleanUp frees all of them at once. */
+int rtx_scene_remove_marked_device(rtx_ctx* ctx, const uint8_t* d_marks, void* stream, size_t* n_removed);
 
 /* ---- render: RayTracing::RayTrace (RayTracing.h:31-38, RayTracing.cu:797-867) together with the
  * zero-fill that precedes it in RayTracingManager::Update (RayTracingManager.cu:86).

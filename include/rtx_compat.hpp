@@ -24,6 +24,7 @@
 
 #include "rtx.h"
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
 #include <cmath>
@@ -429,6 +430,21 @@ public:
         const float p[3] = {middlePos.x, middlePos.y, middlePos.z}, n[3] = {normal.x, normal.y, normal.z}, c[3] = {color.x, color.y, color.z};
         check(rtx_scene_set_plane(ctx(), index, p, n, c, width, height), "rtx_scene_set_plane");
     }
+    // Objects removed, by creation index (rtx_scene_remove_objects: any order, no duplicates; all or nothing).  No reference
+    // counterpart: Scene3D.h:15-25 creates objects and Scene3D::CleanUp frees all of them at once.  A survivor of old index i is
+    // object i - |{r removed : r < i}| afterwards: callers renumber what they hold by that rule, as m_planes is here.
+    void RemoveObjects(const size_t n, const unsigned* indices)
+    {
+        check(rtx_scene_remove_objects(ctx(), n, indices), "rtx_scene_remove_objects");
+        std::vector<unsigned> gone(indices, indices + n), planes;
+        std::sort(gone.begin(), gone.end());
+        for (const unsigned i : m_planes) {
+            const auto at = std::lower_bound(gone.begin(), gone.end(), i);
+            if (at == gone.end() || *at != i) planes.push_back(i - (unsigned)(at - gone.begin()));
+        }
+        m_planes.swap(planes);
+    }
+    void RemoveObject(const unsigned index) { RemoveObjects(1, &index); }
     DeviceObjectArray<Object3D*> GetObjects()
     {
         DeviceObjectArray<Object3D*> a;

@@ -51,6 +51,7 @@ OPT_SHADOW_GRID = 29
 STAT_SHADOW_GRID_FRAMES = 146
 STAT_SHADOW_GRID_FALLBACK_POINTS = 147
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
+STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
@@ -139,6 +140,8 @@ _SIGNATURES = [
     ("rtx_scene_set_spheres", C.c_int, [_P, C.c_uint, C.c_size_t, _P]),
     ("rtx_scene_set_spheres_device", C.c_int, [_P, C.c_uint, C.c_size_t, _P, _P]),
     ("rtx_scene_set_plane", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]),
+    ("rtx_scene_remove_objects", C.c_int, [_P, C.c_size_t, C.POINTER(C.c_uint)]),
+    ("rtx_scene_remove_marked_device", C.c_int, [_P, _P, _P, C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_get_light", C.c_int, [_P, C.POINTER(Light)]),
     ("rtx_scene_set_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light)]),
@@ -403,6 +406,25 @@ class Context:
         """rtx_scene_set_plane: every field of plane `index`, as add_plane would have stored it."""
         self._check(lib().rtx_scene_set_plane(self._h, index, (C.c_float * 3)(*pos), (C.c_float * 3)(*normal),
                                               (C.c_float * 3)(*color), width, height))
+
+    def remove_objects(self, indices):
+        """rtx_scene_remove_objects: removes the objects with these creation indices (spheres and planes, any order, no duplicates).
+        A survivor of old index i is object i - |{r removed : r < i}| afterwards.  Blocking."""
+        w = np.atleast_1d(np.asarray(indices))
+        if w.dtype != np.uint32:
+            w = w.astype(np.int64)
+            if w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF):
+                raise ValueError("remove_objects: an index does not fit an unsigned int")
+        v = np.ascontiguousarray(w.astype(np.uint32)).reshape(-1)
+        self._check(lib().rtx_scene_remove_objects(self._h, v.size, v.ctypes.data_as(C.POINTER(C.c_uint)) if v.size else None))
+
+    def remove_marked_device(self, d_ptr, stream=None):
+        """rtx_scene_remove_marked_device: removes every object whose byte of the object_count bytes at d_ptr (device memory, e.g. a
+        uint8 torch tensor's data_ptr()) is not 0, ordered after what `stream` (a hipStream_t; None: the context's) holds.
+        Blocking.  Returns how many were removed."""
+        n = C.c_size_t(0)
+        self._check(lib().rtx_scene_remove_marked_device(self._h, d_ptr, stream, C.byref(n)))
+        return n.value
 
     def set_light(self, light=None):
         """rtx_scene_set_light (None: the reference's light)."""

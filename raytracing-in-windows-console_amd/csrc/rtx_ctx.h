@@ -211,7 +211,7 @@ struct rtx_ctx {
 
     hipStream_t aux_stream = nullptr; // the balancing passes' stream (created with the first pass)
     double scene_drift = 0.0;        // how far any sphere can have moved since the context was created (rtx_update_objects:
-                                     // |dt| x the largest |speed x mover|; rtx_scene_set_spheres: the largest move; other scene edits add 1e3):
+                                     // |dt| x the largest |speed x mover|; rtx_scene_set_spheres: the largest move; other scene edits and removals add 1e3):
                                      // dispatch orders go stale with it
     float max_speed = 0.0f;          // largest |speed * mover| any sphere was given: what a physics step moves it by per unit of dt
     int64_t opt_batch = -1;         // -1 auto (on), 0 off: rtx_submit_slabs renders consecutive slabs of one stream with one launch
@@ -347,6 +347,16 @@ struct rtx_ctx {
     uint64_t stat_scene_edits = 0;      // edit calls that changed something
     uint32_t stat_edit_move_bits = 0;   // RTX_STAT_SCENE_EDIT_MOVE
 
+    // objects removed in place (rtx_scene_remove_objects, rtx_scene_remove_marked_device; rtx_post.hip): rtx_compact_objects moves the
+    // survivors into the spare set of the eight scene arrays (sphere geom / color / od / motion, plane a / b / c / od: allocated at the
+    // first removal with the live array's capacity, regrown when the live one has grown), which is then swapped with the live set;
+    // the removed indices travel in d_remove_lists (words; grown by doubling), a device form's marks arrive in the pinned h_remove_marks
+    DeviceArray d_spare[8];
+    DeviceArray d_remove_lists;
+    uint8_t* h_remove_marks = nullptr;
+    size_t remove_marks_cap = 0;
+    uint64_t stat_scene_removed = 0;    // RTX_STAT_SCENE_REMOVED
+
     std::string error;
     const char* last_kernel = "";
 };
@@ -363,6 +373,12 @@ int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip
 // src_device: read in place, or copied into the context's scratch first (`stage`: a group member's copy of the root's rows).
 // `after`, if not null, is an event the edit is ordered behind.
 int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* rows, int src_device, bool stage, hipEvent_t after);
+// rtx_post.hip: removes the objects of a validated, ascending, non-empty list of creation indices from THIS context alone (not
+// inside a capture), blocking: the device arrays are compacted on the device, then the host's books follow
+int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending);
+// ... and its first half alone: uploads pending appends and allocates what the removal needs (the second set of arrays, the list
+// buffer); moves nothing.  A group prepares every member before any of them compacts.
+int rtx_remove_prepare(rtx_ctx* ctx, const std::vector<uint32_t>& ascending);
 void rtx_query_release(rtx_ctx* ctx);                    // rtx_query.cpp: frees the grid (rtx_destroy)
 // rtx_query.cpp: the world grid for a launch on `stream` that reads its lists -- the one grid object the queries use, brought up to date
 // if the scene changed since its last build (a build blocks, as a query's does, and counts in RTX_STAT_QUERY_GRID_BUILDS); `stream` is

@@ -531,6 +531,30 @@ int scene_set_plane(rtx_ctx* root, unsigned index, const float pos[3], const flo
     return RTX_OK;
 }
 
+int scene_remove_prepare(rtx_ctx* root, const std::vector<uint32_t>& ascending)
+{
+    rtx_group* g = root->group;
+    int status = RTX_OK;
+    for (int r = 1; r < g->n && status == RTX_OK; r++) {
+        const int rc = rtx_remove_prepare(g->member[(size_t)r], ascending);
+        if (rc != RTX_OK) status = member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return status;
+}
+
+int scene_remove_objects(rtx_ctx* root, const std::vector<uint32_t>& ascending)
+{
+    rtx_group* g = root->group;
+    int status = RTX_OK;
+    for (int r = 1; r < g->n && status == RTX_OK; r++) {
+        const int rc = rtx_remove_objects_here(g->member[(size_t)r], ascending);
+        if (rc != RTX_OK) status = member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return status;
+}
+
 int set_option(rtx_ctx* root, int option, int64_t value)
 {
     rtx_group* g = root->group;

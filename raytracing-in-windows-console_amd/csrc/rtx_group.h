@@ -34,6 +34,11 @@ int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float*
 int scene_set_spheres(rtx_ctx* root, unsigned first, size_t n, const float* rows);
 int scene_set_spheres_device(rtx_ctx* root, unsigned first, size_t n, const float* d_rows, hipEvent_t after);
 int scene_set_plane(rtx_ctx* root, unsigned index, const float pos[3], const float normal[3], const float rgb[3], float width, float height);
+// a removal (the root has validated the set and compacted its own replica): every other member compacts its replica by the same
+// ascending list of creation indices, from host memory
+int scene_remove_objects(rtx_ctx* root, const std::vector<uint32_t>& ascending);
+// before that, and before the root compacts: every other member allocates what its removal needs (rtx_remove_prepare)
+int scene_remove_prepare(rtx_ctx* root, const std::vector<uint32_t>& ascending);
 int set_option(rtx_ctx* root, int option, int64_t value);
 int update_objects(rtx_ctx* root, double dt); // every member steps its own replica (the same arithmetic on the same values)
 

@@ -919,4 +919,70 @@ inline EditEffect edit_effect(float move, unsigned flags)
     return e;
 }
 
+// ------------------------------------------------------------------------------------------------ objects removed in place
+
+// The host part of rtx_scene_remove_objects.  The caller lists creation indices in any order; the set R is checked before
+// anything is touched: removal_fault returns the position in `indices` of the first entry that is no index (>= count) or that
+// repeats an earlier entry, or n if there is none -- and then `ascending` is R in ascending order.
+inline size_t removal_fault(size_t count, size_t n, const unsigned* indices, std::vector<uint32_t>& ascending)
+{
+    ascending.clear();
+    std::vector<bool> listed(count, false);
+    for (size_t j = 0; j < n; j++) {
+        const size_t i = indices[j];
+        if (i >= count || listed[i]) return j;
+        listed[i] = true;
+    }
+    ascending.reserve(n);
+    for (size_t i = 0; i < count && ascending.size() < n; i++) {
+        if (listed[i]) ascending.push_back((uint32_t)i);
+    }
+    return n;
+}
+
+constexpr uint32_t kNoIndex = 0xFFFFFFFFu;
+
+// THE RULE by which survivors are renumbered: an object of old index i that is not in the ascending list `removed` has the new
+// index i - |{r in removed : r < i}| (kNoIndex for a removed one).  It holds for creation indices against R and, within a kind,
+// for local indices against that kind's removed locals; rtx_compact_objects (rtx_post_kernels.inc) does the same search on the device.
+inline uint32_t index_after_removal(const std::vector<uint32_t>& removed, uint32_t i)
+{
+    const auto at = std::lower_bound(removed.begin(), removed.end(), i);
+    if (at != removed.end() && *at == i) return kNoIndex;
+    return i - (uint32_t)(at - removed.begin());
+}
+
+// What the books look like afterwards: kind_of / local_of of the survivors in their order (local_of recounted), the object
+// counts, and per kind the ascending local indices of the removed objects -- the second list the kernel searches.
+struct RemovalPlan {
+    std::vector<uint8_t> kind_of;
+    std::vector<uint32_t> local_of;
+    std::vector<uint32_t> removed_spheres, removed_planes;
+    uint32_t ns = 0, np = 0; // survivors
+};
+
+inline RemovalPlan plan_removal(const std::vector<uint8_t>& kind_of, const std::vector<uint32_t>& ascending)
+{
+    RemovalPlan p;
+    const size_t left = kind_of.size() - ascending.size();
+    p.kind_of.reserve(left);
+    p.local_of.reserve(left);
+    uint32_t seen_spheres = 0, seen_planes = 0; // old local index of the object in hand
+    size_t next = 0;                            // the next removed index to meet
+    for (size_t i = 0; i < kind_of.size(); i++) {
+        const bool sphere = kind_of[i] == 2;
+        uint32_t& seen = sphere ? seen_spheres : seen_planes;
+        if (next < ascending.size() && ascending[next] == i) {
+            (sphere ? p.removed_spheres : p.removed_planes).push_back(seen);
+            next++;
+        } else {
+            uint32_t& kept = sphere ? p.ns : p.np;
+            p.kind_of.push_back(kind_of[i]);
+            p.local_of.push_back(kept++);
+        }
+        seen++;
+    }
+    return p;
+}
+
 } // namespace rtxplan

@@ -1,8 +1,8 @@
 // rtx_post.hip -- what RayTracingManager::Update runs around the trace kernel, on the GPU:
 // UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319),
 // plus rtx_update, the whole of Update in one call.
-// Also the edits of scene objects in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane): their kernel sits
-// beside the physics step's, which moves the same arrays.
+// Also the edits of scene objects in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane) and their removal
+// (rtx_scene_remove_objects, rtx_scene_remove_marked_device): their kernels sit beside the physics step's, which moves the same arrays.
 #include "rtx_ctx.h"
 #include "rtx_group.h"
 #include "rtx_device.hpp"
@@ -461,7 +461,195 @@ int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* r
     return RTX_OK;
 }
 
+// Everything of a removal that can fail for want of memory, before anything is moved: pending appends uploaded, the second set of
+// arrays and the list buffer large enough.  Changes nothing a launch reads; a device group prepares every member before the first
+// one compacts, so that running out of memory leaves every replica as it was.
+int rtx_remove_prepare(rtx_ctx* ctx, const std::vector<uint32_t>& ascending)
+{
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = rtx_sync_scene(ctx); // every pending append is on the device: ns_uploaded == ns, np_uploaded == np
+    if (rc != RTX_OK) return rc;
+    const size_t n = ascending.size();
+    DeviceArray* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
+                                  &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
+    for (int a = 0; a < 8; a++) {
+        DeviceArray& spare = ctx->d_spare[a];
+        if (spare.cap >= live[a]->cap) continue;
+        // (every earlier removal has been waited for, and no launch reads a spare set)
+        void* p = nullptr;
+        if (hipMalloc(&p, live[a]->cap * sizeof(float4)) != hipSuccess) {
+            (void)hipGetLastError();
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the second set of scene arrays");
+        }
+        if (spare.p) hipFree(spare.p);
+        spare.p = p;
+        spare.cap = live[a]->cap;
+    }
+    // the lists: R, then the removed sphere locals, then the removed plane locals -- 2 |R| words
+    if (ctx->d_remove_lists.cap < 2 * n) {
+        size_t cap = ctx->d_remove_lists.cap ? ctx->d_remove_lists.cap : 1024;
+        while (cap < 2 * n) cap *= 2;
+        void* p = nullptr;
+        if (hipMalloc(&p, cap * sizeof(uint32_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the removal lists");
+        }
+        if (ctx->d_remove_lists.p) hipFree(ctx->d_remove_lists.p);
+        ctx->d_remove_lists.p = p;
+        ctx->d_remove_lists.cap = cap;
+    }
+    return RTX_OK;
+}
+
+int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending)
+{
+    int rc = rtx_remove_prepare(ctx, ascending); // (nothing left to do where a group has prepared this member already)
+    if (rc != RTX_OK) return rc;
+    // cell lists being built ahead of time on the side stream read the spheres: the move waits for them (as an edit does)
+    for (auto& sl : ctx->cell_cache) {
+        if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
+    }
+    rtxplan::RemovalPlan plan = rtxplan::plan_removal(ctx->kind_of, ascending);
+    const size_t n = ascending.size();
+    // the kernel's argument order: the two plain arrays of a kind, then the two that carry the creation index in .w
+    DeviceArray* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
+                                  &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
+    const bool moves[2] = {plan.ns > 0, plan.np > 0}; // (a kind without survivors has nothing to move: its count drops to 0)
+    std::vector<uint32_t> lists(ascending);
+    lists.insert(lists.end(), plan.removed_spheres.begin(), plan.removed_spheres.end());
+    lists.insert(lists.end(), plan.removed_planes.begin(), plan.removed_planes.end());
+    const uint32_t* d_gidx = (const uint32_t*)ctx->d_remove_lists.p;
+    const uint32_t* d_local[2] = {d_gidx + n, d_gidx + n + plan.removed_spheres.size()};
+    const uint32_t n_local[2] = {(uint32_t)plan.removed_spheres.size(), (uint32_t)plan.removed_planes.size()};
+    const uint32_t count[2] = {ctx->ns, ctx->np};
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_remove_lists.p, lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    for (int kind = 0; kind < 2; kind++) {
+        if (!moves[kind]) continue;
+        DeviceArray* const* from = live + 4 * kind;
+        const DeviceArray* to = ctx->d_spare + 4 * kind;
+        hipLaunchKernelGGL(rtx::rtx_compact_objects, dim3((count[kind] + rtx::kThreads - 1) / rtx::kThreads), dim3(rtx::kThreads), 0, ctx->stream,
+                           (const float4*)from[0]->p, (const float4*)from[1]->p, (const float4*)from[2]->p, (const float4*)from[3]->p,
+                           (float4*)to[0].p, (float4*)to[1].p, (float4*)to[2].p, (float4*)to[3].p, count[kind], d_gidx, (uint32_t)n,
+                           d_local[kind], n_local[kind]);
+        RTX_HIP(ctx, hipGetLastError());
+    }
+    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the one wait: the survivors are in the second set, the lists are free
+    for (int a = 0; a < 8; a++) {
+        if (moves[a / 4]) std::swap(*live[a], ctx->d_spare[a]);
+    }
+    // the books, all in one place: what a context holds to which the survivors were added in their order
+    std::vector<float> refl;
+    refl.reserve(plan.kind_of.size());
+    uint32_t n_reflective = 0;
+    size_t next = 0;
+    for (size_t i = 0; i < ctx->refl.size(); i++) {
+        if (next < n && ascending[next] == i) {
+            next++;
+            continue;
+        }
+        refl.push_back(ctx->refl[i]);
+        n_reflective += ctx->refl[i] > 0.0f ? 1u : 0u;
+    }
+    ctx->refl.swap(refl);
+    ctx->n_reflective = n_reflective; // (0: the mirror path is simply not taken any more)
+    ctx->refl_dirty = true;
+    ctx->refl_gen++;
+    if (ctx->h_centres.size() == ctx->ns) {
+        // the sort's input at the next re-sort, by sphere index
+        size_t kept = 0, gone = 0;
+        for (size_t k = 0; k < ctx->h_centres.size(); k++) {
+            if (gone < plan.removed_spheres.size() && plan.removed_spheres[gone] == k) {
+                gone++;
+            } else {
+                ctx->h_centres[kept++] = ctx->h_centres[k];
+            }
+        }
+        ctx->h_centres.resize(kept);
+    }
+    ctx->kind_of.swap(plan.kind_of);
+    ctx->local_of.swap(plan.local_of);
+    ctx->ns = ctx->ns_uploaded = plan.ns;
+    ctx->np = ctx->np_uploaded = plan.np;
+    ctx->next_gidx = plan.ns + plan.np;
+    ctx->scene_drift += 1.0e3; // (an edit: every dispatch order is stale)
+    // scene and list generations, view density, physics bound, cell policy, world grid: counts and addresses changed, so the sorted
+    // copy is re-sorted, cell lists and grid are rebuilt and recorded graphs are refused, exactly as after rtx_scene_add_*
+    rtx_scene_edited(ctx);
+    ctx->stat_scene_removed += n;
+    return RTX_OK;
+}
+
+namespace {
+
+// R is checked and not empty: the context itself, then the other members of its group
+int remove_checked(rtx_ctx* ctx, const std::vector<uint32_t>& ascending)
+{
+    // on a group: every member's memory first, then the moves -- running out of memory touches no replica
+    int rc = ctx->group ? rtxgroup::scene_remove_prepare(ctx, ascending) : RTX_OK;
+    if (rc != RTX_OK) return rc;
+    if ((rc = rtx_remove_objects_here(ctx, ascending)) != RTX_OK) return rc;
+    return ctx->group ? rtxgroup::scene_remove_objects(ctx, ascending) : RTX_OK;
+}
+
+} // namespace
+
 extern "C" {
+
+int rtx_scene_remove_objects(rtx_ctx* ctx, size_t n, const unsigned* indices)
+{
+    if (!ctx) return RTX_ERR_INVALID_ARGUMENT;
+    if (n && !indices) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_remove_objects: the indices are NULL");
+    if (n == 0) return RTX_OK;
+    // all or nothing: the set is checked before anything is touched (and, on a group, before any rank is)
+    std::vector<uint32_t> ascending;
+    const size_t bad = rtxplan::removal_fault(ctx->next_gidx, n, indices, ascending);
+    if (bad < n) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT,
+                        "rtx_scene_remove_objects: index " + std::to_string(indices[bad]) + " (entry " + std::to_string(bad) + ") " +
+                            (indices[bad] >= ctx->next_gidx ? "is past rtx_scene_count" : "is listed twice"));
+    }
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = check_not_capturing(ctx, "rtx_scene_remove_objects", ctx->stream);
+    if (rc != RTX_OK) return rc;
+    return remove_checked(ctx, ascending);
+}
+
+int rtx_scene_remove_marked_device(rtx_ctx* ctx, const uint8_t* d_marks, void* stream_v, size_t* n_removed)
+{
+    if (!ctx) return RTX_ERR_INVALID_ARGUMENT;
+    const size_t count = ctx->next_gidx;
+    if (count == 0) {
+        if (n_removed) *n_removed = 0;
+        return RTX_OK;
+    }
+    if (!d_marks) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_scene_remove_marked_device: the marks are NULL");
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
+    int rc = check_not_capturing(ctx, "rtx_scene_remove_marked_device", st);
+    if (rc != RTX_OK) return rc;
+    if (ctx->remove_marks_cap < count) {
+        size_t cap = ctx->remove_marks_cap ? ctx->remove_marks_cap : 4096;
+        while (cap < count) cap *= 2;
+        uint8_t* p = nullptr;
+        if (hipHostMalloc((void**)&p, cap, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed while growing the removal marks");
+        }
+        if (ctx->h_remove_marks) hipHostFree(ctx->h_remove_marks);
+        ctx->h_remove_marks = p;
+        ctx->remove_marks_cap = cap;
+    }
+    // after everything queued so far on the caller's stream (the kernel that wrote the marks); the first of the two waits
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_remove_marks, d_marks, count, hipMemcpyDeviceToHost, st));
+    RTX_HIP(ctx, hipStreamSynchronize(st));
+    std::vector<uint32_t> ascending;
+    for (size_t i = 0; i < count; i++) {
+        if (ctx->h_remove_marks[i]) ascending.push_back((uint32_t)i);
+    }
+    if (!ascending.empty() && (rc = remove_checked(ctx, ascending)) != RTX_OK) return rc;
+    if (n_removed) *n_removed = ascending.size();
+    return RTX_OK;
+}
 
 int rtx_scene_set_spheres(rtx_ctx* ctx, unsigned first, size_t n, const float* xyzr_rgb)
 {

@@ -110,6 +110,47 @@ __global__ __launch_bounds__(kThreads) void rtx_write_spheres(const float* rows,
     }
 }
 
+// ---------------------------------------------------------------- rtx_scene_remove_objects
+// No reference counterpart (Scene3D.h:15-25 creates objects, Scene3D::CleanUp frees all of them at once).  Compacts the four
+// float4 arrays of one kind -- spheres: plain0/1 = geom, motion, idx0/1 = color, od; planes: plain0/1 = a, b, idx0/1 = c, od; the
+// idx arrays carry the creation index in .w -- OUT OF PLACE: one source object per thread; the survivor of local index k goes to
+// k' = k - |{removed locals < k}| of the destination set with g' = g - |{removed creation indices < g}| in its two .w words, every
+// other bit as it was (pure moves).  The destinations of one thread are the sources of another and a launch has no order, hence
+// the second set; the host swaps the sets afterwards.  Both lists are ascending, in global memory (L2-resident: 4 bytes per
+// removed object) and searched by bisection: about log2 |R| dependent loads per thread against the 8 x 16 bytes it moves.
+__device__ __forceinline__ uint32_t count_below(const uint32_t* list, uint32_t n, uint32_t v)
+{
+    uint32_t lo = 0u, hi = n; // the first position whose entry is >= v
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (list[mid] < v) {
+            lo = mid + 1u;
+        } else {
+            hi = mid;
+        }
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(kThreads) void rtx_compact_objects(const float4* plain0, const float4* plain1, const float4* idx0, const float4* idx1,
+                                                                float4* out_plain0, float4* out_plain1, float4* out_idx0, float4* out_idx1,
+                                                                uint32_t count, const uint32_t* removed_gidx, uint32_t n_gidx,
+                                                                const uint32_t* removed_local, uint32_t n_local)
+{
+    const uint32_t k = blockIdx.x * kThreads + threadIdx.x;
+    if (k >= count) return;
+    const uint32_t below = count_below(removed_local, n_local, k);
+    if (below < n_local && removed_local[below] == k) return; // removed
+    const float4 i0 = idx0[k], i1 = idx1[k], p0 = plain0[k], p1 = plain1[k];
+    const uint32_t g = __float_as_uint(i0.w);
+    const float w = __uint_as_float(g - count_below(removed_gidx, n_gidx, g));
+    const uint32_t to = k - below; // (<= k < count: inside every destination array, which holds at least `count`)
+    out_plain0[to] = p0;
+    out_plain1[to] = p1;
+    out_idx0[to] = make_float4(i0.x, i0.y, i0.z, w); // (built anew: with i0.w = w this compiler's alloca promotion gave the kernel 6144 bytes of LDS, profiles/r14_scene_remove_resource_usage.txt)
+    out_idx1[to] = make_float4(i1.x, i1.y, i1.z, w);
+}
+
 // sorted[p] = geom[order[p]]: the direction-sorted copy of the sphere array, from the live one.
 __global__ __launch_bounds__(kThreads) void rtx_gather_spheres(const float4* geom, const float4* od, const uint32_t* order, float4* sorted_geom,
                                                                float4* sorted_od, uint32_t ns)
