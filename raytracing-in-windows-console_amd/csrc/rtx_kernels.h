@@ -7,6 +7,7 @@
 
 #include "rtx_grid.hpp"
 #include "rtx_lights.hpp"
+#include "rtx_plan.hpp"
 
 // Kernel-side mode numbers = enum RenderingMode (RayTracingManager.h:21).
 enum {
@@ -253,31 +254,23 @@ int rtx_k_launch_expand(const ExpandArgs* e, int mode, unsigned blocks, void* st
 const char* rtx_k_launch_trace(const KArgs* a, int mode, int cull, void* stream, int* hip_error);
 // The batched form (culling kernels without per-wave refinement, records or compact words): a->batch_n frames of kb in one launch.
 const char* rtx_k_launch_trace_batch(const KArgs* a, const KBatch* kb, int mode, void* stream, int* hip_error);
-// a->compact == 3 asks rtx_k_launch_trace for the closest hits alone (8 bytes per pixel into a->out, whatever the mode); this
-// shades them into a->out as `mode`'s records / words / values (a->compact 0 / 1 / 2).  Character modes only.
-const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* s, int mode, void* stream, int* hip_error);
-// The mirror path's second and third launches: secondary hits of every reflective pixel into r->hits2, then the shading (with
-// s's shadow test) and the blend into a->out as for rtx_k_launch_shadow.  Character modes only.
-const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream, int* hip_error);
-const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* s, const ReflectArgs* r, int mode, void* stream, int* hip_error);
-// The same two shading launches for a set of several lights (rtx_scene_set_lights; r == NULL: no mirror).
-const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream, int* hip_error);
-// The mirror path's second and third launches for a chain of c->depth levels (any set of lights).
-const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream, int* hip_error);
-const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream,
-                                            int* hip_error);
-// The chain under RTX_OPT_REFLECT_SHADOWS: the shadow tests of the deeper levels (after rtx_k_launch_reflect_chain), and the shade
-// launch that reads their result.
-const char* rtx_k_launch_chain_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs, void* stream,
-                                      int* hip_error);
-const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                                   int mode, void* stream, int* hip_error);
-// The grid path's launches (RTX_OPT_SHADOW_GRID): the tests (r, c, cs are read only with gs->deep), and the shade launch that reads
-// their result: r == NULL no mirror, c == NULL one bounce, cs == NULL a chain without the deeper levels' words.
-const char* rtx_k_launch_grid_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                     const GridShadowArgs* gs, void* stream, int* hip_error);
-const char* rtx_k_launch_grid_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                    const uint32_t* dark0, int mode, void* stream, int* hip_error);
+// The launches behind the trace launch, as rtxplan::plan_shading (rtx_plan.hpp) orders them.  a->compact == 3 asks
+// rtx_k_launch_trace for the closest hits alone (8 bytes per pixel into a->out, whatever the mode); the passes add to the hit
+// buffer, and the shade launch of `family` writes a->out as `mode`'s records / words / values (a->compact 0 / 1 / 2).  Character
+// modes only.  What a pass or a family does not take may be NULL; what it takes and finds missing or invalid (a light set of 0 or
+// more than 8, a chain whose depth or stride does not fit the launch, no room for its words) refuses the launch: NULL.
+struct TileArgs {
+    const KArgs* a;
+    const ShadowArgs* shadow;      // rtx_shadow_shade, rtx_reflect_shade
+    const LightsArgs* lights;      // every other family; rtx_chain_shadow, rtx_grid_shadow
+    const ReflectArgs* reflect;    // the mirror path
+    const ChainArgs* chain;        // ... through the chain kernels
+    const ChainShadowArgs* deep;   // ... with the deeper levels shadow-tested
+    const GridShadowArgs* grid;    // rtx_grid_shadow (which takes reflect, chain and deep by value: zero-filled where there is none)
+    const uint32_t* dark0;         // the grid families: GridShadowArgs::dark0
+};
+const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream, int* hip_error);
+const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const TileArgs* t, int mode, void* stream, int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

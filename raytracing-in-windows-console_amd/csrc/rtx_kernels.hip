@@ -1399,136 +1399,117 @@ static const char* launch_shade(const KArgs* a, int mode, const ShadeNames& name
     return names.s[mode][a->compact];
 }
 
-static bool lights_ok(const LightsArgs* l) { return l->lights.n != 0u && l->lights.n <= (uint32_t)rtxlights::kMaxLights; }
-static bool chain_ok(const KArgs* a, const ChainArgs* c)
+// What a pass or a shade family takes of TileArgs, and so what must be there for its launch: the table of the refusals.
+enum : unsigned {
+    kTakesShadow = 1u << 0,  // t->shadow
+    kTakesLights = 1u << 1,  // t->lights, a set of 1 .. kMaxLights
+    kTakesReflect = 1u << 2, // t->reflect
+    kTakesChain = 1u << 3,   // t->chain, its depth in range and its stride the launch's pixels
+    kTakesDeep = 1u << 4,    // t->deep with its words
+    kTakesDark0 = 1u << 5,   // t->dark0
+    kTakesGrid = 1u << 6,    // t->grid: a usable grid over a scene with spheres, room for level 0's words and the fallback count;
+                             // reflect, chain and deep by value (they are read, and then checked, only with GridShadowArgs::deep)
+};
+static const unsigned kPassTakes[rtxplan::kShadePasses] = {
+    0u,                                                        // kPassNone
+    kTakesReflect,                                             // rtx_reflect_hit
+    kTakesReflect | kTakesChain,                               // rtx_reflect_chain
+    kTakesLights | kTakesReflect | kTakesChain | kTakesDeep,   // rtx_chain_shadow
+    kTakesLights | kTakesGrid,                                 // rtx_grid_shadow
+};
+static const unsigned kFamilyTakes[rtxplan::kShadeFamilies] = {
+    kTakesShadow,                                              // rtx_shadow_shade
+    kTakesLights,                                              // rtx_lights_shade
+    kTakesShadow | kTakesReflect,                              // rtx_reflect_shade
+    kTakesLights | kTakesReflect,                              // rtx_lights_reflect_shade
+    kTakesLights | kTakesReflect | kTakesChain,                // rtx_lights_chain_shade
+    kTakesLights | kTakesReflect | kTakesChain | kTakesDeep,   // rtx_lights_chain_shadow_shade
+    kTakesLights | kTakesDark0,                                // rtx_grid_shade
+    kTakesLights | kTakesReflect | kTakesDark0,                // rtx_grid_reflect_shade
+    kTakesLights | kTakesReflect | kTakesChain | kTakesDark0,  // rtx_grid_chain_shade
+    kTakesLights | kTakesReflect | kTakesChain | kTakesDeep | kTakesDark0, // rtx_grid_chain_shadow_shade
+};
+
+static bool tile_args_ok(const TileArgs* t, unsigned takes)
 {
-    return c->depth != 0u && c->depth <= (uint32_t)kMaxReflectDepth && c->px == a->W * (a->row_end - a->row0);
+    const KArgs* a = t->a;
+    if ((takes & kTakesShadow) && t->shadow == nullptr) return false;
+    if ((takes & kTakesLights) && (t->lights == nullptr || t->lights->lights.n == 0u || t->lights->lights.n > (uint32_t)rtxlights::kMaxLights)) return false;
+    if ((takes & kTakesReflect) && t->reflect == nullptr) return false;
+    if ((takes & kTakesChain) &&
+        (t->chain == nullptr || t->chain->depth == 0u || t->chain->depth > (uint32_t)kMaxReflectDepth || t->chain->px != a->W * (a->row_end - a->row0))) {
+        return false;
+    }
+    if ((takes & kTakesDeep) && (t->deep == nullptr || t->deep->dark == nullptr)) return false;
+    if ((takes & kTakesDark0) && t->dark0 == nullptr) return false;
+    if (takes & kTakesGrid) {
+        const GridShadowArgs* gs = t->grid;
+        if (gs == nullptr || gs->dark0 == nullptr || gs->fallback == nullptr || gs->grid.ok == 0u || a->ns == 0u) return false;
+        if (t->reflect == nullptr || t->chain == nullptr || t->deep == nullptr) return false;
+        if (gs->deep != 0u && !tile_args_ok(t, kTakesChain | kTakesDeep)) return false;
+    }
+    return true;
 }
 
-extern "C" const char* rtx_k_launch_shadow(const KArgs* a, const ShadowArgs* sh, int mode, void* stream_v, int* hip_error)
-{
-    static const ShadeNames names("rtx_shadow_shade");
-    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL((rtx::rtx_shadow_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *sh);
-    });
-}
-
-extern "C" const char* rtx_k_launch_reflect_hit(const KArgs* a, const ReflectArgs* r, void* stream_v, int* hip_error)
+extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream_v, int* hip_error)
 {
     using namespace rtx;
     *hip_error = 0;
     dim3 grid;
-    if (!tile_grid(a, grid)) return nullptr;
+    if (pass == rtxplan::kPassNone || (unsigned)pass >= (unsigned)rtxplan::kShadePasses || !tile_grid(t->a, grid) || !tile_args_ok(t, kPassTakes[pass])) return nullptr;
     const dim3 block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_reflect_hit, grid, block, 0, (hipStream_t)stream_v, *a, *r);
+    hipStream_t st = (hipStream_t)stream_v;
+    const char* name = nullptr;
+    switch (pass) {
+    case rtxplan::kPassReflectHit:
+        hipLaunchKernelGGL(rtx_reflect_hit, grid, block, 0, st, *t->a, *t->reflect);
+        name = "rtx_reflect_hit";
+        break;
+    case rtxplan::kPassReflectChain:
+        hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, st, *t->a, *t->reflect, *t->chain);
+        name = "rtx_reflect_chain";
+        break;
+    case rtxplan::kPassChainShadow:
+        hipLaunchKernelGGL(rtx_chain_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
+        name = "rtx_chain_shadow";
+        break;
+    default:
+        hipLaunchKernelGGL(rtx_grid_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, *t->grid);
+        name = "rtx_grid_shadow";
+        break;
+    }
     *hip_error = (int)hipGetLastError();
-    return "rtx_reflect_hit";
+    return name;
 }
 
-extern "C" const char* rtx_k_launch_reflect_shade(const KArgs* a, const ShadowArgs* sh, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
+extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const TileArgs* t, int mode, void* stream_v, int* hip_error)
 {
-    static const ShadeNames names("rtx_reflect_shade");
-    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL((rtx::rtx_reflect_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *sh, *r);
-    });
-}
-
-extern "C" const char* rtx_k_launch_lights_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, int mode, void* stream_v, int* hip_error)
-{
-    static const ShadeNames plain("rtx_lights_shade"), mirror("rtx_lights_reflect_shade");
+    using namespace rtxplan;
+    static const std::vector<ShadeNames> kNames = [] {
+        std::vector<ShadeNames> v;
+        for (int f = 0; f < kShadeFamilies; f++) v.emplace_back(shade_family_name((ShadeFamily)f));
+        return v;
+    }();
     *hip_error = 0;
-    if (!lights_ok(l)) return nullptr;
-    return launch_shade(a, mode, r != nullptr ? mirror : plain, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
-        if (r != nullptr) {
-            hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r);
-        } else {
-            hipLaunchKernelGGL((rtx::rtx_lights_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l);
-        }
-    });
-}
-
-extern "C" const char* rtx_k_launch_reflect_chain(const KArgs* a, const ReflectArgs* r, const ChainArgs* c, void* stream_v, int* hip_error)
-{
-    using namespace rtx;
-    *hip_error = 0;
-    dim3 grid;
-    if (!tile_grid(a, grid) || !chain_ok(a, c)) return nullptr;
-    const dim3 block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, (hipStream_t)stream_v, *a, *r, *c);
-    *hip_error = (int)hipGetLastError();
-    return "rtx_reflect_chain";
-}
-
-extern "C" const char* rtx_k_launch_lights_chain_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, int mode, void* stream_v,
-                                                       int* hip_error)
-{
-    static const ShadeNames names("rtx_lights_chain_shade");
-    *hip_error = 0;
-    if (!lights_ok(l) || !chain_ok(a, c)) return nullptr;
-    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c);
-    });
-}
-
-extern "C" const char* rtx_k_launch_chain_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                                 void* stream_v, int* hip_error)
-{
-    using namespace rtx;
-    *hip_error = 0;
-    dim3 grid;
-    if (!tile_grid(a, grid) || !lights_ok(l) || !chain_ok(a, c) || cs->dark == nullptr) return nullptr;
-    const dim3 block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_chain_shadow, grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c, *cs);
-    *hip_error = (int)hipGetLastError();
-    return "rtx_chain_shadow";
-}
-
-extern "C" const char* rtx_k_launch_lights_chain_shadow_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c,
-                                                              const ChainShadowArgs* cs, int mode, void* stream_v, int* hip_error)
-{
-    static const ShadeNames names("rtx_lights_chain_shadow_shade");
-    *hip_error = 0;
-    if (!lights_ok(l) || !chain_ok(a, c) || cs->dark == nullptr) return nullptr;
-    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
-        hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<decltype(m)::value, decltype(o)::value>), grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c,
-                           *cs);
-    });
-}
-
-extern "C" const char* rtx_k_launch_grid_shadow(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                                const GridShadowArgs* gs, void* stream_v, int* hip_error)
-{
-    using namespace rtx;
-    *hip_error = 0;
-    dim3 grid;
-    if (!tile_grid(a, grid) || !lights_ok(l) || gs->dark0 == nullptr || gs->fallback == nullptr || gs->grid.ok == 0u || a->ns == 0u) return nullptr;
-    if (gs->deep != 0u && (!chain_ok(a, c) || cs->dark == nullptr)) return nullptr;
-    const dim3 block(kThreads, 1, 1);
-    hipLaunchKernelGGL(rtx_grid_shadow, grid, block, 0, (hipStream_t)stream_v, *a, *l, *r, *c, *cs, *gs);
-    *hip_error = (int)hipGetLastError();
-    return "rtx_grid_shadow";
-}
-
-extern "C" const char* rtx_k_launch_grid_shade(const KArgs* a, const LightsArgs* l, const ReflectArgs* r, const ChainArgs* c, const ChainShadowArgs* cs,
-                                               const uint32_t* dark0, int mode, void* stream_v, int* hip_error)
-{
-    static const ShadeNames plain("rtx_grid_shade"), mirror("rtx_grid_reflect_shade"), chain("rtx_grid_chain_shade"), deep("rtx_grid_chain_shadow_shade");
-    *hip_error = 0;
-    if (!lights_ok(l) || dark0 == nullptr) return nullptr;
-    if (c != nullptr && (r == nullptr || !chain_ok(a, c))) return nullptr;
-    if (cs != nullptr && (c == nullptr || cs->dark == nullptr)) return nullptr;
-    const ShadeNames& names = cs != nullptr ? deep : (c != nullptr ? chain : (r != nullptr ? mirror : plain));
-    return launch_shade(a, mode, names, hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+    if ((unsigned)family >= (unsigned)kShadeFamilies || !tile_args_ok(t, kFamilyTakes[family])) return nullptr;
+    return launch_shade(t->a, mode, kNames[family], hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
         constexpr int M = decltype(m)::value, O = decltype(o)::value;
         hipStream_t st = (hipStream_t)stream_v;
-        if (cs != nullptr) {
-            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *a, *l, *r, *c, *cs, dark0);
-        } else if (c != nullptr) {
-            hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *a, *l, *r, *c, dark0);
-        } else if (r != nullptr) {
-            hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *a, *l, *r, dark0);
-        } else {
-            hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *a, *l, dark0);
+        switch (family) {
+        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow); break;
+        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O>), grid, block, 0, st, *t->a, *t->lights); break;
+        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect); break;
+        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect); break;
+        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain); break;
+        case kLightsChainShadowShade:
+            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
+            break;
+        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, t->dark0); break;
+        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0); break;
+        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0); break;
+        default:
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0);
+            break;
         }
     });
 }

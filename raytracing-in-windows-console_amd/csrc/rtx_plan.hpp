@@ -985,4 +985,111 @@ inline RemovalPlan plan_removal(const std::vector<uint8_t>& kind_of, const std::
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ shading
+//
+// Which launches make up a frame, and how the per-stream hit buffer is laid out.  A frame in the reference's state is ONE trace
+// launch (direct).  Otherwise the trace launch leaves the closest hits (8 bytes per pixel), up to two tile passes follow, and a
+// shade launch of one of ten kernel families writes the frame:
+//
+//   path                levels     secondary          shadow pass                                  family (grid / else)
+//   shaded              1          -                  grid: rtx_grid_shadow                        rtx_grid_shade / several: rtx_lights_shade, else rtx_shadow_shade
+//   mirror, not chain   2          rtx_reflect_hit    grid: rtx_grid_shadow (deep 0)               rtx_grid_reflect_shade / several: rtx_lights_reflect_shade, else rtx_reflect_shade
+//   mirror, chain       depth + 1  rtx_reflect_chain  grid: rtx_grid_shadow (deep = deep), else    rtx_grid_chain[_shadow]_shade / rtx_lights_chain[_shadow]_shade
+//                                                     deep: rtx_chain_shadow                       (_shadow: deep)
+//
+// The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
+// deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
+
+enum ShadePath { kPathDirect, kPathShaded, kPathMirror };
+enum ShadePass { kPassNone, kPassReflectHit, kPassReflectChain, kPassChainShadow, kPassGridShadow, kShadePasses };
+enum ShadeFamily {
+    kShadowShade, kLightsShade, kReflectShade, kLightsReflectShade, kLightsChainShade, kLightsChainShadowShade,
+    kGridShade, kGridReflectShade, kGridChainShade, kGridChainShadowShade, kShadeFamilies
+};
+
+inline const char* shade_family_name(ShadeFamily f)
+{
+    static const char* const kName[kShadeFamilies] = {"rtx_shadow_shade", "rtx_lights_shade", "rtx_reflect_shade", "rtx_lights_reflect_shade",
+                                                      "rtx_lights_chain_shade", "rtx_lights_chain_shadow_shade", "rtx_grid_shade", "rtx_grid_reflect_shade",
+                                                      "rtx_grid_chain_shade", "rtx_grid_chain_shadow_shade"};
+    return kName[f];
+}
+
+// rtx_shadow_shade and rtx_reflect_shade take the one light (ShadowArgs); every other family, and the two shadow passes, the set.
+inline bool shade_takes_light_set(ShadeFamily f) { return f != kShadowShade && f != kReflectShade; }
+
+constexpr int kShadedModeLo = 0, kShadedModeHi = 3; // RTX_BIT_ASCII .. RTX_RGB_PIXEL: RGB_NORMALS and SDL do not shade
+
+struct ShadingRequest { // what the decision reads of the call, the options and the scene
+    int mode = 0;
+    bool shadows = false;            // RTX_OPT_SHADOWS
+    int shadow_check = 0;            // RTX_OPT_SHADOW_CHECK: 1 and 2 are the brute references and keep their launches
+    bool lights_check = false;       // RTX_OPT_LIGHTS_CHECK: the several-lights kernels for a set of one
+    size_t n_lights = 1;
+    bool light0_is_reference = true; // light 0 is the reference's light, bit for bit
+    uint32_t n_reflective = 0;       // objects with a reflectivity above 0
+    int reflect_check = 0;           // RTX_OPT_REFLECT_CHECK: 2 takes the mirror path with nothing reflective
+    uint32_t reflect_depth = 1;      // RTX_OPT_REFLECT_DEPTH
+    bool reflect_depth_check = false; // RTX_OPT_REFLECT_DEPTH_CHECK: the chain kernels at depth 1
+    bool reflect_shadows = false;    // RTX_OPT_REFLECT_SHADOWS
+    bool shadow_grid = false;        // RTX_OPT_SHADOW_GRID
+    uint32_t ns = 0;
+    bool grid_usable = false;        // the world grid was built and can be walked; known only after its build (shading_wants_grid)
+};
+
+struct ShadingPlan {
+    ShadePath path = kPathDirect;
+    ShadePass secondary = kPassNone;   // between the trace launch and the shadow pass
+    ShadePass shadow_pass = kPassNone; // between the hits and the shade launch
+    ShadeFamily family = kShadeFamilies; // (direct: none)
+    bool deep = false;                 // the deeper levels are shadow-tested: the shadow pass writes their words, the family reads them
+    bool dark0 = false;                // level 0's words exist (rtx_grid_shadow writes them, a grid family reads them)
+    uint32_t levels = 0;               // hit arrays
+    uint32_t bytes_per_px = 0;         // of the hit buffer; 0: none
+    uint32_t deep_off = 0, dark0_off = 0; // bytes per pixel in front of the deep / dark0 words (level j's hits: 8 j)
+    bool chain() const { return secondary == kPassReflectChain; }
+};
+
+inline ShadePath shading_path(const ShadingRequest& q)
+{
+    if (q.mode < kShadedModeLo || q.mode > kShadedModeHi) return kPathDirect;
+    if (q.n_reflective != 0 || q.reflect_check == 2) return kPathMirror; // (takes precedence, and runs the shadow test itself)
+    if (q.shadows || q.n_lights != 1 || q.lights_check || !q.light0_is_reference) return kPathShaded;
+    return kPathDirect; // the state the reference has: every launch is the reference's
+}
+
+// Does the frame ask for shadow tests through the world grid?  By the options and the scene alone: the caller then brings the
+// grid up to date (a build blocks, so a capturing stream is refused) and plans with grid_usable set to what came of it.
+inline bool shading_wants_grid(const ShadingRequest& q)
+{
+    return shading_path(q) != kPathDirect && q.shadow_grid && q.shadows && q.shadow_check == 0 && q.ns != 0;
+}
+
+inline ShadingPlan plan_shading(const ShadingRequest& q)
+{
+    ShadingPlan p;
+    p.path = shading_path(q);
+    if (p.path == kPathDirect) return p;
+    const bool mirror = p.path == kPathMirror;
+    const bool grid = shading_wants_grid(q) && q.grid_usable;
+    const bool several = q.n_lights >= 2 || q.lights_check;
+    p.deep = mirror && q.reflect_shadows && q.shadows && q.n_reflective != 0;
+    const bool chain = mirror && (q.reflect_depth > 1 || q.reflect_depth_check || p.deep);
+    p.secondary = chain ? kPassReflectChain : (mirror ? kPassReflectHit : kPassNone);
+    p.shadow_pass = grid ? kPassGridShadow : (p.deep ? kPassChainShadow : kPassNone);
+    if (chain) {
+        p.family = grid ? (p.deep ? kGridChainShadowShade : kGridChainShade) : (p.deep ? kLightsChainShadowShade : kLightsChainShade);
+    } else if (mirror) {
+        p.family = grid ? kGridReflectShade : (several ? kLightsReflectShade : kReflectShade);
+    } else {
+        p.family = grid ? kGridShade : (several ? kLightsShade : kShadowShade);
+    }
+    p.dark0 = grid;
+    p.levels = chain ? q.reflect_depth + 1u : (mirror ? 2u : 1u);
+    p.deep_off = 8u * p.levels;
+    p.dark0_off = p.deep_off + (p.deep ? 4u : 0u);
+    p.bytes_per_px = p.dark0_off + (p.dark0 ? 4u : 0u);
+    return p;
+}
+
 } // namespace rtxplan

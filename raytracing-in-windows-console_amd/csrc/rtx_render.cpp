@@ -45,9 +45,31 @@ bool uses_two_level(const rtx_ctx* ctx, bool view_dense = false)
     return uses_culling_kernel(ctx) && ctx->ns > 0 && (ctx->opt_two_level >= 1 || (ctx->opt_two_level < 0 && ctx->ns >= from));
 }
 
+// What rtxplan::plan_shading reads of the call, the options and the scene (grid_usable: not known yet).
+rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
+{
+    static_assert(RTX_BIT_ASCII == rtxplan::kShadedModeLo && RTX_RGB_PIXEL == rtxplan::kShadedModeHi, "the modes that shade");
+    const rtx_light ref = rtx_reference_light();
+    rtxplan::ShadingRequest q;
+    q.mode = mode;
+    q.shadows = ctx->opt_shadows != 0;
+    q.shadow_check = (int)ctx->opt_shadow_check;
+    q.lights_check = ctx->opt_lights_check != 0;
+    q.n_lights = ctx->n_lights;
+    q.light0_is_reference = std::memcmp(&ctx->lights[0], &ref, sizeof ref) == 0;
+    q.n_reflective = ctx->n_reflective;
+    q.reflect_check = (int)ctx->opt_reflect_check;
+    q.reflect_depth = (uint32_t)ctx->opt_reflect_depth;
+    q.reflect_depth_check = ctx->opt_reflect_depth_check != 0;
+    q.reflect_shadows = ctx->opt_reflect_shadows != 0;
+    q.shadow_grid = ctx->opt_shadow_grid != 0;
+    q.ns = ctx->ns;
+    return q;
+}
+
 // A stream in capture (rtx_graph_begin) records launches: nothing that synchronises or keeps per-launch state may
 // run.  Checked before anything is queued, so that a refused call leaves the capture as it found it.
-int check_recordable(rtx_ctx* ctx, hipStream_t stream, bool* capturing)
+int check_recordable(rtx_ctx* ctx, hipStream_t stream, int mode, bool* capturing)
 {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     RTX_HIP(ctx, hipStreamIsCapturing(stream, &st));
@@ -59,7 +81,65 @@ int check_recordable(rtx_ctx* ctx, hipStream_t stream, bool* capturing)
     if (uses_two_level(ctx)) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches with the two-level pre-pass cannot be recorded (its counters alternate per launch)");
     }
+    if (rtxplan::shading_wants_grid(shading_request(ctx, mode))) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID: "
+                                                       "the lists change with physics, and their build allocates and waits)");
+    }
     return RTX_OK;
+}
+
+// The scene on the device as the host has it, and the direction-sorted copies the trace kernels read rebuilt around this camera
+// at the first launch after a scene edit.  Not while capturing (check_recordable).
+int scene_up_to_date(rtx_ctx* ctx, const float cam_pos[3])
+{
+    int rc;
+    if ((rc = rtx_sync_scene(ctx)) != RTX_OK) return rc;
+    if (ctx->opt_sorted_store != 0 && ctx->sorted_gen != ctx->scene_gen && ctx->ns >= 256u) {
+        if ((rc = rtx_sort_scene(ctx, cam_pos)) != RTX_OK) return rc;
+        ctx->lists_gen++; // (cell lists hold positions in those arrays)
+        ctx->cell_policy.invalidate();
+    }
+    return RTX_OK;
+}
+
+struct RenderCall { // what the arguments of a call come to
+    uint64_t W = 0, H = 0, row0 = 0, rows = 0, out_row_base = 0;
+    void* d_out = nullptr;
+    bool own = false, compact = false, values = false;
+};
+
+// The culling pyramids' planes of camera `p` (rtxplan::EdgeBasis) into a launch's or a batched frame's arguments.
+template <class Args>
+void fill_edge_basis(Args& a, const rtx_params* p, const RenderCall& c)
+{
+    const rtxplan::EdgeBasis eb = rtxplan::edge_basis(p->inv_v, p->element1, p->element2, (uint64_t)c.W, (uint64_t)c.H);
+    for (int k = 0; k < 3; k++) {
+        a.edge_up_p[k] = eb.up_p[k];
+        a.edge_up_q[k] = eb.up_q[k];
+        a.edge_right_p[k] = eb.right_p[k];
+        a.edge_right_q[k] = eb.right_q[k];
+        a.edge_fwd[k] = eb.fwd[k];
+    }
+    a.edge_pp = eb.pp;
+    a.edge_qrqr = eb.qrqr;
+    a.edge_qcqc = eb.qcqc;
+}
+
+// What rtxplan::plan_tiles reads of the call and the options (view_dense, in_flight: the caller's).
+rtxplan::TileRequest tile_request(const rtx_ctx* ctx, const RenderCall& c, double aspect, bool cull)
+{
+    rtxplan::TileRequest q;
+    q.W = c.W;
+    q.H = c.H;
+    q.rows = c.rows;
+    q.ns = ctx->ns;
+    q.aspect = aspect;
+    q.n_cu = ctx->n_cu;
+    q.cull = cull;
+    q.opt_subtiles = (int)ctx->opt_subtiles;
+    q.opt_tile_log2w = (int)ctx->opt_tile_log2w;
+    q.opt_refine = (int)ctx->opt_refine;
+    return q;
 }
 
 } // namespace
@@ -567,26 +647,10 @@ rtx_ctx::TileOrder* tile_order_set(rtx_ctx* ctx, hipStream_t stream, const uint6
     return to;
 }
 
-// ---- the light / shadow path (RTX_OPT_SHADOWS, rtx_scene_set_light)
-
-// Does a launch of `mode` take the two-launch path?  Not in the state the reference has (shadows off, its light): there every
-// launch is today's.  Never for RGB_NORMALS and SDL, which do not shade.
-bool shadow_path(const rtx_ctx* ctx, int mode)
-{
-    if (mode < RTX_BIT_ASCII || mode > RTX_RGB_PIXEL) return false;
-    const rtx_light ref = rtx_reference_light();
-    return ctx->opt_shadows != 0 || ctx->n_lights != 1 || ctx->opt_lights_check != 0 || std::memcmp(&ctx->lights[0], &ref, sizeof ref) != 0;
-}
-
-// Is the shading launch of either path the several-lights kernel?  A set of one light keeps rtx_shadow_shade / rtx_reflect_shade.
-bool lights_kernels(const rtx_ctx* ctx) { return ctx->n_lights >= 2 || ctx->opt_lights_check != 0; }
-
-// Is the shadow test asked to go through the world grid (RTX_OPT_SHADOW_GRID)?  By the options and the scene alone: whether the
-// grid is usable is known after its build (grid_shadow_args).  Checks 1 and 2 keep today's launches: they are the brute reference.
-bool grid_shadows_wanted(const rtx_ctx* ctx) { return ctx->opt_shadow_grid != 0 && ctx->opt_shadows != 0 && ctx->opt_shadow_check == 0 && ctx->ns != 0; }
+// ---- the launches of a frame (rtxplan::plan_shading: the light / shadow path, the mirror path, shadow tests through the world grid)
 
 // The grid up to date for a launch set on `stream` (rtx_grid_ensure: a build blocks) and what rtx_grid_shadow reads of it.
-// *in_effect = false: no usable grid (RTX_STAT_QUERY_BRUTE), every launch is today's.
+// *in_effect = false: no usable grid (RTX_STAT_QUERY_BRUTE), the frame is planned without one.
 int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool* in_effect)
 {
     *in_effect = false;
@@ -606,19 +670,6 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
     gs->n_large = g.n_large;
     gs->fallback = ctx->d_shadow_grid_fallback;
     *in_effect = true;
-    return RTX_OK;
-}
-
-// rtx_grid_shadow on `stream`, behind the launches that left the hits: level 0's words into gs->dark0, the deeper levels' into
-// cs->dark when gs->deep is set.
-int launch_grid_shadow(rtx_ctx* ctx, const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const ChainShadowArgs& cs,
-                       const GridShadowArgs& gs, hipStream_t stream)
-{
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback, 0, sizeof(uint32_t), stream));
-    int herr = 0;
-    const char* name = rtx_k_launch_grid_shadow(&a, &la, &ra, &ca, &cs, &gs, stream, &herr);
-    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow grid pass: invalid frame geometry, depth or light set");
-    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow grid kernel launch");
     return RTX_OK;
 }
 
@@ -703,61 +754,6 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     return la;
 }
 
-// Trace the closest hits of `a` into the stream's hit buffer, then shade them into a.out (rtx_shadow_shade, or rtx_lights_shade
-// for a set of several lights).
-int launch_shadow_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
-{
-    const size_t rows = a.row_end - a.row0;
-    const size_t px = (size_t)a.W * rows;
-    void* hits = nullptr;
-    int rc;
-    GridShadowArgs gs;
-    bool grid = false; // (never while capturing: rtx_render_rows has refused)
-    if (grid_shadows_wanted(ctx) && (rc = grid_shadow_args(ctx, stream, &gs, &grid)) != RTX_OK) return rc;
-    if ((rc = hit_buffer(ctx, stream, px * (grid ? 12u : 8u), capturing, &hits)) != RTX_OK) return rc;
-    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
-    if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
-    int herr = 0;
-    const char* name = nullptr;
-    if (grid) {
-        // the tests through the world grid, then the shade family that reads their words: any light set, a set of one included
-        const LightsArgs la = lights_args(ctx, hits);
-        ReflectArgs ra;
-        ChainArgs ca;
-        ChainShadowArgs cs;
-        std::memset(&ra, 0, sizeof ra);
-        std::memset(&ca, 0, sizeof ca);
-        std::memset(&cs, 0, sizeof cs);
-        gs.dark0 = (uint32_t*)((uint2*)hits + px);
-        if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
-        name = rtx_k_launch_grid_shade(&a, &la, nullptr, nullptr, nullptr, gs.dark0, mode, stream, &herr);
-        if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
-        if (name && herr == 0) ctx->stat_shadow_grid_frames++;
-    } else if (lights_kernels(ctx)) {
-        const LightsArgs la = lights_args(ctx, hits);
-        name = rtx_k_launch_lights_shade(&a, &la, nullptr, mode, stream, &herr);
-    } else {
-        const ShadowArgs sa = shadow_args(ctx, hits);
-        name = rtx_k_launch_shadow(&a, &sa, mode, stream, &herr);
-    }
-    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "shadow pass: invalid rendering mode or output form");
-    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "shadow shading kernel launch");
-    ctx->last_kernel = name;
-    ctx->stat_shadow_frames++;
-    return RTX_OK;
-}
-
-// ---- the mirror path (rtx_scene_set_reflectivity)
-
-// Does a launch of `mode` take the three-launch mirror path?  Only while some object reflects (an O(1) count), or under
-// RTX_OPT_REFLECT_CHECK 2; it takes precedence over shadow_path and runs the shadow test itself.  The character modes only.
-bool reflect_path(const rtx_ctx* ctx, int mode)
-{
-    if (mode < RTX_BIT_ASCII || mode > RTX_RGB_PIXEL) return false;
-    return ctx->n_reflective != 0 || ctx->opt_reflect_check == 2;
-}
-
 // The device copies of the reflectivities after a change, a scene edit or a new sort: spheres by index and by sorted position,
 // planes by index (at least one entry each, so that the kernels always get an array).  Waits for the frames in flight first.
 int upload_reflectivity(rtx_ctx* ctx)
@@ -786,139 +782,127 @@ int upload_reflectivity(rtx_ctx* ctx)
     return RTX_OK;
 }
 
-// Are the deeper levels shadow-tested (RTX_OPT_REFLECT_SHADOWS)?  Only with shadows on and while some object reflects.
-bool reflect_shadows(const rtx_ctx* ctx) { return ctx->opt_reflect_shadows != 0 && ctx->opt_shadows != 0 && ctx->n_reflective != 0; }
-
-// Do the mirror path's second and third launches go through the chain kernels?  Not at depth 1 unless the check option asks, or the
-// deeper levels are shadow-tested.
-bool chain_kernels(const rtx_ctx* ctx) { return ctx->opt_reflect_depth > 1 || ctx->opt_reflect_depth_check != 0 || reflect_shadows(ctx); }
-
-// Closest hits (rtx_trace, kOutHit), the secondary hits of the reflective pixels (rtx_reflect_hit), then shading with the shadow
-// test and the blend into a.out (rtx_reflect_shade).  The stream's hit buffer holds both hit arrays: 16 bytes per pixel.
-// With RTX_OPT_REFLECT_DEPTH > 1 (or RTX_OPT_REFLECT_DEPTH_CHECK 1): closest hits, rtx_reflect_chain (every level in one launch),
-// rtx_lights_chain_shade; the hit buffer holds depth + 1 hit arrays.  With RTX_OPT_REFLECT_SHADOWS in effect: the chain kernels at
-// any depth, rtx_chain_shadow after rtx_reflect_chain (the deeper levels' dark lights, a word per pixel behind the hit arrays) and
-// rtx_lights_chain_shadow_shade, which reads them.
-int launch_reflect_path(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
+// The launches of one frame on `stream`, as rtxplan::plan_shading lays them out: the trace launch alone (direct), or the closest
+// hits into the stream's hit buffer, the plan's secondary pass and shadow pass, and the shade launch of the plan's family into a.out.
+int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t stream, bool capturing)
 {
-    int rc;
-    if (ctx->refl_dirty) {
+    using namespace rtxplan;
+    int rc, herr = 0;
+    ShadingRequest req = shading_request(ctx, mode);
+    const bool mirror = shading_path(req) == kPathMirror;
+    if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
+    if (mirror && ctx->refl_dirty) {
         if (capturing) {
             return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: the reflectivities are not uploaded yet (render once before capturing)");
         }
         if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
     }
-    const bool chain = chain_kernels(ctx);
-    const bool deep_shadows = reflect_shadows(ctx);
-    const size_t depth = (size_t)ctx->opt_reflect_depth;
-    const size_t px = (size_t)a.W * (a.row_end - a.row0);
-    void* hits = nullptr;
-    GridShadowArgs gs;
-    bool grid = false; // (never while capturing: rtx_render_rows has refused)
-    if (grid_shadows_wanted(ctx) && (rc = grid_shadow_args(ctx, stream, &gs, &grid)) != RTX_OK) return rc;
-    // (the grid path's level-0 words follow everything else: 4 more bytes per pixel)
-    const size_t hit_bytes = chain ? px * (8u * (depth + 1u) + (deep_shadows ? 4u : 0u)) : px * 16u;
-    if ((rc = hit_buffer(ctx, stream, hit_bytes + (grid ? px * 4u : 0u), capturing, &hits)) != RTX_OK) return rc;
-    gs.dark0 = grid ? (uint32_t*)((char*)hits + hit_bytes) : nullptr;
-    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
-    if (!ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
-    if (chain && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
-    if (deep_shadows && !ctx->d_reflect_shadow_points) {
-        RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_shadow_points, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t)));
-    }
-    if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
-    ReflectArgs ra;
-    std::memset(&ra, 0, sizeof ra);
-    ra.hits = (const uint2*)hits;
-    ra.hits2 = (uint2*)hits + px;
-    ra.k_sph = (const float*)(a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.p : ctx->d_refl_sph.p);
-    ra.k_pl = (const float*)ctx->d_refl_pl.p;
-    ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
-    ra.longest = ctx->d_reflect_longest;
-    int herr = 0;
-    const char* name = nullptr;
-    ctx->reflect_rays_valid = chain;
-    ctx->reflect_shadow_points_valid = deep_shadows;
-    if (chain) {
-        RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
-        ChainArgs ca;
-        std::memset(&ca, 0, sizeof ca);
-        ca.depth = (uint32_t)depth;
-        ca.px = (uint32_t)px;
-        ca.rays = ctx->d_reflect_rays;
-        name = rtx_k_launch_reflect_chain(&a, &ra, &ca, stream, &herr);
-        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry or depth");
-        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "reflection chain kernel launch");
-        const LightsArgs la = lights_args(ctx, hits);
-        if (grid) {
-            // rtx_grid_shadow decides level 0 and, in place of rtx_chain_shadow, the deeper levels; the grid family shades
-            ChainShadowArgs cs;
-            std::memset(&cs, 0, sizeof cs);
-            if (deep_shadows) {
-                RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
-                cs.dark = (uint32_t*)((uint2*)hits + px * (depth + 1u));
-                cs.points = ctx->d_reflect_shadow_points;
-            }
-            gs.deep = deep_shadows ? 1u : 0u;
-            if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
-            name = rtx_k_launch_grid_shade(&a, &la, &ra, &ca, deep_shadows ? &cs : nullptr, gs.dark0, mode, stream, &herr);
-            if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
-            if (name && herr == 0) ctx->stat_shadow_grid_frames++;
-        } else if (deep_shadows) {
-            RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t), stream));
-            ChainShadowArgs cs;
-            std::memset(&cs, 0, sizeof cs);
-            cs.dark = (uint32_t*)((uint2*)hits + px * (depth + 1u));
-            cs.points = ctx->d_reflect_shadow_points;
-            name = rtx_k_launch_chain_shadow(&a, &la, &ra, &ca, &cs, stream, &herr);
-            if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry, depth or light set");
-            if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "chain shadow kernel launch");
-            name = rtx_k_launch_lights_chain_shadow_shade(&a, &la, &ra, &ca, &cs, mode, stream, &herr);
-        } else {
-            name = rtx_k_launch_lights_chain_shade(&a, &la, &ra, &ca, mode, stream, &herr);
-        }
-        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
-        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "chain shading kernel launch");
+    GridShadowArgs gs; // (never while capturing: check_recordable has refused)
+    if (shading_wants_grid(req) && (rc = grid_shadow_args(ctx, stream, &gs, &req.grid_usable)) != RTX_OK) return rc;
+    const ShadingPlan plan = plan_shading(req);
+    if (plan.path == kPathDirect) {
+        const char* name = rtx_k_launch_trace(&a, mode, cull, stream, &herr);
+        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
+        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch");
         ctx->last_kernel = name;
-        ctx->stat_reflect_frames++;
         return RTX_OK;
     }
-    name = rtx_k_launch_reflect_hit(&a, &ra, stream, &herr);
-    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid frame geometry");
-    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "secondary hit kernel launch");
-    if (grid) {
-        const LightsArgs la = lights_args(ctx, hits);
-        ChainArgs ca;
-        ChainShadowArgs cs;
-        std::memset(&ca, 0, sizeof ca);
-        std::memset(&cs, 0, sizeof cs);
-        if ((rc = launch_grid_shadow(ctx, a, la, ra, ca, cs, gs, stream)) != RTX_OK) return rc;
-        name = rtx_k_launch_grid_shade(&a, &la, &ra, nullptr, nullptr, gs.dark0, mode, stream, &herr);
-        if (name && herr == 0 && (rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
-        if (name && herr == 0) ctx->stat_shadow_grid_frames++;
-    } else if (lights_kernels(ctx)) {
-        const LightsArgs la = lights_args(ctx, hits);
-        name = rtx_k_launch_lights_shade(&a, &la, &ra, mode, stream, &herr);
-    } else {
-        const ShadowArgs sa = shadow_args(ctx, hits);
-        name = rtx_k_launch_reflect_shade(&a, &sa, &ra, mode, stream, &herr);
+
+    // the hit buffer, the counters this plan's kernels write, the closest hits
+    const size_t px = (size_t)a.W * (a.row_end - a.row0);
+    const size_t per_level = RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t);
+    void* hit_base = nullptr;
+    if ((rc = hit_buffer(ctx, stream, px * plan.bytes_per_px, capturing, &hit_base)) != RTX_OK) return rc;
+    char* const hits = (char*)hit_base;
+    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
+    if (mirror && !ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
+    if (plan.chain() && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, per_level));
+    if (plan.deep && !ctx->d_reflect_shadow_points) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_shadow_points, per_level));
+    if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
+    if (mirror) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
+    if (plan.chain()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays, 0, per_level, stream));
+    if (plan.deep) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, per_level, stream));
+    if (plan.dark0) RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback, 0, sizeof(uint32_t), stream));
+    if (mirror) { // (the other paths leave reflect_rays_valid as it is)
+        ctx->reflect_rays_valid = plan.chain();
+        ctx->reflect_shadow_points_valid = plan.deep;
     }
-    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "mirror pass: invalid rendering mode or output form");
-    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "mirror shading kernel launch");
+
+    // every argument struct once, from the plan's offsets; what the plan has none of stays zero
+    ShadowArgs sa;
+    LightsArgs la;
+    ReflectArgs ra;
+    ChainArgs ca;
+    ChainShadowArgs cs;
+    TileArgs t;
+    std::memset(&ra, 0, sizeof ra);
+    std::memset(&ca, 0, sizeof ca);
+    std::memset(&cs, 0, sizeof cs);
+    std::memset(&t, 0, sizeof t);
+    t.a = &a;
+    t.reflect = &ra;
+    t.chain = &ca;
+    t.deep = &cs;
+    if (shade_takes_light_set(plan.family)) {
+        la = lights_args(ctx, hits);
+        t.lights = &la;
+    } else {
+        sa = shadow_args(ctx, hits);
+        t.shadow = &sa;
+    }
+    if (mirror) {
+        ra.hits = (const uint2*)hits;
+        ra.hits2 = (uint2*)(hits + 8u * px); // level 1's
+        ra.k_sph = (const float*)(a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.p : ctx->d_refl_sph.p);
+        ra.k_pl = (const float*)ctx->d_refl_pl.p;
+        ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
+        ra.longest = ctx->d_reflect_longest;
+    }
+    if (plan.chain()) {
+        ca.depth = plan.levels - 1u;
+        ca.px = (uint32_t)px;
+        ca.rays = ctx->d_reflect_rays;
+    }
+    if (plan.deep) {
+        cs.dark = (uint32_t*)(hits + plan.deep_off * px);
+        cs.points = ctx->d_reflect_shadow_points;
+    }
+    if (plan.dark0) {
+        gs.dark0 = (uint32_t*)(hits + plan.dark0_off * px);
+        gs.deep = plan.deep ? 1u : 0u;
+        t.grid = &gs;
+        t.dark0 = gs.dark0;
+    }
+
+    // the passes, the shade launch
+    static const struct {
+        const char *refused, *launch;
+    } kPassText[kShadePasses] = {{"", ""},
+                                 {"mirror pass: invalid frame geometry", "secondary hit kernel launch"},
+                                 {"mirror pass: invalid frame geometry or depth", "reflection chain kernel launch"},
+                                 {"mirror pass: invalid frame geometry, depth or light set", "chain shadow kernel launch"},
+                                 {"shadow grid pass: invalid frame geometry, depth or light set", "shadow grid kernel launch"}};
+    for (const ShadePass pass : {plan.secondary, plan.shadow_pass}) {
+        if (pass == kPassNone) continue;
+        if (!rtx_k_launch_pass(pass, &t, stream, &herr)) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, kPassText[pass].refused);
+        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, kPassText[pass].launch);
+    }
+    const char* name = rtx_k_launch_shade(plan.family, &t, mode, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, mirror ? "mirror pass: invalid rendering mode or output form" : "shadow pass: invalid rendering mode or output form");
+    if (herr != 0) {
+        return rtx_hip_fail(ctx, (hipError_t)herr, plan.chain() ? "chain shading kernel launch" : (mirror ? "mirror shading kernel launch" : "shadow shading kernel launch"));
+    }
+    if (plan.dark0) {
+        if ((rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
+        ctx->stat_shadow_grid_frames++;
+    }
     ctx->last_kernel = name;
-    ctx->stat_reflect_frames++;
+    (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     return RTX_OK;
 }
 
 // ---- the pieces of rtx_render_rows
-
-struct RenderCall { // what the arguments of a call come to
-    uint64_t W = 0, H = 0, row0 = 0, rows = 0, out_row_base = 0;
-    void* d_out = nullptr;
-    bool own = false, compact = false, values = false;
-};
 
 int validate_render_call(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, size_t rows, void* d_out, size_t out_row_base, unsigned flags, RenderCall* c)
 {
@@ -974,17 +958,7 @@ void fill_frame_args(const rtx_ctx* ctx, const rtx_params* p, const RenderCall& 
     a.far = p->cam_far;
     a.fW = (float)c.W; // (float)(params->x), RayTracing.cu:17
     a.fH = (float)c.H;
-    const rtxplan::EdgeBasis eb = rtxplan::edge_basis(p->inv_v, p->element1, p->element2, (uint64_t)c.W, (uint64_t)c.H);
-    for (int k = 0; k < 3; k++) {
-        a.edge_up_p[k] = eb.up_p[k];
-        a.edge_up_q[k] = eb.up_q[k];
-        a.edge_right_p[k] = eb.right_p[k];
-        a.edge_right_q[k] = eb.right_q[k];
-        a.edge_fwd[k] = eb.fwd[k];
-    }
-    a.edge_pp = eb.pp;
-    a.edge_qrqr = eb.qrqr;
-    a.edge_qcqc = eb.qcqc;
+    fill_edge_basis(a, p, c);
     a.W = (uint32_t)c.W;
     a.H = (uint32_t)c.H;
     a.row0 = (uint32_t)c.row0;
@@ -1196,7 +1170,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
                  hipStream_t stream, unsigned flags, bool* done)
 {
     *done = false;
-    if (shadow_path(ctx, mode) || reflect_path(ctx, mode)) return RTX_OK; // (two or three launches per slab)
+    if (rtxplan::shading_path(shading_request(ctx, mode)) != rtxplan::kPathDirect) return RTX_OK; // (several launches per slab)
     if (n < 2 || n > (size_t)kMaxBatch || mode < RTX_BIT_ASCII || mode >= RTX_SDL || (flags & ~(unsigned)RTX_RENDER_COMPACT) != 0u) return RTX_OK;
     if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt_refine == 1) return RTX_OK;
     for (size_t i = 0; i < n; i++) {
@@ -1212,29 +1186,12 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
         return RTX_OK;
     }
     bool capturing = false;
-    if ((rc = check_recordable(ctx, stream, &capturing)) != RTX_OK) return rc;
-    if (!capturing) {
-        if ((rc = rtx_sync_scene(ctx)) != RTX_OK) return rc;
-        if (ctx->opt_sorted_store != 0 && ctx->sorted_gen != ctx->scene_gen && ctx->ns >= 256u) {
-            if ((rc = rtx_sort_scene(ctx, params[0].cam_pos)) != RTX_OK) return rc;
-            ctx->lists_gen++;
-            ctx->cell_policy.invalidate();
-        }
-    }
+    if ((rc = check_recordable(ctx, stream, mode, &capturing)) != RTX_OK) return rc;
+    if (!capturing && (rc = scene_up_to_date(ctx, params[0].cam_pos)) != RTX_OK) return rc;
     KArgs a;
     fill_frame_args(ctx, &params[0], c, a);
     const double aspect = pixel_aspect(&params[0]);
-    rtxplan::TileRequest q;
-    q.W = c.W;
-    q.H = c.H;
-    q.rows = c.rows;
-    q.ns = ctx->ns;
-    q.aspect = aspect;
-    q.n_cu = ctx->n_cu;
-    q.cull = true;
-    q.opt_subtiles = (int)ctx->opt_subtiles;
-    q.opt_tile_log2w = (int)ctx->opt_tile_log2w;
-    q.opt_refine = (int)ctx->opt_refine;
+    rtxplan::TileRequest q = tile_request(ctx, c, aspect, true);
     // the plan of the whole batch: as many 256-pixel tiles as all its frames have, so that the sub-tile count is chosen for
     // the grid the GPU really sees (one dispatch round where that is possible)
     if (ctx->opt_subtiles == 0) q.rows = c.rows * n;
@@ -1273,17 +1230,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
         f.ox = p.cam_pos[0];
         f.oy = p.cam_pos[1];
         f.oz = p.cam_pos[2];
-        const rtxplan::EdgeBasis eb = rtxplan::edge_basis(p.inv_v, p.element1, p.element2, (uint64_t)c.W, (uint64_t)c.H);
-        for (int k = 0; k < 3; k++) {
-            f.edge_up_p[k] = eb.up_p[k];
-            f.edge_up_q[k] = eb.up_q[k];
-            f.edge_right_p[k] = eb.right_p[k];
-            f.edge_right_q[k] = eb.right_q[k];
-            f.edge_fwd[k] = eb.fwd[k];
-        }
-        f.edge_pp = eb.pp;
-        f.edge_qrqr = eb.qrqr;
-        f.edge_qcqc = eb.qcqc;
+        fill_edge_basis(f, &p, c);
         f.out = (uint8_t*)d_outs[i];
     }
     int herr = 0;
@@ -1316,25 +1263,13 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
     bool capturing = false;
-    if ((rc = check_recordable(ctx, stream, &capturing)) != RTX_OK) return rc;
-    if (capturing && grid_shadows_wanted(ctx) && (shadow_path(ctx, mode) || reflect_path(ctx, mode))) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID: "
-                                                       "the lists change with physics, and their build allocates and waits)");
-    }
+    if ((rc = check_recordable(ctx, stream, mode, &capturing)) != RTX_OK) return rc;
     if (capturing && c.own) {
         // the zero-fill of the context's buffer is decided from what earlier launches left in it (dirty_hi): a recorded
         // launch would replay that decision whatever the replays in between have written
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: recorded launches need a caller buffer (d_out), not the context's own");
     }
-    if (!capturing) {
-        if ((rc = rtx_sync_scene(ctx)) != RTX_OK) return rc;
-        // the direction-sorted copies the trace kernels read: rebuilt at the first launch after a scene edit, around this camera
-        if (ctx->opt_sorted_store != 0 && ctx->sorted_gen != ctx->scene_gen && ctx->ns >= 256u) {
-            if ((rc = rtx_sort_scene(ctx, p->cam_pos)) != RTX_OK) return rc;
-            ctx->lists_gen++; // (cell lists hold positions in those arrays)
-            ctx->cell_policy.invalidate();
-        }
-    }
+    if (!capturing && (rc = scene_up_to_date(ctx, p->cam_pos)) != RTX_OK) return rc;
     if ((rc = zero_fill_semantics(ctx, mode, c.W, c.H, c.d_out, c.own, c.compact, flags, stream)) != RTX_OK) return rc;
     if (c.rows == 0) return RTX_OK;
 
@@ -1344,17 +1279,7 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     // ---- plan (rtx_plan.hpp): tile shape -- for a dense scene, or for a view that the launches before this one found locally dense
     const int cull = uses_culling_kernel(ctx) ? 1 : 0;
     const double aspect = pixel_aspect(p);
-    rtxplan::TileRequest q;
-    q.W = c.W;
-    q.H = c.H;
-    q.rows = c.rows;
-    q.ns = ctx->ns;
-    q.aspect = aspect;
-    q.n_cu = ctx->n_cu;
-    q.cull = cull != 0;
-    q.opt_subtiles = (int)ctx->opt_subtiles;
-    q.opt_tile_log2w = (int)ctx->opt_tile_log2w;
-    q.opt_refine = (int)ctx->opt_refine;
+    rtxplan::TileRequest q = tile_request(ctx, c, aspect, cull != 0);
     const bool adapt = view_adaptation_applies(ctx, q, capturing);
     q.view_dense = adapt && ctx->view_density.dense();
     q.in_flight = ctx->render_streams_seen >= 2; // (of the last 16 two-level launches: prepare_cells keeps count)
@@ -1382,19 +1307,7 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     rtxplan::DispatchOrder::Decision od;
     if (cull && (rc = dispatch_order_args(ctx, stream, p, c, shape, capturing, static_order, a, &to, &od)) != RTX_OK) return rc;
     if (adapt && (rc = density_feedback_args(ctx, stream, q.view_dense, a)) != RTX_OK) return rc;
-    if (reflect_path(ctx, mode)) {
-        if ((rc = launch_reflect_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
-    } else if (shadow_path(ctx, mode)) {
-        ctx->reflect_shadow_points_valid = false; // (not the mirror path: RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
-        if ((rc = launch_shadow_path(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
-    } else {
-        ctx->reflect_shadow_points_valid = false;
-        int herr = 0;
-        const char* name = rtx_k_launch_trace(&a, mode, cull, stream, &herr);
-        if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
-        if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "trace kernel launch");
-        ctx->last_kernel = name;
-    }
+    if ((rc = launch_frame(ctx, a, mode, cull, stream, capturing)) != RTX_OK) return rc;
     if (adapt && (rc = density_feedback_collect(ctx, stream)) != RTX_OK) return rc;
     if (to && (rc = dispatch_order_derive(ctx, stream, shape, a, to, od)) != RTX_OK) return rc;
     return RTX_OK;
@@ -1429,11 +1342,8 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
     if (join) {
         // refuse what cannot be recorded before the fork below pulls the render streams into a capture
         bool capturing = false;
-        const int rc = check_recordable(ctx, join, &capturing);
+        const int rc = check_recordable(ctx, join, mode, &capturing);
         if (rc != RTX_OK) return rc;
-        if (capturing && grid_shadows_wanted(ctx) && (shadow_path(ctx, mode) || reflect_path(ctx, mode))) {
-            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID)");
-        }
     }
     // distinct render streams of this call, each with its event
     std::vector<rtx_ctx::JoinEvent*> used;

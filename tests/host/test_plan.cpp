@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -813,8 +814,191 @@ static void test_edge_basis()
     }
 }
 
+// ---- plan_shading: which launches make up a frame, and the hit buffer's layout
+
+static ShadingRequest shading_request() // the reference's state: RGB_ASCII, its one light, nothing on
+{
+    ShadingRequest q;
+    q.mode = 2;
+    q.ns = 300;
+    return q;
+}
+
+static bool ends_with(const char* s, const char* tail)
+{
+    const size_t n = std::strlen(s), m = std::strlen(tail);
+    return n >= m && std::strcmp(s + n - m, tail) == 0;
+}
+
+static void test_shading_table()
+{
+    struct Row {
+        const char* what;
+        ShadingRequest q;
+        ShadePath path;
+        const char* family; // nullptr: direct
+        ShadePass secondary, shadow_pass;
+        bool deep;
+        uint32_t levels, bytes, deep_off, dark0_off;
+    };
+    std::vector<Row> rows;
+    const auto add = [&](const char* what, const ShadingRequest& q, ShadePath path, const char* family, ShadePass secondary, ShadePass shadow_pass, bool deep,
+                         uint32_t levels, uint32_t bytes, uint32_t deep_off, uint32_t dark0_off) {
+        rows.push_back(Row{what, q, path, family, secondary, shadow_pass, deep, levels, bytes, deep_off, dark0_off});
+    };
+    ShadingRequest q = shading_request();
+    add("reference state", q, kPathDirect, nullptr, kPassNone, kPassNone, false, 0, 0, 0, 0);
+    q.shadows = true;
+    add("shadows, one light", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.shadow_grid = true;
+    add("grid wanted but unusable", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.grid_usable = true;
+    add("grid, one light", q, kPathShaded, "rtx_grid_shade", kPassNone, kPassGridShadow, false, 1, 12, 8, 8);
+    q.shadow_check = 1;
+    add("grid option under shadow check 1", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.shadow_check = 2;
+    add("grid option under shadow check 2", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.shadow_check = 0;
+    q.ns = 0;
+    add("grid option without spheres", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q = shading_request();
+    q.light0_is_reference = false;
+    add("another light, shadows off", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.shadow_grid = q.grid_usable = true;
+    add("grid option with shadows off", q, kPathShaded, "rtx_shadow_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q = shading_request();
+    q.lights_check = true;
+    add("lights check, one light", q, kPathShaded, "rtx_lights_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q = shading_request();
+    q.n_lights = 2;
+    add("two lights", q, kPathShaded, "rtx_lights_shade", kPassNone, kPassNone, false, 1, 8, 8, 8);
+    q.shadows = q.shadow_grid = q.grid_usable = true;
+    add("two lights, grid", q, kPathShaded, "rtx_grid_shade", kPassNone, kPassGridShadow, false, 1, 12, 8, 8);
+    q = shading_request();
+    q.n_reflective = 1;
+    add("a mirror, one light", q, kPathMirror, "rtx_reflect_shade", kPassReflectHit, kPassNone, false, 2, 16, 16, 16);
+    q.reflect_shadows = true;
+    add("reflect-shadows with shadows off", q, kPathMirror, "rtx_reflect_shade", kPassReflectHit, kPassNone, false, 2, 16, 16, 16);
+    q.reflect_shadows = false;
+    q.n_lights = 2;
+    add("two lights and a mirror at depth 1", q, kPathMirror, "rtx_lights_reflect_shade", kPassReflectHit, kPassNone, false, 2, 16, 16, 16);
+    q.shadows = q.shadow_grid = q.grid_usable = true;
+    add("... with the grid", q, kPathMirror, "rtx_grid_reflect_shade", kPassReflectHit, kPassGridShadow, false, 2, 20, 16, 16);
+    q.shadows = q.shadow_grid = q.grid_usable = false;
+    q.reflect_depth_check = true;
+    add("depth check at depth 1", q, kPathMirror, "rtx_lights_chain_shade", kPassReflectChain, kPassNone, false, 2, 16, 16, 16);
+    q.reflect_depth_check = false;
+    q.reflect_depth = 3;
+    add("depth 3", q, kPathMirror, "rtx_lights_chain_shade", kPassReflectChain, kPassNone, false, 4, 32, 32, 32);
+    q.n_lights = 1;
+    add("depth 3, one light", q, kPathMirror, "rtx_lights_chain_shade", kPassReflectChain, kPassNone, false, 4, 32, 32, 32);
+    q.n_lights = 2;
+    q.shadows = q.shadow_grid = q.grid_usable = true;
+    add("depth 3 with the grid", q, kPathMirror, "rtx_grid_chain_shade", kPassReflectChain, kPassGridShadow, false, 4, 36, 32, 32);
+    q.shadow_grid = false;
+    q.reflect_shadows = true;
+    add("depth 3 with reflect-shadows", q, kPathMirror, "rtx_lights_chain_shadow_shade", kPassReflectChain, kPassChainShadow, true, 4, 36, 32, 36);
+    q.shadow_grid = true;
+    add("depth 3 with reflect-shadows and grid", q, kPathMirror, "rtx_grid_chain_shadow_shade", kPassReflectChain, kPassGridShadow, true, 4, 40, 32, 36);
+    q.reflect_depth = 4;
+    add("depth 4 with reflect-shadows and grid", q, kPathMirror, "rtx_grid_chain_shadow_shade", kPassReflectChain, kPassGridShadow, true, 5, 48, 40, 44);
+    q.shadow_grid = false;
+    q.reflect_depth = 1;
+    add("reflect-shadows at depth 1", q, kPathMirror, "rtx_lights_chain_shadow_shade", kPassReflectChain, kPassChainShadow, true, 2, 20, 16, 20);
+    q = shading_request();
+    q.reflect_check = 2;
+    q.shadows = q.reflect_shadows = true;
+    add("reflect check 2 with nothing reflective", q, kPathMirror, "rtx_reflect_shade", kPassReflectHit, kPassNone, false, 2, 16, 16, 16);
+    q.n_reflective = 1;
+    q.n_lights = 2;
+    q.reflect_depth = 3;
+    q.shadow_grid = q.grid_usable = true;
+    for (int mode = 4; mode <= 5; mode++) {
+        q.mode = mode;
+        add("RGB_NORMALS / SDL whatever the options", q, kPathDirect, nullptr, kPassNone, kPassNone, false, 0, 0, 0, 0);
+    }
+    q.mode = 6;
+    add("a mode past the last", q, kPathDirect, nullptr, kPassNone, kPassNone, false, 0, 0, 0, 0);
+    q.mode = -1;
+    add("a mode before the first", q, kPathDirect, nullptr, kPassNone, kPassNone, false, 0, 0, 0, 0);
+    for (const Row& r : rows) {
+        const ShadingPlan p = plan_shading(r.q);
+        const bool ok = p.path == r.path && (r.family ? p.family != kShadeFamilies && std::strcmp(shade_family_name(p.family), r.family) == 0 : p.family == kShadeFamilies) &&
+                        p.secondary == r.secondary && p.shadow_pass == r.shadow_pass && p.deep == r.deep && p.levels == r.levels && p.bytes_per_px == r.bytes &&
+                        p.deep_off == r.deep_off && p.dark0_off == r.dark0_off;
+        if (!ok) std::printf("shading table row: %s\n", r.what);
+        CHECK(ok);
+    }
+}
+
+static void test_shading_invariants()
+{
+    size_t n = 0, n_grid = 0, n_deep = 0;
+    ShadingRequest q;
+    for (q.mode = 0; q.mode < 6; q.mode++)
+    for (int shadows = 0; shadows < 2; shadows++)
+    for (q.shadow_check = 0; q.shadow_check < 3; q.shadow_check++)
+    for (int lights_check = 0; lights_check < 2; lights_check++)
+    for (int lights = 0; lights < 3; lights++) // one reference / one other / two
+    for (q.n_reflective = 0; q.n_reflective < 2; q.n_reflective++)
+    for (q.reflect_check = 0; q.reflect_check < 3; q.reflect_check++)
+    for (q.reflect_depth = 1; q.reflect_depth <= 4; q.reflect_depth++)
+    for (int bits = 0; bits < 32; bits++) {
+        q.shadows = shadows != 0;
+        q.lights_check = lights_check != 0;
+        q.n_lights = lights == 2 ? 2 : 1;
+        q.light0_is_reference = lights == 0;
+        q.reflect_depth_check = (bits & 1) != 0;
+        q.reflect_shadows = (bits & 2) != 0;
+        q.shadow_grid = (bits & 4) != 0;
+        q.grid_usable = (bits & 8) != 0;
+        q.ns = (bits & 16) ? 1u : 0u;
+        const ShadingPlan p = plan_shading(q);
+        n++;
+        // direct if and only if no hit buffer, and then nothing else either
+        CHECK((p.path == kPathDirect) == (p.bytes_per_px == 0));
+        CHECK(p.path == shading_path(q));
+        if (p.path == kPathDirect) {
+            CHECK(p.family == kShadeFamilies && p.secondary == kPassNone && p.shadow_pass == kPassNone && !p.deep && !p.dark0 && p.levels == 0);
+            CHECK(q.mode > kShadedModeHi || (!q.shadows && lights == 0 && !q.lights_check && q.n_reflective == 0 && q.reflect_check != 2));
+            CHECK(!shading_wants_grid(q));
+            continue;
+        }
+        CHECK(q.mode <= kShadedModeHi);
+        CHECK(p.family < kShadeFamilies);
+        const char* name = shade_family_name(p.family);
+        const bool grid_family = std::strncmp(name, "rtx_grid_", 9) == 0;
+        const bool chain_family = std::strstr(name, "_chain_") != nullptr;
+        // a grid family if and only if the pass is rtx_grid_shadow, and only where it was wanted and usable
+        CHECK(grid_family == (p.shadow_pass == kPassGridShadow) && grid_family == p.dark0);
+        CHECK(!p.dark0 || (shading_wants_grid(q) && q.grid_usable));
+        CHECK(shading_wants_grid(q) == (q.shadow_grid && q.shadows && q.shadow_check == 0 && q.ns != 0));
+        ShadingRequest usable = q;
+        usable.grid_usable = true;
+        CHECK(shading_wants_grid(q) == plan_shading(usable).dark0); // false whenever the plan could not use a grid
+        // deep words if and only if the family reads them, and then a pass writes them
+        CHECK(p.deep == ends_with(name, "chain_shadow_shade"));
+        CHECK(!p.deep || p.shadow_pass == kPassGridShadow || p.shadow_pass == kPassChainShadow);
+        CHECK((p.shadow_pass == kPassChainShadow) == (p.deep && !p.dark0));
+        CHECK(p.shadow_pass == kPassNone || shade_takes_light_set(p.family)); // the shadow passes read the set
+        // a chain family if and only if the secondary pass is rtx_reflect_chain; the mirror path always has a secondary pass
+        CHECK(chain_family == (p.secondary == kPassReflectChain) && p.chain() == chain_family);
+        CHECK((p.path == kPathMirror) == (p.secondary != kPassNone));
+        CHECK(p.levels == (p.path == kPathShaded ? 1u : (p.chain() ? q.reflect_depth + 1u : 2u)));
+        // the layout: hit arrays, deep words, dark0, disjoint and in that order, nothing else
+        CHECK(p.bytes_per_px == 8u * p.levels + (p.deep ? 4u : 0u) + (p.dark0 ? 4u : 0u));
+        CHECK(p.deep_off == 8u * p.levels && p.dark0_off == p.deep_off + (p.deep ? 4u : 0u) && p.bytes_per_px == p.dark0_off + (p.dark0 ? 4u : 0u));
+        n_grid += p.dark0 ? 1 : 0;
+        n_deep += p.deep ? 1 : 0;
+    }
+    CHECK(n == 6u * 2 * 3 * 2 * 3 * 2 * 3 * 4 * 32);
+    CHECK(n_grid > 1000 && n_deep > 1000);
+}
+
 int main()
 {
+    test_shading_table();
+    test_shading_invariants();
     test_edge_basis();
     test_direction_order();
     test_view_density();

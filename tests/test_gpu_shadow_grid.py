@@ -175,11 +175,11 @@ def _assert_same(got, want, what):
         assert np.array_equal(got[key], want[key]), "%s, %s %s: %s" % (what, O.MODE_NAMES[mode], form, U.first_diff(got[key], want[key], S, 1 << 30))
 
 
-def _assert_not_empty(R, c, p, ref, what):
+def _assert_not_empty(R, c, p, ref, what, render=T._rows):
     """At least 5 % of the reference's visible pixels are dark and 5 % lit (against the all-lit frame); the grid has cells."""
     c.set_option(R.OPT_SHADOW_GRID, 0)
     c.set_option(R.OPT_SHADOW_CHECK, 2)
-    lit = T._rows(R, c, p, O.RGB_ASCII, R.RENDER_VALUES).view(np.float32).reshape(-1, 8)
+    lit = render(R, c, p, O.RGB_ASCII, R.RENDER_VALUES).view(np.float32).reshape(-1, 8)
     c.set_option(R.OPT_SHADOW_CHECK, 0)
     v = ref[(O.RGB_ASCII, "values")].view(np.float32).reshape(-1, 8)
     W = int(p.x)
@@ -273,6 +273,81 @@ def test_three_lights_over_the_floor_and_mirrors(R, ctx):
     assert names == {"rtx_grid_chain_shadow_shade"}
     _assert_same(got, ref, "three lights, depth 2")
     _assert_not_empty(R, ctx, p, ref, "three lights, depth 2")
+    _reset(R, ctx)
+
+
+# One context, one stream, another hit-buffer layout at every frame (rtxplan::plan_shading, csrc/rtx_plan.hpp): the buffer is
+# reused at a smaller size, grows, and level 0's words move.  (mirrors, depth, RTX_OPT_REFLECT_SHADOWS, RTX_OPT_SHADOW_GRID) ->
+# the family that shades and the hit buffer's bytes per pixel, under two lights with shadows on.
+LAYOUT_STEPS = [
+    ((0, 1, 0, 0), "rtx_lights_shade", 8),
+    ((1, 3, 1, 1), "rtx_grid_chain_shadow_shade", 40),
+    ((1, 1, 0, 0), "rtx_lights_reflect_shade", 16),
+    ((1, 3, 1, 0), "rtx_lights_chain_shadow_shade", 36),
+    ((1, 1, 0, 1), "rtx_grid_reflect_shade", 20),
+    ((0, 1, 0, 1), "rtx_grid_shade", 12),
+    ((0, 1, 0, 0), "rtx_lights_shade", 8),
+]
+SLAB = (5, 14)  # rows 5 .. 18 of 21: hit indices are relative to row0, and the only tile row has 14 of its 16 rows
+
+
+def _slab(R, c, p, mode, flags=0):
+    import torch
+    row0, rows = SLAB
+    S = 32 if flags & R.RENDER_VALUES else (20 if mode >= O.RGB_ASCII else 12)
+    buf = torch.full((rows * int(p.x) * S,), 0xEE, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    c.render_rows(p, mode, row0, rows, d_out=buf.data_ptr(), out_row_base=row0, flags=flags)
+    c.synchronize()
+    return buf.cpu().numpy()
+
+
+def test_one_stream_changes_the_hit_buffer_layout_from_frame_to_frame(R, ctx):
+    _reset(R, ctx)
+    p, sph, pl = _load(R, ctx, "e", 37, 21)
+    mirrors = {len(sph): 0.5}
+    mirrors.update({i: 0.4 for i in range(0, len(sph), 4)})
+    _set_lights(R, ctx, [(1.0, 50.0, 0.0), (0.0, 30.0, 100.0)])
+    keys = [(O.RGB_ASCII, "values"), (O.RGB_ASCII, "records"), (O.BIT_PIXEL, "values"), (O.BIT_PIXEL, "records")]
+
+    def set_step(opts, grid_allowed):
+        mirror, depth, deep, grid = opts
+        if mirror:
+            T._set_k(ctx, mirrors)
+        else:
+            T._clear_k(ctx, len(sph) + len(pl))
+        ctx.set_option(R.OPT_REFLECT_DEPTH, depth)
+        ctx.set_option(R.OPT_REFLECT_SHADOWS, deep)
+        ctx.set_option(R.OPT_SHADOW_GRID, grid if grid_allowed else 0)
+
+    def render(key):
+        mode, form = key
+        return _slab(R, ctx, p, mode, R.RENDER_VALUES if form == "values" else 0)
+
+    # the brute reference of every option set, once, before the sequence (so that the sequence alone decides the layouts)
+    ref = {}
+    for opts, _, _ in LAYOUT_STEPS:
+        if opts[:3] in ref:
+            continue
+        set_step(opts, False)
+        ctx.set_option(R.OPT_SHADOW_CHECK, 1)
+        ref[opts[:3]] = {key: render(key) for key in keys}
+        ctx.set_option(R.OPT_SHADOW_CHECK, 0)
+    assert len(ref) == 3
+    # the sequence, once per mode and form: every frame another layout
+    for key in keys:
+        for step, (opts, family, bytes_per_px) in enumerate(LAYOUT_STEPS):
+            set_step(opts, True)
+            frames0 = ctx.get_option(R.STAT_SHADOW_GRID_FRAMES)
+            got = render(key)
+            what = "step %d (%s, %d B/px), %s %s" % (step, family, bytes_per_px, O.MODE_NAMES[key[0]], key[1])
+            assert ctx.last_kernel.split("<")[0] == family, (what, ctx.last_kernel)
+            assert ctx.get_option(R.STAT_SHADOW_GRID_FRAMES) == frames0 + opts[3], what
+            _assert_same({key: got}, {key: ref[opts[:3]][key]}, what)
+    for opts3 in ref:  # (after the sequence: the grid is built)
+        set_step(opts3 + (0,), False)
+        _assert_not_empty(R, ctx, p, ref[opts3], "layout steps, mirrors %d depth %d deep %d" % opts3, render=_slab)
+    T._clear_k(ctx, len(sph) + len(pl))
     _reset(R, ctx)
 
 
