@@ -16,8 +16,17 @@
 //   Wire format: compact pixel words by default (4 instead of 12 / 20 bytes per pixel cross xGMI; the root expands them
 //   through record_words<MODE>, rtx_expand, or -- rtx_update -- minimises straight from the words), or records.
 //
-// Single caller thread (the reference drives the path from its main thread, Engine3D.cpp:81-107): the launches of all ranks
-// are queued by that thread, device by device; nothing here blocks except where the ABI says so.
+// One caller thread drives it (as the reference's main thread does, Engine3D.cpp:81-107); it queues the launches of all ranks
+// device by device, or hands every rank other than the root to a submission thread of its own (RTX_OPT_GROUP_THREADS).  Nothing
+// here blocks except where the ABI says so.
+//
+// What is written ONCE in this file:
+//   * the row partition is rtxplan::slab_of, the chunk size rtxplan::frames_per_chunk (rtx_plan.hpp: pure, tested on the CPU);
+//   * gather(): m >= 1 frames of one size through the ranks -- ev_free, a job per rank (trace, copy, ev_done), the root's own
+//     launch, wait_posted, the RCCL send / recv loop or the ev_done waits, the statistics.  rtx_render / rtx_update hand it one
+//     frame (gather_frame), a group's rtx_submit_frames a chunk of frames at a time (render_frames), so the exchange the tests
+//     walk at N = 1 and on a repeated device is the exchange a node of distinct devices runs;
+//   * on_members(): a call replicated to members 1 .. n-1, stopped at the first failure, the root's device current again after it.
 #include "rtx_group.h"
 
 #include <dlfcn.h>
@@ -221,8 +230,20 @@ void stop_workers(rtx_group* g)
     g->workers.clear();
 }
 
-// rows of rank r for a frame of H rows: the partition SURVEY.md 8(e) names (and sharding.row_bounds uses)
-inline uint64_t bound(uint64_t H, int r, int n) { return H * (uint64_t)r / (uint64_t)n; }
+// A call replicated to every member other than the root -- call(member) returns an RTX status -- up to the first failure, which is
+// reported on the root by rank.  The members' calls make their own devices current; the caller's thread gets the root's back.
+template <class Call>
+int on_members(rtx_ctx* root, Call call)
+{
+    rtx_group* g = root->group;
+    int status = RTX_OK;
+    for (int r = 1; r < g->n && status == RTX_OK; r++) {
+        const int rc = call(g->member[(size_t)r]);
+        if (rc != RTX_OK) status = member_fail(root, r, g->member[(size_t)r], rc);
+    }
+    (void)hipSetDevice(root->device);
+    return status;
+}
 
 bool rccl_wanted(const rtx_group* g)
 {
@@ -256,106 +277,112 @@ bool rccl_ready(rtx_ctx* root, rtx_group* g)
     return true;
 }
 
-// The frame of `p` sharded over the ranks into d_dst on the root's device, S bytes per pixel (4: compact words; 12 / 20:
-// records), rank r's rows at byte offset bound(r) * W * S; complete in stream order on the root's stream.
-// own_frame: d_dst is the root's own frame buffer (records): the root's launch then goes through the context's zero-fill
-// bookkeeping exactly as a single-device rtx_render would.
-int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, bool compact, uint8_t* d_dst, bool own_frame, unsigned root_flags)
-{
-    const uint64_t W = p->x, H = p->y;
-    const uint64_t S = compact ? 4u : (mode >= RTX_RGB_ASCII ? 20u : 12u);
-    const unsigned slab_flags = compact ? (unsigned)RTX_RENDER_COMPACT : (unsigned)RTX_RENDER_DEFAULT;
-    const int n = g->n;
-    const bool use_rccl = rccl_wanted(g) && rccl_ready(root, g);
-    const bool root_through_rccl = use_rccl && g->opt_exchange == RTX_EXCHANGE_RCCL_ALL;
-    g->exchange_in_use = use_rccl ? RTX_EXCHANGE_RCCL : RTX_EXCHANGE_PEER_COPY;
-    int rc;
+// bytes per pixel on the wire, and the flags a slab is traced with
+inline uint64_t wire_bytes(int mode, bool compact) { return compact ? 4u : (mode >= RTX_RGB_ASCII ? 20u : 12u); }
+inline unsigned wire_flags(bool compact) { return compact ? (unsigned)RTX_RENDER_COMPACT : (unsigned)RTX_RENDER_DEFAULT; }
 
-    if (root_through_rccl) {
-        // (before any job is posted: nothing below this point returns while a rank's submission thread is at work)
-        const size_t need = (size_t)(bound(H, 1, n) * W * S);
-        if (g->root_slab_cap < need) {
-            RTX_HIP(root, hipSetDevice(root->device));
-            if (g->d_root_slab) {
-                RTX_HIP(root, hipStreamSynchronize(root->stream));
-                hipFree(g->d_root_slab);
-            }
-            g->d_root_slab = nullptr;
-            g->root_slab_cap = 0;
-            if (hipMalloc((void**)&g->d_root_slab, need) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the root's slab");
-            g->root_slab_cap = need;
-        }
-    }
+// RCCL or peer copies for the frames about to be gathered?  (all_too: the caller can send the root's own rows through RCCL,
+// RTX_EXCHANGE_RCCL_ALL; a caller that cannot leaves that setting to peer copies)
+bool choose_exchange(rtx_ctx* root, rtx_group* g, bool all_too)
+{
+    const bool use_rccl = rccl_wanted(g) && (all_too || g->opt_exchange != RTX_EXCHANGE_RCCL_ALL) && rccl_ready(root, g);
+    g->exchange_in_use = use_rccl ? RTX_EXCHANGE_RCCL : RTX_EXCHANGE_PEER_COPY;
+    return use_rccl;
+}
+
+// frames of W x H whose slabs, S bytes per pixel, every rank's buffer holds together (16 at most); 0: one slab alone is too large
+size_t slabs_per_buffer(const rtx_group* g, uint64_t W, uint64_t H, uint64_t S)
+{
+    return rtxplan::frames_per_chunk(W, H, S, g->n, [g](int r) { return g->member[(size_t)r]->capacity; });
+}
+
+// m frames (1 <= m <= kMaxChunk) of one size, params[i] into dests[i] on the root's device, sharded over the ranks: S bytes per
+// pixel (4: compact words; 12 / 20: records), rank r's rows at byte offset slab_of(r).row0 * W * S of every frame; complete in
+// stream order on the root's stream.  The caller has chosen the exchange and checked that m slabs fit every rank's buffer.
+//   root_launch(rows0): queues the root's own rows [0, rows0) of the m frames on its stream -- the part that differs by caller.
+//   root_through_rccl (m == 1, RTX_EXCHANGE_RCCL_ALL): root_launch traces into d_root_slab, and rank 0 sends that to itself.
+// Every rank traces with ONE call, rtx_submit_slabs on its member context: one batched launch where the plan allows
+// (RTX_OPT_BATCH), the plain rtx_render_rows for a frame alone.
+template <class RootLaunch>
+int gather(rtx_ctx* root, rtx_group* g, size_t m, const rtx_params* params, int mode, bool compact, void* const* dests, bool use_rccl,
+           bool root_through_rccl, RootLaunch root_launch)
+{
+    const uint64_t W = params[0].x, H = params[0].y, S = wire_bytes(mode, compact);
+    const unsigned slab_flags = wire_flags(compact);
+    const int n = g->n;
     // ---- every rank traces its rows (and, with peer copies, sends them): a job per rank, on its submission thread
     const bool threaded = threads_in_use(g);
     std::vector<int> rcs((size_t)n, RTX_OK);
-    for (int r = 1; r < n; r++) {
-        const uint64_t rows = bound(H, r + 1, n) - bound(H, r, n);
-        if (rows * W * S > g->member[(size_t)r]->capacity) return rtx_fail(root, RTX_ERR_TOO_LARGE, "frame larger than the group was created for");
-    }
     if (!use_rccl) {
-        // the destination may still be read by what the root queued before this frame (the previous frame's expansion or
+        // the destination may still be read by what the root queued before these frames (the previous frame's expansion or
         // minimise pass): the ranks' copies wait for that, their traces do not have to
         RTX_HIP(root, hipSetDevice(root->device));
         RTX_HIP(root, hipEventRecord(g->ev_free, root->stream));
     }
-    uint64_t moved = 0;
     for (int r = 1; r < n; r++) {
-        const uint64_t r0 = bound(H, r, n), rows = bound(H, r + 1, n) - r0;
-        if (rows == 0) continue;
-        rtx_ctx* m = g->member[(size_t)r];
-        const size_t bytes = (size_t)(rows * W * S);
-        moved += bytes;
-        const rtx_params pp = *p;
-        uint8_t* dst = d_dst + r0 * W * S;
+        const rtxplan::Slab s = rtxplan::slab_of(H, r, n);
+        if (s.rows == 0) continue;
+        rtx_ctx* mem = g->member[(size_t)r];
+        const size_t bytes = (size_t)(s.rows * W * S), at = (size_t)(s.row0 * W * S), frame_bytes = (size_t)(H * W * S);
         hipEvent_t ev_free = g->ev_free, ev_done = g->ev_done[(size_t)r];
         const int root_device = root->device;
+        // (compact destinations are the group's word buffer: the frames of a chunk lie H * W words apart)
+        const bool strided = compact && m > 1 && g->direct[(size_t)r];
+        char* direct_flag = &g->direct[(size_t)r];
         post(g, r, [=]() -> int {
-            // the member's own frame buffer is its slab: rows [r0, r0 + rows) at its start
-            const int rc2 = rtx_render_rows(m, &pp, mode, (size_t)r0, (size_t)rows, m->d_frame, (size_t)r0, m->stream, slab_flags);
-            if (rc2 != RTX_OK) return rc2;
-            m->dirty_hi = m->capacity; // (the buffer is used as scratch: whatever a later plain render on this member assumes about it is void)
-            if (!use_rccl) {
-                RTX_HIP(m, hipSetDevice(m->device));
-                RTX_HIP(m, hipStreamWaitEvent(m->stream, ev_free, 0));
-                RTX_HIP(m, hipMemcpyPeerAsync(dst, root_device, m->d_frame, m->device, bytes, m->stream));
-                RTX_HIP(m, hipEventRecord(ev_done, m->stream));
+            // the member's own frame buffer is its slab buffer: rows [row0, row0 + rows) of the m frames back to back at its start
+            void* slabs[rtxplan::kMaxChunk];
+            void* streams[rtxplan::kMaxChunk];
+            for (size_t i = 0; i < m; i++) {
+                slabs[i] = mem->d_frame + i * bytes;
+                streams[i] = mem->stream;
             }
+            const int rc2 = rtx_submit_slabs(mem, m, params, mode, (size_t)s.row0, (size_t)s.rows, slabs, (size_t)s.row0, streams, nullptr, slab_flags);
+            if (rc2 != RTX_OK) return rc2;
+            mem->dirty_hi = mem->capacity; // (the buffer is used as scratch: whatever a later plain render on this member assumes about it is void)
+            if (use_rccl) return RTX_OK;
+            RTX_HIP(mem, hipSetDevice(mem->device));
+            RTX_HIP(mem, hipStreamWaitEvent(mem->stream, ev_free, 0));
+            bool copied = false;
+            if (strided) {
+                // the chunk's slabs lie back to back here and a frame apart on the root: one strided copy.  A runtime that
+                // refuses the strided form between two devices gets the plain copies below, from then on.
+                copied = hipMemcpy2DAsync((uint8_t*)dests[0] + at, frame_bytes, mem->d_frame, bytes, bytes, m, hipMemcpyDeviceToDevice, mem->stream) == hipSuccess;
+                if (!copied) {
+                    (void)hipGetLastError();
+                    *direct_flag = 0;
+                }
+            }
+            for (size_t i = 0; i < m && !copied; i++) {
+                RTX_HIP(mem, hipMemcpyPeerAsync((uint8_t*)dests[i] + at, root_device, mem->d_frame + i * bytes, mem->device, bytes, mem->stream));
+            }
+            RTX_HIP(mem, hipEventRecord(ev_done, mem->stream));
             return RTX_OK;
         }, threaded, rcs);
     }
     {
-        const uint64_t rows0 = bound(H, 1, n);
-        if (root_through_rccl) {
-            // test form (one-GPU box: RCCL at N = 1): the root's rows too are traced into a slab and travel through the exchange
-            rc = rows0 ? rtx_render_rows(root, p, mode, 0, (size_t)rows0, g->d_root_slab, 0, root->stream, slab_flags) : RTX_OK;
-            if (rc == RTX_OK && own_frame) rc = rtx_frame_zero_semantics(root, mode, W, H, 0u);
-        } else if (own_frame) {
-            rc = rtx_render_rows(root, p, mode, 0, (size_t)rows0, nullptr, 0, root->stream, RTX_RENDER_DEFAULT);
-        } else {
-            rc = rtx_render_rows(root, p, mode, 0, (size_t)rows0, d_dst, 0, root->stream, root_flags | slab_flags);
-        }
-    }
-    {
-        // (the ranks' submissions are waited for whatever the root's own launch returned: their jobs hold pointers into this frame)
+        // (the ranks' submissions are waited for whatever the root's own launch returned: their jobs hold pointers into the caller's frame)
+        const int rc = root_launch(rtxplan::slab_of(H, 0, n).rows);
         const int wrc = wait_posted(root, g, threaded, rcs);
         if (rc != RTX_OK) return rc;
         if (wrc != RTX_OK) return wrc;
     }
 
     // ---- the slabs travel to the root
+    uint64_t moved = 0; // bytes per frame
     if (use_rccl) {
-        moved = 0;
         RcclApi* api = rccl_api(nullptr);
         ncclResult_t nrc = api->GroupStart();
         for (int r = root_through_rccl ? 0 : 1; r < n && nrc == ncclSuccess; r++) {
-            const uint64_t r0 = bound(H, r, n), rows = bound(H, r + 1, n) - r0;
-            if (rows == 0) continue;
-            rtx_ctx* m = g->member[(size_t)r];
-            const size_t bytes = (size_t)(rows * W * S);
-            const void* src = r == 0 ? (const void*)g->d_root_slab : (const void*)m->d_frame;
-            nrc = api->Send(src, bytes, ncclChar, 0, g->comms[(size_t)r], m->stream);
-            if (nrc == ncclSuccess) nrc = api->Recv(d_dst + r0 * W * S, bytes, ncclChar, r, g->comms[0], root->stream);
+            const rtxplan::Slab s = rtxplan::slab_of(H, r, n);
+            if (s.rows == 0) continue;
+            rtx_ctx* mem = g->member[(size_t)r];
+            const size_t bytes = (size_t)(s.rows * W * S), at = (size_t)(s.row0 * W * S);
+            const uint8_t* src = r == 0 ? g->d_root_slab : mem->d_frame;
+            for (size_t i = 0; i < m && nrc == ncclSuccess; i++) {
+                nrc = api->Send(src + i * bytes, bytes, ncclChar, 0, g->comms[(size_t)r], mem->stream);
+                if (nrc == ncclSuccess) nrc = api->Recv((uint8_t*)dests[i] + at, bytes, ncclChar, r, g->comms[0], root->stream);
+            }
             moved += bytes;
         }
         const ncclResult_t erc = api->GroupEnd();
@@ -368,13 +395,50 @@ int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, boo
         // (the copies were queued by the ranks' jobs, behind ev_free; the root's stream goes on when they have landed)
         RTX_HIP(root, hipSetDevice(root->device));
         for (int r = 1; r < n; r++) {
-            if (bound(H, r + 1, n) - bound(H, r, n) == 0) continue;
+            const rtxplan::Slab s = rtxplan::slab_of(H, r, n);
+            if (s.rows == 0) continue;
             RTX_HIP(root, hipStreamWaitEvent(root->stream, g->ev_done[(size_t)r], 0));
+            moved += s.rows * W * S;
         }
     }
-    g->stat_gathers++;
+    g->stat_gathers += m;
     g->stat_last_bytes = moved;
     return RTX_OK;
+}
+
+// One frame into d_dst.  own_frame: d_dst is the root's own frame buffer (records): the root's launch then goes through the
+// context's zero-fill bookkeeping exactly as a single-device rtx_render would.
+int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, bool compact, uint8_t* d_dst, bool own_frame)
+{
+    const uint64_t W = p->x, H = p->y, S = wire_bytes(mode, compact);
+    const bool use_rccl = choose_exchange(root, g, true);
+    const bool root_through_rccl = use_rccl && g->opt_exchange == RTX_EXCHANGE_RCCL_ALL;
+    if (root_through_rccl) {
+        // (before any job is posted: nothing in gather() returns while a rank's submission thread is at work)
+        const size_t need = (size_t)(rtxplan::slab_of(H, 0, g->n).rows * W * S);
+        if (g->root_slab_cap < need) {
+            RTX_HIP(root, hipSetDevice(root->device));
+            if (g->d_root_slab) {
+                RTX_HIP(root, hipStreamSynchronize(root->stream));
+                hipFree(g->d_root_slab);
+            }
+            g->d_root_slab = nullptr;
+            g->root_slab_cap = 0;
+            if (hipMalloc((void**)&g->d_root_slab, need) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the root's slab");
+            g->root_slab_cap = need;
+        }
+    }
+    if (slabs_per_buffer(g, W, H, S) == 0) return rtx_fail(root, RTX_ERR_TOO_LARGE, "frame larger than the group was created for");
+    void* dest = d_dst;
+    return gather(root, g, 1, p, mode, compact, &dest, use_rccl, root_through_rccl, [&](uint64_t rows0) -> int {
+        if (root_through_rccl) {
+            // test form (one-GPU box: RCCL at N = 1): the root's rows too are traced into a slab and travel through the exchange
+            const int rc = rows0 ? rtx_render_rows(root, p, mode, 0, (size_t)rows0, g->d_root_slab, 0, root->stream, wire_flags(compact)) : RTX_OK;
+            return (rc == RTX_OK && own_frame) ? rtx_frame_zero_semantics(root, mode, W, H, 0u) : rc;
+        }
+        if (own_frame) return rtx_render_rows(root, p, mode, 0, (size_t)rows0, nullptr, 0, root->stream, RTX_RENDER_DEFAULT);
+        return rtx_render_rows(root, p, mode, 0, (size_t)rows0, d_dst, 0, root->stream, wire_flags(compact));
+    });
 }
 
 int ensure_words(rtx_ctx* root, rtx_group* g, uint64_t W, uint64_t H)
@@ -439,120 +503,61 @@ void destroy(rtx_group* g)
 
 int scene_clear(rtx_ctx* root)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_clear(g->member[(size_t)r]);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_clear(m); });
 }
+
+// (rtx_scene_add_* return the new object's index, or an error code negated)
+inline int status_of_index(int idx) { return idx < 0 ? -idx : RTX_OK; }
 
 int scene_add_sphere(rtx_ctx* root, const float pos[3], float radius, const float rgb[3])
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int idx = rtx_scene_add_sphere(g->member[(size_t)r], pos, radius, rgb);
-        if (idx < 0) return member_fail(root, r, g->member[(size_t)r], -idx);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return status_of_index(rtx_scene_add_sphere(m, pos, radius, rgb)); });
 }
 
 int scene_add_plane(rtx_ctx* root, const float pos[3], const float normal[3], const float rgb[3], float width, float height)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int idx = rtx_scene_add_plane(g->member[(size_t)r], pos, normal, rgb, width, height);
-        if (idx < 0) return member_fail(root, r, g->member[(size_t)r], -idx);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return status_of_index(rtx_scene_add_plane(m, pos, normal, rgb, width, height)); });
 }
 
 int scene_set_sphere_motion(rtx_ctx* root, unsigned index, int mover, float speed)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_sphere_motion(g->member[(size_t)r], index, mover, speed);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_sphere_motion(m, index, mover, speed); });
 }
 
 int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_lights(g->member[(size_t)r], n, lights);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_lights(m, n, lights); });
 }
 
 int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_reflectivity(g->member[(size_t)r], first, n, k);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_reflectivity(m, first, n, k); });
 }
 
 int scene_set_spheres(rtx_ctx* root, unsigned first, size_t n, const float* rows)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_spheres(g->member[(size_t)r], first, n, rows);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    (void)hipSetDevice(root->device);
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_spheres(m, first, n, rows); });
 }
 
 int scene_set_spheres_device(rtx_ctx* root, unsigned first, size_t n, const float* d_rows, hipEvent_t after)
 {
-    rtx_group* g = root->group;
     // every member keeps its own books from its own result words: the same values, so the same decisions
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_edit_spheres_here(g->member[(size_t)r], first, n, d_rows, root->device, true, after);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    (void)hipSetDevice(root->device);
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_edit_spheres_here(m, first, n, d_rows, root->device, true, after); });
 }
 
 int scene_set_plane(rtx_ctx* root, unsigned index, const float pos[3], const float normal[3], const float rgb[3], float width, float height)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_scene_set_plane(g->member[(size_t)r], index, pos, normal, rgb, width, height);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    (void)hipSetDevice(root->device);
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_plane(m, index, pos, normal, rgb, width, height); });
 }
 
 int scene_remove_prepare(rtx_ctx* root, const std::vector<uint32_t>& ascending)
 {
-    rtx_group* g = root->group;
-    int status = RTX_OK;
-    for (int r = 1; r < g->n && status == RTX_OK; r++) {
-        const int rc = rtx_remove_prepare(g->member[(size_t)r], ascending);
-        if (rc != RTX_OK) status = member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    (void)hipSetDevice(root->device);
-    return status;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_remove_prepare(m, ascending); });
 }
 
 int scene_remove_objects(rtx_ctx* root, const std::vector<uint32_t>& ascending)
 {
-    rtx_group* g = root->group;
-    int status = RTX_OK;
-    for (int r = 1; r < g->n && status == RTX_OK; r++) {
-        const int rc = rtx_remove_objects_here(g->member[(size_t)r], ascending);
-        if (rc != RTX_OK) status = member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    (void)hipSetDevice(root->device);
-    return status;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_remove_objects_here(m, ascending); });
 }
 
 int set_option(rtx_ctx* root, int option, int64_t value)
@@ -584,21 +589,12 @@ int set_option(rtx_ctx* root, int option, int64_t value)
         g->opt_wire = value;
         return RTX_OK;
     }
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_set_option(g->member[(size_t)r], option, value);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_set_option(m, option, value); });
 }
 
 int update_objects(rtx_ctx* root, double dt)
 {
-    rtx_group* g = root->group;
-    for (int r = 1; r < g->n; r++) {
-        const int rc = rtx_update_objects(g->member[(size_t)r], dt);
-        if (rc != RTX_OK) return member_fail(root, r, g->member[(size_t)r], rc);
-    }
-    return RTX_OK;
+    return on_members(root, [&](rtx_ctx* m) { return rtx_update_objects(m, dt); });
 }
 
 int render_frame(rtx_ctx* root, const rtx_params* p, int mode, void* d_out, unsigned flags)
@@ -613,30 +609,44 @@ int render_frame(rtx_ctx* root, const rtx_params* p, int mode, void* d_out, unsi
         return rtx_render_rows(root, p, mode, 0, (size_t)H, d_out, 0, root->stream, flags);
     }
     if (!own && (((uintptr_t)d_out & 3u) != 0)) return rtx_fail(root, RTX_ERR_INVALID_ARGUMENT, "output buffer must be 4-byte aligned");
+    // RTX_RENDER_ZERO_TAIL on a caller's buffer of 12-byte records: bytes [12 W H, 20 W H) read as zero
+    auto zero_tail = [&]() -> int {
+        if (own || mode >= RTX_RGB_ASCII || !(flags & RTX_RENDER_ZERO_TAIL)) return RTX_OK;
+        RTX_HIP(root, hipSetDevice(root->device));
+        RTX_HIP(root, hipMemsetAsync((uint8_t*)d_out + 12 * W * H, 0, 8 * W * H, root->stream));
+        return RTX_OK;
+    };
     if (!wire_is_compact(g)) {
-        if (!own && mode < RTX_RGB_ASCII && (flags & RTX_RENDER_ZERO_TAIL)) {
-            RTX_HIP(root, hipSetDevice(root->device));
-            RTX_HIP(root, hipMemsetAsync((uint8_t*)d_out + 12 * W * H, 0, 8 * W * H, root->stream));
-        }
-        return gather_frame(root, g, p, mode, false, own ? root->d_frame : (uint8_t*)d_out, own, 0u);
+        if ((rc = zero_tail()) != RTX_OK) return rc;
+        return gather_frame(root, g, p, mode, false, own ? root->d_frame : (uint8_t*)d_out, own);
     }
     // compact words into the group's buffer, then the records (rtx_expand: the same record_words<MODE> the trace kernel uses)
     if ((rc = ensure_words(root, g, W, H)) != RTX_OK) return rc;
-    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false, 0u)) != RTX_OK) return rc;
-    if (own) {
-        if ((rc = rtx_frame_zero_semantics(root, mode, W, H, 0u)) != RTX_OK) return rc;
-    } else if (mode < RTX_RGB_ASCII && (flags & RTX_RENDER_ZERO_TAIL)) {
-        RTX_HIP(root, hipSetDevice(root->device));
-        RTX_HIP(root, hipMemsetAsync((uint8_t*)d_out + 12 * W * H, 0, 8 * W * H, root->stream));
-    }
+    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false)) != RTX_OK) return rc;
+    if ((rc = own ? rtx_frame_zero_semantics(root, mode, W, H, 0u) : zero_tail()) != RTX_OK) return rc;
     const rtx_segment seg = {0u, 0u, W * H};
     return rtx_expand(root, mode, g->d_words, own ? (void*)root->d_frame : d_out, &seg, 1, root->stream);
 }
 
+namespace {
+
+// The caller's distinct streams other than the root's own, in the order of their first appearance.
+std::vector<hipStream_t> foreign_streams(const rtx_ctx* root, size_t n, void* const* streams)
+{
+    std::vector<hipStream_t> out;
+    for (size_t i = 0; streams && i < n; i++) {
+        hipStream_t s = (hipStream_t)streams[i];
+        if (s && s != root->stream && std::find(out.begin(), out.end(), s) == out.end()) out.push_back(s);
+    }
+    return out;
+}
+
+} // namespace
+
 // n whole frames, sharded, into d_outs[i] (records, on the root's device): every rank traces its rows of a chunk of frames
-// with ONE call (rtx_submit_slabs on its member context: one batched launch where the plan allows, RTX_OPT_BATCH), the slabs
-// of the chunk are gathered, the root expands.  The host cost per frame of a sharded launch-by-launch loop (a launch, a copy
-// and two events per rank and frame: ~15 us per rank on the caller's one thread) is paid once per chunk instead.
+// with ONE call, the slabs of the chunk are gathered (gather()), the root expands.  The host cost per frame of a sharded
+// launch-by-launch loop (a launch, a copy and two events per rank and frame: ~15 us per rank on the caller's one thread) is
+// paid once per chunk instead.
 int render_frames(rtx_ctx* root, size_t n, const rtx_params* params, int mode, void* const* d_outs, void* const* streams)
 {
     rtx_group* g = root->group;
@@ -648,17 +658,11 @@ int render_frames(rtx_ctx* root, size_t n, const rtx_params* params, int mode, v
     }
     // the frames are traced and assembled on the root's own stream: first order it after whatever the caller's streams hold for
     // these buffers (on one device rtx_submit_frames queues frame i ON streams[i]; here the streams are made to wait at the end)
-    if (streams) {
-        RTX_HIP(root, hipSetDevice(root->device));
-        for (size_t i = 0; i < n; i++) {
-            hipStream_t sc = (hipStream_t)streams[i];
-            if (!sc || sc == root->stream) continue;
-            bool seen = false;
-            for (size_t k = 0; k < i; k++) seen = seen || streams[k] == streams[i];
-            if (seen) continue;
-            RTX_HIP(root, hipEventRecord(g->ev_done[0], sc));
-            RTX_HIP(root, hipStreamWaitEvent(root->stream, g->ev_done[0], 0));
-        }
+    const std::vector<hipStream_t> foreign = foreign_streams(root, n, streams);
+    if (streams) RTX_HIP(root, hipSetDevice(root->device));
+    for (hipStream_t sc : foreign) {
+        RTX_HIP(root, hipEventRecord(g->ev_done[0], sc));
+        RTX_HIP(root, hipStreamWaitEvent(root->stream, g->ev_done[0], 0));
     }
     bool uniform = mode != RTX_SDL && N > 1;
     for (size_t i = 1; i < n && uniform; i++) {
@@ -672,139 +676,35 @@ int render_frames(rtx_ctx* root, size_t n, const rtx_params* params, int mode, v
     } else {
         const uint64_t W = params[0].x, H = params[0].y;
         const bool compact = wire_is_compact(g);
-        const uint64_t S = compact ? 4u : (mode >= RTX_RGB_ASCII ? 20u : 12u);
-        const unsigned slab_flags = compact ? (unsigned)RTX_RENDER_COMPACT : (unsigned)RTX_RENDER_DEFAULT;
         // frames per chunk: what the batched kernel takes, and what the ranks' slab buffers (their frame buffers) hold
-        size_t chunk = 16;
-        for (int r = 1; r < N; r++) {
-            const uint64_t rows = bound(H, r + 1, N) - bound(H, r, N);
-            if (rows) chunk = std::min<size_t>(chunk, (size_t)(g->member[(size_t)r]->capacity / (rows * W * S)));
-        }
+        const size_t chunk = slabs_per_buffer(g, W, H, wire_bytes(mode, compact));
         if (chunk == 0) return rtx_fail(root, RTX_ERR_TOO_LARGE, "frame larger than the group was created for");
-        const bool use_rccl = rccl_wanted(g) && g->opt_exchange != RTX_EXCHANGE_RCCL_ALL && rccl_ready(root, g);
-        g->exchange_in_use = use_rccl ? RTX_EXCHANGE_RCCL : RTX_EXCHANGE_PEER_COPY;
-        std::vector<void*> ptrs(chunk), strs(chunk);
+        const bool use_rccl = choose_exchange(root, g, false);
+        void* dests[rtxplan::kMaxChunk];
+        void* on_root[rtxplan::kMaxChunk];
         for (size_t first = 0; first < n; first += chunk) {
             const size_t m = std::min(chunk, n - first);
             if (compact && (rc = ensure_words(root, g, W, H * m)) != RTX_OK) return rc;
-            // where frame i of the chunk is assembled: its words in the group's buffer, or its records in the caller's
-            auto dest = [&](size_t i) { return compact ? (uint8_t*)(g->d_words + i * W * H) : (uint8_t*)d_outs[first + i]; };
-            const bool threaded = threads_in_use(g);
-            std::vector<int> rcs((size_t)N, RTX_OK);
-            if (!use_rccl) {
-                RTX_HIP(root, hipSetDevice(root->device));
-                RTX_HIP(root, hipEventRecord(g->ev_free, root->stream));
+            for (size_t i = 0; i < m; i++) {
+                // where frame i of the chunk is assembled: its words in the group's buffer, or its records in the caller's
+                dests[i] = compact ? (void*)(g->d_words + i * W * H) : d_outs[first + i];
+                on_root[i] = root->stream;
             }
-            uint64_t moved = 0;
-            const rtx_params* pfirst = &params[first];
-            uint8_t* dest0 = dest(0);
-            for (int r = 1; r < N; r++) {
-                const uint64_t r0 = bound(H, r, N), rows = bound(H, r + 1, N) - r0;
-                if (rows == 0) continue;
-                rtx_ctx* mem = g->member[(size_t)r];
-                const size_t bytes = (size_t)(rows * W * S);
-                moved += bytes * m;
-                hipEvent_t ev_free = g->ev_free, ev_done = g->ev_done[(size_t)r];
-                const int root_device = root->device;
-                const bool strided = compact && m > 1 && g->direct[(size_t)r];
-                auto* direct_flag = &g->direct[(size_t)r];
-                std::vector<uint8_t*> dests(m);
-                for (size_t i = 0; i < m; i++) dests[i] = dest(i) + r0 * W * S;
-                post(g, r, [=]() -> int {
-                    // the rank's rows of the chunk's frames back to back in its buffer: ONE call, one batched launch where the plan allows
-                    std::vector<void*> p2(m), s2(m);
-                    for (size_t i = 0; i < m; i++) {
-                        p2[i] = mem->d_frame + i * bytes;
-                        s2[i] = mem->stream;
-                    }
-                    const int rc2 = rtx_submit_slabs(mem, m, pfirst, mode, (size_t)r0, (size_t)rows, p2.data(), (size_t)r0, s2.data(), nullptr, slab_flags);
-                    if (rc2 != RTX_OK) return rc2;
-                    mem->dirty_hi = mem->capacity;
-                    if (!use_rccl) {
-                        RTX_HIP(mem, hipSetDevice(mem->device));
-                        RTX_HIP(mem, hipStreamWaitEvent(mem->stream, ev_free, 0));
-                        bool copied = false;
-                        if (strided) {
-                            // the chunk's slabs lie back to back here and H*W words apart on the root: one strided copy.  A runtime
-                            // that refuses the strided form between two devices gets the plain copies below, from then on.
-                            copied = hipMemcpy2DAsync(dest0 + r0 * W * S, (size_t)(H * W * S), mem->d_frame, bytes, bytes, m, hipMemcpyDeviceToDevice, mem->stream) == hipSuccess;
-                            if (!copied) {
-                                (void)hipGetLastError();
-                                *direct_flag = 0;
-                            }
-                        }
-                        if (!copied) {
-                            for (size_t i = 0; i < m; i++) {
-                                RTX_HIP(mem, hipMemcpyPeerAsync(dests[i], root_device, mem->d_frame + i * bytes, mem->device, bytes, mem->stream));
-                            }
-                        }
-                        RTX_HIP(mem, hipEventRecord(ev_done, mem->stream));
-                    }
-                    return RTX_OK;
-                }, threaded, rcs);
-            }
-            {
-                const uint64_t rows0 = bound(H, 1, N);
-                for (size_t i = 0; i < m; i++) {
-                    ptrs[i] = dest(i);
-                    strs[i] = root->stream;
-                }
-                rc = rows0 ? rtx_submit_slabs(root, m, &params[first], mode, 0, (size_t)rows0, ptrs.data(), 0, strs.data(), nullptr, slab_flags) : RTX_OK;
-            }
-            {
-                const int wrc = wait_posted(root, g, threaded, rcs);
-                if (rc != RTX_OK) return rc;
-                if (wrc != RTX_OK) return wrc;
-            }
-            if (use_rccl) {
-                moved = 0;
-                RcclApi* api = rccl_api(nullptr);
-                ncclResult_t nrc = api->GroupStart();
-                for (int r = 1; r < N && nrc == ncclSuccess; r++) {
-                    const uint64_t r0 = bound(H, r, N), rows = bound(H, r + 1, N) - r0;
-                    if (rows == 0) continue;
-                    rtx_ctx* mem = g->member[(size_t)r];
-                    const size_t bytes = (size_t)(rows * W * S);
-                    for (size_t i = 0; i < m && nrc == ncclSuccess; i++) {
-                        nrc = api->Send(mem->d_frame + i * bytes, bytes, ncclChar, 0, g->comms[(size_t)r], mem->stream);
-                        if (nrc == ncclSuccess) nrc = api->Recv(dest(i) + r0 * W * S, bytes, ncclChar, r, g->comms[0], root->stream);
-                        moved += bytes;
-                    }
-                }
-                const ncclResult_t erc = api->GroupEnd();
-                if (nrc == ncclSuccess) nrc = erc;
-                if (nrc != ncclSuccess) return rtx_fail(root, RTX_ERR_HIP, std::string("RCCL exchange failed: ") + (api->GetErrorString ? api->GetErrorString(nrc) : "?"));
-                RTX_HIP(root, hipSetDevice(root->device));
-            } else {
-                RTX_HIP(root, hipSetDevice(root->device));
-                for (int r = 1; r < N; r++) {
-                    if (bound(H, r + 1, N) - bound(H, r, N) == 0) continue;
-                    RTX_HIP(root, hipStreamWaitEvent(root->stream, g->ev_done[(size_t)r], 0));
-                }
-            }
-            g->stat_gathers += m;
-            g->stat_last_bytes = moved / m;
-            if (compact) {
-                for (size_t i = 0; i < m; i++) {
-                    const rtx_segment seg = {0u, 0u, W * H};
-                    if ((rc = rtx_expand(root, mode, g->d_words + i * W * H, d_outs[first + i], &seg, 1, root->stream)) != RTX_OK) return rc;
-                }
+            rc = gather(root, g, m, &params[first], mode, compact, dests, use_rccl, false, [&](uint64_t rows0) -> int {
+                return rows0 ? rtx_submit_slabs(root, m, &params[first], mode, 0, (size_t)rows0, dests, 0, on_root, nullptr, wire_flags(compact)) : RTX_OK;
+            });
+            if (rc != RTX_OK) return rc;
+            for (size_t i = 0; compact && i < m; i++) {
+                const rtx_segment seg = {0u, 0u, W * H};
+                if ((rc = rtx_expand(root, mode, g->d_words + i * W * H, d_outs[first + i], &seg, 1, root->stream)) != RTX_OK) return rc;
             }
         }
     }
     // the caller's streams see the frames once the root's stream has them
-    bool any = false;
-    for (size_t i = 0; i < n; i++) any = any || (streams && streams[i] && (hipStream_t)streams[i] != root->stream);
-    if (any) {
+    if (!foreign.empty()) {
         RTX_HIP(root, hipSetDevice(root->device));
         RTX_HIP(root, hipEventRecord(g->ev_done[0], root->stream));
-        for (size_t i = 0; i < n; i++) {
-            hipStream_t s = (hipStream_t)streams[i];
-            if (!s || s == root->stream) continue;
-            bool seen = false;
-            for (size_t k = 0; k < i; k++) seen = seen || streams[k] == streams[i];
-            if (!seen) RTX_HIP(root, hipStreamWaitEvent(s, g->ev_done[0], 0));
-        }
+        for (hipStream_t s : foreign) RTX_HIP(root, hipStreamWaitEvent(s, g->ev_done[0], 0));
     }
     return RTX_OK;
 }
@@ -824,6 +724,19 @@ int run_on_ranks(rtx_ctx* root, const std::function<int(int, rtx_ctx*)>& fn)
 }
 
 bool threads_active(rtx_ctx* root) { return root->group != nullptr && threads_in_use(root->group); }
+
+int run_phases(rtx_ctx* root, const std::function<int(int, rtx_ctx*)>& queue, const std::function<int(int, rtx_ctx*)>& await)
+{
+    if (threads_active(root)) {
+        return run_on_ranks(root, [&](int r, rtx_ctx* m) -> int {
+            const int rc = queue(r, m);
+            return rc != RTX_OK ? rc : await(r, m);
+        });
+    }
+    const int rc = run_on_ranks(root, queue);
+    const int rcw = run_on_ranks(root, await); // (also after a failure: nothing may still be running on a rank's buffers)
+    return rc != RTX_OK ? rc : rcw;
+}
 
 bool update_direct_wanted(const rtx_ctx* root)
 {
@@ -853,7 +766,7 @@ int render_words(rtx_ctx* root, const rtx_params* p, int mode, const uint32_t** 
     if (rc != RTX_OK) return rc;
     if (mode == RTX_SDL) return rtx_fail(root, RTX_ERR_INVALID_MODE, "no pixel words in RTX_SDL");
     if ((rc = ensure_words(root, g, p->x, p->y)) != RTX_OK) return rc;
-    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false, 0u)) != RTX_OK) return rc;
+    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false)) != RTX_OK) return rc;
     *d_words = g->d_words;
     return RTX_OK;
 }
@@ -941,8 +854,9 @@ int rtx_group_rows(const rtx_ctx* ctx, size_t h, int rank, size_t* row0, size_t*
 {
     const int n = rtx_group_size(ctx);
     if (!ctx || !row0 || !rows || rank < 0 || rank >= n) return RTX_ERR_INVALID_ARGUMENT;
-    *row0 = (size_t)bound(h, rank, n);
-    *rows = (size_t)(bound(h, rank + 1, n) - bound(h, rank, n));
+    const rtxplan::Slab s = rtxplan::slab_of(h, rank, n);
+    *row0 = (size_t)s.row0;
+    *rows = (size_t)s.rows;
     return RTX_OK;
 }
 

@@ -57,6 +57,10 @@ int render_words(rtx_ctx* root, const rtx_params* p, int mode, const uint32_t** 
 // Returns when all have returned; the first failure by rank, reported on the root.
 int run_on_ranks(rtx_ctx* root, const std::function<int(int, rtx_ctx*)>& fn);
 bool threads_active(rtx_ctx* root); // the ranks other than the root have submission threads (started here if they are wanted and not yet running)
+// Two phases on every rank, `queue` (device work) and `await` (waiting for it): with submission threads a rank does both in one go
+// (the ranks wait side by side); on the caller's thread alone everything is queued first, so that the ranks' device work still
+// overlaps, and then awaited on every rank -- also after a failure: nothing may still be running on a rank's buffers.
+int run_phases(rtx_ctx* root, const std::function<int(int, rtx_ctx*)>& queue, const std::function<int(int, rtx_ctx*)>& await);
 // rtx_update without a gather (RTX_OPT_GROUP_UPDATE): wanted for this group?  ... and what rtx_post.hip reports back
 bool update_direct_wanted(const rtx_ctx* root);
 void update_direct_done(rtx_ctx* root, bool ok); // ok: counted; not ok: the group gathers on its root from now on

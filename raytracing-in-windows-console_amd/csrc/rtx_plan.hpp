@@ -985,6 +985,35 @@ inline RemovalPlan plan_removal(const std::vector<uint8_t>& kind_of, const std::
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ row partition of a device group
+
+// Rank r of n traces rows [H r / n, H (r + 1) / n) of a frame of H rows (sharding.row_bounds states the same
+// rule in Python): the slabs tile the frame in rank order, their row counts differ by at most one, and H < n leaves empty ones.
+struct Slab {
+    uint64_t row0 = 0, rows = 0;
+};
+
+inline Slab slab_of(uint64_t H, int rank, int n)
+{
+    const uint64_t lo = H * (uint64_t)rank / (uint64_t)n, hi = H * ((uint64_t)rank + 1u) / (uint64_t)n;
+    return {lo, hi - lo};
+}
+
+constexpr size_t kMaxChunk = 16; // frames a rank traces with one call (what the batched kernel takes)
+
+// Frames per chunk of a group's rtx_submit_frames: at most kMaxChunk, and no more than every rank other than the root holds of
+// its slabs (px_bytes per pixel) in its buffer of capacity_of(r) bytes; a rank without rows sets no limit.  0: one slab is too large.
+template <class CapacityOf>
+inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n, CapacityOf capacity_of)
+{
+    size_t chunk = kMaxChunk;
+    for (int r = 1; r < n; r++) {
+        const uint64_t rows = slab_of(H, r, n).rows;
+        if (rows) chunk = std::min<size_t>(chunk, (size_t)((uint64_t)capacity_of(r) / (rows * W * px_bytes)));
+    }
+    return chunk;
+}
+
 // ------------------------------------------------------------------------------------------------ shading
 //
 // Which launches make up a frame, and how the per-stream hit buffer is laid out.  A frame in the reference's state is ONE trace

@@ -273,7 +273,9 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
     };
     std::vector<Part> part((size_t)N);
     for (int r = 0; r < N; r++) {
-        if (rtx_group_rows(root, H, r, &part[(size_t)r].row0, &part[(size_t)r].rows) != RTX_OK) return rtx_fail(root, RTX_ERR_INVALID_ARGUMENT, "rtx_group_rows failed");
+        const rtxplan::Slab s = rtxplan::slab_of(H, r, N);
+        part[(size_t)r].row0 = (size_t)s.row0;
+        part[(size_t)r].rows = (size_t)s.rows;
     }
     std::vector<MinRun> runs((size_t)N);
     // a rank's device work: trace (its rows and the one above), minimise, the two words of the result on their way to the host
@@ -319,20 +321,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         RTX_HIP(m, hipStreamSynchronize(m->stream));
         return RTX_OK;
     };
-    // With a submission thread per rank a rank queues and waits in one go (the ranks wait side by side); on the caller's thread alone
-    // everything is queued first, so that the ranks' device work still overlaps.
-    const bool threads = rtxgroup::threads_active(root);
-    int rc;
-    if (threads) {
-        rc = rtxgroup::run_on_ranks(root, [&](int r, rtx_ctx* m) -> int {
-            const int rc2 = queue_rows(r, m);
-            return rc2 != RTX_OK ? rc2 : await_rows(r, m);
-        });
-    } else {
-        rc = rtxgroup::run_on_ranks(root, queue_rows);
-        const int rcw = rtxgroup::run_on_ranks(root, await_rows); // (also after a failure: nothing may still be running on a rank's buffers)
-        if (rc == RTX_OK) rc = rcw;
-    }
+    int rc = rtxgroup::run_phases(root, queue_rows, await_rows);
     if (rc != RTX_OK) {
         (void)hipSetDevice(root->device);
         return rc;
@@ -342,16 +331,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         part[(size_t)r].offset = at;
         at += part[(size_t)r].bytes;
     }
-    if (threads) {
-        rc = rtxgroup::run_on_ranks(root, [&](int r, rtx_ctx* m) -> int {
-            const int rc2 = queue_copy(r, m);
-            return rc2 != RTX_OK ? rc2 : await_copy(r, m);
-        });
-    } else {
-        rc = rtxgroup::run_on_ranks(root, queue_copy);
-        const int rcw = rtxgroup::run_on_ranks(root, await_copy);
-        if (rc == RTX_OK) rc = rcw;
-    }
+    rc = rtxgroup::run_phases(root, queue_copy, await_copy);
     RTX_HIP(root, hipSetDevice(root->device));
     if (rc != RTX_OK) return rc;
     *out_bytes = at;

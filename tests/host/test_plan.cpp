@@ -995,8 +995,70 @@ static void test_shading_invariants()
     CHECK(n_grid > 1000 && n_deep > 1000);
 }
 
+// The row partition of a device group: for every frame height and group size the slabs tile [0, H) in rank order, as evenly as
+// whole rows allow, by the rule every other statement of it (sharding.row_bounds, rtx_group_rows) follows: H r / n.
+static void test_group_slabs()
+{
+    for (uint64_t H = 1; H <= 300; H++) {
+        for (int n = 1; n <= 64; n++) {
+            uint64_t next = 0, lo = H, hi = 0, empty = 0;
+            for (int r = 0; r < n; r++) {
+                const Slab s = slab_of(H, r, n);
+                CHECK(s.row0 == H * (uint64_t)r / (uint64_t)n);
+                CHECK(s.row0 + s.rows == H * (uint64_t)(r + 1) / (uint64_t)n);
+                CHECK(s.row0 == next); // no gap, no overlap, rank order
+                next = s.row0 + s.rows;
+                lo = std::min(lo, s.rows);
+                hi = std::max(hi, s.rows);
+                empty += s.rows == 0 ? 1u : 0u;
+            }
+            CHECK(next == H);
+            CHECK(hi - lo <= 1);
+            CHECK(empty == (H < (uint64_t)n ? (uint64_t)n - H : 0u)); // fewer rows than ranks: H slabs of one row, the rest empty
+            if (H < (uint64_t)n) CHECK(hi == 1 && lo == 0);
+        }
+    }
+}
+
+// Frames per chunk, against the rule said directly: the smallest capacity_r / (rows_r W S) over the ranks r >= 1 that have
+// rows, and no more than 16.
+static void test_frames_per_chunk()
+{
+    static_assert(kMaxChunk == 16, "what the batched kernel takes");
+    std::mt19937_64 rng(16);
+    const uint64_t wire[3] = {4, 12, 20};
+    for (int it = 0; it < 20000; it++) {
+        const uint64_t W = 1 + rng() % 400, H = 1 + rng() % 300, S = wire[rng() % 3];
+        const int n = 1 + (int)(rng() % 64);
+        std::vector<uint64_t> cap((size_t)n);
+        for (auto& c : cap) c = rng() % (40 * W * H / (uint64_t)n + 2);
+        uint64_t want = 16;
+        for (int r = 1; r < n; r++) {
+            const uint64_t rows = H * (uint64_t)(r + 1) / (uint64_t)n - H * (uint64_t)r / (uint64_t)n;
+            if (rows > 0) want = std::min(want, cap[(size_t)r] / (rows * W * S));
+        }
+        CHECK(frames_per_chunk(W, H, S, n, [&](int r) { return cap[(size_t)r]; }) == (size_t)want);
+    }
+    const auto with = [](std::vector<uint64_t> cap, uint64_t W, uint64_t H, uint64_t S) {
+        return frames_per_chunk(W, H, S, (int)cap.size(), [&](int r) { return cap[(size_t)r]; });
+    };
+    // 64 x 3 on 8 ranks: rows 0 0 1 0 0 1 0 1 -- the five ranks without rows set no limit, whatever their buffers hold; neither does the root
+    CHECK(with({0, 0, 256 * 5, 0, 0, 256 * 7, 0, 256 * 6}, 64, 3, 4) == 5);
+    CHECK(with({0, 0, 256 * 5 - 1, 0, 0, 256 * 7, 0, 256 * 6}, 64, 3, 4) == 4);
+    // the limit of 16, and a group of one
+    CHECK(with({0, 1u << 30, 1u << 30}, 97, 41, 20) == 16);
+    CHECK(with({0, 97 * 14 * 20 * 16, 97 * 14 * 20 * 17}, 97, 41, 20) == 16); // (rows 13 14 14)
+    CHECK(with({0, 97 * 14 * 20 * 16 - 1, 97 * 14 * 20 * 17}, 97, 41, 20) == 15);
+    CHECK(with({0}, 400, 150, 12) == 16);
+    // zero: one slab alone is larger than its rank's buffer
+    CHECK(with({1u << 30, 97 * 14 * 20 - 1, 1u << 30}, 97, 41, 20) == 0);
+    CHECK(with({1u << 30, 97 * 14 * 20, 1u << 30}, 97, 41, 20) == 1);
+}
+
 int main()
 {
+    test_group_slabs();
+    test_frames_per_chunk();
     test_shading_table();
     test_shading_invariants();
     test_edge_basis();

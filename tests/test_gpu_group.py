@@ -295,6 +295,68 @@ def test_submit_frames_on_a_group_shards_a_chunk_of_frames_per_call(R, ranks, wi
         assert g.get_option(R.STAT_GROUP_GATHERS) == 2 * n
 
 
+
+@pytest.mark.parametrize("ranks,W,H", [(5, 97, 41), (8, 64, 3), (2, 333, 1)])
+def test_chunk_of_frames_ragged_and_empty_slabs_both_wires_threads_on_and_off(R, ranks, W, H):
+    """rtx_submit_frames through the group's one gather where the single-frame tests do not reach: a chunk of 3 frames from three
+    cameras on a foreign stream, ragged slabs (97x41 over 5), five empty ones (64x3 over 8: rows 0 0 1 0 0 1 0 1) and a frame of
+    one row, both wires, the ranks' jobs on the caller's thread and on submission threads.  Every frame equals the frame a single
+    device renders for its camera, a call counts 3 gathers, and every slab but the root's crossed, S bytes per pixel."""
+    import torch
+    n = 3
+    cams = [R.camera_params(W, H, pos=(0.5 * i, 0.2 * i, -0.3 * i), rot=(0.004 * i, float(np.float32(np.pi)) + 0.02 * i, 0.0)) for i in range(n)]
+    modes = (R.RGB_ASCII, R.BIT_ASCII)
+    with R.Context(W, H) as one:
+        one.set_reference_default_scene()
+        want = {mode: [one.render_to_host(c, mode)[:(20 if mode >= 2 else 12) * W * H].copy() for c in cams] for mode in modes}
+    if H > 3:
+        assert len({a.tobytes() for a in want[R.RGB_ASCII]}) == n      # (the cameras see different frames)
+    bufs = [torch.empty(20 * W * H, dtype=torch.uint8, device="cuda") for _ in range(n)]
+    side = torch.cuda.Stream()
+    crossed = (H - H // ranks) * W          # pixels of every slab but the root's, rows [0, H / N)
+    with R.Context(W, H, devices=[0] * ranks) as g:
+        g.set_reference_default_scene()
+        assert g.group_rows(H, 0) == (0, H // ranks)
+        for threads in (0, 1):
+            g.set_option(R.OPT_GROUP_THREADS, threads)
+            for wire in (R.WIRE_COMPACT, R.WIRE_RECORDS):
+                g.set_option(R.OPT_GROUP_WIRE, wire)
+                for mode in modes:
+                    rec = 20 if mode >= 2 else 12
+                    with torch.cuda.stream(side):
+                        for b in bufs:
+                            b.fill_(0xEE)                 # (on the foreign stream: the group must order its writes after it)
+                    before = g.get_option(R.STAT_GROUP_GATHERS)
+                    g.submit_frames(cams, mode, [b.data_ptr() for b in bufs], [side.cuda_stream] * n)
+                    side.synchronize()                    # the caller's stream was made to wait for the frames
+                    for i in range(n):
+                        got = bufs[i][:rec * W * H].cpu().numpy()
+                        assert np.array_equal(got, want[mode][i]), (threads, wire, R.MODE_NAMES[mode], i, U.first_diff(got, want[mode][i], rec, W))
+                    assert g.get_option(R.STAT_GROUP_GATHERS) - before == n
+                    assert g.get_option(R.STAT_GROUP_BYTES) == (4 if wire == R.WIRE_COMPACT else rec) * crossed
+                    assert g.get_option(R.STAT_GROUP_EXCHANGE) == R.EXCHANGE_PEER_COPY
+
+
+def test_rccl_all_at_one_device_and_submit_frames_do_not_interfere(R):
+    """devices=[0] under RTX_EXCHANGE_RCCL_ALL: a group of one has no chunk to shard, so rtx_submit_frames goes frame by frame, and
+    each frame's root slab travels through ncclSend / ncclRecv exactly as rtx_render's does."""
+    import torch
+    gold = U.load_golden()["C2_RGB_ASCII"]
+    p, sph, pl = R.config_inputs("C2")
+    W, H = int(p.x), int(p.y)
+    bufs = [torch.full((20 * W * H,), 0xEE, dtype=torch.uint8, device="cuda") for _ in range(2)]
+    torch.cuda.synchronize()
+    with R.Context(W, H, devices=[0]) as c:
+        c.set_scene(sph, pl)
+        c.set_option(R.OPT_GROUP_EXCHANGE, R.EXCHANGE_RCCL_ALL)
+        c.submit_frames([p, p], R.RGB_ASCII, [b.data_ptr() for b in bufs], [None, None])
+        c.synchronize()
+        for b in bufs:
+            assert _sha(b.cpu().numpy()) == gold["frame_sha256"]
+        assert c.get_option(R.STAT_GROUP_EXCHANGE) == R.EXCHANGE_RCCL, c.exchange_note
+        assert c.get_option(R.STAT_GROUP_GATHERS) == 2
+
+
 # ---- rtx_update without a gather: every rank minimises and copies its own rows (RTX_OPT_GROUP_UPDATE)
 
 @pytest.mark.parametrize("ranks,W,H", [(7, 400, 150), (5, 97, 41), (8, 64, 3), (2, 333, 1), (16, 320, 180), (3, 1, 9), (4, 2, 8)])
