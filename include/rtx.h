@@ -311,6 +311,16 @@ enum rtx_stat {
     RTX_STAT_SCENE_REMOVED = 150,   /* objects removed so far by rtx_scene_remove_objects / rtx_scene_remove_marked_device calls that succeeded
                                      * (|R| per call); every member of a device group counts its own, alike.  No reference
                                      * counterpart (Scene3D.h:15-25 creates objects, Scene3D::CleanUp frees all of them at once) */
+    RTX_STAT_DELTA_FRAMES = 151,    /* frames rtx_update_delta has handed out so far, key frames included.  No reference counterpart
+                                     * (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+    RTX_STAT_DELTA_KEYFRAMES = 152, /* ... of which were key frames (RTX_DELTA_KEY).  No reference counterpart
+                                     * (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+    RTX_STAT_DELTA_CELLS = 153,     /* cells the last delta launch (rtx_delta_words, or an rtx_update_delta that returned RTX_DELTA_DIFF)
+                                     * found changed; 0 before the first.  Two words per context, counted on the device.  Reading it
+                                     * waits for the device.  No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+    RTX_STAT_DELTA_RUNS = 154,      /* ... and the runs they form: the cursor escapes of that stream.  With RTX_STAT_DELTA_CELLS a caller
+                                     * can tell when a key frame would have been shorter.  Reading it waits for the device.
+                                     * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -699,6 +709,60 @@ int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int 
  * be in flight; host_out must stay valid and unread until rtx_update_end. */
 int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, int* ticket);
 int rtx_update_end(rtx_ctx* ctx, int ticket, size_t* out_bytes);
+
+/* ---- delta frames: only the console cells that changed since the previous frame, addressed by cursor escapes.
+ * No reference counterpart: the reference's printer homes the cursor and rewrites the whole screen every frame
+ * (PrintMachine.cpp:257-306) from the stream Update hands it (RayTracingManager.cu:150), minimised in space only.
+ *
+ * THE RULE, on pixel words (RTX_RENDER_COMPACT).  Inputs: one of the five character modes, W, H and two arrays cur and prev of W*H
+ * words.  R(w) is the S-byte record rtx_expand writes for word w in that mode (S = 12 or 20), head(w) its first S-1 bytes, glyph(w)
+ * its last byte.  Slot g = row*W + col; column W-1 is never a cell.
+ *   changed(g)  iff  col < W-1, cur[g] != prev[g] and cur[g] != 0xffffffff
+ *   start(g)    iff  changed(g) and (col == 0 or not changed(g-1))
+ * A changed slot emits, in this order: if start(g), the cursor escape ESC [ <row+1> ; <col+1> H (decimal, no leading zeros: the
+ * frame's cell (0,0) is screen cell (1,1), where ESC [ H puts it); then R(cur[g]) whole if start(g) or head(cur[g]) != head(cur[g-1]),
+ * otherwise glyph(cur[g]) alone.  Every other slot emits nothing.  The stream is the concatenation in slot order; a frame equal to its
+ * predecessor gives 0 bytes.  The head comparison is stricter than Minimize's (which compares colour digits only, so that a miss in
+ * front of a black hit loses its '3' / '4' selector): replaying a delta over the previous frame's grid of records gives exactly
+ * the current frame's grid of records, for any words.
+ * Limits: W-1 <= 99999 and H <= 99999 (the escape is at most 14 bytes); anything larger is RTX_ERR_INVALID_ARGUMENT.  RTX_SDL and
+ * anything that is no mode: RTX_ERR_INVALID_MODE.
+ * Out of scope: a form whose launch writes host memory itself (RTX_OPT_UPDATE_HOST_WRITE), a pipelined begin / end form, a device
+ * group's gather-free direct update (RTX_OPT_GROUP_UPDATE), bridging short unchanged gaps between runs, and choosing a key frame
+ * automatically when it would be shorter -- RTX_STAT_DELTA_CELLS and RTX_STAT_DELTA_RUNS let a caller decide. */
+enum rtx_delta_flags {
+    RTX_DELTA_DEFAULT = 0,
+    RTX_DELTA_KEYFRAME = 1 /* rtx_update_delta: a key frame whatever the context holds */
+};
+enum rtx_delta_kind {
+    RTX_DELTA_KEY = 0, /* the whole frame, byte for byte rtx_update's stream: the consumer homes the cursor first */
+    RTX_DELTA_DIFF = 1 /* the rule's stream against the frame handed out before: no cursor home */
+};
+/* The largest stream either kind can be for a w x h frame of `mode`: the larger of the rule's maximum (per row S c + cup r over c
+ * changed cells in r runs) and the key frame's S*w*h.  0 for arguments the other two calls refuse.  Pure host arithmetic.
+ * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150; its buffers are 20*W*H, PrintMachine.cpp:140). */
+size_t rtx_delta_bound(int mode, size_t w, size_t h);
+/* The rule as a pass of its own over the caller's device buffers: d_cur and d_prev W*H words each (4-byte aligned), d_out the
+ * stream (16-byte aligned, out_capacity bytes; less than rtx_delta_bound(mode, w, h) returns RTX_ERR_TOO_LARGE before anything is
+ * launched), *out_bytes its length.  On the context's stream; blocking, like rtx_minimize_words, and with its launches:
+ * RTX_OPT_MINIMIZE_FUSED 0 / 1 / 2 means here what it means there (a launch that gave up is redone as three and counted in
+ * RTX_STAT_MINIMIZE_FALLBACKS).  Bytes of d_out past *out_bytes are not written.  On a device group: the root's device alone.
+ * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
+int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cur, const void* d_prev,
+                    void* d_out, size_t out_capacity, size_t* out_bytes);
+/* rtx_update with a memory of the frame before: physics as rtx_update does it, the frame traced as pixel words by the same path
+ * (every shading option applies; a device group traces sharded and gathers), then
+ *   a KEY frame (*kind = RTX_DELTA_KEY: byte for byte what rtx_update returns for the frame) when the context holds no valid
+ *   previous frame, when the previous frame's W, H or mode differ, when `flags` has RTX_DELTA_KEYFRAME, or when rtx_update or
+ *   rtx_update_begin ran on the context since the last call;
+ *   otherwise the rule's stream against the frame the last successful call handed out (*kind = RTX_DELTA_DIFF).
+ * The two frames live in two word buffers of the context that swap roles (allocated at the first call; the delta's output buffer
+ * at first use, rtx_delta_bound bytes).  host_out: room for host_capacity bytes; a stream longer than that returns
+ * RTX_ERR_TOO_LARGE, copies nothing, and the next call gives a key frame (so does a call that failed for any other reason).
+ * Blocking.  Unknown flag bits: RTX_ERR_INVALID_ARGUMENT.
+ * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
+int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags,
+                     void* host_out, size_t host_capacity, size_t* out_bytes, int* kind);
 
 /* ---- ansi256_from_rgb (ANSIRGB.h:141-189) on its own: the xterm-256 index (16..255) of each packed 0xRRGGBB
  * value first_rgb, first_rgb+1, ..., first_rgb+count-1 (first_rgb + count <= 2^24), one byte per value into

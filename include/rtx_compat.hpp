@@ -208,7 +208,8 @@ struct Device {
 // class is headless (the caller reads GetBackBuffer / GetPrintSize itself).  One deliberate difference: the
 // reference's thread re-prints the same buffer in a busy loop between frames; this one sleeps on a condition
 // variable until SetDataInBackBuffer flags a new frame (a terminal gains nothing from identical bytes), and a frame
-// that arrives while the previous one is still being written replaces it, as in the reference.
+// that arrives while the previous one is still being written replaces it, as in the reference.  With delta frames
+// (SetDeltaInBackBuffer) the cursor is homed in front of key frames only.
 class PrintMachine {
 public:
     static void Start(const size_t x, const size_t y)
@@ -244,9 +245,38 @@ public:
             std::memcpy(s.backBuffer.data(), data, size);
             s.shouldSwap = true; // FlagForBufferSwap
             s.backBufferPrintSize = size;
+            s.backIsKey = true;
             s.framesSet++;
         }
         s.wake.notify_all();
+    }
+    // Delta frames (RayTracingManager::SetDeltaFrames; rtx_update_delta in rtx.h).  No reference counterpart: its printer rewrites the
+    // whole screen (PrintMachine.cpp:257-306).  A key frame replaces the back buffer, as SetDataInBackBuffer does.  A delta that
+    // arrives while an unprinted frame still sits in the back buffer is APPENDED to it -- deltas applied in order are correct,
+    // replacing one is not -- and where that would exceed GetMaxSize() nothing is taken and false is returned: the caller hands
+    // in a key frame instead.
+    static bool SetDeltaInBackBuffer(const char* data, const size_t size, const bool key)
+    {
+        State& s = state();
+        {
+            std::lock_guard<std::mutex> lock(s.mutex);
+            const size_t at = (!key && s.shouldSwap) ? s.backBufferPrintSize : 0;
+            if (at + size > s.maxSize) return false;
+            std::memcpy(s.backBuffer.data() + at, data, size);
+            if (at == 0) s.backIsKey = key;
+            s.shouldSwap = true;
+            s.backBufferPrintSize = at + size;
+            s.framesSet++;
+        }
+        s.wake.notify_all();
+        return true;
+    }
+    // In delta mode the printer does not rely on where a frame leaves the cursor: the status lines are addressed to row H + 1.
+    static void SetDeltaMode(const bool on)
+    {
+        State& s = state();
+        std::lock_guard<std::mutex> lock(s.mutex);
+        s.deltaMode = on;
     }
     static const char* GetBackBuffer() { return state().backBuffer.data(); }
     static size_t GetPrintSize() { return state().backBufferPrintSize; }
@@ -304,6 +334,7 @@ private:
         for (;;) {
             size_t size = 0;
             unsigned long long upto = 0;
+            bool key = true, delta_mode = false;
             {
                 std::unique_lock<std::mutex> lock(s.mutex);
                 s.wake.wait(lock, [&] { return s.shouldSwap || s.terminate; });
@@ -312,8 +343,10 @@ private:
                 size = s.backBufferPrintSize;     // m_printSize = m_backBufferPrintSize
                 s.printBuffer.swap(s.backBuffer); // m_printBuffer.swap(m_backBuffer)
                 upto = s.framesSet;
+                key = s.backIsKey;
+                delta_mode = s.deltaMode;
             }
-            write_all(s.fd, "\x1b[H", 3);         // ResetConsolePointer: cursor home
+            if (key) write_all(s.fd, "\x1b[H", 3); // ResetConsolePointer: cursor home (a delta addresses its own cells)
             write_all(s.fd, s.printBuffer.data(), size);
             printed_this_second++;
             const auto now = std::chrono::steady_clock::now();
@@ -323,8 +356,10 @@ private:
                 second = now;
             }
             if (s.statusLines) {
-                char line[128];
-                const int n = std::snprintf(line, sizeof line, "\x1b[mRendering FPS: %d    \nPrinting FPS: %d    \n", s.renderingFps, printing_fps);
+                char line[160];
+                int n = 0;
+                if (delta_mode) n = std::snprintf(line, sizeof line, "\x1b[%zu;1H", s.height + 1); // (a delta leaves the cursor anywhere)
+                n += std::snprintf(line + n, sizeof line - (size_t)n, "\x1b[mRendering FPS: %d    \nPrinting FPS: %d    \n", s.renderingFps, printing_fps);
                 write_all(s.fd, line, (size_t)n);
             } else {
                 write_all(s.fd, "\x1b[m", 3);
@@ -344,6 +379,8 @@ private:
         std::mutex mutex; // m_backBufferMutex
         std::condition_variable wake, done;
         bool shouldSwap = false, terminate = false, statusLines = true;
+        bool backIsKey = true;  // the back buffer starts with a whole frame (else with a delta: no cursor home in front of it)
+        bool deltaMode = false; // SetDeltaMode
         unsigned long long framesSet = 0, framesPrinted = 0;
         int fd = 1, renderingFps = 0;
         std::thread printer;
@@ -581,9 +618,32 @@ public:
         }
         const rtx_params p = rtx_compat::to_rtx_params(params);
         size_t newSize = 0;
+        if (m_deltaFrames) {
+            // only the cells that changed (rtx_update_delta): a key frame first, after SetDeltaFrames, and whenever the library
+            // decides on one (another size or mode); the printer appends deltas it has not written yet
+            int kind = RTX_DELTA_KEY;
+            rtx_compat::check(m_ctx, rtx_update_delta(m_ctx, &p, (int)currentRenderingMode, dt, /*run_physics=*/1, m_wantKey ? RTX_DELTA_KEYFRAME : RTX_DELTA_DEFAULT,
+                                                      m_minimizedResultArray, PrintMachine::GetMaxSize(), &newSize, &kind), "rtx_update_delta");
+            m_wantKey = false;
+            if (!PrintMachine::SetDeltaInBackBuffer(m_minimizedResultArray, newSize, kind == RTX_DELTA_KEY)) {
+                // the unprinted deltas have outgrown the back buffer: the same frame once more (no physics), whole, replaces them
+                rtx_compat::check(m_ctx, rtx_update_delta(m_ctx, &p, (int)currentRenderingMode, 0.0, /*run_physics=*/0, RTX_DELTA_KEYFRAME,
+                                                          m_minimizedResultArray, PrintMachine::GetMaxSize(), &newSize, &kind), "rtx_update_delta");
+                PrintMachine::SetDeltaInBackBuffer(m_minimizedResultArray, newSize, true);
+            }
+            return;
+        }
         rtx_compat::check(m_ctx, rtx_update(m_ctx, &p, (int)currentRenderingMode, dt, /*run_physics=*/1,
                                             m_minimizedResultArray, &newSize), "rtx_update");
         PrintMachine::SetDataInBackBuffer(m_minimizedResultArray, newSize);
+    }
+    // Extension, no reference counterpart (PrintMachine.cpp:257-306 rewrites the screen; RayTracingManager.cu:150 hands over whole
+    // frames): Update sends only the console cells that changed since the frame before.  Off by default, and then nothing changes.
+    void SetDeltaFrames(const bool on)
+    {
+        m_deltaFrames = on;
+        m_wantKey = true;
+        PrintMachine::SetDeltaMode(on);
     }
     void SetRenderingMode(const RenderingMode newRenderMode) { currentRenderingMode = newRenderMode; }
     // Extensions, no reference counterpart (its light is a constant, RayTracing.cu:132,143-157): the point light (nullptr: the
@@ -595,5 +655,6 @@ public:
 private:
     rtx_ctx* m_ctx = nullptr;
     char* m_minimizedResultArray = nullptr;
+    bool m_deltaFrames = false, m_wantKey = true; // SetDeltaFrames
     RenderingMode currentRenderingMode = BIT_ASCII; // RayTracingManager.h:53
 };

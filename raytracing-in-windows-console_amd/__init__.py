@@ -53,6 +53,9 @@ STAT_SHADOW_GRID_FALLBACK_POINTS = 147
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
+STAT_DELTA_FRAMES, STAT_DELTA_KEYFRAMES, STAT_DELTA_CELLS, STAT_DELTA_RUNS = 151, 152, 153, 154
+DELTA_DEFAULT, DELTA_KEYFRAME = 0, 1  # enum rtx_delta_flags
+DELTA_KEY, DELTA_DIFF = 0, 1          # enum rtx_delta_kind
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 NO_OBJECT, SOME_OBJECT = 0xFFFFFFFF, 0xFFFFFFFE
 NO_HIT = 99999999.0  # the t of a ray that hits nothing (RayTracing.h:21)
@@ -172,6 +175,10 @@ _SIGNATURES = [
     ("rtx_update", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_size_t)]),
     ("rtx_update_begin", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_double, C.c_int, _P, C.POINTER(C.c_int)]),
     ("rtx_update_end", C.c_int, [_P, C.c_int, C.POINTER(C.c_size_t)]),
+    ("rtx_delta_bound", C.c_size_t, [C.c_int, C.c_size_t, C.c_size_t]),
+    ("rtx_delta_words", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("rtx_update_delta", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_double, C.c_int, C.c_uint, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_int)]),
     ("rtx_ansi256_map", C.c_int, [_P, C.c_uint32, C.c_size_t, _P, _P]),
     ("rtx_host_alloc", _P, [_P, C.c_size_t]),
     ("rtx_host_free", None, [_P, _P]),
@@ -233,6 +240,11 @@ def synth_scene(seed, n_spheres, n_planes, e1, e2):
     if rc != OK:
         raise RtxError(rc, "rtx_synth_scene")
     return sph, pl
+
+
+def delta_bound(mode, w, h):
+    """rtx_delta_bound: the most bytes a delta or a key frame of a w x h frame can take (0 for arguments the delta calls refuse)."""
+    return lib().rtx_delta_bound(mode, w, h)
 
 
 # BASELINE.json configs: (W, H, spheres, planes, LCG seed)  (SURVEY.md Appendix D)
@@ -639,6 +651,22 @@ class Context:
         n = C.c_size_t()
         self._check(lib().rtx_update(self._h, C.byref(params), mode, dt, 1 if run_physics else 0, ptr, C.byref(n)))
         return arr[:n.value]  # a view of the pinned buffer: valid until the next update()
+
+    def delta_words(self, mode, w, h, d_cur, d_prev, d_out, out_capacity):
+        """rtx_delta_words: the delta of two frames of pixel words (device pointers) into d_out; returns the stream's length."""
+        n = C.c_size_t()
+        self._check(lib().rtx_delta_words(self._h, mode, w, h, d_cur, d_prev, d_out, out_capacity, C.byref(n)))
+        return n.value
+
+    def update_delta(self, params, mode, dt=0.0, run_physics=False, flags=DELTA_DEFAULT, capacity=None):
+        """rtx_update_delta: (stream, kind) -- the whole frame as update() returns it (DELTA_KEY) or only the cells that changed since
+        the frame the last call handed out (DELTA_DIFF).  `capacity`: the host_capacity passed (default: delta_bound's)."""
+        need = delta_bound(mode, int(params.x), int(params.y))
+        ptr, _, arr = self._pinned_buffer(max(need, 20 * int(params.x) * int(params.y), 16))
+        n, kind = C.c_size_t(), C.c_int(-1)
+        self._check(lib().rtx_update_delta(self._h, C.byref(params), mode, dt, 1 if run_physics else 0, flags, ptr,
+                                           need if capacity is None else capacity, C.byref(n), C.byref(kind)))
+        return arr[:n.value], kind.value  # a view of the pinned buffer: valid until the next update() / update_delta()
 
     def ansi256_map(self, first_rgb, count, d_out, stream=None):
         """rtx_ansi256_map: xterm-256 indices of packed 0xRRGGBB values first_rgb .. first_rgb+count-1 into d_out."""

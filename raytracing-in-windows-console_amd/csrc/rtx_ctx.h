@@ -43,6 +43,9 @@ struct MinInput {
     bool words = false; // data: pixel words, else S-byte records
     const void* data = nullptr;
     uint32_t lead = 0;
+    // a delta (rtx_delta_words): `data` is the current frame's words, `prev` the previous frame's, `counts` the launch's two counters
+    const void* prev = nullptr;
+    void* counts = nullptr;
 };
 
 // ... and, once launched, where it writes and where its result words are.
@@ -356,6 +359,21 @@ struct rtx_ctx {
     uint8_t* h_remove_marks = nullptr;
     size_t remove_marks_cap = 0;
     uint64_t stat_scene_removed = 0;    // RTX_STAT_SCENE_REMOVED
+
+    // delta frames (rtx_delta_words, rtx_update_delta; rtx_post.hip): the previous and the current frame's pixel words in two
+    // buffers that swap roles (delta_at: the one the last successful call handed out), the delta's own output buffer (sized by
+    // rtx_delta_bound at first use) and the two counters of the last delta launch (changed cells, runs)
+    uint32_t* d_delta_words[2] = {nullptr, nullptr};
+    size_t delta_words_cap[2] = {0, 0};
+    unsigned delta_at = 0;
+    bool delta_valid = false;           // delta_words[delta_at] is the frame the consumer shows: W, H and mode as below
+    size_t delta_w = 0, delta_h = 0;
+    int delta_mode = -1;
+    uint8_t* d_delta_out = nullptr;
+    size_t delta_out_cap = 0;
+    unsigned long long* d_delta_counts = nullptr;
+    bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
+    uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
 
     std::string error;
     const char* last_kernel = "";

@@ -1121,4 +1121,51 @@ inline ShadingPlan plan_shading(const ShadingRequest& q)
     return p;
 }
 
+// ------------------------------------------------------------------------------------------------ delta frames
+//
+// rtx_delta_words / rtx_update_delta (rtx.h) emit, for every run of changed cells of a row, a cursor escape ESC [ row+1 ; col+1 H
+// and then each cell's record (S bytes) or its glyph alone.  How long such a stream can get -- what the output buffers and the
+// block's LDS image are sized by.
+
+constexpr size_t kDeltaMaxIndex = 99999; // the largest row and column index (W - 1 <= 99999, H <= 99999): five digits each
+constexpr size_t kDeltaMaxCup = 14;      // ESC [ 5 digits ; 5 digits H
+
+constexpr size_t decimal_digits(size_t v) { return v < 10 ? 1 : 1 + decimal_digits(v / 10); }
+
+// Bytes of the cursor escape in front of a run that starts at cell (row, col), both counted from 0.
+constexpr size_t cup_length(size_t row, size_t col) { return 4 + decimal_digits(row + 1) + decimal_digits(col + 1); }
+
+// The most bytes n consecutive slots can emit when a cell costs at most S bytes and a run's escape at most `cup`: c changed cells
+// in r runs give S c + cup r, with r <= c and -- every run but the first needs a slot in front of it that is not a changed cell, an
+// unchanged cell or a row's last column -- c + r - 1 <= n.  For a given c the best r is min(c, n + 1 - c), so the sum rises with
+// slope S + cup up to c = (n + 1) / 2 and with slope S - cup behind it: the maximum is at the bend or at c = n.  (cup > S for the
+// 12-byte records: there a row of alternating cells is longer than a row that changed everywhere.)
+constexpr size_t delta_run_value(size_t S, size_t cup, size_t n, size_t c) { return c > n ? 0 : S * c + cup * (c < n + 1 - c ? c : n + 1 - c); }
+
+constexpr size_t delta_run_bound(size_t S, size_t cup, size_t n)
+{
+    const size_t a = delta_run_value(S, cup, n, (n + 1) / 2), b = delta_run_value(S, cup, n, (n + 1) / 2 + 1), c = delta_run_value(S, cup, n, n);
+    return a > b ? (a > c ? a : c) : (b > c ? b : c);
+}
+
+// ... of a W x H frame: the rows' sums, a row's W - 1 cells with the longest escape the row can need (its last cell's).  Rows whose
+// numbers have the same count of digits share a bound.
+inline size_t delta_bound(size_t S, size_t W, size_t H)
+{
+    if (W < 2 || H == 0) return 0;
+    size_t total = 0;
+    for (size_t lo = 0, hi = 9; lo < H; lo = hi, hi = hi * 10 + 9) { // rows lo .. hi - 1: row + 1 has the digits of lo + 1
+        const size_t rows = (hi < H ? hi : H) - lo;
+        total += rows * delta_run_bound(S, cup_length(lo, W - 2), W - 1);
+    }
+    return total;
+}
+
+// ... of one block of `slots` consecutive slots anywhere in any frame within the limits: the block's LDS image.
+constexpr size_t delta_block_bound(size_t S, size_t slots) { return delta_run_bound(S, kDeltaMaxCup, slots); }
+
+static_assert(cup_length(0, 0) == 6 && cup_length(99998, 99998) == kDeltaMaxCup && cup_length(8, 9) == 7, "the cursor escape");
+static_assert(delta_block_bound(12, 1024) == 513 * 12 + 512 * 14 && delta_block_bound(20, 1024) == 1024 * 20 + 14,
+              "a block inside one long row can need more than 1024 S bytes");
+
 } // namespace rtxplan

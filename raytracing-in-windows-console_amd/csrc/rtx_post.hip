@@ -51,6 +51,8 @@ MinInput records_input(int mode, size_t w, size_t h, const void* d_records) { re
 
 MinInput words_input(int mode, size_t w, size_t h, const void* d_words, uint32_t lead = 0) { return MinInput{mode, w, h, true, d_words, lead}; }
 
+MinInput delta_input(int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_counts) { return MinInput{mode, w, h, true, d_cur, 0u, d_prev, d_counts}; }
+
 // f(Src()) with the slot source (rtx_post_kernels.inc) of `in`: the one place where a mode and an input form pick the kernels.
 template <class F>
 int with_source(rtx_ctx* ctx, const MinInput& in, F f)
@@ -61,6 +63,17 @@ int with_source(rtx_ctx* ctx, const MinInput& in, F f)
             f(rtx::RecordSource<20>());
         } else {
             f(rtx::RecordSource<12>());
+        }
+        return RTX_OK;
+    }
+    if (in.prev) {
+        switch (in.mode) {
+        case RTX_BIT_ASCII: f(rtx::DeltaSource<RTX_K_BIT_ASCII>()); break;
+        case RTX_BIT_PIXEL: f(rtx::DeltaSource<RTX_K_BIT_PIXEL>()); break;
+        case RTX_RGB_ASCII: f(rtx::DeltaSource<RTX_K_RGB_ASCII>()); break;
+        case RTX_RGB_PIXEL: f(rtx::DeltaSource<RTX_K_RGB_PIXEL>()); break;
+        case RTX_RGB_NORMALS: f(rtx::DeltaSource<RTX_K_RGB_NORMALS>()); break;
+        default: return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "no pixel words in this mode");
         }
         return RTX_OK;
     }
@@ -85,9 +98,10 @@ int launch_minimize_chain(rtx_ctx* ctx, const MinRun& run)
     uint64_t* offsets = total + 8;
     uint32_t* sums = (uint32_t*)(offsets + n_blocks);
     hipStream_t st = ctx->stream;
+    if (in.counts) RTX_HIP(ctx, hipMemsetAsync(in.counts, 0, 2 * sizeof(unsigned long long), st)); // (a delta's counters: the scatter pass adds to them)
     const int rc = with_source(ctx, in, [&](auto src) {
         using Src = decltype(src);
-        const auto* p = (const typename Src::Elem*)in.data;
+        const typename Src::In p = Src::input(in.data, in.prev, in.counts);
         hipLaunchKernelGGL((rtx::rtx_min_count<Src>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, p, n_slots, (uint32_t)in.w, in.lead, sums);
         hipLaunchKernelGGL(rtx::rtx_min_offsets, dim3(1), dim3(rtx::kThreads), 0, st, sums, n_blocks, offsets, total);
         hipLaunchKernelGGL((rtx::rtx_min_scatter<Src>), dim3(n_blocks), dim3(rtx::kThreads), 0, st, p, n_slots, (uint32_t)in.w, in.lead, offsets, run.out);
@@ -144,9 +158,10 @@ int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_o
     uint64_t* grp = agg + ctx->look_blocks;
     const uint32_t ng = (uint32_t)(ctx->look_blocks / rtx::kLookGroup);
     const uint32_t polls = ctx->opt_min_fused == 2 ? 0u : rtx::kLookPolls;
+    if (in.counts) RTX_HIP(ctx, hipMemsetAsync(in.counts, 0, 2 * sizeof(unsigned long long), ctx->stream));
     rc = with_source(ctx, in, [&](auto src) {
         using Src = decltype(src);
-        hipLaunchKernelGGL((rtx::rtx_min_fused<Src>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, ctx->stream, (const typename Src::Elem*)in.data, n_slots,
+        hipLaunchKernelGGL((rtx::rtx_min_fused<Src>), dim3((unsigned)n_blocks), dim3(rtx::kThreads), 0, ctx->stream, Src::input(in.data, in.prev, in.counts), n_slots,
                            (uint32_t)in.w, in.lead, agg, grp, ng, epoch, polls, d_out, total);
     });
     if (rc != RTX_OK) return rc;
@@ -777,9 +792,100 @@ int rtx_minimize_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d
     return minimize_and_wait(ctx, words_input(mode, w, h, d_words), d_out, out_bytes);
 }
 
+size_t rtx_delta_bound(int mode, size_t w, size_t h)
+{
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL || w == 0 || h == 0 || w - 1 > rtxplan::kDeltaMaxIndex || h > rtxplan::kDeltaMaxIndex) return 0;
+    const size_t S = mode >= RTX_RGB_ASCII ? RTX_SIZE_RGB : RTX_SIZE_8BIT;
+    return std::max(rtxplan::delta_bound(S, w, h), S * w * h); // (a key frame of rtx_update_delta: Minimize's S W H)
+}
+
+int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_out, size_t out_capacity, size_t* out_bytes)
+{
+    if (!ctx || !out_bytes || !d_cur || !d_prev || !d_out) return RTX_ERR_INVALID_ARGUMENT;
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_delta_words: not a character mode");
+    if (w == 0 || h == 0 || w - 1 > rtxplan::kDeltaMaxIndex || h > rtxplan::kDeltaMaxIndex) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_delta_words: w - 1 and h must be in [0, 99999], h and w at least 1");
+    }
+    if ((((uintptr_t)d_cur | (uintptr_t)d_prev) & 3u) != 0 || ((uintptr_t)d_out & 15u) != 0) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_delta_words: words must be 4-byte, the output 16-byte aligned");
+    }
+    if (out_capacity < rtx_delta_bound(mode, w, h)) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_delta_words: the output holds less than rtx_delta_bound");
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    if (!ctx->d_delta_counts && hipMalloc((void**)&ctx->d_delta_counts, 2 * sizeof(unsigned long long)) != hipSuccess) {
+        ctx->d_delta_counts = nullptr;
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
+    }
+    ctx->delta_counts_valid = true;
+    return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts), d_out, out_bytes);
+}
+
+int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags, void* host_out, size_t host_capacity,
+                     size_t* out_bytes, int* kind)
+{
+    if (!ctx || !params || !host_out || !out_bytes || !kind) return RTX_ERR_INVALID_ARGUMENT;
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_update_delta: not a character mode");
+    if ((flags & ~(unsigned)RTX_DELTA_KEYFRAME) != 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: unknown flag bits");
+    const size_t W = (size_t)params->x, H = (size_t)params->y;
+    if (W == 0 || H == 0 || W - 1 > rtxplan::kDeltaMaxIndex || H > rtxplan::kDeltaMaxIndex) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: x - 1 and y must be in [0, 99999], x and y at least 1");
+    }
+    if (20 * (uint64_t)W * (uint64_t)H > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
+    int rc;
+    // RayTracingManager.cu:89-107: physics first, as rtx_update
+    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    const bool key = !ctx->delta_valid || ctx->delta_w != W || ctx->delta_h != H || ctx->delta_mode != mode || (flags & RTX_DELTA_KEYFRAME) != 0;
+    const unsigned at = ctx->delta_at ^ 1u; // the buffer that does NOT hold the frame handed out last: nothing of this call reads it before it is written
+    ctx->delta_valid = false;               // until this call has handed its frame out
+    // the words: traced straight into the pair's buffer; a group's gathered words are copied into it
+    const uint32_t* d_words = nullptr;
+    if ((rc = ensure_words_buffer(ctx, &ctx->d_delta_words[at], &ctx->delta_words_cap[at], W * H)) != RTX_OK) return rc;
+    if ((rc = trace_words(ctx, params, mode, &ctx->d_delta_words[at], &ctx->delta_words_cap[at], &d_words)) != RTX_OK) return rc;
+    if (d_words != ctx->d_delta_words[at]) {
+        RTX_HIP(ctx, hipMemcpyAsync(ctx->d_delta_words[at], d_words, W * H * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    size_t n = 0;
+    const uint8_t* d_stream = nullptr;
+    if (key) {
+        // what rtx_update makes of the frame: Minimize of the words into the context's buffer
+        if ((rc = rtx_minimize_words(ctx, mode, W, H, ctx->d_delta_words[at], nullptr, &n)) != RTX_OK) return rc;
+        d_stream = ctx->d_min;
+    } else {
+        const size_t bound = rtx_delta_bound(mode, W, H);
+        if (ctx->delta_out_cap < bound) {
+            if (ctx->d_delta_out) {
+                RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                hipFree(ctx->d_delta_out);
+            }
+            ctx->d_delta_out = nullptr;
+            ctx->delta_out_cap = 0;
+            if (hipMalloc((void**)&ctx->d_delta_out, bound) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta buffer");
+            ctx->delta_out_cap = bound;
+        }
+        if ((rc = rtx_delta_words(ctx, mode, W, H, ctx->d_delta_words[at], ctx->d_delta_words[at ^ 1u], ctx->d_delta_out, ctx->delta_out_cap, &n)) != RTX_OK) return rc;
+        d_stream = ctx->d_delta_out;
+    }
+    if (n > host_capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_delta: the stream is longer than host_capacity (the next call gives a key frame)");
+    if (n) {
+        RTX_HIP(ctx, hipMemcpyAsync(host_out, d_stream, n, hipMemcpyDeviceToHost, ctx->stream));
+        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->delta_at = at;
+    ctx->delta_valid = true;
+    ctx->delta_w = W;
+    ctx->delta_h = H;
+    ctx->delta_mode = mode;
+    ctx->stat_delta_frames++;
+    if (key) ctx->stat_delta_keyframes++;
+    *out_bytes = n;
+    *kind = key ? RTX_DELTA_KEY : RTX_DELTA_DIFF;
+    return RTX_OK;
+}
+
 int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, size_t* out_bytes)
 {
     if (!ctx || !params || !host_out || !out_bytes) return RTX_ERR_INVALID_ARGUMENT;
+    ctx->delta_valid = false; // (the consumer's screen is about to show this frame: the next rtx_update_delta gives a key frame)
     int rc;
     // RayTracingManager.cu:89-107: physics first
     if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
@@ -838,6 +944,7 @@ int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int 
 int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, int* ticket)
 {
     if (!ctx || !params || !host_out || !ticket) return RTX_ERR_INVALID_ARGUMENT;
+    ctx->delta_valid = false; // (as rtx_update: the next rtx_update_delta gives a key frame)
     if (mode < RTX_BIT_ASCII || mode > RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode");
     const size_t w = (size_t)params->x, h = (size_t)params->y;
     if (w == 0 || h == 0 || 20 * w * h > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");

@@ -1,7 +1,8 @@
 // rtx_post_kernels.inc -- the device code of rtx_post.hip (included there, once): the physics step (UpdateObjects), the sphere gather
 // of the direction-sorted scene copy, the xterm-256 mapper over a range, and Minimize from records or from pixel words -- as one launch
 // (rtx_min_fused, with the look-back it finds its offsets by) or as the chain rtx_min_count / rtx_min_offsets / rtx_min_scatter.  The
-// host side (buffers, launches, the Update entry points): rtx_post.hip.
+// host side (buffers, launches, the Update entry points): rtx_post.hip.  Delta frames (rtx_delta_words) are a third slot source of the
+// same Minimize kernels, DeltaSource, over two frames of pixel words.
 namespace rtx {
 
 constexpr int kThreads = 256;
@@ -300,13 +301,14 @@ __device__ __noinline__ uint32_t record_length_walk(const uint8_t* __restrict__ 
 template <int S>
 struct RecordSource {
     typedef uint8_t Elem;  // the input
+    typedef const uint8_t* __restrict__ In; // ... as the kernels receive it
     typedef Slot<S> Item;  // what a thread keeps of a slot
     static constexpr uint32_t kS = S;
     static constexpr uint32_t kWave = kHaloOff + kSlotsPerBlock * S;
     static constexpr uint32_t kStage = kWave + 16;
     static constexpr uint32_t kBytes = kStage;
 
-    static __device__ __forceinline__ void stage(const uint8_t* __restrict__ in, uint64_t base, uint64_t n_slots, uint32_t, uint8_t* s)
+    static __device__ __forceinline__ void stage(const uint8_t* __restrict__ in, uint64_t base, uint64_t n_slots, uint32_t, uint8_t* s, uint32_t)
     {
         const uint64_t b0 = base * S;
         const uint64_t total_bytes = n_slots * S;
@@ -337,6 +339,9 @@ struct RecordSource {
     }
 
     static __device__ __forceinline__ void stage_tables() {}
+    static In input(const void* data, const void*, void*) { return (In)data; }
+    static __device__ __forceinline__ void tally_put(const uint32_t*) {}
+    static __device__ __forceinline__ void tally_add(In) {}
 
     // Emitted length of slot g (column col, staged at li); `rec` receives the record when the slot is a pixel.
     static __device__ __forceinline__ uint32_t length(const uint8_t* __restrict__ in, const uint8_t* s, uint64_t g, int li, uint32_t col, uint32_t W, uint32_t,
@@ -424,6 +429,7 @@ __device__ __noinline__ uint32_t word_length_walk(const uint32_t* __restrict__ w
 template <int MODE>
 struct WordSource {
     typedef uint32_t Elem;
+    typedef const uint32_t* __restrict__ In;
     typedef uint32_t Item;
     static constexpr uint32_t kS = (MODE == RTX_K_RGB_ASCII || MODE == RTX_K_RGB_PIXEL || MODE == RTX_K_RGB_NORMALS) ? 20u : 12u;
     static constexpr uint32_t kWave = (2 + kSlotsPerBlock + 2) * 4;
@@ -437,7 +443,7 @@ struct WordSource {
         return s_digits;
     }
 
-    static __device__ __forceinline__ void stage(const uint32_t* __restrict__ words, uint64_t base, uint64_t n_slots, uint32_t lead, uint8_t* s)
+    static __device__ __forceinline__ void stage(const uint32_t* __restrict__ words, uint64_t base, uint64_t n_slots, uint32_t lead, uint8_t* s, uint32_t)
     {
         uint32_t* s_w = reinterpret_cast<uint32_t*>(s);
         const uint32_t tid = threadIdx.x;
@@ -460,6 +466,9 @@ struct WordSource {
     }
 
     static __device__ __forceinline__ void stage_tables() { digits()[threadIdx.x] = digits_word(threadIdx.x); }
+    static In input(const void* data, const void*, void*) { return (In)data; }
+    static __device__ __forceinline__ void tally_put(const uint32_t*) {}
+    static __device__ __forceinline__ void tally_add(In) {}
 
     // Emitted length of slot g (column col, staged at s_w[2 + li]); `w` receives its word.  Selects, and one branch for the rare walk.
     static __device__ __forceinline__ uint32_t length(const uint32_t* __restrict__ words, const uint8_t* s, uint64_t g, int li, uint32_t col, uint32_t W,
@@ -499,6 +508,169 @@ struct WordSource {
         } else if (len == 1u) {
             // the row's newline, or the glyph alone (the last byte of the record: ' ' for a miss)
             dst[0] = newline ? (uint8_t)'\n' : (w == kCompactMiss ? (uint8_t)' ' : (uint8_t)(w >> 24));
+        }
+    }
+};
+
+// ---- delta frames: two frames of pixel words, `cur` and the one before it, `prev`; only the cells that changed are emitted, each
+// run of them addressed by a cursor escape (rtx_delta_words in rtx.h states the rule).  No reference counterpart: its printer homes
+// the cursor and rewrites the screen (PrintMachine.cpp:257-306).  Slot rules:
+//   * column W-1, an empty slot (0xffffffff) of cur, cur == prev   -> nothing
+//   * a changed slot whose left neighbour in the row did not change (or column 0): a run starts -> ESC [ row+1 ; col+1 H, then the
+//     whole record
+//   * any other changed slot -> the whole record if its first S-1 bytes differ from those of the record to its left, else its glyph
+// The first S-1 bytes of a record are a function of the colour key and of the '3' / '4' selector, which differs between a hit and a
+// miss in the two ASCII modes only (record_words): the head key.  Everything looks one slot back and no further, so there is no walk.
+struct DeltaInput {
+    const uint32_t* cur;
+    const uint32_t* prev;
+    unsigned long long* counts; // [0] changed cells, [1] runs of the launch, zeroed by the host
+};
+
+template <int MODE>
+__device__ __forceinline__ uint32_t head_key(uint32_t w)
+{
+    constexpr bool kAscii = (MODE == RTX_K_BIT_ASCII || MODE == RTX_K_RGB_ASCII);
+    return colour_key<MODE>(w) | ((kAscii && w != kCompactMiss) ? (1u << 24) : 0u);
+}
+
+__device__ __forceinline__ uint32_t decimal_length(uint32_t v) // v <= 99999
+{
+    return 1u + (v >= 10u ? 1u : 0u) + (v >= 100u ? 1u : 0u) + (v >= 1000u ? 1u : 0u) + (v >= 10000u ? 1u : 0u);
+}
+
+__device__ __forceinline__ void put_decimal(uint8_t* dst, uint32_t v, uint32_t n)
+{
+    for (uint32_t i = n; i-- > 0u;) {
+        const uint32_t q = v / 10u;
+        dst[i] = (uint8_t)(48u + (v - 10u * q));
+        v = q;
+    }
+}
+
+// The block's buffer, in dwords: [0] the row and [1] the column of the block's first slot, [kCur - 1] the word of cur in front of
+// the block (0xffffffff where the frame begins), [kCur + li] cur of slot base + li, the same of prev from kPrev, the scan's partial
+// sums behind them.  The image is built over all of it once every thread holds its own slots.
+template <int MODE>
+struct DeltaSource {
+    typedef uint32_t Elem;
+    typedef DeltaInput In;
+    struct Item {
+        uint32_t w, row1, col1; // the word; row + 1 and column + 1 where a run starts
+    };
+    static constexpr uint32_t kS = (MODE == RTX_K_RGB_ASCII || MODE == RTX_K_RGB_PIXEL || MODE == RTX_K_RGB_NORMALS) ? 20u : 12u;
+    static constexpr uint32_t kCur = 4, kPrev = kCur + kSlotsPerBlock + 4;
+    static constexpr uint32_t kWave = (kPrev + kSlotsPerBlock) * 4;
+    static constexpr uint32_t kStage = kWave + (kThreads / 64) * 4;
+    // the image: a block inside one long row -- 513 cells in 512 runs of 12-byte records, or 1024 cells of 20 bytes behind one
+    // escape -- emits more than 1024 S bytes
+    static constexpr uint32_t kBytes = ((uint32_t)rtxplan::delta_block_bound(kS, kSlotsPerBlock) + 15u) & ~15u;
+    static_assert(kBytes >= rtxplan::delta_block_bound(kS, kSlotsPerBlock) && kBytes > kSlotsPerBlock * kS, "the image holds the longest stream a block can emit");
+    static_assert(kStage <= kBytes, "words + partial sums fit the image's space");
+
+    static In input(const void* cur, const void* prev, void* counts) { return In{(const uint32_t*)cur, (const uint32_t*)prev, (unsigned long long*)counts}; }
+
+    static __device__ __forceinline__ uint32_t* tally()
+    {
+        __shared__ uint32_t s_tally[kThreads / 64];
+        return s_tally;
+    }
+
+    static __device__ __forceinline__ void stage_words(const uint32_t* __restrict__ words, uint64_t base, uint64_t n_slots, uint32_t* s_w)
+    {
+        const uint32_t tid = threadIdx.x;
+        const uint64_t g0 = base + (uint64_t)tid * kPerThread;
+        if (g0 + kPerThread <= n_slots && ((uintptr_t)(words + g0) & 15u) == 0u) {
+            *reinterpret_cast<uint4*>(s_w + tid * kPerThread) = *reinterpret_cast<const uint4*>(words + g0); // (kCur and kPrev are multiples of 4)
+        } else {
+#pragma unroll
+            for (int k = 0; k < kPerThread; k++) {
+                s_w[tid * kPerThread + k] = g0 + k < n_slots ? words[g0 + k] : kNoWord;
+            }
+        }
+    }
+
+    static __device__ __forceinline__ void stage(In in, uint64_t base, uint64_t n_slots, uint32_t, uint8_t* s, uint32_t W)
+    {
+        uint32_t* s_w = reinterpret_cast<uint32_t*>(s);
+        stage_words(in.cur, base, n_slots, s_w + kCur);
+        stage_words(in.prev, base, n_slots, s_w + kPrev);
+        // the block's first row by one scalar division (64-bit only where the slot does not fit 32 bits), as first_column
+        const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane((base >> 32) == 0u ? (uint32_t)base / W : (uint32_t)(base / W));
+        if (threadIdx.x == 0u) {
+            s_w[0] = row0;
+            s_w[1] = (uint32_t)(base - (uint64_t)row0 * W);
+            s_w[kCur - 1] = base > 0u ? in.cur[base - 1u] : kNoWord;
+            s_w[kPrev - 1] = base > 0u ? in.prev[base - 1u] : kNoWord;
+        }
+    }
+
+    static __device__ __forceinline__ void stage_tables() { WordSource<MODE>::stage_tables(); }
+
+    // Emitted length of slot g (column col, staged at li): 0, 1 (the glyph), S (the record) or S + the escape's 6 .. 14 bytes.
+    static __device__ __forceinline__ uint32_t length(In, const uint8_t* s, uint64_t, int li, uint32_t col, uint32_t W, uint32_t, Item& it)
+    {
+        const uint32_t* s_w = reinterpret_cast<const uint32_t*>(s);
+        const uint32_t w = s_w[kCur + li], left = s_w[kCur + li - 1];
+        const bool changed = col != W - 1u && w != s_w[kPrev + li] && w != kNoWord;
+        const bool left_changed = col != 0u && left != s_w[kPrev + li - 1] && left != kNoWord; // (column col - 1 < W - 1: a cell)
+        const bool start = changed && !left_changed;
+        uint32_t len = !changed ? 0u : ((start || head_key<MODE>(w) != head_key<MODE>(left)) ? kS : 1u);
+        it.w = w;
+        it.row1 = it.col1 = 0u;
+        if (start) {
+            it.row1 = s_w[0] + (s_w[1] + (uint32_t)li) / W + 1u; // (32-bit: column + 1024 < 2^31)
+            it.col1 = col + 1u;
+            len += 4u + decimal_length(it.row1) + decimal_length(it.col1);
+        }
+        return len;
+    }
+
+    static __device__ __forceinline__ void emit(uint8_t* dst, uint32_t len, bool, const Item& it)
+    {
+        if (len > kS) {
+            const uint32_t nr = decimal_length(it.row1), nc = decimal_length(it.col1);
+            dst[0] = 0x1bu;
+            dst[1] = (uint8_t)'[';
+            put_decimal(dst + 2, it.row1, nr);
+            dst[2u + nr] = (uint8_t)';';
+            put_decimal(dst + 3u + nr, it.col1, nc);
+            dst[3u + nr + nc] = (uint8_t)'H';
+            dst += len - kS;
+            len = kS;
+        }
+        WordSource<MODE>::emit(dst, len, false, it.w); // the record, its glyph, or nothing
+    }
+
+    // The launch's counts: each wave's sum before a barrier of the caller's, then one atomic instruction of two lanes per block.
+    static __device__ __forceinline__ void tally_put(const uint32_t* len)
+    {
+        uint32_t v = 0u; // changed cells | runs << 16
+#pragma unroll
+        for (int k = 0; k < kPerThread; k++) {
+            v += (len[k] != 0u ? 1u : 0u) + (len[k] > kS ? 0x10000u : 0u);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            v += (uint32_t)__shfl_xor((int)v, d);
+        }
+        if ((threadIdx.x & 63u) == 0u) {
+            tally()[threadIdx.x >> 6] = v;
+        }
+    }
+
+    static __device__ __forceinline__ void tally_add(In in)
+    {
+        if (threadIdx.x < 2u) {
+            uint32_t v = 0u;
+#pragma unroll
+            for (int k = 0; k < kThreads / 64; k++) {
+                v += tally()[k];
+            }
+            const uint32_t mine = threadIdx.x == 0u ? (v & 0xffffu) : (v >> 16); // (at most 1024 cells and 512 runs per block)
+            if (v != 0u) {
+                atomicAdd(&in.counts[threadIdx.x], (unsigned long long)mine);
+            }
         }
     }
 };
@@ -677,10 +849,10 @@ struct MinBlock {
 // kImage: the block's image follows, which needs each thread's four slots consecutive; else (a count: only the sum matters) slot
 // k of thread t is k * kThreads + t, so that consecutive lanes read consecutive slots (bank-conflict free at the records' stride).
 template <class Src, bool kImage>
-__device__ __forceinline__ void min_lengths(const typename Src::Elem* __restrict__ in, uint64_t n_slots, uint32_t W, uint32_t lead, uint8_t* s, MinBlock<Src>& m)
+__device__ __forceinline__ void min_lengths(typename Src::In in, uint64_t n_slots, uint32_t W, uint32_t lead, uint8_t* s, MinBlock<Src>& m)
 {
     const uint64_t base = (uint64_t)blockIdx.x * kSlotsPerBlock;
-    Src::stage(in, base, n_slots, lead, s);
+    Src::stage(in, base, n_slots, lead, s, W);
     if (kImage) {
         Src::stage_tables();
     }
@@ -718,7 +890,7 @@ __device__ __forceinline__ void min_image(const MinBlock<Src>& m, uint8_t* s)
 }
 
 template <class Src>
-__global__ __launch_bounds__(kThreads) void rtx_min_count(const typename Src::Elem* __restrict__ in, uint64_t n_slots, uint32_t W, uint32_t lead, uint32_t* block_sums)
+__global__ __launch_bounds__(kThreads) void rtx_min_count(typename Src::In in, uint64_t n_slots, uint32_t W, uint32_t lead, uint32_t* block_sums)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_buf[Src::kStage];
     MinBlock<Src> m;
@@ -729,7 +901,7 @@ __global__ __launch_bounds__(kThreads) void rtx_min_count(const typename Src::El
 }
 
 template <class Src>
-__global__ __launch_bounds__(kThreads) void rtx_min_scatter(const typename Src::Elem* __restrict__ in, uint64_t n_slots, uint32_t W, uint32_t lead,
+__global__ __launch_bounds__(kThreads) void rtx_min_scatter(typename Src::In in, uint64_t n_slots, uint32_t W, uint32_t lead,
                                                             const uint64_t* __restrict__ offsets, uint8_t* out)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_buf[16 + Src::kBytes]; // (the image starts at G's 16-byte phase)
@@ -738,12 +910,14 @@ __global__ __launch_bounds__(kThreads) void rtx_min_scatter(const typename Src::
     min_lengths<Src, true>(in, n_slots, W, lead, s_buf, m);
     const uint32_t pad = (uint32_t)(G & 15u);
     min_image(m, s_buf + pad);
+    Src::tally_put(m.len);
     __syncthreads();
+    Src::tally_add(in);
     copy_out_image(s_buf, pad, m.n, G, out);
 }
 
 template <class Src>
-__global__ __launch_bounds__(kThreads) void rtx_min_fused(const typename Src::Elem* __restrict__ in, uint64_t n_slots, uint32_t W, uint32_t lead, uint64_t* agg,
+__global__ __launch_bounds__(kThreads) void rtx_min_fused(typename Src::In in, uint64_t n_slots, uint32_t W, uint32_t lead, uint64_t* agg,
                                                           uint64_t* grp, uint32_t ng, uint32_t epoch, uint32_t max_polls, uint8_t* out, uint64_t* total_out)
 {
     // (What bounds this launch is the order its dependency imposes on the whole GPU -- every block reads and counts, then every
@@ -761,12 +935,14 @@ __global__ __launch_bounds__(kThreads) void rtx_min_fused(const typename Src::El
         __hip_atomic_store(&agg[b], ((uint64_t)epoch << 32) | m.n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     min_image(m, s_buf); // the output bytes, built while the other blocks publish their lengths
+    Src::tally_put(m.len); // (a delta source's counts; the look-back's barrier stands between the two halves)
     if (!look_back(b, m.n, agg, grp, ng, epoch, max_polls, &s_G, &s_ok)) {
         if (threadIdx.x == 0) {
             total_out[1] = epoch; // the host runs the chain over the same input
         }
         return;
     }
+    Src::tally_add(in);
     copy_out_image(s_buf, 0u, m.n, s_G, out);
     if (b == gridDim.x - 1u && threadIdx.x == 0) {
         total_out[0] = s_G + m.n; // length of the minimised stream
