@@ -6,6 +6,8 @@
 // sqrt and division (hipcc's default), no reassociation, denormals kept.
 #pragma once
 
+#include "rtx_unit.hpp"
+
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -123,6 +125,38 @@ __device__ __forceinline__ V3 normalize_gpu(V3 a)
     const float length = rcp_sqrt_cr(a.x * a.x + a.y * a.y + a.z * a.z);
     return v3(a.x * length, a.y * length, a.z * length);
 }
+
+// ---- normalising a vector that is already normalised (the reference does it four times per shaded pixel).
+// Its squared length is within a few ulps of 1.0f, where the factor RN(1 / RN(sqrt(len2))) is a function of the bit offset
+// from 1.0f alone (rtx_unit.hpp): a 16-entry LDS table, filled by every workgroup at its head, replaces the rsq, the rcp and
+// their correction steps (ten instructions, two of them transcendental) by a subtract, a compare, a mask and one LDS read.
+// Squared lengths outside the window -- a vector that was not normalised after all, a scene scaled until lengths overflow --
+// take the generic expansions of 1.0f / sqrtf(x), the lanes concerned only, behind one wave-uniform branch; rcp_sqrt_cr
+// returns the same bits for every input (tests/test_gpu_math.py), and four more inlined copies of its short sequence cost the
+// trace kernels scalar-register spills inside the pass loop.  The result is normalize_gpu's for every input
+// (tests/gpu_checks/unit_check.hip: all 2^32 squared lengths).
+__device__ __forceinline__ void unit_table_fill(uint32_t* s_unit, uint32_t tid)
+{
+    if (tid < kUnitEntries) s_unit[tid] = unit_rescale_bits((int32_t)tid + kUnitKMin);
+}
+
+__device__ __forceinline__ float unit_rescale(float len2, const uint32_t* s_unit)
+{
+    const uint32_t slot = unit_slot(__float_as_uint(len2));
+    float r = __uint_as_float(s_unit[slot & (kUnitEntries - 1u)]); // (masked: lanes outside the window read some entry and drop it)
+    const bool odd = slot >= kUnitEntries;
+    if (__builtin_expect(__ballot(odd) != 0ull, 0)) {
+        if (odd) r = rcp_generic(sqrt_generic(len2));
+    }
+    return r;
+}
+
+// normalize_gpu for a vector that normalize_gpu produced: the same bits for any vector
+__device__ __forceinline__ V3 renormalize_gpu(V3 a, const uint32_t* s_unit)
+{
+    const float length = unit_rescale(a.x * a.x + a.y * a.y + a.z * a.z, s_unit);
+    return v3(a.x * length, a.y * length, a.z * length);
+}
 // MyMath.cu:29-34
 __device__ __forceinline__ float clampf(float v, float lo, float hi)
 {
@@ -236,13 +270,13 @@ __device__ __forceinline__ bool plane_hit(const Ray& r, V3 p, V3 n, float width,
 
 // BlinnPhongShading with the call-site constants, RayTracing.cu:41-79 and :143-157, given nn = normalize_gpu(normal): a
 // plane's comes ready-made from the trace kernel's per-workgroup table, a sphere's is computed by the caller.  Every other
-// operation is the reference's, in its order.
+// operation is the reference's, in its order (s_unit: the workgroup's table of unit_table_fill).
 // od in: object colour / 255.0f (RayTracing.cu:144; the division is done once per object at upload,
 // the same IEEE operation on the same operands); out: shaded colour clamped to <= 255.
-__device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 od)
+__device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 od, const uint32_t* s_unit)
 {
     const V3 point = add(r.o, mulf(r.d, distance));
-    const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
+    const V3 viewDir = renormalize_gpu(mulf(r.d, -1.0f), s_unit); // (r.d is normalised; the squared length is r.a's operations again)
 
     V3 lightDir = sub(v3(1.0f, 50.0f, 0.0f), point);
     float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
@@ -250,7 +284,7 @@ __device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 o
     const float divDistance = rcp_cr(dist);
     lightDir = normalize_gpu(lightDir);
 
-    const V3 nv = normalize_gpu(viewDir);
+    const V3 nv = renormalize_gpu(viewDir, s_unit);
 
     const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
     // lightDiffuseColour (1,1,1) * intensity * 2000 * divDistance, per component

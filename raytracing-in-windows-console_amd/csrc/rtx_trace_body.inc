@@ -16,6 +16,7 @@
     // per plane: {n, num} {xlo, xhi, zlo, zhi} {od, gidx} {normalize_gpu(n), its shadingValue} {shade_nn()'s nn, 0}
     __shared__ float4 s_plane[kPlaneRow * kPlaneTable];
     __shared__ uint32_t s_digits[256];           // three decimal digits of 0..255, NUL padded
+    __shared__ uint32_t s_unit[kUnitEntries];    // rescale factors of nearly-unit squared lengths (rtx_unit.hpp)
     __shared__ __attribute__((aligned(4))) uint8_t s_ramp[68]; // the glyph ramp (RayTracing.h:97-115)
     __shared__ uint32_t s_wcnt[2][8];            // survivors per wave and half of the current step, double-buffered
     __shared__ float s_frustum[16];              // the macro tile's five plane normals
@@ -132,6 +133,7 @@
 
     // ---- per-workgroup tables (visible after the first barrier below)
     s_digits[tid] = digits_word(tid);
+    unit_table_fill(s_unit, tid);
     // the glyph ramp is requested now and written to LDS after the staging loop (first read: encode), so that no
     // wave waits for it here
     uint32_t ramp4 = 0u;
@@ -456,13 +458,13 @@
                     n0 = normalize_gpu(sub(add(ray.o, mulf(ray.d, b.t)), v3(wgeom.x, wgeom.y, wgeom.z)));
                     od = v3(wod.x, wod.y, wod.z);
                 }
-                normal = normalize_gpu(n0);                                         // RayTracing.cu:129
+                normal = renormalize_gpu(n0, s_unit);                                  // RayTracing.cu:129
                 shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // Dot(normal, (1,0,0)), :133
-                nn = normalize_gpu(normal);                                         // BlinnPhongShading, RayTracing.cu:52
+                nn = renormalize_gpu(normal, s_unit);                                  // BlinnPhongShading, RayTracing.cu:52
             }
             distance = b.t;
             if (MODE != RTX_K_RGB_NORMALS && MODE != RTX_K_SDL) {
-                colour = ABL(16u) ? mulf(od, 255.0f) : shade_nn(ray, distance, nn, od);
+                colour = ABL(16u) ? mulf(od, 255.0f) : shade_nn(ray, distance, nn, od, s_unit);
             }
         }
 
