@@ -3,6 +3,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_kernels.h"
+#include "rtx_mem.hpp"
 #include "rtx_plan.hpp"
 
 #include <hip/hip_runtime.h>
@@ -11,10 +12,10 @@
 #include <string>
 #include <vector>
 
-struct DeviceArray {
-    void* p = nullptr;
-    size_t cap = 0; // elements
-};
+using rtxmem::DeviceBuf;
+using rtxmem::Event;
+using rtxmem::PinnedBuf;
+using rtxmem::Stream;
 
 struct HostPlane {
     float4 a, b, c, od;
@@ -72,28 +73,28 @@ inline uint32_t float_to_bits(float f)
     return u;
 }
 
+// Every buffer, event and stream below is an owner (rtx_mem.hpp): it goes with the context, or with the set it is a member of.  Who
+// waits for what before outgrown storage is freed is said where it grows; DESIGN.md 3, "Ownership".
 struct rtx_ctx {
     int device = 0;
     rtx_group* group = nullptr;     // not null: this context is the root of a device group (rtx_group_create)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    Stream stream;                  // (declared first: destroyed after everything that was queued on it is gone)
+    Event ev_start, ev_stop;        // (with timing: rtx_timer_*)
     size_t max_w = 0, max_h = 0, capacity = 0;
-    uint8_t* d_frame = nullptr;
-    uint8_t* d_min = nullptr;       // minimise output (allocated on first use)
-    void* d_scan = nullptr;         // minimise scratch
-    size_t scan_bytes = 0;
-    uint32_t* d_words = nullptr;    // rtx_update's pixel words (W * H; allocated on first use)
-    size_t words_cap = 0;
+    DeviceBuf<uint8_t> d_frame;
+    DeviceBuf<uint8_t> d_min;       // minimise output (allocated on first use)
+    DeviceBuf<uint8_t> d_scan;      // minimise scratch (bytes)
+    DeviceBuf<uint32_t> d_words;    // rtx_update's pixel words (W * H; allocated on first use)
     int64_t opt_update_words = -1;  // -1 auto (on), 0 off: rtx_update traces pixel words and minimises from them
     int64_t opt_update_host_write = -1; // RTX_OPT_UPDATE_HOST_WRITE: -1 auto (frames up to 2^17 slots), 0 off, 1 on
     uint64_t stat_host_writes = 0;
-    uint64_t* h_pair = nullptr;     // two pinned words: a rank's stream length and failure word (rtx_update on a group, RTX_OPT_GROUP_UPDATE)
-    uint64_t* d_look = nullptr;     // rtx_min_fused's look-back tables (agg, grp: rtx_post.hip), zeroed when allocated
-    size_t look_blocks = 0;         // ... sized for this many blocks
+    PinnedBuf<uint64_t> h_pair;     // two pinned words: a rank's stream length and failure word (rtx_update on a group, RTX_OPT_GROUP_UPDATE)
+    DeviceBuf<uint64_t> d_look;     // rtx_min_fused's look-back tables (agg, grp: rtx_post.hip), zeroed when allocated
+    size_t look_blocks() const { return d_look.capacity() / 2; } // ... sized for this many blocks
     uint32_t look_epoch = 0;        // of the last fused launch (0: none yet; never used as a tag)
     int64_t opt_min_fused = -1;     // RTX_OPT_MINIMIZE_FUSED: -1 auto (on), 0 three launches, 1 on, 2 on with blocks that give up (tests)
     uint64_t stat_min_fallbacks = 0; // fused minimise launches that gave up and were redone as three launches
-    uint8_t* d_grey = nullptr;
+    DeviceBuf<uint8_t> d_grey;
     size_t dirty_hi = 0;            // bytes of d_frame that may be non-zero
 
     // scene: host staging for objects not yet uploaded + device SoA (the device copy is the truth
@@ -102,10 +103,11 @@ struct rtx_ctx {
     std::vector<HostPlane> h_planes;
     uint32_t ns = 0, np = 0, next_gidx = 0;
     uint32_t ns_uploaded = 0, np_uploaded = 0;
-    DeviceArray d_sph_geom, d_sph_color, d_sph_od, d_sph_motion, d_pl_a, d_pl_b, d_pl_c, d_pl_od;
+    DeviceBuf<float4> d_sph_geom, d_sph_color, d_sph_od, d_sph_motion, d_pl_a, d_pl_b, d_pl_c, d_pl_od;
     // the direction-sorted copy of the sphere array that staging reads (rtx_sort_scene): geometry by sorted position, sorted
     // position -> sphere index, sphere index -> sorted position; valid while sorted_gen == scene_gen
-    DeviceArray d_sorted_geom, d_sorted_od, d_sorted_idx, d_pos_of;
+    DeviceBuf<float4> d_sorted_geom, d_sorted_od;
+    DeviceBuf<uint32_t> d_sorted_idx, d_pos_of;
     std::vector<float4> h_centres;  // cx cy cz r as created, by sphere index (the sort's input; the device copy moves under physics)
     uint64_t sorted_gen = 0;
     int64_t opt_sorted_store = -1;  // -1 auto (on), 0 off
@@ -122,9 +124,8 @@ struct rtx_ctx {
     // set is never shared by frames in flight on different streams)
     struct CellScratch {
         hipStream_t stream = nullptr;
-        uint32_t* list = nullptr;                 // cells x capacity sphere indices
-        uint32_t* count = nullptr;                // two alternating buffers of one counter per cell
-        size_t list_words = 0, count_words = 0;
+        DeviceBuf<uint32_t> list;                 // cells x capacity sphere indices
+        DeviceBuf<uint32_t> count;                // two alternating buffers of one counter per cell
         uint32_t n_cells = 0;                     // the cell grid the counters were last zeroed for
         uint32_t flip = 0;                        // which counter buffer the next launch accumulates into
     };
@@ -137,11 +138,11 @@ struct rtx_ctx {
     struct TileOrder {
         hipStream_t stream = nullptr;
         uint64_t key[3] = {0, 0, 0}; // identifies the tile grid the buffers describe
-        uint32_t* cost = nullptr;
-        uint32_t* order = nullptr;   // two orders of `cap` tiles: the one in use and the one a balancing pass writes
-        float* factor = nullptr;     // per-tile correction of the estimate (rtx_balance_tiles)
-        hipEvent_t ev_rec = nullptr, ev_done = nullptr;
-        size_t cap = 0;              // tiles the buffers hold
+        DeviceBuf<uint32_t> cost;
+        DeviceBuf<uint32_t> order;   // two orders of `cap` tiles: the one in use and the one a balancing pass writes
+        DeviceBuf<float> factor;     // per-tile correction of the estimate (rtx_balance_tiles)
+        Event ev_rec, ev_done;
+        size_t cap() const { return factor.capacity(); } // tiles the buffers hold
         uint64_t last_use = 0;       // ctx->order_clock at the last launch (least recently used set is recycled)
         bool frozen = false;         // a recorded (HIP graph) launch reads the order in use: nothing is derived for this set any more
         uint32_t frozen_refs = 0;    // ... by this many live graphs (rtx_graph_destroy of the last one releases the set)
@@ -158,10 +159,8 @@ struct rtx_ctx {
     // cameras within the motion budget it was binned with (rtxplan::CellCachePolicy).  A set is (re)built on the render
     // stream that missed, or ahead of time on the side stream; readers on other streams wait for `ev_built` once.
     struct CellCacheSlot {
-        uint32_t* list = nullptr;
-        uint32_t* count = nullptr;
-        size_t list_words = 0, count_words = 0;
-        hipEvent_t ev_built = nullptr;
+        DeviceBuf<uint32_t> list, count;
+        Event ev_built;
         bool ever_built = false;
         bool built_on_aux = false;              // the last build ran on the side stream
         bool known_ready = false;               // the last build is known to have finished (hipEventQuery said so once)
@@ -171,21 +170,20 @@ struct rtx_ctx {
         // right after a stream's last launch reading it.  A rebuild waits for exactly these -- not for everything the
         // render streams have queued since, which would drain the frames in flight at every rebuild.
         std::vector<hipStream_t> readers;
-        std::vector<hipEvent_t> done;           // in use: done[0 .. n_done)
+        std::vector<Event> done;                // in use: done[0 .. n_done)
         size_t n_done = 0;
     };
     CellCacheSlot cell_cache[2];
     rtxplan::CellCachePolicy cell_policy;
     // capacity feedback: the binning passes keep the longest list needed in d_cell_max; it is copied to the pinned word
     // h_cell_max after a build (and now and then on the per-frame path) and read, unsynchronised, when the next launch is planned
-    uint32_t* d_cell_max = nullptr;
-    volatile uint32_t* h_cell_max = nullptr;
+    DeviceBuf<uint32_t> d_cell_max;
+    PinnedBuf<volatile uint32_t> h_cell_max;
     uint32_t cell_cap_floor = 0;                // capacity the lists of the current grid are planned with at least
     uint64_t cell_grid_id[3] = {0, 0, 0};       // the grid (and scene generation) the two words above belong to
     uint64_t per_frame_bins = 0;
     struct XcdOrder {                           // static dispatch order of a two-level grid: a cell's tiles share an XCD
-        uint32_t* p = nullptr;
-        size_t cap = 0;
+        DeviceBuf<uint32_t> p;
         uint64_t key[2] = {0, 0};               // (tile grid, cell shape)
         uint64_t last_use = 0;
     };
@@ -194,9 +192,9 @@ struct rtx_ctx {
     int64_t opt_xcd_order = -1;                 // -1 auto (on for two-level grids), 0 off
     // view-density feedback (rtxplan::ViewDensity): the longest candidate list the trace workgroups of an epoch (8 culling
     // launches) report, copied to the pinned word when the epoch ends and taken as an observation once that copy has landed
-    uint32_t* d_longest = nullptr;              // three words in rotation: the epoch being filled, the next one (zeroed), the one before (being copied)
-    volatile uint32_t* h_longest = nullptr;
-    hipEvent_t ev_longest = nullptr;
+    DeviceBuf<uint32_t> d_longest;              // three words in rotation: the epoch being filled, the next one (zeroed), the one before (being copied)
+    PinnedBuf<volatile uint32_t> h_longest;
+    Event ev_longest;
     bool longest_copy_pending = false;
     uint32_t longest_epoch = 0, longest_launches = 0;
     rtxplan::ViewDensity view_density;
@@ -204,7 +202,7 @@ struct rtx_ctx {
     uint64_t stat_density_switches = 0;
     hipStream_t recent_streams[16] = {nullptr}; // the render streams of the last two-level launches
     unsigned recent_pos = 0, render_streams_seen = 0;
-    hipEvent_t ev_physics = nullptr;            // orders a build on the side stream after the physics steps queued so far
+    Event ev_physics;                           // orders a build on the side stream after the physics steps queued so far
     bool ns_moved_since_build = false;          // rtx_update_objects ran since the last such ordering
     uint64_t scene_gen = 1;                     // bumped by every scene edit: object counts / array addresses (recorded graphs belong to one)
     uint64_t lists_gen = 1;                     // ... and by the first physics step after one: what cell lists belong to
@@ -212,7 +210,7 @@ struct rtx_ctx {
     uint64_t stat_order_passes = 0;
     uint64_t stat_cell_builds = 0, stat_cell_prefetches = 0, stat_cell_hits = 0, stat_cell_per_frame = 0;
 
-    hipStream_t aux_stream = nullptr; // the balancing passes' stream (created with the first pass)
+    Stream aux_stream;                // the balancing passes' stream (created with the first pass)
     double scene_drift = 0.0;        // how far any sphere can have moved since the context was created (rtx_update_objects:
                                      // |dt| x the largest |speed x mover|; rtx_scene_set_spheres: the largest move; other scene edits and removals add 1e3):
                                      // dispatch orders go stale with it
@@ -224,10 +222,10 @@ struct rtx_ctx {
     int n_cu = 0;                   // compute units of the device
 
     // events of rtx_submit_slabs' fork/join: one for `after`, one per distinct render stream seen
-    hipEvent_t ev_fork = nullptr;
+    Event ev_fork;
     struct JoinEvent {
         hipStream_t stream = nullptr;
-        hipEvent_t ev = nullptr;
+        Event ev;
     };
     std::vector<JoinEvent> join_events;
 
@@ -235,14 +233,12 @@ struct rtx_ctx {
     // buffer, scan scratch and events; the copy of slot k's stream to the host runs on copy_stream while slot
     // k^1 is being traced
     struct UpdateSlot {
-        uint8_t* d_frame = nullptr;  // (the record form only)
-        uint32_t* d_words = nullptr; // (the word form only)
-        size_t words_cap = 0;
-        uint8_t* d_min = nullptr;
-        void* d_scan = nullptr;
-        size_t scan_bytes = 0;
-        uint64_t* h_total = nullptr; // pinned
-        hipEvent_t ev_ready = nullptr, ev_copied = nullptr;
+        DeviceBuf<uint8_t> d_frame;  // (the record form only)
+        DeviceBuf<uint32_t> d_words; // (the word form only)
+        DeviceBuf<uint8_t> d_min;
+        DeviceBuf<uint8_t> d_scan;   // (bytes)
+        PinnedBuf<uint64_t> h_total;
+        Event ev_ready, ev_copied;
         size_t bytes = 0;
         bool busy = false;
         // a small frame whose Minimize launch writes the caller's buffer itself (RTX_OPT_UPDATE_HOST_WRITE): nothing was waited for in
@@ -251,14 +247,13 @@ struct rtx_ctx {
         MinRun run; // the Minimize launch of the slot's frame
     };
     UpdateSlot upd[2];
-    hipStream_t copy_stream = nullptr;
+    Stream copy_stream;
     unsigned upd_next = 0;
 
     // light and hard shadows (RTX_OPT_SHADOWS, rtx_scene_set_light): with shadows off and the reference's light every launch is
     // today's one-pass trace; otherwise rtx_render_rows traces the closest hit into a hit buffer (8 bytes per pixel) and
     // rtx_shadow_shade shades from it.  One hit buffer per render stream (launches on one stream are ordered; frames on two
-    // streams never share one), allocated at the first two-pass launch on that stream, for at most kMaxHitStreams streams; an
-    // outgrown buffer is freed, or kept until the context is destroyed if a recorded graph may still read it.
+    // streams never share one), for at most kMaxHitStreams streams.
     // the lights (rtx_scene_set_lights; rtx_scene_set_light sets a set of one).  A set of one launches what it always has; two or
     // more (or RTX_OPT_LIGHTS_CHECK 1) shade with rtx_lights_shade / rtx_lights_reflect_shade, which get the set by value.
     rtx_light lights[RTX_MAX_LIGHTS] = {rtx_reference_light()};
@@ -267,16 +262,15 @@ struct rtx_ctx {
     int64_t opt_shadows = 0;
     int64_t opt_shadow_check = 0;
     uint64_t stat_shadow_frames = 0;
-    uint32_t* d_shadow_longest = nullptr; // the longest occluder list of the last two-pass launch (one word)
+    DeviceBuf<uint32_t> d_shadow_longest; // the longest occluder list of the last two-pass launch (one word)
     static constexpr int kMaxHitStreams = 64;
     struct HitScratch {
         hipStream_t stream = nullptr;
-        void* p = nullptr;
-        size_t bytes = 0;
+        DeviceBuf<uint8_t> p;
         bool recorded = false; // a launch recorded into a graph reads this buffer
     };
     std::vector<HitScratch> hit_scratch;
-    std::vector<void*> hit_retired;
+    std::vector<DeviceBuf<uint8_t>> hit_retired; // outgrown buffers that a recorded graph may still read
 
     // one-bounce mirrors (rtx_scene_set_reflectivity): k by creation index, and how many objects have k > 0 (the path is taken
     // while that is not 0, or under RTX_OPT_REFLECT_CHECK 2).  Then rtx_render_rows traces the closest hits, rtx_reflect_hit the
@@ -287,22 +281,22 @@ struct rtx_ctx {
     uint32_t n_reflective = 0;
     bool refl_dirty = true;
     uint64_t refl_gen = 0;
-    DeviceArray d_refl_sph, d_refl_sorted, d_refl_pl;
+    DeviceBuf<float> d_refl_sph, d_refl_sorted, d_refl_pl;
     std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
     int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;
-    uint32_t* d_reflect_longest = nullptr; // the longest candidate list of the last launch set on the path (one word)
+    DeviceBuf<uint32_t> d_reflect_longest; // the longest candidate list of the last launch set on the path (one word)
     // mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): at depth 1 with the check option 0 every launch is the one-bounce path's;
     // otherwise rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade folds the chain, through 8 (depth + 1)
     // bytes per pixel of the stream's hit buffer.  The depth travels in the kernel arguments.
     int64_t opt_reflect_depth = 1;
     int64_t opt_reflect_depth_check = 0;
-    uint32_t* d_reflect_rays = nullptr; // secondary rays per level of the last launch set on the chain kernels (RTX_MAX_REFLECT_DEPTH words)
+    DeviceBuf<uint32_t> d_reflect_rays; // secondary rays per level of the last launch set on the chain kernels (RTX_MAX_REFLECT_DEPTH words)
     bool reflect_rays_valid = false;    // the launch set queued last took the chain kernels (else RTX_STAT_REFLECT_RAYS reads 0)
     // shadows seen in mirrors (RTX_OPT_REFLECT_SHADOWS): in effect while RTX_OPT_SHADOWS is 1 and the mirror path is taken; then the
     // chain kernels at any depth, rtx_chain_shadow between them, and 4 more bytes per pixel of the hit buffer (the dark words)
     int64_t opt_reflect_shadows = 0;
-    uint32_t* d_reflect_shadow_points = nullptr; // hit points tested per level by the last launch set (RTX_MAX_REFLECT_DEPTH words)
+    DeviceBuf<uint32_t> d_reflect_shadow_points; // hit points tested per level by the last launch set (RTX_MAX_REFLECT_DEPTH words)
     bool reflect_shadow_points_valid = false;    // the launch set queued last ran rtx_chain_shadow (else the counters read 0)
 
     // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
@@ -313,17 +307,19 @@ struct rtx_ctx {
         bool dirty = true;            // the scene changed since the last build
         bool brute = false;           // the last build gave up (more than kLargeCap large spheres): queries test every sphere
         uint32_t n_cells = 0, n_large = 0, pairs = 0;
-        DeviceArray cell_count, cell_fill, is_large, pair_tmp, list_geom, list_gidx; // (elements: words / bytes / float4)
-        uint32_t* d_large = nullptr;  // kLargeCap sphere indices
-        uint32_t* d_words = nullptr;  // [0] pairs, [1] large spheres, [2] fallback rays of the last call, [4..10] bounds
-        void* d_ray = nullptr;        // rtx_pick's ray and hit (48 bytes)
-        hipEvent_t ev_built = nullptr, ev_done = nullptr;
+        DeviceBuf<uint32_t> cell_count, cell_fill, pair_tmp, list_gidx;
+        DeviceBuf<uint8_t> is_large;
+        DeviceBuf<float4> list_geom;
+        DeviceBuf<uint32_t> d_large;  // kLargeCap sphere indices
+        DeviceBuf<uint32_t> d_words;  // [0] pairs, [1] large spheres, [2] fallback rays of the last call, [4..10] bounds
+        DeviceBuf<uint8_t> d_ray;     // rtx_pick's ray and hit (48 bytes)
+        Event ev_built, ev_done;
         bool query_pending = false;   // ev_done has been recorded since the last build
         // render launches that read the lists (RTX_OPT_SHADOW_GRID): an event per render stream, recorded behind the stream's last
         // such launch; a rebuild waits for those marked pending
         struct Reader {
             hipStream_t stream = nullptr;
-            hipEvent_t ev = nullptr;
+            Event ev;
             bool pending = false;
         };
         std::vector<Reader> readers;
@@ -338,40 +334,37 @@ struct rtx_ctx {
     // rtx_grid_*shade family shades from its words: 4 more bytes per pixel of the stream's hit buffer
     int64_t opt_shadow_grid = 0;
     uint64_t stat_shadow_grid_frames = 0;
-    uint32_t* d_shadow_grid_fallback = nullptr; // segments of the last launch set on the path that tested every sphere (one word)
+    DeviceBuf<uint32_t> d_shadow_grid_fallback; // segments of the last launch set on the path that tested every sphere (one word)
 
     // objects edited in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane; rtx_post.hip): rows that
-    // come from the host, or from another member of a device group, are staged in d_edit_rows (floats; grown by doubling);
+    // come from the host, or from another member of a device group, are staged in d_edit_rows (floats);
     // rtx_write_spheres leaves its two result words in d_edit_result, which the call copies to the pinned pair and waits for
-    DeviceArray d_edit_rows;
-    uint32_t* d_edit_result = nullptr;
-    uint32_t* h_edit_result = nullptr;
-    hipEvent_t ev_edit = nullptr;       // orders a device-form edit after what the caller's stream holds
+    DeviceBuf<float> d_edit_rows;
+    DeviceBuf<uint32_t> d_edit_result;
+    PinnedBuf<uint32_t> h_edit_result;
+    Event ev_edit;                      // orders a device-form edit after what the caller's stream holds
     uint64_t stat_scene_edits = 0;      // edit calls that changed something
     uint32_t stat_edit_move_bits = 0;   // RTX_STAT_SCENE_EDIT_MOVE
 
     // objects removed in place (rtx_scene_remove_objects, rtx_scene_remove_marked_device; rtx_post.hip): rtx_compact_objects moves the
-    // survivors into the spare set of the eight scene arrays (sphere geom / color / od / motion, plane a / b / c / od: allocated at the
-    // first removal with the live array's capacity, regrown when the live one has grown), which is then swapped with the live set;
-    // the removed indices travel in d_remove_lists (words; grown by doubling), a device form's marks arrive in the pinned h_remove_marks
-    DeviceArray d_spare[8];
-    DeviceArray d_remove_lists;
-    uint8_t* h_remove_marks = nullptr;
-    size_t remove_marks_cap = 0;
+    // survivors into the spare set of the eight scene arrays (sphere geom / color / od / motion, plane a / b / c / od: as large as the
+    // live ones), which is then swapped with the live set; the removed indices travel in d_remove_lists (words), a device form's marks
+    // arrive in the pinned h_remove_marks
+    DeviceBuf<float4> d_spare[8];
+    DeviceBuf<uint32_t> d_remove_lists;
+    PinnedBuf<uint8_t> h_remove_marks;
     uint64_t stat_scene_removed = 0;    // RTX_STAT_SCENE_REMOVED
 
     // delta frames (rtx_delta_words, rtx_update_delta; rtx_post.hip): the previous and the current frame's pixel words in two
     // buffers that swap roles (delta_at: the one the last successful call handed out), the delta's own output buffer (sized by
     // rtx_delta_bound at first use) and the two counters of the last delta launch (changed cells, runs)
-    uint32_t* d_delta_words[2] = {nullptr, nullptr};
-    size_t delta_words_cap[2] = {0, 0};
+    DeviceBuf<uint32_t> d_delta_words[2];
     unsigned delta_at = 0;
     bool delta_valid = false;           // delta_words[delta_at] is the frame the consumer shows: W, H and mode as below
     size_t delta_w = 0, delta_h = 0;
     int delta_mode = -1;
-    uint8_t* d_delta_out = nullptr;
-    size_t delta_out_cap = 0;
-    unsigned long long* d_delta_counts = nullptr;
+    DeviceBuf<uint8_t> d_delta_out;
+    DeviceBuf<unsigned long long> d_delta_counts;
     bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
     uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
 
@@ -397,7 +390,6 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
 // ... and its first half alone: uploads pending appends and allocates what the removal needs (the second set of arrays, the list
 // buffer); moves nothing.  A group prepares every member before any of them compacts.
 int rtx_remove_prepare(rtx_ctx* ctx, const std::vector<uint32_t>& ascending);
-void rtx_query_release(rtx_ctx* ctx);                    // rtx_query.cpp: frees the grid (rtx_destroy)
 // rtx_query.cpp: the world grid for a launch on `stream` that reads its lists -- the one grid object the queries use, brought up to date
 // if the scene changed since its last build (a build blocks, as a query's does, and counts in RTX_STAT_QUERY_GRID_BUILDS); `stream` is
 // ordered after the build.  Not inside a graph capture.  Then rtx_grid_read, behind the launches: a later rebuild waits for them.

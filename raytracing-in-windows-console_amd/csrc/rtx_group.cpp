@@ -113,12 +113,10 @@ struct rtx_group {
     std::vector<int> device;
     bool distinct = true;         // no device appears twice in the list
     std::vector<char> direct;     // per rank: its device and the root's address each other's memory (same device, or peer access enabled) and strided copies between them work
-    std::vector<hipEvent_t> ev_done; // per rank, on its device: its slab has arrived on the root (peer copies)
-    hipEvent_t ev_free = nullptr;    // root's device: the destination may be overwritten
-    uint32_t* d_words = nullptr;     // root's device: the frame as compact words (W * H)
-    size_t words_cap = 0;
-    uint8_t* d_root_slab = nullptr;  // root's device: its own slab, only when the root's rows travel through RCCL too (RTX_EXCHANGE_RCCL_ALL)
-    size_t root_slab_cap = 0;
+    std::vector<Event> ev_done;      // per rank, on its device: its slab has arrived on the root (peer copies)
+    Event ev_free;                   // root's device: the destination may be overwritten
+    DeviceBuf<uint32_t> d_words;     // root's device: the frame as compact words (W * H)
+    DeviceBuf<uint8_t> d_root_slab;  // root's device: its own slab, only when the root's rows travel through RCCL too (RTX_EXCHANGE_RCCL_ALL)
     int64_t opt_exchange = RTX_EXCHANGE_AUTO, opt_wire = RTX_WIRE_AUTO;
     std::vector<ncclComm_t> comms;   // RCCL communicators, one per rank (empty: not initialised)
     bool rccl_failed = false;        // initialisation was tried and failed: peer copies from then on
@@ -334,7 +332,7 @@ int gather(rtx_ctx* root, rtx_group* g, size_t m, const rtx_params* params, int 
             void* slabs[rtxplan::kMaxChunk];
             void* streams[rtxplan::kMaxChunk];
             for (size_t i = 0; i < m; i++) {
-                slabs[i] = mem->d_frame + i * bytes;
+                slabs[i] = mem->d_frame.get() + i * bytes;
                 streams[i] = mem->stream;
             }
             const int rc2 = rtx_submit_slabs(mem, m, params, mode, (size_t)s.row0, (size_t)s.rows, slabs, (size_t)s.row0, streams, nullptr, slab_flags);
@@ -347,14 +345,14 @@ int gather(rtx_ctx* root, rtx_group* g, size_t m, const rtx_params* params, int 
             if (strided) {
                 // the chunk's slabs lie back to back here and a frame apart on the root: one strided copy.  A runtime that
                 // refuses the strided form between two devices gets the plain copies below, from then on.
-                copied = hipMemcpy2DAsync((uint8_t*)dests[0] + at, frame_bytes, mem->d_frame, bytes, bytes, m, hipMemcpyDeviceToDevice, mem->stream) == hipSuccess;
+                copied = hipMemcpy2DAsync((uint8_t*)dests[0] + at, frame_bytes, mem->d_frame.get(), bytes, bytes, m, hipMemcpyDeviceToDevice, mem->stream) == hipSuccess;
                 if (!copied) {
                     (void)hipGetLastError();
                     *direct_flag = 0;
                 }
             }
             for (size_t i = 0; i < m && !copied; i++) {
-                RTX_HIP(mem, hipMemcpyPeerAsync((uint8_t*)dests[i] + at, root_device, mem->d_frame + i * bytes, mem->device, bytes, mem->stream));
+                RTX_HIP(mem, hipMemcpyPeerAsync((uint8_t*)dests[i] + at, root_device, mem->d_frame.get() + i * bytes, mem->device, bytes, mem->stream));
             }
             RTX_HIP(mem, hipEventRecord(ev_done, mem->stream));
             return RTX_OK;
@@ -378,7 +376,7 @@ int gather(rtx_ctx* root, rtx_group* g, size_t m, const rtx_params* params, int 
             if (s.rows == 0) continue;
             rtx_ctx* mem = g->member[(size_t)r];
             const size_t bytes = (size_t)(s.rows * W * S), at = (size_t)(s.row0 * W * S);
-            const uint8_t* src = r == 0 ? g->d_root_slab : mem->d_frame;
+            const uint8_t* src = r == 0 ? g->d_root_slab.get() : mem->d_frame.get();
             for (size_t i = 0; i < m && nrc == ncclSuccess; i++) {
                 nrc = api->Send(src + i * bytes, bytes, ncclChar, 0, g->comms[(size_t)r], mem->stream);
                 if (nrc == ncclSuccess) nrc = api->Recv((uint8_t*)dests[i] + at, bytes, ncclChar, r, g->comms[0], root->stream);
@@ -416,16 +414,9 @@ int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, boo
     if (root_through_rccl) {
         // (before any job is posted: nothing in gather() returns while a rank's submission thread is at work)
         const size_t need = (size_t)(rtxplan::slab_of(H, 0, g->n).rows * W * S);
-        if (g->root_slab_cap < need) {
+        if (g->d_root_slab.capacity() < need) {
             RTX_HIP(root, hipSetDevice(root->device));
-            if (g->d_root_slab) {
-                RTX_HIP(root, hipStreamSynchronize(root->stream));
-                hipFree(g->d_root_slab);
-            }
-            g->d_root_slab = nullptr;
-            g->root_slab_cap = 0;
-            if (hipMalloc((void**)&g->d_root_slab, need) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the root's slab");
-            g->root_slab_cap = need;
+            if (g->d_root_slab.reserve(need, rtxmem::after_stream(root->stream)) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the root's slab");
         }
     }
     if (slabs_per_buffer(g, W, H, S) == 0) return rtx_fail(root, RTX_ERR_TOO_LARGE, "frame larger than the group was created for");
@@ -433,7 +424,7 @@ int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, boo
     return gather(root, g, 1, p, mode, compact, &dest, use_rccl, root_through_rccl, [&](uint64_t rows0) -> int {
         if (root_through_rccl) {
             // test form (one-GPU box: RCCL at N = 1): the root's rows too are traced into a slab and travel through the exchange
-            const int rc = rows0 ? rtx_render_rows(root, p, mode, 0, (size_t)rows0, g->d_root_slab, 0, root->stream, wire_flags(compact)) : RTX_OK;
+            const int rc = rows0 ? rtx_render_rows(root, p, mode, 0, (size_t)rows0, g->d_root_slab.get(), 0, root->stream, wire_flags(compact)) : RTX_OK;
             return (rc == RTX_OK && own_frame) ? rtx_frame_zero_semantics(root, mode, W, H, 0u) : rc;
         }
         if (own_frame) return rtx_render_rows(root, p, mode, 0, (size_t)rows0, nullptr, 0, root->stream, RTX_RENDER_DEFAULT);
@@ -444,16 +435,9 @@ int gather_frame(rtx_ctx* root, rtx_group* g, const rtx_params* p, int mode, boo
 int ensure_words(rtx_ctx* root, rtx_group* g, uint64_t W, uint64_t H)
 {
     const size_t need = (size_t)(W * H);
-    if (g->words_cap >= need) return RTX_OK;
+    if (g->d_words.capacity() >= need) return RTX_OK;
     RTX_HIP(root, hipSetDevice(root->device));
-    if (g->d_words) {
-        RTX_HIP(root, hipDeviceSynchronize());
-        hipFree(g->d_words);
-    }
-    g->d_words = nullptr;
-    g->words_cap = 0;
-    if (hipMalloc((void**)&g->d_words, need * sizeof(uint32_t)) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the group's word buffer");
-    g->words_cap = need;
+    if (g->d_words.reserve(need, rtxmem::after_device()) != hipSuccess) return rtx_fail(root, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the group's word buffer");
     return RTX_OK;
 }
 
@@ -489,15 +473,10 @@ void destroy(rtx_group* g)
         if ((size_t)r < g->member.size() && g->member[(size_t)r]) rtx_destroy(g->member[(size_t)r]);
     }
     for (size_t r = 0; r < g->ev_done.size(); r++) {
-        if (g->ev_done[r]) {
-            hipSetDevice(g->device[r]);
-            hipEventDestroy(g->ev_done[r]);
-        }
+        hipSetDevice(g->device[r]); // (an event goes on the device it was created on)
+        g->ev_done[r].release();
     }
-    if (!g->device.empty()) hipSetDevice(g->device[0]);
-    if (g->ev_free) hipEventDestroy(g->ev_free);
-    if (g->d_words) hipFree(g->d_words);
-    if (g->d_root_slab) hipFree(g->d_root_slab);
+    if (!g->device.empty()) hipSetDevice(g->device[0]); // ev_free and the buffers are the root's device's
     delete g;
 }
 
@@ -618,14 +597,14 @@ int render_frame(rtx_ctx* root, const rtx_params* p, int mode, void* d_out, unsi
     };
     if (!wire_is_compact(g)) {
         if ((rc = zero_tail()) != RTX_OK) return rc;
-        return gather_frame(root, g, p, mode, false, own ? root->d_frame : (uint8_t*)d_out, own);
+        return gather_frame(root, g, p, mode, false, own ? root->d_frame.get() : (uint8_t*)d_out, own);
     }
     // compact words into the group's buffer, then the records (rtx_expand: the same record_words<MODE> the trace kernel uses)
     if ((rc = ensure_words(root, g, W, H)) != RTX_OK) return rc;
-    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false)) != RTX_OK) return rc;
+    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words.get(), false)) != RTX_OK) return rc;
     if ((rc = own ? rtx_frame_zero_semantics(root, mode, W, H, 0u) : zero_tail()) != RTX_OK) return rc;
     const rtx_segment seg = {0u, 0u, W * H};
-    return rtx_expand(root, mode, g->d_words, own ? (void*)root->d_frame : d_out, &seg, 1, root->stream);
+    return rtx_expand(root, mode, g->d_words.get(), own ? (void*)root->d_frame.get() : d_out, &seg, 1, root->stream);
 }
 
 namespace {
@@ -687,7 +666,7 @@ int render_frames(rtx_ctx* root, size_t n, const rtx_params* params, int mode, v
             if (compact && (rc = ensure_words(root, g, W, H * m)) != RTX_OK) return rc;
             for (size_t i = 0; i < m; i++) {
                 // where frame i of the chunk is assembled: its words in the group's buffer, or its records in the caller's
-                dests[i] = compact ? (void*)(g->d_words + i * W * H) : d_outs[first + i];
+                dests[i] = compact ? (void*)(g->d_words.get() + i * W * H) : d_outs[first + i];
                 on_root[i] = root->stream;
             }
             rc = gather(root, g, m, &params[first], mode, compact, dests, use_rccl, false, [&](uint64_t rows0) -> int {
@@ -696,7 +675,7 @@ int render_frames(rtx_ctx* root, size_t n, const rtx_params* params, int mode, v
             if (rc != RTX_OK) return rc;
             for (size_t i = 0; compact && i < m; i++) {
                 const rtx_segment seg = {0u, 0u, W * H};
-                if ((rc = rtx_expand(root, mode, g->d_words + i * W * H, d_outs[first + i], &seg, 1, root->stream)) != RTX_OK) return rc;
+                if ((rc = rtx_expand(root, mode, g->d_words.get() + i * W * H, d_outs[first + i], &seg, 1, root->stream)) != RTX_OK) return rc;
             }
         }
     }
@@ -766,8 +745,8 @@ int render_words(rtx_ctx* root, const rtx_params* p, int mode, const uint32_t** 
     if (rc != RTX_OK) return rc;
     if (mode == RTX_SDL) return rtx_fail(root, RTX_ERR_INVALID_MODE, "no pixel words in RTX_SDL");
     if ((rc = ensure_words(root, g, p->x, p->y)) != RTX_OK) return rc;
-    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words, false)) != RTX_OK) return rc;
-    *d_words = g->d_words;
+    if ((rc = gather_frame(root, g, p, mode, true, (uint8_t*)g->d_words.get(), false)) != RTX_OK) return rc;
+    *d_words = g->d_words.get();
     return RTX_OK;
 }
 
@@ -788,18 +767,18 @@ int rtx_group_create(int ndev, const int* devices, size_t max_w, size_t max_h, r
         for (int q = 0; q < r; q++) g->distinct = g->distinct && g->device[(size_t)q] != g->device[(size_t)r];
     }
     g->member.assign((size_t)ndev, nullptr);
-    g->ev_done.assign((size_t)ndev, nullptr);
+    g->ev_done.resize((size_t)ndev);
     rtx_ctx* root = nullptr;
     int rc = RTX_OK;
     for (int r = 0; r < ndev && rc == RTX_OK; r++) {
         rc = rtx_create(g->device[(size_t)r], max_w, max_h, &g->member[(size_t)r]);
-        if (rc == RTX_OK && hipEventCreateWithFlags(&g->ev_done[(size_t)r], hipEventDisableTiming) != hipSuccess) {
+        if (rc == RTX_OK && g->ev_done[(size_t)r].ensure() != hipSuccess) {
             rc = rtx_fail(nullptr, RTX_ERR_HIP, "rtx_group_create: hipEventCreate failed");
         }
     }
     root = g->member[0];
     if (rc == RTX_OK) {
-        if (hipSetDevice(g->device[0]) != hipSuccess || hipEventCreateWithFlags(&g->ev_free, hipEventDisableTiming) != hipSuccess) {
+        if (hipSetDevice(g->device[0]) != hipSuccess || g->ev_free.ensure() != hipSuccess) {
             rc = rtx_fail(nullptr, RTX_ERR_HIP, "rtx_group_create: hipEventCreate failed");
         }
     }

@@ -25,24 +25,13 @@ size_t min_scan_bytes(uint64_t n_slots) { return (size_t)min_blocks(n_slots) * (
 
 int ensure_min_buffers(rtx_ctx* ctx, uint64_t n_slots, bool need_out)
 {
-    const size_t need = min_scan_bytes(n_slots);
-    if (ctx->scan_bytes < need) {
-        if (ctx->d_scan) {
-            hipFree(ctx->d_scan);
-            ctx->d_scan = nullptr;
-            ctx->scan_bytes = 0;
-        }
-        if (hipMalloc(&ctx->d_scan, need) != hipSuccess) {
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the minimise scratch");
-        }
-        ctx->scan_bytes = need;
-
+    // (every minimise launch that used the old scratch has been waited for by the call that queued it)
+    if (ctx->d_scan.reserve(min_scan_bytes(n_slots), rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the minimise scratch");
     }
-    if (need_out && !ctx->d_min) {
-        // m_minimizedResultArray is as large as the frame (RayTracingManager.cu:66)
-        if (hipMalloc((void**)&ctx->d_min, ctx->capacity) != hipSuccess) {
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the minimise buffer");
-        }
+    // m_minimizedResultArray is as large as the frame (RayTracingManager.cu:66)
+    if (need_out && !ctx->d_min.get() && ctx->d_min.reserve(ctx->capacity, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the minimise buffer");
     }
     return RTX_OK;
 }
@@ -115,22 +104,12 @@ int launch_minimize_chain(rtx_ctx* ctx, const MinRun& run)
 // epoch afterwards.  One set per context: every minimise launch runs on the context's stream, one after the other.
 int ensure_look_tables(rtx_ctx* ctx, size_t n_blocks)
 {
-    if (ctx->look_blocks >= n_blocks && ctx->d_look) return RTX_OK;
-    if (ctx->d_look) {
-        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(ctx->d_look);
-        ctx->d_look = nullptr;
-        ctx->look_blocks = 0;
-    }
-    size_t cap = 4096;
-    while (cap < n_blocks) cap *= 2;
-    const size_t bytes = 2 * cap * sizeof(uint64_t); // agg[cap], then 64 replicas of grp[cap / 64]
-    if (hipMalloc((void**)&ctx->d_look, bytes) != hipSuccess) {
-        ctx->d_look = nullptr;
+    if (ctx->look_blocks() >= n_blocks) return RTX_OK;
+    // agg[cap], then 64 replicas of grp[cap / 64]: 2 cap words, cap doubled from 4096
+    if (ctx->d_look.reserve_doubling(2 * n_blocks, 2 * 4096, rtxmem::after_stream(ctx->stream)) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the minimise look-back tables");
     }
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_look, 0, bytes, ctx->stream));
-    ctx->look_blocks = cap;
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_look.get(), 0, ctx->d_look.capacity() * sizeof(uint64_t), ctx->stream));
     return RTX_OK;
 }
 
@@ -149,14 +128,14 @@ int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_o
     if (rc != RTX_OK) return rc;
     if (++ctx->look_epoch == 0u) {
         // the tags have wrapped: forget every entry
-        RTX_HIP(ctx, hipMemsetAsync(ctx->d_look, 0, 2 * ctx->look_blocks * sizeof(uint64_t), ctx->stream));
+        RTX_HIP(ctx, hipMemsetAsync(ctx->d_look.get(), 0, 2 * ctx->look_blocks() * sizeof(uint64_t), ctx->stream));
         ctx->look_epoch = 1u;
     }
     const uint32_t epoch = ctx->look_epoch;
     uint64_t* total = pair ? pair : (uint64_t*)d_scan;
-    uint64_t* agg = ctx->d_look;
-    uint64_t* grp = agg + ctx->look_blocks;
-    const uint32_t ng = (uint32_t)(ctx->look_blocks / rtx::kLookGroup);
+    uint64_t* agg = ctx->d_look.get();
+    uint64_t* grp = agg + ctx->look_blocks();
+    const uint32_t ng = (uint32_t)(ctx->look_blocks() / rtx::kLookGroup);
     const uint32_t polls = ctx->opt_min_fused == 2 ? 0u : rtx::kLookPolls;
     if (in.counts) RTX_HIP(ctx, hipMemsetAsync(in.counts, 0, 2 * sizeof(unsigned long long), ctx->stream));
     rc = with_source(ctx, in, [&](auto src) {
@@ -190,9 +169,9 @@ int minimize_and_wait(rtx_ctx* ctx, const MinInput& in, void* d_out, size_t* out
 {
     int rc = ensure_min_buffers(ctx, (uint64_t)in.w * in.h, d_out == nullptr);
     if (rc != RTX_OK) return rc;
-    if (!d_out) d_out = ctx->d_min;
+    if (!d_out) d_out = ctx->d_min.get();
     MinRun run;
-    if ((rc = launch_minimize(ctx, ctx->d_scan, in, (uint8_t*)d_out, &run)) != RTX_OK) return rc;
+    if ((rc = launch_minimize(ctx, ctx->d_scan.get(), in, (uint8_t*)d_out, &run)) != RTX_OK) return rc;
     uint64_t got[2] = {0, 0}, total = 0;
     RTX_HIP(ctx, hipMemcpyAsync(got, run.d_total, sizeof got, hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -205,29 +184,21 @@ int minimize_and_wait(rtx_ctx* ctx, const MinInput& in, void* d_out, size_t* out
 // the record form (RTX_OPT_UPDATE_WORDS = 0) or the mode has no words (RTX_SDL).
 bool update_from_words(const rtx_ctx* ctx, int mode) { return mode != RTX_SDL && ctx->opt_update_words != 0; }
 
-int ensure_words_buffer(rtx_ctx* ctx, uint32_t** buf, size_t* cap, size_t need)
+int ensure_words_buffer(rtx_ctx* ctx, DeviceBuf<uint32_t>& buf, size_t need)
 {
-    if (*cap >= need) return RTX_OK;
-    if (*buf) {
-        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        hipFree(*buf);
-    }
-    *buf = nullptr;
-    *cap = 0;
-    if (hipMalloc((void**)buf, need * sizeof(uint32_t)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the pixel-word buffer");
-    *cap = need;
+    if (buf.reserve(need, rtxmem::after_stream(ctx->stream)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the pixel-word buffer");
     return RTX_OK;
 }
 
 // The frame of `p` as W*H pixel words in *d_words, complete in stream order on the context's stream: sharded over the
 // group's devices and gathered, or one launch into `own` (grown as needed).
-int trace_words(rtx_ctx* ctx, const rtx_params* p, int mode, uint32_t** own, size_t* own_cap, const uint32_t** d_words)
+int trace_words(rtx_ctx* ctx, const rtx_params* p, int mode, DeviceBuf<uint32_t>& own, const uint32_t** d_words)
 {
     if (ctx->group) return rtxgroup::render_words(ctx, p, mode, d_words);
-    int rc = ensure_words_buffer(ctx, own, own_cap, (size_t)p->x * (size_t)p->y);
+    int rc = ensure_words_buffer(ctx, own, (size_t)p->x * (size_t)p->y);
     if (rc != RTX_OK) return rc;
-    if ((rc = rtx_render_rows(ctx, p, mode, 0, (size_t)p->y, *own, 0, ctx->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc;
-    *d_words = *own;
+    if ((rc = rtx_render_rows(ctx, p, mode, 0, (size_t)p->y, own.get(), 0, ctx->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc;
+    *d_words = own.get();
     return RTX_OK;
 }
 
@@ -246,27 +217,24 @@ int update_host_write(rtx_ctx* ctx, const rtx_params* p, int mode, void* host_ou
         (void)hipGetLastError(); // pageable memory: the usual way
         return RTX_OK;
     }
-    if (!ctx->h_pair) {
-        if (hipHostMalloc((void**)&ctx->h_pair, 2 * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
-            ctx->h_pair = nullptr;
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for the stream's length");
-        }
+    if (ctx->h_pair.reserve(2, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for the stream's length");
     }
     void* d_pair = nullptr;
-    RTX_HIP(ctx, hipHostGetDevicePointer(&d_pair, ctx->h_pair, 0));
+    RTX_HIP(ctx, hipHostGetDevicePointer(&d_pair, ctx->h_pair.get(), 0));
     const size_t W = (size_t)p->x, H = (size_t)p->y;
     const uint32_t* d_words = nullptr;
-    int rc = trace_words(ctx, p, mode, &ctx->d_words, &ctx->words_cap, &d_words);
+    int rc = trace_words(ctx, p, mode, ctx->d_words, &d_words);
     if (rc != RTX_OK) return rc;
     if ((rc = ensure_min_buffers(ctx, (uint64_t)W * H, false)) != RTX_OK) return rc;
-    ctx->h_pair[0] = 0;
-    ctx->h_pair[1] = 0;
+    ctx->h_pair.get()[0] = 0;
+    ctx->h_pair.get()[1] = 0;
     MinRun run;
-    if ((rc = launch_minimize(ctx, ctx->d_scan, words_input(mode, W, H, d_words), (uint8_t*)d_host, &run, (uint64_t*)d_pair)) != RTX_OK) return rc;
+    if ((rc = launch_minimize(ctx, ctx->d_scan.get(), words_input(mode, W, H, d_words), (uint8_t*)d_host, &run, (uint64_t*)d_pair)) != RTX_OK) return rc;
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t total = 0;
     // (blocks that gave up: the chain, into the same buffer, its length read back the usual way)
-    if ((rc = settle_minimize(ctx, run, ctx->h_pair, &total)) != RTX_OK) return rc;
+    if ((rc = settle_minimize(ctx, run, ctx->h_pair.get(), &total)) != RTX_OK) return rc;
     ctx->stat_host_writes++;
     *out_bytes = (size_t)total;
     *done = true;
@@ -299,17 +267,16 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         if (q.rows == 0) return RTX_OK;
         RTX_HIP(m, hipSetDevice(m->device));
         const size_t above = q.row0 > 0 ? 1u : 0u;
-        int rc2 = ensure_words_buffer(m, &m->d_words, &m->words_cap, (q.rows + above) * W);
+        int rc2 = ensure_words_buffer(m, m->d_words, (q.rows + above) * W);
         if (rc2 != RTX_OK) return rc2;
-        if (!m->h_pair && hipHostMalloc((void**)&m->h_pair, 2 * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
-            m->h_pair = nullptr;
+        if (m->h_pair.reserve(2, rtxmem::nothing()) != hipSuccess) {
             return rtx_fail(m, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for a rank's stream length");
         }
-        if ((rc2 = rtx_render_rows(m, p, mode, q.row0 - above, q.rows + above, m->d_words, q.row0 - above, m->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc2;
+        if ((rc2 = rtx_render_rows(m, p, mode, q.row0 - above, q.rows + above, m->d_words.get(), q.row0 - above, m->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc2;
         if ((rc2 = ensure_min_buffers(m, (uint64_t)W * q.rows, true)) != RTX_OK) return rc2;
         MinRun& run = runs[(size_t)r];
-        if ((rc2 = launch_minimize(m, m->d_scan, words_input(mode, W, q.rows, m->d_words + above * W, (uint32_t)(above * W)), m->d_min, &run)) != RTX_OK) return rc2;
-        RTX_HIP(m, hipMemcpyAsync(m->h_pair, run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
+        if ((rc2 = launch_minimize(m, m->d_scan.get(), words_input(mode, W, q.rows, m->d_words.get() + above * W, (uint32_t)(above * W)), m->d_min.get(), &run)) != RTX_OK) return rc2;
+        RTX_HIP(m, hipMemcpyAsync(m->h_pair.get(), run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
         return RTX_OK;
     };
     auto await_rows = [&](int r, rtx_ctx* m) -> int {
@@ -318,7 +285,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         RTX_HIP(m, hipSetDevice(m->device));
         RTX_HIP(m, hipStreamSynchronize(m->stream));
         uint64_t total = 0;
-        const int rc2 = settle_minimize(m, runs[(size_t)r], m->h_pair, &total);
+        const int rc2 = settle_minimize(m, runs[(size_t)r], m->h_pair.get(), &total);
         if (rc2 != RTX_OK) return rc2;
         q.bytes = (size_t)total;
         return RTX_OK;
@@ -327,7 +294,7 @@ int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host
         const Part& q = part[(size_t)r];
         if (q.bytes == 0) return RTX_OK;
         RTX_HIP(m, hipSetDevice(m->device));
-        RTX_HIP(m, hipMemcpyAsync((uint8_t*)host_out + q.offset, m->d_min, q.bytes, hipMemcpyDeviceToHost, m->stream));
+        RTX_HIP(m, hipMemcpyAsync((uint8_t*)host_out + q.offset, m->d_min.get(), q.bytes, hipMemcpyDeviceToHost, m->stream));
         return RTX_OK;
     };
     auto await_copy = [&](int r, rtx_ctx* m) -> int {
@@ -370,7 +337,7 @@ int check_sphere_range(rtx_ctx* ctx, const char* who, unsigned first, size_t n)
 // an edit waits for its result: not inside a graph capture, on either stream
 int check_not_capturing(rtx_ctx* ctx, const char* who, hipStream_t other)
 {
-    for (hipStream_t s : {ctx->stream, other}) {
+    for (hipStream_t s : {ctx->stream.get(), other}) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         RTX_HIP(ctx, hipStreamIsCapturing(s, &cs));
         if (cs != hipStreamCaptureStatusNone) {
@@ -392,46 +359,36 @@ int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* r
         if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
     }
     if (after) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, after, 0));
-    if (!ctx->d_edit_result) {
-        RTX_HIP(ctx, hipMalloc((void**)&ctx->d_edit_result, 2 * sizeof(uint32_t)));
-        RTX_HIP(ctx, hipHostMalloc((void**)&ctx->h_edit_result, 2 * sizeof(uint32_t), hipHostMallocDefault));
-    }
+    RTX_HIP(ctx, ctx->d_edit_result.reserve(2, rtxmem::nothing()));
+    RTX_HIP(ctx, ctx->h_edit_result.reserve(2, rtxmem::nothing()));
     const float* d_rows = rows;
     if (src_device < 0 || stage) {
         const size_t need = 7 * n;
-        if (ctx->d_edit_rows.cap < need) {
-            // (every earlier edit has been waited for: nothing reads the old scratch)
-            size_t cap = ctx->d_edit_rows.cap ? ctx->d_edit_rows.cap : 7 * 1024;
-            while (cap < need) cap *= 2;
-            void* p = nullptr;
-            if (hipMalloc(&p, cap * sizeof(float)) != hipSuccess) {
-                (void)hipGetLastError();
-                return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the scene edit scratch");
-            }
-            if (ctx->d_edit_rows.p) hipFree(ctx->d_edit_rows.p);
-            ctx->d_edit_rows.p = p;
-            ctx->d_edit_rows.cap = cap;
+        // (every earlier edit has been waited for: nothing reads the old scratch)
+        if (ctx->d_edit_rows.reserve_doubling(need, 7 * 1024, rtxmem::nothing()) != hipSuccess) {
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the scene edit scratch");
         }
         if (src_device < 0) {
-            RTX_HIP(ctx, hipMemcpyAsync(ctx->d_edit_rows.p, rows, need * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            RTX_HIP(ctx, hipMemcpyAsync(ctx->d_edit_rows.get(), rows, need * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         } else {
-            RTX_HIP(ctx, hipMemcpyPeerAsync(ctx->d_edit_rows.p, ctx->device, rows, src_device, need * sizeof(float), ctx->stream));
+            RTX_HIP(ctx, hipMemcpyPeerAsync(ctx->d_edit_rows.get(), ctx->device, rows, src_device, need * sizeof(float), ctx->stream));
         }
-        d_rows = (const float*)ctx->d_edit_rows.p;
+        d_rows = ctx->d_edit_rows.get();
     }
     const uint32_t k0 = ctx->local_of[first];
-    const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.p != nullptr;
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_edit_result, 0, 2 * sizeof(uint32_t), ctx->stream));
+    const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr;
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_edit_result.get(), 0, 2 * sizeof(uint32_t), ctx->stream));
     const unsigned blocks = (unsigned)((n + rtx::kThreads - 1) / rtx::kThreads);
     hipLaunchKernelGGL(rtx::rtx_write_spheres, dim3(blocks), dim3(rtx::kThreads), 0, ctx->stream, d_rows, k0, (uint32_t)n,
-                       (float4*)ctx->d_sph_geom.p, (float4*)ctx->d_sph_color.p, (float4*)ctx->d_sph_od.p,
-                       sorted ? (float4*)ctx->d_sorted_geom.p : nullptr, sorted ? (float4*)ctx->d_sorted_od.p : nullptr,
-                       sorted ? (const uint32_t*)ctx->d_pos_of.p : nullptr, ctx->d_edit_result);
+                       ctx->d_sph_geom.get(), ctx->d_sph_color.get(), ctx->d_sph_od.get(),
+                       sorted ? ctx->d_sorted_geom.get() : nullptr, sorted ? ctx->d_sorted_od.get() : nullptr,
+                       sorted ? ctx->d_pos_of.get() : nullptr, ctx->d_edit_result.get());
     RTX_HIP(ctx, hipGetLastError());
-    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_edit_result, ctx->d_edit_result, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_edit_result.get(), ctx->d_edit_result.get(), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the one wait: the edit is applied, the rows are free, the words are here
-    const uint32_t flags = ctx->h_edit_result[1];
-    const rtxplan::EditEffect eff = rtxplan::edit_effect(bits_to_float(ctx->h_edit_result[0]), flags);
+    const uint32_t* const result = ctx->h_edit_result.get();
+    const uint32_t flags = result[1];
+    const rtxplan::EditEffect eff = rtxplan::edit_effect(bits_to_float(result[0]), flags);
     ctx->qgrid.dirty = true; // (the world grid lists spheres where they were)
     ctx->ns_moved_since_build = true;
     ctx->stat_scene_edits++;
@@ -442,7 +399,7 @@ int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* r
         ctx->cell_policy.invalidate();
         ctx->stat_edit_move_bits = 0x7f800000u;
     } else {
-        ctx->stat_edit_move_bits = ctx->h_edit_result[0];
+        ctx->stat_edit_move_bits = result[0];
     }
     ctx->scene_drift += eff.drift_add;
     if (eff.unsettle_physics) ctx->physics_settled = false;
@@ -465,33 +422,17 @@ int rtx_remove_prepare(rtx_ctx* ctx, const std::vector<uint32_t>& ascending)
     int rc = rtx_sync_scene(ctx); // every pending append is on the device: ns_uploaded == ns, np_uploaded == np
     if (rc != RTX_OK) return rc;
     const size_t n = ascending.size();
-    DeviceArray* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
-                                  &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
+    const DeviceBuf<float4>* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
+                                              &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
     for (int a = 0; a < 8; a++) {
-        DeviceArray& spare = ctx->d_spare[a];
-        if (spare.cap >= live[a]->cap) continue;
         // (every earlier removal has been waited for, and no launch reads a spare set)
-        void* p = nullptr;
-        if (hipMalloc(&p, live[a]->cap * sizeof(float4)) != hipSuccess) {
-            (void)hipGetLastError();
+        if (ctx->d_spare[a].reserve(live[a]->capacity(), rtxmem::nothing()) != hipSuccess) {
             return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the second set of scene arrays");
         }
-        if (spare.p) hipFree(spare.p);
-        spare.p = p;
-        spare.cap = live[a]->cap;
     }
     // the lists: R, then the removed sphere locals, then the removed plane locals -- 2 |R| words
-    if (ctx->d_remove_lists.cap < 2 * n) {
-        size_t cap = ctx->d_remove_lists.cap ? ctx->d_remove_lists.cap : 1024;
-        while (cap < 2 * n) cap *= 2;
-        void* p = nullptr;
-        if (hipMalloc(&p, cap * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the removal lists");
-        }
-        if (ctx->d_remove_lists.p) hipFree(ctx->d_remove_lists.p);
-        ctx->d_remove_lists.p = p;
-        ctx->d_remove_lists.cap = cap;
+    if (ctx->d_remove_lists.reserve_doubling(2 * n, 1024, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed while growing the removal lists");
     }
     return RTX_OK;
 }
@@ -507,30 +448,30 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
     rtxplan::RemovalPlan plan = rtxplan::plan_removal(ctx->kind_of, ascending);
     const size_t n = ascending.size();
     // the kernel's argument order: the two plain arrays of a kind, then the two that carry the creation index in .w
-    DeviceArray* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
-                                  &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
+    DeviceBuf<float4>* const live[8] = {&ctx->d_sph_geom, &ctx->d_sph_motion, &ctx->d_sph_color, &ctx->d_sph_od,
+                                        &ctx->d_pl_a,     &ctx->d_pl_b,       &ctx->d_pl_c,      &ctx->d_pl_od};
     const bool moves[2] = {plan.ns > 0, plan.np > 0}; // (a kind without survivors has nothing to move: its count drops to 0)
     std::vector<uint32_t> lists(ascending);
     lists.insert(lists.end(), plan.removed_spheres.begin(), plan.removed_spheres.end());
     lists.insert(lists.end(), plan.removed_planes.begin(), plan.removed_planes.end());
-    const uint32_t* d_gidx = (const uint32_t*)ctx->d_remove_lists.p;
+    const uint32_t* d_gidx = ctx->d_remove_lists.get();
     const uint32_t* d_local[2] = {d_gidx + n, d_gidx + n + plan.removed_spheres.size()};
     const uint32_t n_local[2] = {(uint32_t)plan.removed_spheres.size(), (uint32_t)plan.removed_planes.size()};
     const uint32_t count[2] = {ctx->ns, ctx->np};
-    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_remove_lists.p, lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_remove_lists.get(), lists.data(), lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     for (int kind = 0; kind < 2; kind++) {
         if (!moves[kind]) continue;
-        DeviceArray* const* from = live + 4 * kind;
-        const DeviceArray* to = ctx->d_spare + 4 * kind;
+        DeviceBuf<float4>* const* from = live + 4 * kind;
+        const DeviceBuf<float4>* to = ctx->d_spare + 4 * kind;
         hipLaunchKernelGGL(rtx::rtx_compact_objects, dim3((count[kind] + rtx::kThreads - 1) / rtx::kThreads), dim3(rtx::kThreads), 0, ctx->stream,
-                           (const float4*)from[0]->p, (const float4*)from[1]->p, (const float4*)from[2]->p, (const float4*)from[3]->p,
-                           (float4*)to[0].p, (float4*)to[1].p, (float4*)to[2].p, (float4*)to[3].p, count[kind], d_gidx, (uint32_t)n,
+                           (const float4*)from[0]->get(), (const float4*)from[1]->get(), (const float4*)from[2]->get(), (const float4*)from[3]->get(),
+                           to[0].get(), to[1].get(), to[2].get(), to[3].get(), count[kind], d_gidx, (uint32_t)n,
                            d_local[kind], n_local[kind]);
         RTX_HIP(ctx, hipGetLastError());
     }
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the one wait: the survivors are in the second set, the lists are free
     for (int a = 0; a < 8; a++) {
-        if (moves[a / 4]) std::swap(*live[a], ctx->d_spare[a]);
+        if (moves[a / 4]) live[a]->swap(ctx->d_spare[a]);
     }
     // the books, all in one place: what a context holds to which the survivors were added in their order
     std::vector<float> refl;
@@ -622,24 +563,16 @@ int rtx_scene_remove_marked_device(rtx_ctx* ctx, const uint8_t* d_marks, void* s
     hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     int rc = check_not_capturing(ctx, "rtx_scene_remove_marked_device", st);
     if (rc != RTX_OK) return rc;
-    if (ctx->remove_marks_cap < count) {
-        size_t cap = ctx->remove_marks_cap ? ctx->remove_marks_cap : 4096;
-        while (cap < count) cap *= 2;
-        uint8_t* p = nullptr;
-        if (hipHostMalloc((void**)&p, cap, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed while growing the removal marks");
-        }
-        if (ctx->h_remove_marks) hipHostFree(ctx->h_remove_marks);
-        ctx->h_remove_marks = p;
-        ctx->remove_marks_cap = cap;
+    // (every earlier copy of marks has been waited for)
+    if (ctx->h_remove_marks.reserve_doubling(count, 4096, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed while growing the removal marks");
     }
     // after everything queued so far on the caller's stream (the kernel that wrote the marks); the first of the two waits
-    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_remove_marks, d_marks, count, hipMemcpyDeviceToHost, st));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->h_remove_marks.get(), d_marks, count, hipMemcpyDeviceToHost, st));
     RTX_HIP(ctx, hipStreamSynchronize(st));
     std::vector<uint32_t> ascending;
     for (size_t i = 0; i < count; i++) {
-        if (ctx->h_remove_marks[i]) ascending.push_back((uint32_t)i);
+        if (ctx->h_remove_marks.get()[i]) ascending.push_back((uint32_t)i);
     }
     if (!ascending.empty() && (rc = remove_checked(ctx, ascending)) != RTX_OK) return rc;
     if (n_removed) *n_removed = ascending.size();
@@ -670,7 +603,7 @@ int rtx_scene_set_spheres_device(rtx_ctx* ctx, unsigned first, size_t n, const f
     // after everything queued so far on the caller's stream (the kernel that wrote the rows); a group's members wait for it too
     hipEvent_t after = nullptr;
     if (st != ctx->stream || ctx->group) {
-        if (!ctx->ev_edit) RTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_edit, hipEventDisableTiming));
+        RTX_HIP(ctx, ctx->ev_edit.ensure());
         RTX_HIP(ctx, hipEventRecord(ctx->ev_edit, st));
         after = ctx->ev_edit;
     }
@@ -698,10 +631,10 @@ int rtx_scene_set_plane(rtx_ctx* ctx, unsigned index, const float pos[3], const 
     const float4 c = make_float4(rgb[0], rgb[1], rgb[2], bits_to_float(index));
     const float4 od = make_float4(rgb[0] / 255.0f, rgb[1] / 255.0f, rgb[2] / 255.0f, bits_to_float(index));
     const uint32_t k = ctx->local_of[index];
-    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_a.p + k, &a, sizeof a, hipMemcpyHostToDevice, ctx->stream));
-    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_b.p + k, &b, sizeof b, hipMemcpyHostToDevice, ctx->stream));
-    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_c.p + k, &c, sizeof c, hipMemcpyHostToDevice, ctx->stream));
-    RTX_HIP(ctx, hipMemcpyAsync((float4*)ctx->d_pl_od.p + k, &od, sizeof od, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pl_a.get() + k, &a, sizeof a, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pl_b.get() + k, &b, sizeof b, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pl_c.get() + k, &c, sizeof c, hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pl_od.get() + k, &od, sizeof od, hipMemcpyHostToDevice, ctx->stream));
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     // Cell lists hold spheres only and stay valid; the dispatch orders' estimates are stale.  qgrid.dirty is left as it is: the
     // world grid (rtx_grid.hpp, the build in rtx_query.cpp) lists spheres and takes its bounds from spheres alone -- the query and
@@ -723,10 +656,10 @@ int rtx_update_objects(rtx_ctx* ctx, double dt)
         if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
     }
     const unsigned blocks = (ctx->ns + rtx::kThreads - 1) / rtx::kThreads;
-    const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.p != nullptr;
+    const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr;
     hipLaunchKernelGGL(rtx::rtx_update_spheres, dim3(blocks), dim3(rtx::kThreads), 0, ctx->stream,
-                       (float4*)ctx->d_sph_geom.p, (float4*)ctx->d_sph_motion.p, ctx->ns, dt, sorted ? (float4*)ctx->d_sorted_geom.p : nullptr,
-                       sorted ? (const uint32_t*)ctx->d_pos_of.p : nullptr);
+                       ctx->d_sph_geom.get(), ctx->d_sph_motion.get(), ctx->ns, dt, sorted ? ctx->d_sorted_geom.get() : nullptr,
+                       sorted ? ctx->d_pos_of.get() : nullptr);
     RTX_HIP(ctx, hipGetLastError());
     ctx->ns_moved_since_build = true;
     ctx->qgrid.dirty = true; // (the world grid lists spheres where they were)
@@ -746,7 +679,7 @@ int rtx_update_objects(rtx_ctx* ctx, double dt)
     return ctx->group ? rtxgroup::update_objects(ctx, dt) : RTX_OK; // every rank steps its replica: the same arithmetic on the same values
 }
 
-void* rtx_minimized_device_ptr(rtx_ctx* ctx) { return ctx ? ctx->d_min : nullptr; }
+void* rtx_minimized_device_ptr(rtx_ctx* ctx) { return ctx ? ctx->d_min.get() : nullptr; }
 
 int rtx_ansi256_map(rtx_ctx* ctx, uint32_t first_rgb, size_t count, void* d_out, void* stream_v)
 {
@@ -757,7 +690,7 @@ int rtx_ansi256_map(rtx_ctx* ctx, uint32_t first_rgb, size_t count, void* d_out,
     hipStream_t st = stream_v ? (hipStream_t)stream_v : ctx->stream;
     const uint64_t threads = ((uint64_t)count + 3u) / 4u;
     const unsigned blocks = (unsigned)((threads + rtx::kThreads - 1) / rtx::kThreads);
-    hipLaunchKernelGGL(rtx::rtx_ansi_map, dim3(blocks), dim3(rtx::kThreads), 0, st, first_rgb, (uint64_t)count, ctx->d_grey, (uint8_t*)d_out);
+    hipLaunchKernelGGL(rtx::rtx_ansi_map, dim3(blocks), dim3(rtx::kThreads), 0, st, first_rgb, (uint64_t)count, ctx->d_grey.get(), (uint8_t*)d_out);
     RTX_HIP(ctx, hipGetLastError());
     return RTX_OK;
 }
@@ -769,7 +702,7 @@ int rtx_minimize(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_in, v
     if (w == 0 || h == 0 || w >= (1ull << 31) || h >= (1ull << 31)) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "w/h must be in [1, 2^31)");
     if (!d_in) {
         if (20 * w * h > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
-        d_in = ctx->d_frame;
+        d_in = ctx->d_frame.get();
     }
     if (((uintptr_t)d_in & 15u) != 0 || (d_out && ((uintptr_t)d_out & 15u) != 0)) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "minimise buffers must be 16-byte aligned");
@@ -811,12 +744,11 @@ int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cu
     }
     if (out_capacity < rtx_delta_bound(mode, w, h)) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_delta_words: the output holds less than rtx_delta_bound");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    if (!ctx->d_delta_counts && hipMalloc((void**)&ctx->d_delta_counts, 2 * sizeof(unsigned long long)) != hipSuccess) {
-        ctx->d_delta_counts = nullptr;
+    if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
     }
     ctx->delta_counts_valid = true;
-    return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts), d_out, out_bytes);
+    return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts.get()), d_out, out_bytes);
 }
 
 int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags, void* host_out, size_t host_capacity,
@@ -839,31 +771,22 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     ctx->delta_valid = false;               // until this call has handed its frame out
     // the words: traced straight into the pair's buffer; a group's gathered words are copied into it
     const uint32_t* d_words = nullptr;
-    if ((rc = ensure_words_buffer(ctx, &ctx->d_delta_words[at], &ctx->delta_words_cap[at], W * H)) != RTX_OK) return rc;
-    if ((rc = trace_words(ctx, params, mode, &ctx->d_delta_words[at], &ctx->delta_words_cap[at], &d_words)) != RTX_OK) return rc;
-    if (d_words != ctx->d_delta_words[at]) {
-        RTX_HIP(ctx, hipMemcpyAsync(ctx->d_delta_words[at], d_words, W * H * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    if ((rc = ensure_words_buffer(ctx, ctx->d_delta_words[at], W * H)) != RTX_OK) return rc;
+    if ((rc = trace_words(ctx, params, mode, ctx->d_delta_words[at], &d_words)) != RTX_OK) return rc;
+    if (d_words != ctx->d_delta_words[at].get()) {
+        RTX_HIP(ctx, hipMemcpyAsync(ctx->d_delta_words[at].get(), d_words, W * H * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     }
     size_t n = 0;
     const uint8_t* d_stream = nullptr;
     if (key) {
         // what rtx_update makes of the frame: Minimize of the words into the context's buffer
-        if ((rc = rtx_minimize_words(ctx, mode, W, H, ctx->d_delta_words[at], nullptr, &n)) != RTX_OK) return rc;
-        d_stream = ctx->d_min;
+        if ((rc = rtx_minimize_words(ctx, mode, W, H, ctx->d_delta_words[at].get(), nullptr, &n)) != RTX_OK) return rc;
+        d_stream = ctx->d_min.get();
     } else {
         const size_t bound = rtx_delta_bound(mode, W, H);
-        if (ctx->delta_out_cap < bound) {
-            if (ctx->d_delta_out) {
-                RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                hipFree(ctx->d_delta_out);
-            }
-            ctx->d_delta_out = nullptr;
-            ctx->delta_out_cap = 0;
-            if (hipMalloc((void**)&ctx->d_delta_out, bound) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta buffer");
-            ctx->delta_out_cap = bound;
-        }
-        if ((rc = rtx_delta_words(ctx, mode, W, H, ctx->d_delta_words[at], ctx->d_delta_words[at ^ 1u], ctx->d_delta_out, ctx->delta_out_cap, &n)) != RTX_OK) return rc;
-        d_stream = ctx->d_delta_out;
+        if (ctx->d_delta_out.reserve(bound, rtxmem::after_stream(ctx->stream)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta buffer");
+        if ((rc = rtx_delta_words(ctx, mode, W, H, ctx->d_delta_words[at].get(), ctx->d_delta_words[at ^ 1u].get(), ctx->d_delta_out.get(), ctx->d_delta_out.capacity(), &n)) != RTX_OK) return rc;
+        d_stream = ctx->d_delta_out.get();
     }
     if (n > host_capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_delta: the stream is longer than host_capacity (the next call gives a key frame)");
     if (n) {
@@ -918,10 +841,10 @@ int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int 
             }
         }
         const uint32_t* d_words = nullptr;
-        if ((rc = trace_words(ctx, params, mode, &ctx->d_words, &ctx->words_cap, &d_words)) != RTX_OK) return rc;
+        if ((rc = trace_words(ctx, params, mode, ctx->d_words, &d_words)) != RTX_OK) return rc;
         if ((rc = rtx_minimize_words(ctx, mode, (size_t)params->x, (size_t)params->y, d_words, nullptr, &n)) != RTX_OK) return rc;
         if (n) {
-            RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min, n, hipMemcpyDeviceToHost, ctx->stream));
+            RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min.get(), n, hipMemcpyDeviceToHost, ctx->stream));
             RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
         *out_bytes = n;
@@ -932,7 +855,7 @@ int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int 
     // :146: minimise on the device; :143 then only moves the minimised stream across PCIe
     if ((rc = rtx_minimize(ctx, mode, (size_t)params->x, (size_t)params->y, nullptr, nullptr, &n)) != RTX_OK) return rc;
     if (n) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min, n, hipMemcpyDeviceToHost, ctx->stream));
+        RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min.get(), n, hipMemcpyDeviceToHost, ctx->stream));
         RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     *out_bytes = n;
@@ -959,43 +882,32 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
         // bench.py's default line measured whenever four render streams had been created first.
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest ||
-            hipStreamCreateWithPriority(&ctx->copy_stream, hipStreamNonBlocking, greatest) != hipSuccess) {
+            ctx->copy_stream.ensure_with_priority(hipStreamNonBlocking, greatest) != hipSuccess) {
             (void)hipGetLastError();
-            ctx->copy_stream = nullptr;
-            RTX_HIP(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
+            RTX_HIP(ctx, ctx->copy_stream.ensure(hipStreamNonBlocking));
         }
     }
     // every member under its own null check: a call that fails half-way (out of memory) leaves a slot the next
     // call completes, instead of one that looks initialised with null buffers behind it
     const bool from_words = update_from_words(ctx, mode);
-    if (!from_words && !sl.d_frame) {
-        uint8_t* f = nullptr;
-        if (hipMalloc((void**)&f, ctx->capacity) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for an update slot's frame");
-        const hipError_t me = hipMemsetAsync(f, 0, ctx->capacity, ctx->stream);
+    if (!from_words && !sl.d_frame.get()) {
+        if (sl.d_frame.reserve(ctx->capacity, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for an update slot's frame");
+        const hipError_t me = hipMemsetAsync(sl.d_frame.get(), 0, ctx->capacity, ctx->stream);
         if (me != hipSuccess) {
-            hipFree(f);
+            sl.d_frame.release();
             return rtx_hip_fail(ctx, me, "hipMemsetAsync(update slot frame)");
         }
-        sl.d_frame = f;
     }
-    if (!sl.d_min && hipMalloc((void**)&sl.d_min, ctx->capacity) != hipSuccess) {
-        sl.d_min = nullptr;
+    if (!sl.d_min.get() && sl.d_min.reserve(ctx->capacity, rtxmem::nothing()) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for an update slot's minimise buffer");
     }
-    if (!sl.h_total && hipHostMalloc((void**)&sl.h_total, 2 * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess) {
-        sl.h_total = nullptr;
+    if (sl.h_total.reserve(2, rtxmem::nothing()) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for an update slot");
     }
-    if (!sl.ev_ready) RTX_HIP(ctx, hipEventCreateWithFlags(&sl.ev_ready, hipEventDisableTiming));
-    if (!sl.ev_copied) RTX_HIP(ctx, hipEventCreateWithFlags(&sl.ev_copied, hipEventDisableTiming));
-    const size_t need = min_scan_bytes((uint64_t)w * h);
-    if (sl.scan_bytes < need) {
-        if (sl.d_scan) hipFree(sl.d_scan);
-        sl.d_scan = nullptr;
-        sl.scan_bytes = 0;
-        RTX_HIP(ctx, hipMalloc(&sl.d_scan, need));
-        sl.scan_bytes = need;
-    }
+    RTX_HIP(ctx, sl.ev_ready.ensure());
+    RTX_HIP(ctx, sl.ev_copied.ensure());
+    // (the slot is not busy: the launch that used the old scratch has been waited for)
+    RTX_HIP(ctx, sl.d_scan.reserve(min_scan_bytes((uint64_t)w * h), rtxmem::nothing()));
     int rc;
     if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
     if (from_words && rtxgroup::update_direct_wanted(ctx)) {
@@ -1021,11 +933,11 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
         // a small frame: the Minimize launch stores the stream and its length in host memory itself, and NOTHING is waited for here --
         // rtx_update_end waits for the frame.  (At console sizes the copy form's two waits per frame were what the pipelined Update cost.)
         void *d_host = nullptr, *d_pair = nullptr;
-        if (hipHostGetDevicePointer(&d_host, host_out, 0) == hipSuccess && d_host != nullptr && hipHostGetDevicePointer(&d_pair, sl.h_total, 0) == hipSuccess) {
-            if ((rc = trace_words(ctx, params, mode, &sl.d_words, &sl.words_cap, &d_words)) != RTX_OK) return rc;
-            sl.h_total[0] = 0;
-            sl.h_total[1] = 0;
-            if ((rc = launch_minimize(ctx, sl.d_scan, words_input(mode, w, h, d_words), (uint8_t*)d_host, &sl.run, (uint64_t*)d_pair)) != RTX_OK) return rc;
+        if (hipHostGetDevicePointer(&d_host, host_out, 0) == hipSuccess && d_host != nullptr && hipHostGetDevicePointer(&d_pair, sl.h_total.get(), 0) == hipSuccess) {
+            if ((rc = trace_words(ctx, params, mode, sl.d_words, &d_words)) != RTX_OK) return rc;
+            sl.h_total.get()[0] = 0;
+            sl.h_total.get()[1] = 0;
+            if ((rc = launch_minimize(ctx, sl.d_scan.get(), words_input(mode, w, h, d_words), (uint8_t*)d_host, &sl.run, (uint64_t*)d_pair)) != RTX_OK) return rc;
             RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
             sl.host_write = true;
             ctx->stat_host_writes++;
@@ -1038,35 +950,34 @@ int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     }
     if (from_words) {
         // pixel words into the slot's own buffer (a group: into the group's, gathered), minimised from there
-        if ((rc = trace_words(ctx, params, mode, &sl.d_words, &sl.words_cap, &d_words)) != RTX_OK) return rc;
-        if ((rc = launch_minimize(ctx, sl.d_scan, words_input(mode, w, h, d_words), sl.d_min, &sl.run)) != RTX_OK) return rc;
+        if ((rc = trace_words(ctx, params, mode, sl.d_words, &d_words)) != RTX_OK) return rc;
+        if ((rc = launch_minimize(ctx, sl.d_scan.get(), words_input(mode, w, h, d_words), sl.d_min.get(), &sl.run)) != RTX_OK) return rc;
     } else {
     // the slot's frame buffer is caller-style memory for rtx_render_rows: whole frame, with the zero
     // semantics of the per-frame memset (the buffer starts zeroed; SDL frames write nothing, so clear)
     const bool rgb = mode >= RTX_RGB_ASCII;
     if (mode == RTX_SDL) {
-        RTX_HIP(ctx, hipMemsetAsync(sl.d_frame, 0, 20 * w * h, ctx->stream));
+        RTX_HIP(ctx, hipMemsetAsync(sl.d_frame.get(), 0, 20 * w * h, ctx->stream));
     }
     if (ctx->group) {
-        if ((rc = rtxgroup::render_frame(ctx, params, mode, sl.d_frame, rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) return rc;
-    } else if ((rc = rtx_render_rows(ctx, params, mode, 0, h, sl.d_frame, 0, ctx->stream, rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) {
+        if ((rc = rtxgroup::render_frame(ctx, params, mode, sl.d_frame.get(), rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) return rc;
+    } else if ((rc = rtx_render_rows(ctx, params, mode, 0, h, sl.d_frame.get(), 0, ctx->stream, rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) {
         return rc;
     }
-    if ((rc = launch_minimize(ctx, sl.d_scan, records_input(mode, w, h, sl.d_frame), sl.d_min, &sl.run)) != RTX_OK) return rc;
+    if ((rc = launch_minimize(ctx, sl.d_scan.get(), records_input(mode, w, h, sl.d_frame.get()), sl.d_min.get(), &sl.run)) != RTX_OK) return rc;
     }
-    RTX_HIP(ctx, hipMemcpyAsync(sl.h_total, sl.run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(sl.h_total.get(), sl.run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
     // the length is needed on the host to size the copy: wait for this frame's kernels (the previous frame's
     // copy keeps running on the copy stream meanwhile)
     RTX_HIP(ctx, hipEventSynchronize(sl.ev_ready));
     {
         uint64_t total = 0;
-        if ((rc = settle_minimize(ctx, sl.run, sl.h_total, &total)) != RTX_OK) return rc;
-        sl.h_total[0] = total;
+        if ((rc = settle_minimize(ctx, sl.run, sl.h_total.get(), &total)) != RTX_OK) return rc;
+        sl.bytes = (size_t)total;
     }
-    sl.bytes = (size_t)*sl.h_total;
     if (sl.bytes) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, sl.d_min, sl.bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
+        RTX_HIP(ctx, hipMemcpyAsync(host_out, sl.d_min.get(), sl.bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
     }
     RTX_HIP(ctx, hipEventRecord(sl.ev_copied, ctx->copy_stream));
     sl.busy = true;
@@ -1086,7 +997,7 @@ int rtx_update_end(rtx_ctx* ctx, int ticket, size_t* out_bytes)
         sl.host_write = false;
         sl.busy = false;
         uint64_t total = 0;
-        const int rc = settle_minimize(ctx, sl.run, sl.h_total, &total);
+        const int rc = settle_minimize(ctx, sl.run, sl.h_total.get(), &total);
         if (rc != RTX_OK) return rc;
         *out_bytes = (size_t)total;
         return RTX_OK;
@@ -1113,26 +1024,16 @@ int rtx_sort_scene(rtx_ctx* ctx, const float origin[3])
     rtxplan::direction_order(&ctx->h_centres[0].x, sizeof(float4) / sizeof(float), ns, origin, order, pos_of);
     // (a scene edit: nothing may still read the old copy)
     RTX_HIP(ctx, hipDeviceSynchronize());
-    for (DeviceArray* a : {&ctx->d_sorted_geom, &ctx->d_sorted_od, &ctx->d_sorted_idx, &ctx->d_pos_of}) {
-        const size_t elem = (a == &ctx->d_sorted_geom || a == &ctx->d_sorted_od) ? sizeof(float4) : sizeof(uint32_t);
-        if (a->cap < ns) {
-            if (a->p) hipFree(a->p);
-            a->p = nullptr;
-            a->cap = 0;
-            size_t cap = 1024;
-            while (cap < ns) cap *= 2;
-            if (hipMalloc(&a->p, cap * elem) != hipSuccess) {
-                (void)hipGetLastError();
-                return RTX_OK; // no sorted copy: staging reads the scene array (sorted_gen stays behind)
-            }
-            a->cap = cap;
-        }
+    // no sorted copy where memory is short: staging reads the scene array (sorted_gen stays behind)
+    if (ctx->d_sorted_geom.reserve_doubling(ns, 1024, rtxmem::nothing()) != hipSuccess || ctx->d_sorted_od.reserve_doubling(ns, 1024, rtxmem::nothing()) != hipSuccess ||
+        ctx->d_sorted_idx.reserve_doubling(ns, 1024, rtxmem::nothing()) != hipSuccess || ctx->d_pos_of.reserve_doubling(ns, 1024, rtxmem::nothing()) != hipSuccess) {
+        return RTX_OK;
     }
-    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_sorted_idx.p, order.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pos_of.p, pos_of.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_sorted_idx.get(), order.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    RTX_HIP(ctx, hipMemcpyAsync(ctx->d_pos_of.get(), pos_of.data(), ns * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(rtx::rtx_gather_spheres, dim3((ns + rtx::kThreads - 1) / rtx::kThreads), dim3(rtx::kThreads), 0, ctx->stream,
-                       (const float4*)ctx->d_sph_geom.p, (const float4*)ctx->d_sph_od.p, (const uint32_t*)ctx->d_sorted_idx.p,
-                       (float4*)ctx->d_sorted_geom.p, (float4*)ctx->d_sorted_od.p, ns);
+                       ctx->d_sph_geom.get(), ctx->d_sph_od.get(), ctx->d_sorted_idx.get(),
+                       ctx->d_sorted_geom.get(), ctx->d_sorted_od.get(), ns);
     RTX_HIP(ctx, hipGetLastError());
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the staging vectors go out of scope; other streams may render next)
     ctx->sorted_gen = ctx->scene_gen;

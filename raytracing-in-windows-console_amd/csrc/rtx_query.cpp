@@ -12,19 +12,14 @@
 
 namespace {
 
-int ensure(rtx_ctx* ctx, DeviceArray& a, size_t n, size_t elem)
+// room for n elements, with a quarter to spare (the build has waited for every reader of the old lists)
+template <class T>
+int ensure(rtx_ctx* ctx, DeviceBuf<T>& a, size_t n)
 {
-    if (a.cap >= n && a.p) return RTX_OK;
-    if (a.p) RTX_HIP(ctx, hipFree(a.p));
-    a.p = nullptr;
-    a.cap = 0;
-    const size_t want = n + n / 4 + 64;
-    if (hipMalloc(&a.p, want * elem) != hipSuccess) {
-        a.p = nullptr;
-        (void)hipGetLastError();
+    if (a.capacity() >= n && a.get()) return RTX_OK;
+    if (a.reserve(n + n / 4 + 64, rtxmem::nothing()) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "ray queries: out of device memory for the world grid");
     }
-    a.cap = want;
     return RTX_OK;
 }
 
@@ -32,13 +27,13 @@ int build_grid(rtx_ctx* ctx)
 {
     rtx_ctx::QueryGrid& q = ctx->qgrid;
     hipStream_t st = ctx->stream;
-    if (!q.ev_built) RTX_HIP(ctx, hipEventCreateWithFlags(&q.ev_built, hipEventDisableTiming));
-    if (!q.ev_done) RTX_HIP(ctx, hipEventCreateWithFlags(&q.ev_done, hipEventDisableTiming));
-    if (!q.d_words) {
-        RTX_HIP(ctx, hipMalloc((void**)&q.d_words, 16 * sizeof(uint32_t)));
-        RTX_HIP(ctx, hipMemsetAsync(q.d_words, 0, 16 * sizeof(uint32_t), st));
+    RTX_HIP(ctx, q.ev_built.ensure());
+    RTX_HIP(ctx, q.ev_done.ensure());
+    if (!q.d_words.get()) {
+        RTX_HIP(ctx, q.d_words.reserve(16, rtxmem::nothing()));
+        RTX_HIP(ctx, hipMemsetAsync(q.d_words.get(), 0, 16 * sizeof(uint32_t), st));
     }
-    if (!q.d_large) RTX_HIP(ctx, hipMalloc((void**)&q.d_large, rtxgrid::kLargeCap * sizeof(uint32_t)));
+    RTX_HIP(ctx, q.d_large.reserve(rtxgrid::kLargeCap, rtxmem::nothing()));
     // the lists may still be read by the last query, on whatever stream it ran
     if (q.query_pending) RTX_HIP(ctx, hipStreamWaitEvent(st, q.ev_done, 0));
     q.query_pending = false;
@@ -60,12 +55,12 @@ int build_grid(rtx_ctx* ctx)
     int rc;
     GridBuildArgs b;
     std::memset(&b, 0, sizeof b);
-    b.sph_geom = (const float4*)ctx->d_sph_geom.p;
-    b.sph_od = (const float4*)ctx->d_sph_od.p;
+    b.sph_geom = ctx->d_sph_geom.get();
+    b.sph_od = ctx->d_sph_od.get();
     b.ns = ns;
-    b.bounds = (float*)(q.d_words + 4);
-    b.totals = q.d_words;
-    b.large = q.d_large;
+    b.bounds = (float*)(q.d_words.get() + 4);
+    b.totals = q.d_words.get();
+    b.large = q.d_large.get();
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 0, st));
     float box[7];
     RTX_HIP(ctx, hipMemcpyAsync(box, b.bounds, sizeof box, hipMemcpyDeviceToHost, st));
@@ -79,20 +74,20 @@ int build_grid(rtx_ctx* ctx)
         return RTX_OK;
     }
     q.n_cells = q.plan.n[0] * q.plan.n[1] * q.plan.n[2];
-    if ((rc = ensure(ctx, q.cell_count, (size_t)q.n_cells + 1, sizeof(uint32_t))) != RTX_OK) return rc;
-    if ((rc = ensure(ctx, q.cell_fill, q.n_cells, sizeof(uint32_t))) != RTX_OK) return rc;
-    if ((rc = ensure(ctx, q.is_large, ns, 1)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipMemsetAsync(q.cell_count.p, 0, ((size_t)q.n_cells + 1) * sizeof(uint32_t), st));
-    RTX_HIP(ctx, hipMemsetAsync(q.cell_fill.p, 0, (size_t)q.n_cells * sizeof(uint32_t), st));
+    if ((rc = ensure(ctx, q.cell_count, (size_t)q.n_cells + 1)) != RTX_OK) return rc;
+    if ((rc = ensure(ctx, q.cell_fill, q.n_cells)) != RTX_OK) return rc;
+    if ((rc = ensure(ctx, q.is_large, ns)) != RTX_OK) return rc;
+    RTX_HIP(ctx, hipMemsetAsync(q.cell_count.get(), 0, ((size_t)q.n_cells + 1) * sizeof(uint32_t), st));
+    RTX_HIP(ctx, hipMemsetAsync(q.cell_fill.get(), 0, (size_t)q.n_cells * sizeof(uint32_t), st));
     b.grid = q.plan;
     b.n_cells = q.n_cells;
-    b.cell_count = (uint32_t*)q.cell_count.p;
-    b.cell_fill = (uint32_t*)q.cell_fill.p;
-    b.is_large = (uint8_t*)q.is_large.p;
+    b.cell_count = q.cell_count.get();
+    b.cell_fill = q.cell_fill.get();
+    b.is_large = q.is_large.get();
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 1, st));
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 2, st));
     uint32_t totals[2];
-    RTX_HIP(ctx, hipMemcpyAsync(totals, q.d_words, sizeof totals, hipMemcpyDeviceToHost, st));
+    RTX_HIP(ctx, hipMemcpyAsync(totals, q.d_words.get(), sizeof totals, hipMemcpyDeviceToHost, st));
     RTX_HIP(ctx, hipStreamSynchronize(st));
     q.pairs = totals[0];
     q.n_large = totals[1];
@@ -101,12 +96,12 @@ int build_grid(rtx_ctx* ctx)
         RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
         return RTX_OK;
     }
-    if ((rc = ensure(ctx, q.pair_tmp, q.pairs, sizeof(uint32_t))) != RTX_OK) return rc;
-    if ((rc = ensure(ctx, q.list_geom, q.pairs, sizeof(float4))) != RTX_OK) return rc;
-    if ((rc = ensure(ctx, q.list_gidx, q.pairs, sizeof(uint32_t))) != RTX_OK) return rc;
-    b.pair_tmp = (uint32_t*)q.pair_tmp.p;
-    b.list_geom = (float4*)q.list_geom.p;
-    b.list_gidx = (uint32_t*)q.list_gidx.p;
+    if ((rc = ensure(ctx, q.pair_tmp, q.pairs)) != RTX_OK) return rc;
+    if ((rc = ensure(ctx, q.list_geom, q.pairs)) != RTX_OK) return rc;
+    if ((rc = ensure(ctx, q.list_gidx, q.pairs)) != RTX_OK) return rc;
+    b.pair_tmp = q.pair_tmp.get();
+    b.list_geom = q.list_geom.get();
+    b.list_gidx = q.list_gidx.get();
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 3, st));
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 4, st));
     RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
@@ -135,21 +130,21 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
     a.hits = (uint2*)d_hits;
     a.n = (uint32_t)n;
     a.any = (flags & RTX_QUERY_ANY) ? 1u : 0u;
-    a.sph_geom = (const float4*)ctx->d_sph_geom.p;
-    a.sph_od = (const float4*)ctx->d_sph_od.p;
-    a.pl_a = (const float4*)ctx->d_pl_a.p;
-    a.pl_b = (const float4*)ctx->d_pl_b.p;
-    a.pl_od = (const float4*)ctx->d_pl_od.p;
+    a.sph_geom = ctx->d_sph_geom.get();
+    a.sph_od = ctx->d_sph_od.get();
+    a.pl_a = ctx->d_pl_a.get();
+    a.pl_b = ctx->d_pl_b.get();
+    a.pl_od = ctx->d_pl_od.get();
     a.ns = ctx->ns;
     a.np = ctx->np;
     a.grid = g.plan;
-    a.cell_start = (const uint32_t*)g.cell_count.p;
-    a.list_geom = (const float4*)g.list_geom.p;
-    a.list_gidx = (const uint32_t*)g.list_gidx.p;
-    a.large = g.d_large;
+    a.cell_start = g.cell_count.get();
+    a.list_geom = g.list_geom.get();
+    a.list_gidx = g.list_gidx.get();
+    a.large = g.d_large.get();
     a.n_large = g.n_large;
-    a.fallback = g.d_words + 2;
-    RTX_HIP(ctx, hipMemsetAsync(g.d_words + 2, 0, sizeof(uint32_t), stream));
+    a.fallback = g.d_words.get() + 2;
+    RTX_HIP(ctx, hipMemsetAsync(g.d_words.get() + 2, 0, sizeof(uint32_t), stream));
     const bool walk = !brute && !g.brute && ctx->ns != 0;
     if (!walk) a.grid.ok = 0;
     // without spheres the grid kernel has nothing to walk; the brute kernel's loop is empty as well: either gives the planes' answer
@@ -166,7 +161,7 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
 int rtx_grid_ensure(rtx_ctx* ctx, hipStream_t stream)
 {
     rtx_ctx::QueryGrid& g = ctx->qgrid;
-    if (g.dirty || !g.d_words) {
+    if (g.dirty || !g.d_words.get()) {
         const int rc = build_grid(ctx);
         if (rc != RTX_OK) {
             g.dirty = true;
@@ -190,30 +185,13 @@ int rtx_grid_read(rtx_ctx* ctx, hipStream_t stream)
         if (g.readers.size() >= (size_t)rtx_ctx::kMaxHitStreams) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "shadow grid: more than 64 distinct render streams");
         rtx_ctx::QueryGrid::Reader fresh;
         fresh.stream = stream;
-        RTX_HIP(ctx, hipEventCreateWithFlags(&fresh.ev, hipEventDisableTiming));
-        g.readers.push_back(fresh);
+        RTX_HIP(ctx, fresh.ev.ensure());
+        g.readers.push_back(std::move(fresh));
         rd = &g.readers.back();
     }
     RTX_HIP(ctx, hipEventRecord(rd->ev, stream));
     rd->pending = true;
     return RTX_OK;
-}
-
-void rtx_query_release(rtx_ctx* ctx)
-{
-    rtx_ctx::QueryGrid& q = ctx->qgrid;
-    for (auto& r : q.readers) {
-        if (r.ev) hipEventDestroy(r.ev);
-    }
-    for (DeviceArray* a : {&q.cell_count, &q.cell_fill, &q.is_large, &q.pair_tmp, &q.list_geom, &q.list_gidx}) {
-        if (a->p) hipFree(a->p);
-        a->p = nullptr;
-    }
-    if (q.d_large) hipFree(q.d_large);
-    if (q.d_words) hipFree(q.d_words);
-    if (q.d_ray) hipFree(q.d_ray);
-    if (q.ev_built) hipEventDestroy(q.ev_built);
-    if (q.ev_done) hipEventDestroy(q.ev_done);
 }
 
 bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status)
@@ -229,9 +207,9 @@ bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status)
     case RTX_STAT_QUERY_BRUTE: *value = ctx->qgrid.brute ? 1 : 0; return true;
     case RTX_STAT_QUERY_FALLBACK_RAYS: {
         uint32_t w = 0;
-        if (ctx->qgrid.d_words) {
+        if (ctx->qgrid.d_words.get()) {
             if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(&w, ctx->qgrid.d_words + 2, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) {
+                hipMemcpy(&w, ctx->qgrid.d_words.get() + 2, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) {
                 *status = RTX_ERR_HIP;
             }
         }
@@ -265,11 +243,11 @@ int rtx_query_rays_host(rtx_ctx* ctx, size_t n, const rtx_ray* rays, rtx_ray_hit
     if (flags & ~(unsigned)RTX_QUERY_ANY) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_query_rays_host: unknown flag bits");
     if (n == 0) return RTX_OK;
     if (!rays || !hits) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_query_rays_host: rays or hits is NULL");
-    void* d = nullptr;
-    if (hipMalloc(&d, n * (sizeof(rtx_ray) + sizeof(rtx_ray_hit))) != hipSuccess) {
-        (void)hipGetLastError();
+    DeviceBuf<uint8_t> buf; // (freed when the call returns: the stream has been waited for by then)
+    if (buf.reserve(n * (sizeof(rtx_ray) + sizeof(rtx_ray_hit)), rtxmem::nothing()) != hipSuccess) {
         return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "rtx_query_rays_host: out of device memory for the rays");
     }
+    void* const d = buf.get();
     rtx_ray_hit* d_hits = (rtx_ray_hit*)((char*)d + n * sizeof(rtx_ray));
     int rc = RTX_OK;
     hipError_t e = hipMemcpyAsync(d, rays, n * sizeof(rtx_ray), hipMemcpyHostToDevice, ctx->stream);
@@ -278,7 +256,6 @@ int rtx_query_rays_host(rtx_ctx* ctx, size_t n, const rtx_ray* rays, rtx_ray_hit
         if (rc == RTX_OK) e = hipMemcpyAsync(hits, d_hits, n * sizeof(rtx_ray_hit), hipMemcpyDeviceToHost, ctx->stream);
     }
     const hipError_t es = hipStreamSynchronize(ctx->stream);
-    hipFree(d);
     if (rc != RTX_OK) return rc;
     if (e != hipSuccess) return rtx_hip_fail(ctx, e, "rtx_query_rays_host: copy");
     if (es != hipSuccess) return rtx_hip_fail(ctx, es, "rtx_query_rays_host: hipStreamSynchronize");
@@ -298,7 +275,7 @@ int rtx_pick(rtx_ctx* ctx, const rtx_params* p, size_t col, size_t row, rtx_ray_
     RTX_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cs));
     if (cs != hipStreamCaptureStatusNone) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_pick: not inside a graph capture (it waits for its answer)");
     rtx_ctx::QueryGrid& g = ctx->qgrid;
-    if (!g.d_ray) RTX_HIP(ctx, hipMalloc(&g.d_ray, sizeof(rtx_ray) + 2 * sizeof(rtx_ray_hit)));
+    RTX_HIP(ctx, g.d_ray.reserve(sizeof(rtx_ray) + 2 * sizeof(rtx_ray_hit), rtxmem::nothing()));
     KArgs a;
     std::memset(&a, 0, sizeof a);
     std::memcpy(a.m, p->inv_v, 12 * sizeof(float));
@@ -310,9 +287,9 @@ int rtx_pick(rtx_ctx* ctx, const rtx_params* p, size_t col, size_t row, rtx_ray_
     a.far = p->cam_far;
     a.fW = (float)p->x;
     a.fH = (float)p->y;
-    RTX_HIP(ctx, (hipError_t)rtx_k_launch_pick_ray(&a, (uint32_t)col, (uint32_t)row, g.d_ray, ctx->stream));
-    rtx_ray_hit* d_hit = (rtx_ray_hit*)((char*)g.d_ray + sizeof(rtx_ray));
-    const int rc = query_device(ctx, 1, g.d_ray, d_hit, RTX_QUERY_CLOSEST, ctx->stream, "rtx_pick");
+    RTX_HIP(ctx, (hipError_t)rtx_k_launch_pick_ray(&a, (uint32_t)col, (uint32_t)row, g.d_ray.get(), ctx->stream));
+    rtx_ray_hit* d_hit = (rtx_ray_hit*)(g.d_ray.get() + sizeof(rtx_ray));
+    const int rc = query_device(ctx, 1, g.d_ray.get(), d_hit, RTX_QUERY_CLOSEST, ctx->stream, "rtx_pick");
     if (rc != RTX_OK) return rc;
     RTX_HIP(ctx, hipMemcpyAsync(hit, d_hit, sizeof *hit, hipMemcpyDeviceToHost, ctx->stream));
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));

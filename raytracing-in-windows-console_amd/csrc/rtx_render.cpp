@@ -193,10 +193,7 @@ int zero_fill_semantics(rtx_ctx* ctx, int mode, uint64_t W, uint64_t H, void* d_
 // number of render streams: every stream a process creates shifts how the others share its four hardware queues.
 hipStream_t side_stream(rtx_ctx* ctx)
 {
-    if (!ctx->aux_stream && hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->aux_stream = nullptr;
-    }
+    if (ctx->aux_stream.ensure(hipStreamNonBlocking) != hipSuccess) (void)hipGetLastError();
     return ctx->aux_stream;
 }
 
@@ -205,13 +202,13 @@ hipStream_t side_stream(rtx_ctx* ctx)
 void slot_mark_done(rtx_ctx::CellCacheSlot& sl, hipStream_t stream)
 {
     if (sl.n_done == sl.done.size()) {
-        hipEvent_t ev = nullptr;
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
+        Event ev;
+        if (ev.ensure() != hipSuccess) {
             (void)hipGetLastError();
             hipDeviceSynchronize();
             return;
         }
-        sl.done.push_back(ev);
+        sl.done.push_back(std::move(ev));
     }
     if (hipEventRecord(sl.done[sl.n_done], stream) != hipSuccess) {
         (void)hipGetLastError();
@@ -265,59 +262,38 @@ int cells_per_frame(rtx_ctx* ctx, hipStream_t stream, KArgs& a, const rtxplan::C
         if (ctx->cell_scratch.size() >= 16) {
             // a caller that keeps creating streams: recycle the oldest set (its stream may be gone, so wait for the device)
             hipDeviceSynchronize();
-            rtx_ctx::CellScratch& old = ctx->cell_scratch.front();
-            if (old.list) hipFree(old.list);
-            if (old.count) hipFree(old.count);
             ctx->cell_scratch.erase(ctx->cell_scratch.begin());
         }
         ctx->cell_scratch.emplace_back();
         cs = &ctx->cell_scratch.back();
         cs->stream = stream;
     }
-    if (cs->list_words < need_list) {
-        // launches queued on this stream may still read the old lists
-        if (cs->list) {
-            hipStreamSynchronize(stream);
-            hipFree(cs->list);
-        }
-        cs->list = nullptr;
-        cs->list_words = 0;
-        if (hipMalloc((void**)&cs->list, need_list * sizeof(uint32_t)) != hipSuccess) {
-            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell lists");
-        }
-        cs->list_words = need_list;
+    // launches queued on this stream may still read the old lists
+    if (cs->list.reserve(need_list, rtxmem::after_stream(stream)) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell lists");
     }
-    if (cs->count_words < need_count || cs->n_cells != g.n_cells) {
+    if (cs->count.capacity() < need_count || cs->n_cells != g.n_cells) {
         // (re)start the two alternating counter buffers from zero for this cell grid
-        if (cs->count_words < need_count) {
-            if (cs->count) {
-                hipStreamSynchronize(stream);
-                hipFree(cs->count);
-            }
-            cs->count = nullptr;
-            cs->count_words = 0;
-            if (hipMalloc((void**)&cs->count, need_count * sizeof(uint32_t)) != hipSuccess) {
-                return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell counts");
-            }
-            cs->count_words = need_count;
+        if (cs->count.reserve(need_count, rtxmem::after_stream(stream)) != hipSuccess) {
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell counts");
         }
-        RTX_HIP(ctx, hipMemsetAsync(cs->count, 0, cs->count_words * sizeof(uint32_t), stream));
+        RTX_HIP(ctx, hipMemsetAsync(cs->count.get(), 0, cs->count.capacity() * sizeof(uint32_t), stream));
         cs->n_cells = g.n_cells;
         cs->flip = 0;
     }
     fill_cell_args(a, g);
     a.bin_theta = a.bin_delta = 0.0f;
-    a.cell_list_out = cs->list;
-    a.cell_count_out = cs->count + (size_t)cs->flip * g.n_cells;
-    a.cell_count_zero = cs->count + (size_t)(cs->flip ^ 1u) * g.n_cells;
+    a.cell_list_out = cs->list.get();
+    a.cell_count_out = cs->count.get() + (size_t)cs->flip * g.n_cells;
+    a.cell_count_zero = cs->count.get() + (size_t)(cs->flip ^ 1u) * g.n_cells;
     cs->flip ^= 1u;
-    a.cell_max_out = ctx->d_cell_max;
+    a.cell_max_out = ctx->d_cell_max.get();
     const int be = rtx_k_launch_bin_cells(&a, g.splits, stream);
     if (be != 0) return rtx_hip_fail(ctx, (hipError_t)be, "cell binning launch");
-    if (ctx->d_cell_max && (ctx->per_frame_bins++ & 15u) == 0u) { // (a copy packet between kernels costs a few us: now and then only)
-        RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_cell_max, ctx->d_cell_max, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    if (ctx->d_cell_max.get() && (ctx->per_frame_bins++ & 15u) == 0u) { // (a copy packet between kernels costs a few us: now and then only)
+        RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_cell_max.get(), ctx->d_cell_max.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
     }
-    a.cell_list = cs->list;
+    a.cell_list = cs->list.get();
     a.cell_count = a.cell_count_out;
     ctx->stat_cell_per_frame++;
     return RTX_OK;
@@ -329,30 +305,18 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
 {
     rtx_ctx::CellCacheSlot& sl = ctx->cell_cache[si];
     const size_t need_list = (size_t)g.n_cells * g.cap, need_count = (size_t)g.n_cells;
-    if (sl.list_words < need_list || sl.count_words < need_count) {
-        hipDeviceSynchronize(); // rare (a larger grid or scene): nothing may still read the old buffers
-        if (sl.list_words < need_list) {
-            if (sl.list) hipFree(sl.list);
-            sl.list = nullptr;
-            sl.list_words = 0;
-            if (hipMalloc((void**)&sl.list, need_list * sizeof(uint32_t)) != hipSuccess) {
-                return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell lists");
-            }
-            sl.list_words = need_list;
+    if (sl.list.capacity() < need_list || sl.count.capacity() < need_count) {
+        // rare (a larger grid or scene): nothing may still read the old buffers, on any stream
+        if (sl.list.reserve(need_list, rtxmem::after_device()) != hipSuccess) {
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell lists");
         }
-        if (sl.count_words < need_count) {
-            if (sl.count) hipFree(sl.count);
-            sl.count = nullptr;
-            sl.count_words = 0;
-            if (hipMalloc((void**)&sl.count, need_count * sizeof(uint32_t)) != hipSuccess) {
-                return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell counts");
-            }
-            sl.count_words = need_count;
+        if (sl.count.reserve(need_count, rtxmem::after_device()) != hipSuccess) {
+            return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell counts");
         }
         sl.readers.clear();
         sl.n_done = 0;
     }
-    if (!sl.ev_built) RTX_HIP(ctx, hipEventCreateWithFlags(&sl.ev_built, hipEventDisableTiming));
+    RTX_HIP(ctx, sl.ev_built.ensure());
     // after the slot's previous build, and after the launches that read its old lists: the streams that have not launched
     // anything since their last read of it are marked now, the others were when they moved on (cell_slot_use)
     if (sl.ever_built) RTX_HIP(ctx, hipStreamWaitEvent(build, sl.ev_built, 0));
@@ -370,25 +334,25 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
     if (on_side && ctx->ns_moved_since_build) {
         // the sphere positions the lists are built from are those of this moment: physics steps queued so far (on the
         // context's stream) are done before the pass reads them; rtx_update_objects in turn waits for a pass in flight
-        if (!ctx->ev_physics) RTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_physics, hipEventDisableTiming));
+        RTX_HIP(ctx, ctx->ev_physics.ensure());
         RTX_HIP(ctx, hipEventRecord(ctx->ev_physics, ctx->stream));
         RTX_HIP(ctx, hipStreamWaitEvent(build, ctx->ev_physics, 0));
         ctx->ns_moved_since_build = false;
     }
     (void)render;
     sl.waited.clear();
-    RTX_HIP(ctx, hipMemsetAsync(sl.count, 0, need_count * sizeof(uint32_t), build));
+    RTX_HIP(ctx, hipMemsetAsync(sl.count.get(), 0, need_count * sizeof(uint32_t), build));
     fill_cell_args(a, g);
     a.bin_theta = budget.theta;
     a.bin_delta = budget.delta;
-    a.cell_list_out = sl.list;
-    a.cell_count_out = sl.count;
+    a.cell_list_out = sl.list.get();
+    a.cell_count_out = sl.count.get();
     a.cell_count_zero = nullptr;
-    a.cell_max_out = ctx->d_cell_max;
+    a.cell_max_out = ctx->d_cell_max.get();
     const int be = rtx_k_launch_bin_cells(&a, g.splits, build);
     if (be != 0) return rtx_hip_fail(ctx, (hipError_t)be, "cell binning launch");
     RTX_HIP(ctx, hipEventRecord(sl.ev_built, build));
-    if (ctx->d_cell_max) RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_cell_max, ctx->d_cell_max, sizeof(uint32_t), hipMemcpyDeviceToHost, build));
+    if (ctx->d_cell_max.get()) RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_cell_max.get(), ctx->d_cell_max.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, build));
     sl.ever_built = true;
     sl.known_ready = false;
     sl.built_on_aux = on_side;
@@ -420,8 +384,8 @@ int cell_slot_use(rtx_ctx* ctx, int si, hipStream_t stream, KArgs& a, const rtxp
         sl.readers.push_back(stream);
     }
     fill_cell_args(a, g);
-    a.cell_list = sl.list;
-    a.cell_count = sl.count;
+    a.cell_list = sl.list.get();
+    a.cell_count = sl.count.get();
     return RTX_OK;
 }
 
@@ -445,29 +409,21 @@ const uint32_t* xcd_tile_order(rtx_ctx* ctx, const rtxplan::TileShape& t, const 
     // does not pay a device synchronisation and a blocking upload at every switch
     rtx_ctx::XcdOrder* slot = nullptr;
     for (auto& e : ctx->xcd_orders) {
-        if (e.p && e.key[0] == key[0] && e.key[1] == key[1]) {
+        if (e.p.get() && e.key[0] == key[0] && e.key[1] == key[1]) {
             e.last_use = ++ctx->order_clock;
-            return e.p;
+            return e.p.get();
         }
-        if (!slot || (slot->p && (!e.p || e.last_use < slot->last_use))) slot = &e; // an empty entry, else the least recently used
+        if (!slot || (slot->p.get() && (!e.p.get() || e.last_use < slot->last_use))) slot = &e; // an empty entry, else the least recently used
     }
     // (rare: a new grid) launches in flight may still read the order being replaced
-    if (slot->p) hipDeviceSynchronize();
-    if (slot->cap < n) {
-        if (slot->p) hipFree(slot->p);
-        slot->p = nullptr;
-        slot->cap = 0;
+    if (slot->p.get()) hipDeviceSynchronize();
+    if (slot->p.reserve(n, rtxmem::nothing()) != hipSuccess) {
         slot->key[0] = slot->key[1] = 0;
-        if (hipMalloc((void**)&slot->p, n * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            slot->p = nullptr;
-            return nullptr; // frame order
-        }
-        slot->cap = n;
+        return nullptr; // frame order
     }
     std::vector<uint32_t> order(n);
     rtxplan::xcd_cell_order(t.grid_x, t.grid_y, g.gx, g.gy, order.data());
-    if (hipMemcpy(slot->p, order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(slot->p.get(), order.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipGetLastError();
         slot->key[0] = slot->key[1] = 0;
         return nullptr;
@@ -475,7 +431,7 @@ const uint32_t* xcd_tile_order(rtx_ctx* ctx, const rtxplan::TileShape& t, const 
     slot->key[0] = key[0];
     slot->key[1] = key[1];
     slot->last_use = ++ctx->order_clock;
-    return slot->p;
+    return slot->p.get();
 }
 
 // Two-level culling for this launch: cell lists from the cache when they cover the camera (building or prefetching as
@@ -497,16 +453,12 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
         ctx->render_streams_seen = distinct;
     }
     // capacity feedback: one word per context, reset when the grid or the scene changes
-    if (!ctx->d_cell_max) {
-        void* h = nullptr;
-        if (hipMalloc((void**)&ctx->d_cell_max, sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&h, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            if (ctx->d_cell_max) hipFree(ctx->d_cell_max);
-            ctx->d_cell_max = nullptr; // no feedback: the default capacity and the whole-scene fallback
+    if (!ctx->d_cell_max.get()) {
+        if (ctx->d_cell_max.reserve(1, rtxmem::nothing()) != hipSuccess || ctx->h_cell_max.reserve(1, rtxmem::nothing()) != hipSuccess) {
+            ctx->d_cell_max.release(); // no feedback: the default capacity and the whole-scene fallback
         } else {
-            ctx->h_cell_max = (volatile uint32_t*)h;
-            *ctx->h_cell_max = 0u;
-            RTX_HIP(ctx, hipMemsetAsync(ctx->d_cell_max, 0, sizeof(uint32_t), stream));
+            *ctx->h_cell_max.get() = 0u;
+            RTX_HIP(ctx, hipMemsetAsync(ctx->d_cell_max.get(), 0, sizeof(uint32_t), stream));
         }
     }
     rtxplan::CellGrid g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt_cell_capacity, 0);
@@ -516,14 +468,14 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
         if (std::memcmp(id, ctx->cell_grid_id, sizeof id) != 0) {
             std::memcpy(ctx->cell_grid_id, id, sizeof id);
             ctx->cell_cap_floor = 0;
-            if (ctx->d_cell_max) {
+            if (ctx->d_cell_max.get()) {
                 // (in stream order after earlier passes on this stream; a pass still running on another stream may add its
                 // maximum once more: harmless, it only keeps the lists a little longer than needed)
-                RTX_HIP(ctx, hipMemsetAsync(ctx->d_cell_max, 0, sizeof(uint32_t), stream));
-                *ctx->h_cell_max = 0u;
+                RTX_HIP(ctx, hipMemsetAsync(ctx->d_cell_max.get(), 0, sizeof(uint32_t), stream));
+                *ctx->h_cell_max.get() = 0u;
             }
         }
-        if (ctx->h_cell_max) ctx->cell_cap_floor = rtxplan::cell_capacity_wanted(*ctx->h_cell_max, g.cap > ctx->cell_cap_floor ? g.cap : ctx->cell_cap_floor, ctx->cell_cap_floor);
+        if (ctx->h_cell_max.get()) ctx->cell_cap_floor = rtxplan::cell_capacity_wanted(*ctx->h_cell_max.get(), g.cap > ctx->cell_cap_floor ? g.cap : ctx->cell_cap_floor, ctx->cell_cap_floor);
         if (ctx->cell_cap_floor) g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt_cell_capacity, ctx->cell_cap_floor);
     }
     *static_order = still_only ? nullptr : xcd_tile_order(ctx, shape, g);
@@ -612,12 +564,6 @@ rtx_ctx::TileOrder* tile_order_set(rtx_ctx* ctx, hipStream_t stream, const uint6
             }
             if (lru == ctx->tile_orders.size()) return nullptr; // every set is frozen: frame order
             hipDeviceSynchronize(); // launches (and a pass) may still use its buffers; its stream may be gone
-            rtx_ctx::TileOrder& old = ctx->tile_orders[lru];
-            if (old.cost) hipFree(old.cost);
-            if (old.order) hipFree(old.order);
-            if (old.factor) hipFree(old.factor);
-            if (old.ev_rec) hipEventDestroy(old.ev_rec);
-            if (old.ev_done) hipEventDestroy(old.ev_done);
             ctx->tile_orders.erase(ctx->tile_orders.begin() + (long)lru);
         }
         rtx_ctx::TileOrder fresh;
@@ -625,22 +571,13 @@ rtx_ctx::TileOrder* tile_order_set(rtx_ctx* ctx, hipStream_t stream, const uint6
         std::memcpy(fresh.key, key, sizeof fresh.key);
         // cost: the estimates by tile, then the workgroups' start and end times by dispatch position; two orders: the one in
         // use and the one a balancing pass writes
-        if (hipMalloc((void**)&fresh.cost, 3 * (size_t)n_tiles * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void**)&fresh.order, 2 * (size_t)n_tiles * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void**)&fresh.factor, (size_t)n_tiles * sizeof(float)) != hipSuccess ||
-            hipEventCreateWithFlags(&fresh.ev_rec, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&fresh.ev_done, hipEventDisableTiming) != hipSuccess) {
+        if (fresh.cost.reserve(3 * (size_t)n_tiles, rtxmem::nothing()) != hipSuccess || fresh.order.reserve(2 * (size_t)n_tiles, rtxmem::nothing()) != hipSuccess ||
+            fresh.factor.reserve((size_t)n_tiles, rtxmem::nothing()) != hipSuccess || fresh.ev_rec.ensure() != hipSuccess || fresh.ev_done.ensure() != hipSuccess) {
             (void)hipGetLastError();
-            if (fresh.cost) hipFree(fresh.cost);
-            if (fresh.order) hipFree(fresh.order);
-            if (fresh.factor) hipFree(fresh.factor);
-            if (fresh.ev_rec) hipEventDestroy(fresh.ev_rec);
-            if (fresh.ev_done) hipEventDestroy(fresh.ev_done);
-            return nullptr; // no memory for it: render in frame order
+            return nullptr; // no memory for it: render in frame order (what `fresh` holds goes with it)
         }
-        fresh.cap = n_tiles;
         fresh.id = ctx->next_order_id++;
-        ctx->tile_orders.push_back(fresh);
+        ctx->tile_orders.push_back(std::move(fresh));
         to = &ctx->tile_orders.back();
     }
     to->last_use = ++ctx->order_clock;
@@ -659,22 +596,22 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
     if (rc != RTX_OK) return rc;
     const rtx_ctx::QueryGrid& g = ctx->qgrid;
     if (g.brute || g.plan.ok == 0u || g.n_cells == 0u) return RTX_OK;
-    if (!ctx->d_shadow_grid_fallback) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_grid_fallback, sizeof(uint32_t)));
+    RTX_HIP(ctx, ctx->d_shadow_grid_fallback.reserve(1, rtxmem::nothing()));
     gs->grid = g.plan;
-    gs->cell_start = (const uint32_t*)g.cell_count.p;
-    gs->list_geom = (const float4*)g.list_geom.p;
-    gs->list_gidx = (const uint32_t*)g.list_gidx.p;
-    gs->scene_geom = (const float4*)ctx->d_sph_geom.p;
-    gs->scene_od = (const float4*)ctx->d_sph_od.p;
-    gs->large = g.d_large;
+    gs->cell_start = g.cell_count.get();
+    gs->list_geom = g.list_geom.get();
+    gs->list_gidx = g.list_gidx.get();
+    gs->scene_geom = ctx->d_sph_geom.get();
+    gs->scene_od = ctx->d_sph_od.get();
+    gs->large = g.d_large.get();
     gs->n_large = g.n_large;
-    gs->fallback = ctx->d_shadow_grid_fallback;
+    gs->fallback = ctx->d_shadow_grid_fallback.get();
     *in_effect = true;
     return RTX_OK;
 }
 
 // The hit buffer of `stream` with room for `bytes` (rtx_ctx::HitScratch).  At most kMaxHitStreams distinct streams (as
-// rtx_submit_slabs' join events).  An outgrown buffer is freed (hipFree waits for the device, so no queued launch still reads it),
+// rtx_submit_slabs' join events).  An outgrown buffer is freed (freeing device memory waits for the device, so no queued launch still reads it),
 // unless a recorded graph may read it: then it is kept until rtx_destroy.
 int hit_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, bool capturing, void** out)
 {
@@ -686,29 +623,18 @@ int hit_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, bool capturing, v
         if (ctx->hit_scratch.size() >= (size_t)rtx_ctx::kMaxHitStreams) {
             return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "light / shadow path: more than 64 distinct render streams");
         }
-        ctx->hit_scratch.push_back(rtx_ctx::HitScratch());
+        ctx->hit_scratch.emplace_back();
         hs = &ctx->hit_scratch.back();
         hs->stream = stream;
     }
-    if (hs->bytes < bytes) {
-        if (capturing) {
-            // (hipFree is not allowed while a stream captures; a buffer that grows here is kept)
-            if (hs->p) ctx->hit_retired.push_back(hs->p);
-        } else if (hs->p) {
-            if (hs->recorded) {
-                ctx->hit_retired.push_back(hs->p);
-            } else {
-                RTX_HIP(ctx, hipFree(hs->p));
-            }
-        }
-        hs->p = nullptr;
-        hs->bytes = 0;
+    if (hs->p.capacity() < bytes) {
+        // (nothing may be freed while a stream captures; a buffer that grows here, or that a recorded graph reads, is kept)
+        if (hs->p.get() && (capturing || hs->recorded)) ctx->hit_retired.push_back(std::move(hs->p));
         hs->recorded = false;
-        RTX_HIP(ctx, hipMalloc(&hs->p, bytes));
-        hs->bytes = bytes;
+        RTX_HIP(ctx, hs->p.reserve(bytes, rtxmem::nothing())); // (the free waits for the device itself)
     }
     if (capturing) hs->recorded = true;
-    *out = hs->p;
+    *out = hs->p.get();
     return RTX_OK;
 }
 
@@ -737,7 +663,7 @@ ShadowArgs shadow_args(const rtx_ctx* ctx, const void* hits)
                       l.specular_rgb[0], l.specular_rgb[1], l.specular_rgb[2], l.specular_power};
     sa.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
     sa.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
-    sa.longest = ctx->d_shadow_longest;
+    sa.longest = ctx->d_shadow_longest.get();
     return sa;
 }
 
@@ -750,7 +676,7 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     rtxlights::pack(ctx->n_lights, ctx->lights, &la.lights); // (the set was validated when it was stored)
     la.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
     la.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
-    la.longest = ctx->d_shadow_longest;
+    la.longest = ctx->d_shadow_longest.get();
     return la;
 }
 
@@ -767,16 +693,10 @@ int upload_reflectivity(rtx_ctx* ctx)
     for (size_t p = 0; sorted && p < ns; p++) kso[p] = ks[ctx->h_sorted_idx[p]];
     RTX_HIP(ctx, hipDeviceSynchronize());
     for (const auto& pr : {std::make_pair(&ctx->d_refl_sph, &ks), std::make_pair(&ctx->d_refl_sorted, &kso), std::make_pair(&ctx->d_refl_pl, &kp)}) {
-        DeviceArray& d = *pr.first;
+        DeviceBuf<float>& d = *pr.first;
         const std::vector<float>& h = *pr.second;
-        if (d.cap < h.size()) {
-            if (d.p) RTX_HIP(ctx, hipFree(d.p));
-            d.p = nullptr;
-            d.cap = 0;
-            RTX_HIP(ctx, hipMalloc(&d.p, h.size() * sizeof(float)));
-            d.cap = h.size();
-        }
-        RTX_HIP(ctx, hipMemcpy(d.p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing())); // (the device has just been waited for)
+        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     ctx->refl_dirty = false;
     return RTX_OK;
@@ -814,16 +734,16 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     void* hit_base = nullptr;
     if ((rc = hit_buffer(ctx, stream, px * plan.bytes_per_px, capturing, &hit_base)) != RTX_OK) return rc;
     char* const hits = (char*)hit_base;
-    if (!ctx->d_shadow_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_shadow_longest, sizeof(uint32_t)));
-    if (mirror && !ctx->d_reflect_longest) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_longest, sizeof(uint32_t)));
-    if (plan.chain() && !ctx->d_reflect_rays) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_rays, per_level));
-    if (plan.deep && !ctx->d_reflect_shadow_points) RTX_HIP(ctx, hipMalloc((void**)&ctx->d_reflect_shadow_points, per_level));
+    RTX_HIP(ctx, ctx->d_shadow_longest.reserve(1, rtxmem::nothing()));
+    if (mirror) RTX_HIP(ctx, ctx->d_reflect_longest.reserve(1, rtxmem::nothing()));
+    if (plan.chain()) RTX_HIP(ctx, ctx->d_reflect_rays.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
+    if (plan.deep) RTX_HIP(ctx, ctx->d_reflect_shadow_points.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
-    if (mirror) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest, 0, sizeof(uint32_t), stream));
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest, 0, sizeof(uint32_t), stream));
-    if (plan.chain()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays, 0, per_level, stream));
-    if (plan.deep) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points, 0, per_level, stream));
-    if (plan.dark0) RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback, 0, sizeof(uint32_t), stream));
+    if (mirror) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest.get(), 0, sizeof(uint32_t), stream));
+    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest.get(), 0, sizeof(uint32_t), stream));
+    if (plan.chain()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays.get(), 0, per_level, stream));
+    if (plan.deep) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points.get(), 0, per_level, stream));
+    if (plan.dark0) RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback.get(), 0, sizeof(uint32_t), stream));
     if (mirror) { // (the other paths leave reflect_rays_valid as it is)
         ctx->reflect_rays_valid = plan.chain();
         ctx->reflect_shadow_points_valid = plan.deep;
@@ -854,19 +774,19 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     if (mirror) {
         ra.hits = (const uint2*)hits;
         ra.hits2 = (uint2*)(hits + 8u * px); // level 1's
-        ra.k_sph = (const float*)(a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.p : ctx->d_refl_sph.p);
-        ra.k_pl = (const float*)ctx->d_refl_pl.p;
+        ra.k_sph = a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.get() : ctx->d_refl_sph.get();
+        ra.k_pl = ctx->d_refl_pl.get();
         ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
-        ra.longest = ctx->d_reflect_longest;
+        ra.longest = ctx->d_reflect_longest.get();
     }
     if (plan.chain()) {
         ca.depth = plan.levels - 1u;
         ca.px = (uint32_t)px;
-        ca.rays = ctx->d_reflect_rays;
+        ca.rays = ctx->d_reflect_rays.get();
     }
     if (plan.deep) {
         cs.dark = (uint32_t*)(hits + plan.deep_off * px);
-        cs.points = ctx->d_reflect_shadow_points;
+        cs.points = ctx->d_reflect_shadow_points.get();
     }
     if (plan.dark0) {
         gs.dark0 = (uint32_t*)(hits + plan.dark0_off * px);
@@ -919,7 +839,7 @@ int validate_render_call(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row
     if (own) {
         if (out_row_base != 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "out_row_base must be 0 with the context's buffer");
         if (20 * W * H > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
-        d_out = ctx->d_frame;
+        d_out = ctx->d_frame.get();
     } else if (row0 < out_row_base) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "row0 is before out_row_base");
     }
@@ -966,19 +886,19 @@ void fill_frame_args(const rtx_ctx* ctx, const rtx_params* p, const RenderCall& 
     a.out_row_base = (uint32_t)c.out_row_base;
     a.ns = ctx->ns;
     a.np = ctx->np;
-    a.sph_geom = a.sph_scene_geom = (const float4*)ctx->d_sph_geom.p;
-    a.sph_od = (const float4*)ctx->d_sph_od.p;
-    if (ctx->opt_sorted_store != 0 && ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.p != nullptr) {
+    a.sph_geom = a.sph_scene_geom = ctx->d_sph_geom.get();
+    a.sph_od = ctx->d_sph_od.get();
+    if (ctx->opt_sorted_store != 0 && ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr) {
         // the trace kernels read the direction-sorted copies, by position
-        a.sph_geom = (const float4*)ctx->d_sorted_geom.p;
-        a.sph_od = (const float4*)ctx->d_sorted_od.p;
-        a.sph_sorted_idx = (const uint32_t*)ctx->d_sorted_idx.p;
-        a.sph_pos_of = (const uint32_t*)ctx->d_pos_of.p;
+        a.sph_geom = ctx->d_sorted_geom.get();
+        a.sph_od = ctx->d_sorted_od.get();
+        a.sph_sorted_idx = ctx->d_sorted_idx.get();
+        a.sph_pos_of = ctx->d_pos_of.get();
     }
-    a.pl_a = (const float4*)ctx->d_pl_a.p;
-    a.pl_b = (const float4*)ctx->d_pl_b.p;
-    a.pl_od = (const float4*)ctx->d_pl_od.p;
-    a.grey = ctx->d_grey;
+    a.pl_a = ctx->d_pl_a.get();
+    a.pl_b = ctx->d_pl_b.get();
+    a.pl_od = ctx->d_pl_od.get();
+    a.grey = ctx->d_grey.get();
     a.out = (uint8_t*)c.d_out;
     a.compact = c.values ? 2u : (c.compact ? 1u : 0u);
     a.cells_x = a.cells_y = 1;
@@ -1006,22 +926,18 @@ bool view_adaptation_applies(const rtx_ctx* ctx, const rtxplan::TileRequest& q, 
 // ... the launch's side of it: where its workgroups report to.
 int density_feedback_args(rtx_ctx* ctx, hipStream_t stream, bool view_dense, KArgs& a)
 {
-    if (!ctx->d_longest) {
-        void* h = nullptr;
-        if (hipMalloc((void**)&ctx->d_longest, 3 * sizeof(uint32_t)) != hipSuccess || hipHostMalloc(&h, sizeof(uint32_t), hipHostMallocDefault) != hipSuccess ||
-            hipEventCreateWithFlags(&ctx->ev_longest, hipEventDisableTiming) != hipSuccess) {
+    if (!ctx->d_longest.get()) {
+        if (ctx->d_longest.reserve(3, rtxmem::nothing()) != hipSuccess || ctx->h_longest.reserve(1, rtxmem::nothing()) != hipSuccess || ctx->ev_longest.ensure() != hipSuccess) {
             (void)hipGetLastError();
-            if (ctx->d_longest) hipFree(ctx->d_longest);
-            if (h) hipHostFree(h);
-            ctx->d_longest = nullptr;
+            ctx->d_longest.release();
+            ctx->h_longest.release();
             ctx->opt_view_adapt = 0; // no feedback: the plan follows the scene's numbers alone
             return RTX_OK;
         }
-        ctx->h_longest = (volatile uint32_t*)h;
-        *ctx->h_longest = 0u;
-        RTX_HIP(ctx, hipMemsetAsync(ctx->d_longest, 0, 3 * sizeof(uint32_t), stream));
+        *ctx->h_longest.get() = 0u;
+        RTX_HIP(ctx, hipMemsetAsync(ctx->d_longest.get(), 0, 3 * sizeof(uint32_t), stream));
     }
-    a.longest_list = ctx->d_longest;
+    a.longest_list = ctx->d_longest.get();
     a.longest_from = view_dense ? rtxplan::ViewDensity::kLightDense : rtxplan::ViewDensity::kReportSparse;
     a.longest_slot = ctx->longest_epoch % 3u;
     return RTX_OK;
@@ -1033,18 +949,18 @@ int density_feedback_args(rtx_ctx* ctx, hipStream_t stream, bool view_dense, KAr
 // zeroes (last filled two epochs ago) is never one whose copy is still to run, whatever streams the launches are on.
 int density_feedback_collect(rtx_ctx* ctx, hipStream_t stream)
 {
-    if (!ctx->d_longest || (++ctx->longest_launches & 7u) != 0u) return RTX_OK;
+    if (!ctx->d_longest.get() || (++ctx->longest_launches & 7u) != 0u) return RTX_OK;
     bool landed = !ctx->longest_copy_pending;
     if (ctx->longest_copy_pending) {
         if (hipEventQuery(ctx->ev_longest) == hipSuccess) landed = true;
         else (void)hipGetLastError();
         if (landed) {
-            if (ctx->view_density.observe(*ctx->h_longest)) ctx->stat_density_switches++;
+            if (ctx->view_density.observe(*ctx->h_longest.get())) ctx->stat_density_switches++;
             ctx->longest_copy_pending = false;
         }
     }
     if (landed) {
-        RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_longest, ctx->d_longest + (ctx->longest_epoch % 3u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_longest.get(), ctx->d_longest.get() + (ctx->longest_epoch % 3u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         RTX_HIP(ctx, hipEventRecord(ctx->ev_longest, stream));
         ctx->longest_copy_pending = true;
         ctx->longest_epoch++;
@@ -1093,19 +1009,19 @@ int dispatch_order_args(rtx_ctx* ctx, hipStream_t stream, const rtx_params* p, c
                             ctx->capture_frozen.push_back(e.id);
                             e.frozen_refs++;
                         }
-                        a.tile_order = e.order + (size_t)e.plan.current_half() * e.cap;
+                        a.tile_order = e.order.get() + (size_t)e.plan.current_half() * e.cap();
                     }
                 }
             } else if (one_round && !side_stream(ctx)) {
                 // no side stream for the passes: frame order
             } else if ((to = tile_order_set(ctx, stream, key, (uint32_t)nt)) != nullptr) {
                 if (to->frozen) {
-                    a.tile_order = to->order + (size_t)to->plan.current_half() * to->cap; // as recorded; nothing new is derived
+                    a.tile_order = to->order.get() + (size_t)to->plan.current_half() * to->cap(); // as recorded; nothing new is derived
                 } else {
                     *od = to->plan.next(rtxplan::view_of(p->inv_v, p->cam_pos), ctx->scene_drift, one_round, opt_eff);
                     if (od->switch_order) RTX_HIP(ctx, hipStreamWaitEvent(stream, to->ev_done, 0)); // the pass: by now long done
-                    a.tile_cost = od->leave_estimates ? to->cost : nullptr;
-                    a.tile_order = od->use_order ? to->order + (size_t)od->half * to->cap : nullptr;
+                    a.tile_cost = od->leave_estimates ? to->cost.get() : nullptr;
+                    a.tile_order = od->use_order ? to->order.get() + (size_t)od->half * to->cap() : nullptr;
                     to->base = static_order;
                     to->batch = batch_n != 0;
                     *to_out = to;
@@ -1126,11 +1042,11 @@ int dispatch_order_derive(rtx_ctx* ctx, hipStream_t stream, const rtxplan::TileS
         // every workgroup resident at once: deal the tiles so that the groups of workgroups that share a CU carry equal
         // work, correcting the estimates by how long each group took in the launch just queued (rtx_balance_tiles).
         // The pass is told the order that launch REALLY ran under (none, if the one in hand was stale).
-        uint32_t* next_order = to->order + (size_t)(od.half ^ 1) * to->cap;
+        uint32_t* next_order = to->order.get() + (size_t)(od.half ^ 1) * to->cap();
         hipError_t e = hipEventRecord(to->ev_rec, stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(ctx->aux_stream, to->ev_rec, 0);
         if (e != hipSuccess) return rtx_hip_fail(ctx, e, "tile order events");
-        const int oe = rtx_k_launch_balance_tiles(to->cost, nt, shape.grid_x, (uint32_t)ctx->n_cu, od.prev_is_order ? a.tile_order : nullptr, to->factor,
+        const int oe = rtx_k_launch_balance_tiles(to->cost.get(), nt, shape.grid_x, (uint32_t)ctx->n_cu, od.prev_is_order ? a.tile_order : nullptr, to->factor.get(),
                                                   od.have_factor ? 1 : 0, 1, next_order, ctx->aux_stream);
         if (oe != 0) return rtx_hip_fail(ctx, (hipError_t)oe, "tile order launch");
         e = hipEventRecord(to->ev_done, ctx->aux_stream);
@@ -1139,9 +1055,9 @@ int dispatch_order_derive(rtx_ctx* ctx, hipStream_t stream, const rtxplan::TileS
     } else if (od.sort_now) {
         // the estimates do not depend on the order they were produced under, so one pass settles a static view;
         // the second pass and the periodic ones follow a moving camera / scene
-        uint32_t* cur_order = to->order + (size_t)od.half * to->cap;
+        uint32_t* cur_order = to->order.get() + (size_t)od.half * to->cap();
         // (a batched launch interleaves its frames tile by tile: plain heaviest first, nothing dealt)
-        const int oe = rtx_k_launch_order_tiles(to->cost, nt, shape.grid_x, (uint32_t)ctx->n_cu, to->batch ? 0u : rtxplan::kResidentPerCU * (uint32_t)ctx->n_cu, to->base,
+        const int oe = rtx_k_launch_order_tiles(to->cost.get(), nt, shape.grid_x, (uint32_t)ctx->n_cu, to->batch ? 0u : rtxplan::kResidentPerCU * (uint32_t)ctx->n_cu, to->base,
                                                 cur_order, stream);
         if (oe != 0) return rtx_hip_fail(ctx, (hipError_t)oe, "tile order launch");
         ctx->stat_order_passes++;
@@ -1250,7 +1166,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
 int rtx_frame_zero_semantics(rtx_ctx* ctx, int mode, uint64_t W, uint64_t H, unsigned flags)
 {
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    return zero_fill_semantics(ctx, mode, W, H, ctx->d_frame, true, false, flags, ctx->stream);
+    return zero_fill_semantics(ctx, mode, W, H, ctx->d_frame.get(), true, false, flags, ctx->stream);
 }
 
 int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, size_t rows, void* d_out,
@@ -1349,7 +1265,7 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
     std::vector<rtx_ctx::JoinEvent*> used;
     ctx->join_events.reserve(64); // pointers into the vector stay valid
     if (join) {
-        if (!ctx->ev_fork) RTX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        RTX_HIP(ctx, ctx->ev_fork.ensure());
         RTX_HIP(ctx, hipEventRecord(ctx->ev_fork, join));
         for (size_t i = 0; i < n; i++) {
             hipStream_t s = streams[i] ? static_cast<hipStream_t>(streams[i]) : ctx->stream;
@@ -1362,8 +1278,8 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
                 if (ctx->join_events.size() >= 64) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_submit_slabs: more than 64 distinct streams");
                 rtx_ctx::JoinEvent fresh;
                 fresh.stream = s;
-                RTX_HIP(ctx, hipEventCreateWithFlags(&fresh.ev, hipEventDisableTiming));
-                ctx->join_events.push_back(fresh);
+                RTX_HIP(ctx, fresh.ev.ensure());
+                ctx->join_events.push_back(std::move(fresh));
                 je = &ctx->join_events.back();
             }
             bool seen = false;
