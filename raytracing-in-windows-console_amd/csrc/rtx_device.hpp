@@ -151,6 +151,32 @@ __device__ __forceinline__ float unit_rescale(float len2, const uint32_t* s_unit
     return r;
 }
 
+// ---- divTwoA = 1.0f / (2.0f * a) of a ray (RayTracing.cu:93), a = Dot(d, d) of a direction that fp32 has just normalised: the
+// same window of bit offsets from 1.0f, a second 16-entry table (rtx_unit.hpp: half_recip_bits) beside the first.  One subtract,
+// a compare, a mask and an LDS read replace the doubling, the rcp, its two correction FMAs and its range guard; lanes outside
+// the window take the generic expansion behind one wave-uniform branch.  The result is rcp_generic(2.0f * a)'s for every input
+// (tests/gpu_checks/half_check.hip: all 2^32 values of a).  unit: unit_rescale(a), read from the first table at the same slot
+// and corrected in the same branch, for the shading of the same ray -- viewDir's squared length is a's operations again.
+__device__ __forceinline__ void half_table_fill(uint32_t* s_half, uint32_t tid)
+{
+    if (tid < kUnitEntries) s_half[tid] = half_recip_bits((int32_t)tid + kUnitKMin);
+}
+
+__device__ __forceinline__ float half_recip(float a, const uint32_t* s_half, const uint32_t* s_unit, float& unit)
+{
+    const uint32_t slot = unit_slot(__float_as_uint(a));
+    float r = __uint_as_float(s_half[slot & (kUnitEntries - 1u)]);
+    unit = __uint_as_float(s_unit[slot & (kUnitEntries - 1u)]);
+    const bool odd = slot >= kUnitEntries;
+    if (__builtin_expect(__ballot(odd) != 0ull, 0)) {
+        if (odd) {
+            r = rcp_generic(2.0f * a);
+            unit = rcp_generic(sqrt_generic(a));
+        }
+    }
+    return r;
+}
+
 // normalize_gpu for a vector that normalize_gpu produced: the same bits for any vector
 __device__ __forceinline__ V3 renormalize_gpu(V3 a, const uint32_t* s_unit)
 {
@@ -188,6 +214,17 @@ __device__ __forceinline__ uint32_t u8_sat(float f)
     uint32_t u;
     asm("v_cvt_u32_f32 %0, %1" : "=v"(u) : "v"(f));
     return u & 255u;
+}
+
+// u8_sat(minf(255.0f, f)) -- a colour channel's byte -- without the float clamp: convert, then one integer minimum.  NaN and
+// negatives convert to 0 on both routes (minf(255, NaN) hands the NaN on), everything from 255.0f up, +inf and values past the u32
+// range included, gives 255, and below 255.0f nothing is clamped on either.  Equal for all 2^32 inputs (tests/gpu_checks/
+// half_check.hip); so a colour may arrive clamped or not.  (Not for RGB_NORMALS' normal * 255: that byte is not clamped, it wraps.)
+__device__ __forceinline__ uint32_t u8_clamped(float f)
+{
+    uint32_t u;
+    asm("v_cvt_u32_f32 %0, %1" : "=v"(u) : "v"(f));
+    return u < 255u ? u : 255u;
 }
 
 struct Ray {
@@ -272,11 +309,14 @@ __device__ __forceinline__ bool plane_hit(const Ray& r, V3 p, V3 n, float width,
 // plane's comes ready-made from the trace kernel's per-workgroup table, a sphere's is computed by the caller.  Every other
 // operation is the reference's, in its order (s_unit: the workgroup's table of unit_table_fill).
 // od in: object colour / 255.0f (RayTracing.cu:144; the division is done once per object at upload,
-// the same IEEE operation on the same operands); out: shaded colour clamped to <= 255.
-__device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 od, const uint32_t* s_unit)
+// the same IEEE operation on the same operands); out: shaded colour clamped to <= 255 -- or, CLAMP = false, as it stands before
+// that clamp, for an encoder that takes either (u8_clamped).  a_unit: unit_rescale(r.a).
+template <bool CLAMP>
+__device__ __forceinline__ V3 shade_nn(const Ray& r, float a_unit, float distance, V3 nn, V3 od, const uint32_t* s_unit)
 {
     const V3 point = add(r.o, mulf(r.d, distance));
-    const V3 viewDir = renormalize_gpu(mulf(r.d, -1.0f), s_unit); // (r.d is normalised; the squared length is r.a's operations again)
+    // (r.d is normalised; the squared length of -r.d is r.a's operations again: (-x) * (-x) = x * x exactly)
+    const V3 viewDir = mulf(mulf(r.d, -1.0f), a_unit);
 
     V3 lightDir = sub(v3(1.0f, 50.0f, 0.0f), point);
     float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
@@ -300,6 +340,7 @@ __device__ __forceinline__ V3 shade_nn(const Ray& r, float distance, V3 nn, V3 o
     res.y = 0.2f * od.y + diffuse * od.y + specular * 1.0f;
     res.z = 0.2f * od.z + diffuse * od.z + specular * 1.0f;
     res = mulf(res, 255.0f);
+    if (!CLAMP) return res;
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 

@@ -249,13 +249,13 @@ __device__ __forceinline__ Fields pixel_fields(const KArgs& a, const uint8_t* s_
             f.c1 = u8_sat(normal.y * 255.0f);
             f.c2 = u8_sat(normal.z * 255.0f);
         } else {
-            f.c0 = u8_sat(colour.x);
-            f.c1 = u8_sat(colour.y);
-            f.c2 = u8_sat(colour.z);
+            f.c0 = u8_clamped(colour.x);
+            f.c1 = u8_clamped(colour.y);
+            f.c2 = u8_clamped(colour.z);
         }
         f.glyph = (MODE == RTX_K_RGB_ASCII) ? (uint32_t)s_ramp[ramp_index(shadingValue)] : (uint32_t)' ';
     } else {
-        f.c0 = ansi256_from_rgb(u8_sat(colour.x), u8_sat(colour.y), u8_sat(colour.z), a.grey);
+        f.c0 = ansi256_from_rgb(u8_clamped(colour.x), u8_clamped(colour.y), u8_clamped(colour.z), a.grey);
         f.c1 = f.c2 = 0u;
         f.glyph = (MODE == RTX_K_BIT_ASCII) ? (uint32_t)s_ramp[ramp_index(shadingValue)] : (uint32_t)' ';
     }
@@ -324,16 +324,13 @@ __device__ __forceinline__ void encode_and_store(const KArgs& a, const Camera& c
 }
 
 // Exact tests of one ray against the candidate list (index is wave-uniform: LDS broadcast reads).
-// HOISTED: ray.divTwoA was computed before the loop (dense scenes: several candidates per pass reach the exact test, so
-// once per ray is cheaper than once per exact test; sparse scenes: 1 in 3 passes reaches none)
-template <bool HOISTED>
+// ray.divTwoA was filled before the loop, once per ray (half_recip, or the REFINE kernels' rcp_cr).
 __device__ __forceinline__ void test_candidate(Ray& ray, const float4 sr, const uint32_t* s_idx, const unsigned long long* rare, uint32_t i, Best& best, uint32_t& slow)
 {
     float s;
     const bool rejected = sphere_reject(ray, sr.x, sr.y, sr.z, sr.w, s);
     RTX_X_CANDIDATE_BEGIN();
     if (!rejected) {
-        if (!HOISTED) ray.divTwoA = rcp_cr(2.0f * ray.a); // RayTracing.cu:93; only the hit path reads it
         float t;
         if (sphere_hit(ray, s, sr.w, t)) {
             const uint32_t ki = s_idx[i];
@@ -346,12 +343,11 @@ __device__ __forceinline__ void test_candidate(Ray& ray, const float4 sr, const 
     }
     RTX_X_CANDIDATE_END(rejected, slow);
 }
-template <bool HOISTED>
 __device__ __forceinline__ void scan_candidates(Ray& ray, const float4* s_rec, const uint32_t* s_idx, const unsigned long long* rare, uint32_t total, Best& best,
                                                 uint32_t& slow)
 {
     for (uint32_t i = 0; i < total; i++) {
-        test_candidate<HOISTED>(ray, s_rec[i], s_idx, rare, i, best, slow);
+        test_candidate(ray, s_rec[i], s_idx, rare, i, best, slow);
     }
 }
 
@@ -370,7 +366,7 @@ __device__ __forceinline__ Ray ray_from_tables(const Camera& c, float4 A, float4
     r.d = normalize_gpu(w);
     r.a = dot(r.d, r.d);
     r.fourA = 4.0f * r.a;
-    r.divTwoA = 0.0f; // filled on the hit path only
+    r.divTwoA = 0.0f; // filled by the caller that tests spheres
     return r;
 }
 

@@ -12,7 +12,9 @@ namespace rtx {
 
 // Three decimal digits of i = 0..255, NUL padded (RayTracing.cu:212-229): d0 | d1 << 8 | d2 << 16.  Computed, not
 // loaded: every workgroup fills its LDS table from this at start-up, and a dozen integer instructions are cheaper
-// than a round trip to memory at the head of the kernel.
+// than a round trip to memory at the head of the kernel.  (Measured again in round 20 with the table requested beside the first
+// staging loads and written to LDS after them: C2 in flight 15.89 -> 15.83 us, one launch alone 22.24 -> 22.38, a difference
+// that two runs each do not resolve from the lone launch's own spread; arithmetic stays -- profiles/r20_ab_bench.tsv.)
 __host__ __device__ constexpr uint32_t digits_word(uint32_t i)
 {
     const uint32_t h = i / 100u, r = i - 100u * h, t = r / 10u, u = r - 10u * t;

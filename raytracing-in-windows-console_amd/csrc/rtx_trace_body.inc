@@ -17,6 +17,9 @@
     __shared__ float4 s_plane[kPlaneRow * kPlaneTable];
     __shared__ uint32_t s_digits[256];           // three decimal digits of 0..255, NUL padded
     __shared__ uint32_t s_unit[kUnitEntries];    // rescale factors of nearly-unit squared lengths (rtx_unit.hpp)
+    // 1 / (2 a) of a ray's nearly-unit a, same slots (rtx_device.hpp: half_recip; the REFINE kernels do not use it).  With these
+    // 64 bytes the brute kernels hold 27 280 B of the 27 306 that leave them 6 workgroups per CU: the next table costs them one.
+    __shared__ uint32_t s_half[REFINE ? 1 : kUnitEntries];
     __shared__ __attribute__((aligned(4))) uint8_t s_ramp[68]; // the glyph ramp (RayTracing.h:97-115)
     __shared__ uint32_t s_wcnt[2][8];            // survivors per wave and half of the current step, double-buffered
     __shared__ float s_frustum[16];              // the macro tile's five plane normals
@@ -134,6 +137,7 @@
     // ---- per-workgroup tables (visible after the first barrier below)
     s_digits[tid] = digits_word(tid);
     unit_table_fill(s_unit, tid);
+    if (!REFINE) half_table_fill(s_half, tid);
     // the glyph ramp is requested now and written to LDS after the staging loop (first read: encode), so that no
     // wave waits for it here
     uint32_t ramp4 = 0u;
@@ -287,7 +291,12 @@
         const bool newline_col = col + 1u == a.W;
         // lanes outside the frame trace a clamped pixel (the tables clamp) so every lane runs the same loops
         Ray ray = ray_from_tables(cam, s_col[jx * tw + tx], s_row[jy * th + ty]);
-        if (REFINE) ray.divTwoA = rcp_cr(2.0f * ray.a); // RayTracing.cu:93, once per ray here (see test_candidate)
+        // divTwoA (RayTracing.cu:93), once per ray: from the table by the slot of a, and with it the factor that shading rescales
+        // viewDir by.  (The REFINE kernels keep the computed form and look that factor up where they shade: they sit at the
+        // register limit, and a trial with the table put one of them into scratch.)
+        float a_unit = 0.0f;
+        if (REFINE) ray.divTwoA = rcp_cr(2.0f * ray.a);
+        else ray.divTwoA = half_recip(ray.a, s_half, s_unit, a_unit);
         Best b;
         b.t = kNoHit;
         b.k = 0xffffffffu;
@@ -330,12 +339,12 @@
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the wave's own LDS writes, before it reads them back
                     for (uint32_t q = 0; q < cnt; q++) {
                         const uint32_t i = s_wlist[wave][q];
-                        test_candidate<REFINE>(ray, s_rec[i], s_idx, s_rare_ptr, i, b, slow);
+                        test_candidate(ray, s_rec[i], s_idx, s_rare_ptr, i, b, slow);
                     }
                 }
             }
             if (!refined) {
-                if (!ABL(4u)) scan_candidates<REFINE>(ray, s_rec, s_idx, s_rare_ptr, total, b, slow);
+                if (!ABL(4u)) scan_candidates(ray, s_rec, s_idx, s_rare_ptr, total, b, slow);
             }
         } else {
             // rare: more candidates than the list holds.  Walk the scene again for this sub-tile, folding
@@ -366,7 +375,7 @@
                 tot = stage_chunk<CULL>(cam, fr2, nit, base, c0, c1, j0, j1, s_rec, s_idx, s_wcnt, par, tot, false, (uint32_t)kListCap); // (always fits: tot <= cap - 512 here)
                 if (tot > (uint32_t)(kListCap - kChunk) || base + kChunk >= nit) {
                     lds_barrier();
-                    scan_candidates<REFINE>(ray, s_rec, s_idx, s_rare_ptr, tot, b, slow);
+                    scan_candidates(ray, s_rec, s_idx, s_rare_ptr, tot, b, slow);
                     tot = 0;
                 }
             }
@@ -464,7 +473,9 @@
             }
             distance = b.t;
             if (MODE != RTX_K_RGB_NORMALS && MODE != RTX_K_SDL) {
-                colour = ABL(16u) ? mulf(od, 255.0f) : shade_nn(ray, distance, nn, od, s_unit);
+                if (REFINE) a_unit = unit_rescale(ray.a, s_unit);
+                // (the record and compact encoders clamp the byte themselves; the value floats are compared bit for bit and keep minf)
+                colour = ABL(16u) ? mulf(od, 255.0f) : shade_nn<OUT == kOutValues>(ray, a_unit, distance, nn, od, s_unit);
             }
         }
 

@@ -42,6 +42,26 @@ static_assert(unit_rescale_bits(-8) == 0x3f800002u && unit_rescale_bits(-5) == 0
               unit_rescale_bits(-1) == 0x3f800001u && unit_rescale_bits(0) == 0x3f800000u && unit_rescale_bits(1) == 0x3f800000u &&
               unit_rescale_bits(2) == 0x3f7ffffeu && unit_rescale_bits(3) == 0x3f7ffffeu, "unit rescale rule");
 
+// The same offset k fixes another function of a ray's squared length a: divTwoA = RN(1 / RN(2 a)) of RayTracing.cu:93.
+//   k >= 0:  2a = 2 + k 2^-22 exactly; 1 / (2a) = 1/2 - k 2^-24 + k^2 2^-47 - ..., and below 1/2 the spacing is 2^-25: the first
+//            two terms are 2k steps down from 1/2, the third is far below half a step.
+//   k <  0:  2a = 2 - j 2^-23, j = -k; 1 / (2a) = 1/2 + j 2^-25 + j^2 2^-49 + ..., and above 1/2 the spacing is 2^-24: j / 2 steps
+//            up; for odd j the second-order term puts the value on the upper side of the tie: (j + 1) >> 1.
+// The rule is exact for k in [-4095, +1448] (tests/host/test_half_recip.cpp finds both ends against 1.0f / (2.0f * x));
+// tests/gpu_checks/half_check.hip checks half_recip() of rtx_device.hpp for all 2^32 inputs.
+constexpr uint32_t kHalfBits = 0x3f000000u; // 0.5f
+constexpr int32_t kHalfRuleMin = -4095, kHalfRuleMax = 1448;
+static_assert(kUnitKMin >= kHalfRuleMin && kUnitKMax <= kHalfRuleMax, "window outside the half-reciprocal rule's range");
+
+// bits of RN(1 / RN(2 x)) for bits(x) = bits(1.0f) + k, kHalfRuleMin <= k <= kHalfRuleMax
+RTX_UNIT_HD constexpr uint32_t half_recip_bits(int32_t k)
+{
+    return k >= 0 ? kHalfBits - 2u * (uint32_t)k : kHalfBits + (uint32_t)((1 - k) >> 1);
+}
+static_assert(half_recip_bits(0) == 0x3f000000u && half_recip_bits(1) == 0x3efffffeu && half_recip_bits(3) == 0x3efffffau &&
+              half_recip_bits(-1) == 0x3f000001u && half_recip_bits(-2) == 0x3f000001u && half_recip_bits(-3) == 0x3f000002u &&
+              half_recip_bits(-12) == 0x3f000006u, "half-reciprocal rule");
+
 // Table slot of a squared length, from its bits: below kUnitEntries inside the window; everything else -- including
 // negative values, zeros, infinities and NaNs -- wraps to a large unsigned number.
 RTX_UNIT_HD constexpr uint32_t unit_slot(uint32_t len2_bits) { return len2_bits - (kUnitOneBits + (uint32_t)kUnitKMin); }
