@@ -5,6 +5,7 @@
 #include "rtx_kernels.h"
 #include "rtx_mem.hpp"
 #include "rtx_plan.hpp"
+#include "rtx_sync.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -157,21 +158,13 @@ struct rtx_ctx {
 
     // Coarse-cell lists that outlive a frame (two-level culling): two sets, shared by all render streams, each valid for
     // cameras within the motion budget it was binned with (rtxplan::CellCachePolicy).  A set is (re)built on the render
-    // stream that missed, or ahead of time on the side stream; readers on other streams wait for `ev_built` once.
+    // stream that missed, or ahead of time on the side stream; who waits for whom is `sync`'s contract (rtx_sync.hpp): a rebuild
+    // waits for each stream's last launch that read the set -- not for everything the render streams have queued since, which
+    // would drain the frames in flight at every rebuild.
     struct CellCacheSlot {
         DeviceBuf<uint32_t> list, count;
-        Event ev_built;
-        bool ever_built = false;
+        rtxsync::Shared sync;
         bool built_on_aux = false;              // the last build ran on the side stream
-        bool known_ready = false;               // the last build is known to have finished (hipEventQuery said so once)
-        std::vector<hipStream_t> waited;        // streams that are already ordered after the last build
-        // Launches that read this set: `readers` are the streams whose latest launch read it (no event yet: recorded when the
-        // stream first reads the other set, or when this set is rebuilt, whichever comes first); `done` are events recorded
-        // right after a stream's last launch reading it.  A rebuild waits for exactly these -- not for everything the
-        // render streams have queued since, which would drain the frames in flight at every rebuild.
-        std::vector<hipStream_t> readers;
-        std::vector<Event> done;                // in use: done[0 .. n_done)
-        size_t n_done = 0;
     };
     CellCacheSlot cell_cache[2];
     rtxplan::CellCachePolicy cell_policy;
@@ -300,8 +293,8 @@ struct rtx_ctx {
     bool reflect_shadow_points_valid = false;    // the launch set queued last ran rtx_chain_shadow (else the counters read 0)
 
     // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
-    // context's stream by the first query after a scene edit or a physics step (qgrid.dirty); queries on other streams wait for
-    // ev_built, and a rebuild waits for the last query (ev_done).
+    // context's stream by the first query after a scene edit or a physics step (qgrid.dirty).  The build is the writer of `sync`
+    // (rtx_sync.hpp); queries and the render launches that read the lists (RTX_OPT_SHADOW_GRID), on whatever stream, are its readers.
     struct QueryGrid {
         rtxgrid::Grid plan;
         bool dirty = true;            // the scene changed since the last build
@@ -313,16 +306,7 @@ struct rtx_ctx {
         DeviceBuf<uint32_t> d_large;  // kLargeCap sphere indices
         DeviceBuf<uint32_t> d_words;  // [0] pairs, [1] large spheres, [2] fallback rays of the last call, [4..10] bounds
         DeviceBuf<uint8_t> d_ray;     // rtx_pick's ray and hit (48 bytes)
-        Event ev_built, ev_done;
-        bool query_pending = false;   // ev_done has been recorded since the last build
-        // render launches that read the lists (RTX_OPT_SHADOW_GRID): an event per render stream, recorded behind the stream's last
-        // such launch; a rebuild waits for those marked pending
-        struct Reader {
-            hipStream_t stream = nullptr;
-            Event ev;
-            bool pending = false;
-        };
-        std::vector<Reader> readers;
+        rtxsync::Shared sync;
     };
     QueryGrid qgrid;
     int64_t opt_query_check = 0;
@@ -394,7 +378,9 @@ int rtx_remove_prepare(rtx_ctx* ctx, const std::vector<uint32_t>& ascending);
 // if the scene changed since its last build (a build blocks, as a query's does, and counts in RTX_STAT_QUERY_GRID_BUILDS); `stream` is
 // ordered after the build.  Not inside a graph capture.  Then rtx_grid_read, behind the launches: a later rebuild waits for them.
 int rtx_grid_ensure(rtx_ctx* ctx, hipStream_t stream);
-int rtx_grid_read(rtx_ctx* ctx, hipStream_t stream);
+void rtx_grid_read(rtx_ctx* ctx, hipStream_t stream);
+// rtx_render.cpp: whoever is about to write the sphere arrays on the context's stream waits for a cell-list build in flight on the side stream
+int rtx_wait_side_builds(rtx_ctx* ctx);
 bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status); // rtx_query.cpp: the RTX_STAT_QUERY_* values
 // the zero-fill bookkeeping of the context's own frame buffer for a frame of `mode` whose records something other than
 // rtx_render_rows is about to write there (a group's gathered slabs, its expanded words), on the context's stream

@@ -354,10 +354,7 @@ int rtx_edit_spheres_here(rtx_ctx* ctx, unsigned first, size_t n, const float* r
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     int rc = rtx_sync_scene(ctx);
     if (rc != RTX_OK) return rc;
-    // cell lists being built ahead of time on the side stream read the spheres: the edit waits for them (as a physics step does)
-    for (auto& sl : ctx->cell_cache) {
-        if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
-    }
+    if ((rc = rtx_wait_side_builds(ctx)) != RTX_OK) return rc; // (as a physics step does)
     if (after) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, after, 0));
     RTX_HIP(ctx, ctx->d_edit_result.reserve(2, rtxmem::nothing()));
     RTX_HIP(ctx, ctx->h_edit_result.reserve(2, rtxmem::nothing()));
@@ -441,10 +438,7 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
 {
     int rc = rtx_remove_prepare(ctx, ascending); // (nothing left to do where a group has prepared this member already)
     if (rc != RTX_OK) return rc;
-    // cell lists being built ahead of time on the side stream read the spheres: the move waits for them (as an edit does)
-    for (auto& sl : ctx->cell_cache) {
-        if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
-    }
+    if ((rc = rtx_wait_side_builds(ctx)) != RTX_OK) return rc; // (as an edit does)
     rtxplan::RemovalPlan plan = rtxplan::plan_removal(ctx->kind_of, ascending);
     const size_t n = ascending.size();
     // the kernel's argument order: the two plain arrays of a kind, then the two that carry the creation index in .w
@@ -651,10 +645,7 @@ int rtx_update_objects(rtx_ctx* ctx, double dt)
     int rc = rtx_sync_scene(ctx);
     if (rc != RTX_OK) return rc;
     if (ctx->ns == 0) return RTX_OK;
-    // cell lists being built ahead of time on the side stream read the sphere positions: the step waits for them
-    for (auto& sl : ctx->cell_cache) {
-        if (sl.ever_built && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.ev_built, 0));
-    }
+    if ((rc = rtx_wait_side_builds(ctx)) != RTX_OK) return rc;
     const unsigned blocks = (ctx->ns + rtx::kThreads - 1) / rtx::kThreads;
     const bool sorted = ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr;
     hipLaunchKernelGGL(rtx::rtx_update_spheres, dim3(blocks), dim3(rtx::kThreads), 0, ctx->stream,

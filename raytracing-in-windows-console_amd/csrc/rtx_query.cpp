@@ -23,35 +23,18 @@ int ensure(rtx_ctx* ctx, DeviceBuf<T>& a, size_t n)
     return RTX_OK;
 }
 
-int build_grid(rtx_ctx* ctx)
+// The build proper, on the context's stream, between the two halves of the write (build_grid).
+int fill_grid(rtx_ctx* ctx)
 {
     rtx_ctx::QueryGrid& q = ctx->qgrid;
     hipStream_t st = ctx->stream;
-    RTX_HIP(ctx, q.ev_built.ensure());
-    RTX_HIP(ctx, q.ev_done.ensure());
-    if (!q.d_words.get()) {
-        RTX_HIP(ctx, q.d_words.reserve(16, rtxmem::nothing()));
-        RTX_HIP(ctx, hipMemsetAsync(q.d_words.get(), 0, 16 * sizeof(uint32_t), st));
-    }
-    RTX_HIP(ctx, q.d_large.reserve(rtxgrid::kLargeCap, rtxmem::nothing()));
-    // the lists may still be read by the last query, on whatever stream it ran
-    if (q.query_pending) RTX_HIP(ctx, hipStreamWaitEvent(st, q.ev_done, 0));
-    q.query_pending = false;
-    // ... or by render launches (RTX_OPT_SHADOW_GRID), on their streams
-    for (auto& r : q.readers) {
-        if (r.pending && r.stream != st) RTX_HIP(ctx, hipStreamWaitEvent(st, r.ev, 0));
-        r.pending = false;
-    }
     q.brute = false;
     q.n_cells = q.n_large = q.pairs = 0;
     q.plan = rtxgrid::plan_grid(nullptr, nullptr, 0, 0.0f);
     ctx->stat_query_builds++;
     q.dirty = false;
     const uint32_t ns = ctx->ns;
-    if (ns == 0) {
-        RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
-        return RTX_OK;
-    }
+    if (ns == 0) return RTX_OK;
     int rc;
     GridBuildArgs b;
     std::memset(&b, 0, sizeof b);
@@ -70,7 +53,6 @@ int build_grid(rtx_ctx* ctx)
     q.plan = rtxgrid::plan_grid(box, box + 3, n_finite, load);
     if (!q.plan.ok) {
         q.brute = true; // no usable grid: nothing to walk
-        RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
         return RTX_OK;
     }
     q.n_cells = q.plan.n[0] * q.plan.n[1] * q.plan.n[2];
@@ -93,7 +75,6 @@ int build_grid(rtx_ctx* ctx)
     q.n_large = totals[1];
     if (q.n_large > rtxgrid::kLargeCap) {
         q.brute = true;
-        RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
         return RTX_OK;
     }
     if ((rc = ensure(ctx, q.pair_tmp, q.pairs)) != RTX_OK) return rc;
@@ -104,7 +85,23 @@ int build_grid(rtx_ctx* ctx)
     b.list_gidx = q.list_gidx.get();
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 3, st));
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_grid_build(&b, 4, st));
-    RTX_HIP(ctx, hipEventRecord(q.ev_built, st));
+    return RTX_OK;
+}
+
+int build_grid(rtx_ctx* ctx)
+{
+    rtx_ctx::QueryGrid& q = ctx->qgrid;
+    hipStream_t st = ctx->stream;
+    if (!q.d_words.get()) {
+        RTX_HIP(ctx, q.d_words.reserve(16, rtxmem::nothing()));
+        RTX_HIP(ctx, hipMemsetAsync(q.d_words.get(), 0, 16 * sizeof(uint32_t), st));
+    }
+    RTX_HIP(ctx, q.d_large.reserve(rtxgrid::kLargeCap, rtxmem::nothing()));
+    // the lists may still be read by queries and by render launches (RTX_OPT_SHADOW_GRID), on whatever streams they ran
+    RTX_HIP(ctx, q.sync.begin_write(st));
+    const int rc = fill_grid(ctx);
+    if (rc != RTX_OK) return rc;
+    RTX_HIP(ctx, q.sync.end_write(st, true));
     return RTX_OK;
 }
 
@@ -150,8 +147,7 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
     // without spheres the grid kernel has nothing to walk; the brute kernel's loop is empty as well: either gives the planes' answer
     RTX_HIP(ctx, (hipError_t)rtx_k_launch_query(&a, walk ? 0 : 1, stream));
     ctx->last_kernel = walk ? "rtx_query_grid" : "rtx_query_brute";
-    RTX_HIP(ctx, hipEventRecord(g.ev_done, stream));
-    g.query_pending = true;
+    g.sync.close(stream);
     return RTX_OK;
 }
 
@@ -169,29 +165,14 @@ int rtx_grid_ensure(rtx_ctx* ctx, hipStream_t stream)
         }
     }
     // the caller's stream is ordered after the build (and after the uploads and physics steps queued on the context's stream before it)
-    if (stream != ctx->stream) RTX_HIP(ctx, hipStreamWaitEvent(stream, g.ev_built, 0));
+    RTX_HIP(ctx, g.sync.read(stream));
     return RTX_OK;
 }
 
 // Launches that read the lists have been queued on `stream`: the next rebuild waits for them.
-int rtx_grid_read(rtx_ctx* ctx, hipStream_t stream)
+void rtx_grid_read(rtx_ctx* ctx, hipStream_t stream)
 {
-    rtx_ctx::QueryGrid& g = ctx->qgrid;
-    rtx_ctx::QueryGrid::Reader* rd = nullptr;
-    for (auto& r : g.readers) {
-        if (r.stream == stream) rd = &r;
-    }
-    if (!rd) {
-        if (g.readers.size() >= (size_t)rtx_ctx::kMaxHitStreams) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "shadow grid: more than 64 distinct render streams");
-        rtx_ctx::QueryGrid::Reader fresh;
-        fresh.stream = stream;
-        RTX_HIP(ctx, fresh.ev.ensure());
-        g.readers.push_back(std::move(fresh));
-        rd = &g.readers.back();
-    }
-    RTX_HIP(ctx, hipEventRecord(rd->ev, stream));
-    rd->pending = true;
-    return RTX_OK;
+    ctx->qgrid.sync.close(stream);
 }
 
 bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status)

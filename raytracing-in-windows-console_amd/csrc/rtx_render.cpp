@@ -144,6 +144,16 @@ rtxplan::TileRequest tile_request(const rtx_ctx* ctx, const RenderCall& c, doubl
 
 } // namespace
 
+// Cell lists being built ahead of time on the side stream read the spheres: what writes them on the context's stream (a physics
+// step, an edit, a removal) waits for those builds.
+int rtx_wait_side_builds(rtx_ctx* ctx)
+{
+    for (auto& sl : ctx->cell_cache) {
+        if (sl.sync.written() && sl.built_on_aux) RTX_HIP(ctx, hipStreamWaitEvent(ctx->stream, sl.sync.last_write(), 0));
+    }
+    return RTX_OK;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------ render
@@ -197,46 +207,6 @@ hipStream_t side_stream(rtx_ctx* ctx)
     return ctx->aux_stream;
 }
 
-// An event of the slot's pool recorded on `stream` now: "everything this stream has queued so far that reads the slot".
-// A stream handle the caller has destroyed since cannot be recorded on: then the whole device is waited for instead.
-void slot_mark_done(rtx_ctx::CellCacheSlot& sl, hipStream_t stream)
-{
-    if (sl.n_done == sl.done.size()) {
-        Event ev;
-        if (ev.ensure() != hipSuccess) {
-            (void)hipGetLastError();
-            hipDeviceSynchronize();
-            return;
-        }
-        sl.done.push_back(std::move(ev));
-    }
-    if (hipEventRecord(sl.done[sl.n_done], stream) != hipSuccess) {
-        (void)hipGetLastError();
-        hipDeviceSynchronize();
-        return;
-    }
-    sl.n_done++;
-}
-
-void remove_stream(std::vector<hipStream_t>& v, hipStream_t s)
-{
-    for (size_t i = 0; i < v.size(); i++) {
-        if (v[i] == s) {
-            v[i] = v.back();
-            v.pop_back();
-            return;
-        }
-    }
-}
-
-bool contains(const std::vector<hipStream_t>& v, hipStream_t s)
-{
-    for (hipStream_t e : v) {
-        if (e == s) return true;
-    }
-    return false;
-}
-
 // ---- two-level culling: cell lists
 
 void fill_cell_args(KArgs& a, const rtxplan::CellGrid& g)
@@ -254,19 +224,12 @@ void fill_cell_args(KArgs& a, const rtxplan::CellGrid& g)
 int cells_per_frame(rtx_ctx* ctx, hipStream_t stream, KArgs& a, const rtxplan::CellGrid& g)
 {
     const size_t need_list = (size_t)g.n_cells * g.cap, need_count = 2 * (size_t)g.n_cells;
-    rtx_ctx::CellScratch* cs = nullptr;
-    for (auto& e : ctx->cell_scratch) {
-        if (e.stream == stream) cs = &e;
-    }
-    if (!cs) {
-        if (ctx->cell_scratch.size() >= 16) {
-            // a caller that keeps creating streams: recycle the oldest set (its stream may be gone, so wait for the device)
-            hipDeviceSynchronize();
-            ctx->cell_scratch.erase(ctx->cell_scratch.begin());
-        }
-        ctx->cell_scratch.emplace_back();
-        cs = &ctx->cell_scratch.back();
-        cs->stream = stream;
+    rtx_ctx::CellScratch* cs = rtxsync::find(ctx->cell_scratch, stream);
+    if (!cs && !(cs = rtxsync::add(ctx->cell_scratch, stream, 16))) {
+        // a caller that keeps creating streams: recycle the oldest set (its stream may be gone, so wait for the device)
+        hipDeviceSynchronize();
+        ctx->cell_scratch.erase(ctx->cell_scratch.begin());
+        cs = rtxsync::add(ctx->cell_scratch, stream, 16);
     }
     // launches queued on this stream may still read the old lists
     if (cs->list.reserve(need_list, rtxmem::after_stream(stream)) != hipSuccess) {
@@ -301,7 +264,7 @@ int cells_per_frame(rtx_ctx* ctx, hipStream_t stream, KArgs& a, const rtxplan::C
 
 // Bins into cache slot `si` on `build` (the render stream that missed, or the side stream), with the motion budget the
 // lists are to last for.  Ordered after every launch that still reads the slot's old lists and after its last build.
-int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render, bool on_side, KArgs a, const rtxplan::CellGrid& g, const rtxplan::CellBudget& budget)
+int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, bool on_side, KArgs a, const rtxplan::CellGrid& g, const rtxplan::CellBudget& budget)
 {
     rtx_ctx::CellCacheSlot& sl = ctx->cell_cache[si];
     const size_t need_list = (size_t)g.n_cells * g.cap, need_count = (size_t)g.n_cells;
@@ -313,24 +276,11 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
         if (sl.count.reserve(need_count, rtxmem::after_device()) != hipSuccess) {
             return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the coarse cell counts");
         }
-        sl.readers.clear();
-        sl.n_done = 0;
+        sl.sync.forget_readers();
     }
-    RTX_HIP(ctx, sl.ev_built.ensure());
     // after the slot's previous build, and after the launches that read its old lists: the streams that have not launched
-    // anything since their last read of it are marked now, the others were when they moved on (cell_slot_use)
-    if (sl.ever_built) RTX_HIP(ctx, hipStreamWaitEvent(build, sl.ev_built, 0));
-    for (hipStream_t r : sl.readers) {
-        if (r != build) slot_mark_done(sl, r);
-    }
-    sl.readers.clear();
-    for (size_t i = 0; i < sl.n_done; i++) {
-        if (hipStreamWaitEvent(build, sl.done[i], 0) != hipSuccess) {
-            (void)hipGetLastError();
-            hipDeviceSynchronize();
-        }
-    }
-    sl.n_done = 0;
+    // anything since their last read of it are closed now, the others were when they moved on (cell_slot_use)
+    RTX_HIP(ctx, sl.sync.begin_write(build));
     if (on_side && ctx->ns_moved_since_build) {
         // the sphere positions the lists are built from are those of this moment: physics steps queued so far (on the
         // context's stream) are done before the pass reads them; rtx_update_objects in turn waits for a pass in flight
@@ -339,8 +289,6 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
         RTX_HIP(ctx, hipStreamWaitEvent(build, ctx->ev_physics, 0));
         ctx->ns_moved_since_build = false;
     }
-    (void)render;
-    sl.waited.clear();
     RTX_HIP(ctx, hipMemsetAsync(sl.count.get(), 0, need_count * sizeof(uint32_t), build));
     fill_cell_args(a, g);
     a.bin_theta = budget.theta;
@@ -351,12 +299,9 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
     a.cell_max_out = ctx->d_cell_max.get();
     const int be = rtx_k_launch_bin_cells(&a, g.splits, build);
     if (be != 0) return rtx_hip_fail(ctx, (hipError_t)be, "cell binning launch");
-    RTX_HIP(ctx, hipEventRecord(sl.ev_built, build));
+    RTX_HIP(ctx, sl.sync.end_write(build, !on_side)); // (in order on the stream that built, if it is a render stream)
     if (ctx->d_cell_max.get()) RTX_HIP(ctx, hipMemcpyAsync((void*)ctx->h_cell_max.get(), ctx->d_cell_max.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, build));
-    sl.ever_built = true;
-    sl.known_ready = false;
     sl.built_on_aux = on_side;
-    if (!on_side) sl.waited.push_back(build); // in order on the stream that built
     return RTX_OK;
 }
 
@@ -364,25 +309,10 @@ int cell_slot_build(rtx_ctx* ctx, int si, hipStream_t build, hipStream_t render,
 int cell_slot_use(rtx_ctx* ctx, int si, hipStream_t stream, KArgs& a, const rtxplan::CellGrid& g)
 {
     rtx_ctx::CellCacheSlot& sl = ctx->cell_cache[si];
-    if (!contains(sl.waited, stream)) {
-        RTX_HIP(ctx, hipStreamWaitEvent(stream, sl.ev_built, 0));
-        sl.waited.push_back(stream);
-    }
-    // this stream's reads of the OTHER set end here: mark them, so that a rebuild of that set need not wait for anything
+    RTX_HIP(ctx, sl.sync.read(stream));
+    // this stream's reads of the OTHER set end here: close them, so that a rebuild of that set need not wait for anything
     // this stream queues from now on
-    rtx_ctx::CellCacheSlot& other = ctx->cell_cache[si ^ 1];
-    if (contains(other.readers, stream)) {
-        slot_mark_done(other, stream);
-        remove_stream(other.readers, stream);
-    }
-    if (!contains(sl.readers, stream)) {
-        if (sl.readers.size() >= 32 || sl.n_done >= 64) { // a caller that keeps creating streams: settle everything, start over
-            hipDeviceSynchronize();
-            sl.readers.clear();
-            sl.n_done = 0;
-        }
-        sl.readers.push_back(stream);
-    }
+    ctx->cell_cache[si ^ 1].sync.close(stream);
     fill_cell_args(a, g);
     a.cell_list = sl.list.get();
     a.cell_count = sl.count.get();
@@ -503,14 +433,7 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
     double sx, sy;
     rtxplan::pixel_steps(p->inv_v, p->element1, p->element2, p->x, p->y, &sx, &sy);
     bool ready[2];
-    for (int s = 0; s < 2; s++) {
-        rtx_ctx::CellCacheSlot& sl = ctx->cell_cache[s];
-        if (sl.ever_built && !sl.known_ready) {
-            if (hipEventQuery(sl.ev_built) == hipSuccess) sl.known_ready = true;
-            else (void)hipGetLastError(); // hipErrorNotReady
-        }
-        ready[s] = sl.ever_built && sl.known_ready;
-    }
+    for (int s = 0; s < 2; s++) ready[s] = ctx->cell_cache[s].sync.written() && ctx->cell_cache[s].sync.ready();
     const rtxplan::CellCachePolicy::Decision d = ctx->cell_policy.decide(key, cam, sx * g.cell_w, sy * g.cell_h, ready, still_only);
     int rc = RTX_OK;
     switch (d.action) {
@@ -519,7 +442,7 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
     case rtxplan::CellCachePolicy::kPerFrame:
         return cells_per_frame(ctx, stream, a, g);
     case rtxplan::CellCachePolicy::kBuild:
-        if ((rc = cell_slot_build(ctx, d.slot, stream, stream, false, a, g, d.budget)) != RTX_OK) {
+        if ((rc = cell_slot_build(ctx, d.slot, stream, false, a, g, d.budget)) != RTX_OK) {
             ctx->cell_policy.invalidate();
             return rc;
         }
@@ -537,7 +460,7 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
         // hardware queues (the side stream there: 60 us per frame against 43 without reuse).
         const bool several = ctx->render_streams_seen >= 2;
         hipStream_t side = several ? stream : side_stream(ctx);
-        if (!side || cell_slot_build(ctx, d.prefetch_slot, side, stream, !several, a, g, d.prefetch_budget) != RTX_OK) {
+        if (!side || cell_slot_build(ctx, d.prefetch_slot, side, !several, a, g, d.prefetch_budget) != RTX_OK) {
             ctx->cell_policy.invalidate(); // (the slot was promised to the policy; take everything back and bin this frame alone)
             return cells_per_frame(ctx, stream, a, g);
         }
@@ -595,7 +518,10 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
     int rc = rtx_grid_ensure(ctx, stream);
     if (rc != RTX_OK) return rc;
     const rtx_ctx::QueryGrid& g = ctx->qgrid;
-    if (g.brute || g.plan.ok == 0u || g.n_cells == 0u) return RTX_OK;
+    if (g.brute || g.plan.ok == 0u || g.n_cells == 0u) {
+        rtx_grid_read(ctx, stream); // (nothing of this frame reads the lists: a rebuild need not wait for it)
+        return RTX_OK;
+    }
     RTX_HIP(ctx, ctx->d_shadow_grid_fallback.reserve(1, rtxmem::nothing()));
     gs->grid = g.plan;
     gs->cell_start = g.cell_count.get();
@@ -615,17 +541,9 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
 // unless a recorded graph may read it: then it is kept until rtx_destroy.
 int hit_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, bool capturing, void** out)
 {
-    rtx_ctx::HitScratch* hs = nullptr;
-    for (auto& h : ctx->hit_scratch) {
-        if (h.stream == stream) hs = &h;
-    }
-    if (!hs) {
-        if (ctx->hit_scratch.size() >= (size_t)rtx_ctx::kMaxHitStreams) {
-            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "light / shadow path: more than 64 distinct render streams");
-        }
-        ctx->hit_scratch.emplace_back();
-        hs = &ctx->hit_scratch.back();
-        hs->stream = stream;
+    rtx_ctx::HitScratch* hs = rtxsync::find(ctx->hit_scratch, stream);
+    if (!hs && !(hs = rtxsync::add(ctx->hit_scratch, stream, (size_t)rtx_ctx::kMaxHitStreams))) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "light / shadow path: more than 64 distinct render streams");
     }
     if (hs->p.capacity() < bytes) {
         // (nothing may be freed while a stream captures; a buffer that grows here, or that a recorded graph reads, is kept)
@@ -814,7 +732,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         return rtx_hip_fail(ctx, (hipError_t)herr, plan.chain() ? "chain shading kernel launch" : (mirror ? "mirror shading kernel launch" : "shadow shading kernel launch"));
     }
     if (plan.dark0) {
-        if ((rc = rtx_grid_read(ctx, stream)) != RTX_OK) return rc;
+        rtx_grid_read(ctx, stream);
         ctx->stat_shadow_grid_frames++;
     }
     ctx->last_kernel = name;
@@ -1270,18 +1188,9 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
         for (size_t i = 0; i < n; i++) {
             hipStream_t s = streams[i] ? static_cast<hipStream_t>(streams[i]) : ctx->stream;
             if (s == join) continue; // already ordered
-            rtx_ctx::JoinEvent* je = nullptr;
-            for (auto& e : ctx->join_events) {
-                if (e.stream == s) je = &e;
-            }
-            if (!je) {
-                if (ctx->join_events.size() >= 64) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_submit_slabs: more than 64 distinct streams");
-                rtx_ctx::JoinEvent fresh;
-                fresh.stream = s;
-                RTX_HIP(ctx, fresh.ev.ensure());
-                ctx->join_events.push_back(std::move(fresh));
-                je = &ctx->join_events.back();
-            }
+            rtx_ctx::JoinEvent* je = rtxsync::find(ctx->join_events, s);
+            if (!je && !(je = rtxsync::add(ctx->join_events, s, 64))) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_submit_slabs: more than 64 distinct streams");
+            RTX_HIP(ctx, je->ev.ensure());
             bool seen = false;
             for (auto* u : used) seen = seen || (u == je);
             if (!seen) {

@@ -461,6 +461,47 @@ def test_a_physics_step_rebuilds_once_and_queries_share_the_grid(R, ctx):
     _reset(R, ctx)
 
 
+def test_frames_in_flight_on_three_streams_share_the_grid_across_rebuilds(R, ctx):
+    """Six frames a round, queued round-robin on three streams without a wait between them, a physics step between rounds: every
+    round rebuilds the grid once -- behind the other streams' frames of the round before -- and every frame is the brute path's."""
+    import torch
+    _reset(R, ctx)
+    W, H = 64, 48
+    p, sph, pl = _load(R, ctx, "c", W, H)
+    for i in range(0, len(sph), 2):
+        ctx.set_sphere_motion(i, 1, 3.0)
+    streams = [torch.cuda.Stream() for _ in range(3)]
+    kinds = [(O.RGB_ASCII, 0), (O.BIT_PIXEL, 0)]  # (frame i: stream i % 3, kind i % 2 -- every stream renders both)
+    builds = ctx.get_option(R.STAT_QUERY_GRID_BUILDS)
+    frames = ctx.get_option(R.STAT_SHADOW_GRID_FRAMES)
+    previous = None
+    for rnd in range(4):
+        bufs = [torch.full((W * H * (20 if kinds[i % 2][0] >= O.RGB_ASCII else 12),), 0xEE, dtype=torch.uint8, device="cuda") for i in range(6)]
+        torch.cuda.synchronize()
+        ctx.set_option(R.OPT_SHADOW_GRID, 1)
+        for i, buf in enumerate(bufs):
+            mode, flags = kinds[i % 2]
+            ctx.render_rows(p, mode, 0, H, d_out=buf.data_ptr(), out_row_base=0, stream=streams[i % 3].cuda_stream, flags=flags)
+            assert ctx.last_kernel.startswith("rtx_grid_"), ctx.last_kernel
+        torch.cuda.synchronize()
+        ctx.set_option(R.OPT_SHADOW_GRID, 0)
+        assert ctx.get_option(R.STAT_QUERY_GRID_BUILDS) == builds + rnd + 1
+        assert ctx.get_option(R.STAT_SHADOW_GRID_FRAMES) == frames + 6 * (rnd + 1)
+        ref, _ = _reference(R, ctx, p, modes=[m for m, _ in kinds], forms=["records"])
+        for i, buf in enumerate(bufs):
+            mode = kinds[i % 2][0]
+            want = ref[(mode, "records")]
+            assert np.array_equal(buf.cpu().numpy(), want), "round %d, frame %d (stream %d, %s): %s" % (
+                rnd, i, i % 3, O.MODE_NAMES[mode], U.first_diff(buf.cpu().numpy(), want, 20 if mode >= O.RGB_ASCII else 12, 1 << 30))
+        if previous is not None:
+            assert not np.array_equal(ref[(O.RGB_ASCII, "records")], previous), "the step moved nothing"
+        previous = ref[(O.RGB_ASCII, "records")]
+        if rnd < 3:
+            ctx.update_objects(0.2)
+    ctx.set_scene(sph, pl)
+    _reset(R, ctx)
+
+
 # ---------------------------------------------------------------- 4. slabs, ranks, graphs
 
 def test_ragged_slabs_equal_the_frame(R, ctx):
