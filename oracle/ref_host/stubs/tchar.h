@@ -1,0 +1,2 @@
+/* Stand-in for <tchar.h>: the host build of the reference needs nothing from it. */
+#pragma once

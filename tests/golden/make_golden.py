@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Generates tests/golden/golden.json and c1_scene.npz from the CPU oracle.
 
-The reference cannot run here (no CUDA, no Windows headers) and ships no golden vectors, so the
-vectors are produced by the oracle, which tests/test_oracle_pins.py pins to the known answers
-SURVEY.md 8(c) recorded from the reference's own sources.  Oracle configuration for every entry:
+The reference ships no golden vectors and its host build (oracle/ref_host/) is defined for at most
+1024 objects (C2-C5 have more), so these vectors are produced by the oracle, which tests/test_ref_host.py holds bit for
+bit to that host build and tests/test_oracle_pins.py to the known answers SURVEY.md 8(c) recorded
+(make_ref_golden.py records the host build's own outputs).  Oracle configuration for every entry:
 pinned pow32, saturating float->uint8 (flags = 0), i.e. exactly what the HIP path implements.
 
 Hashes are standard FNV-1a-64 (offset basis 14695981039346656037) of the full zero-initialised
