@@ -25,6 +25,7 @@
 #include "rtx_records.hpp"
 #include "rtx_reflect.hpp"
 #include "rtx_shadow.hpp"
+#include "rtx_workgroup.hpp"
 
 // The experiment build's hooks (ABL, STAMP, RTX_X_*): empty / constant false in the product build.
 #define RTX_X_SECTION_DEVICE
@@ -36,17 +37,10 @@
 
 namespace rtx {
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the wave's outstanding
-// global loads (s_waitcnt vmcnt(0)), which would expose the latency of every prefetch in flight; in
-// these kernels threads exchange data through LDS alone (global memory is read-only input or
-// write-only output), so waiting for LDS operations is sufficient.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-constexpr int kThreads = 256;
+// (rtx_workgroup.hpp: lds_barrier, kThreads, kChunk, kNoHit)
 constexpr int kListCapBrute = 1024;  // candidate records per flush (brute: every sphere is a candidate)
 constexpr int kListCapCull = 704;    // culling kernels: room for one more 512-sphere step while <= 192 are listed; 8 workgroups per CU
 constexpr int kListCapRefine = 640;  // REFINE: ... while <= 128 are listed
-constexpr float kNoHit = 99999999.f; // RayTracing.h:21
 
 // RayTracing.h:97-115 (68 glyphs).
 __constant__ __attribute__((aligned(4))) const char kRamp[68] = {
@@ -195,7 +189,6 @@ constexpr uint32_t kCostPass = 100u, kCostCandidate = 3u, kCostShaded = 330u;
 
 constexpr int kMaxMacro = 128;    // macro tile is at most 128 x 128 pixels
 constexpr int kMaxMacroRefine = 64; // ... 64 x 64 for the REFINE kernels
-constexpr int kChunk = 2 * kThreads; // spheres staged per barrier: two per thread
 constexpr int kPlaneTable = 16;   // planes hoisted into LDS; further planes take the direct path
 constexpr uint32_t kPlaneRow = 5; // float4s per plane in that table (rtx_trace_body.inc: s_plane)
 

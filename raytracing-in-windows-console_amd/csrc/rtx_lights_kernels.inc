@@ -18,16 +18,7 @@
 // through the lights some lane of it is still open for; per light the segment (toL, 1 / len2) is formed once and the list entries
 // whose mask names the light (four mask bytes a word) are tested by the lanes open for it (segment_hits_sphere).
 
-struct LightsShared {
-    float4 occ[kTileList];
-    uint32_t occ_pos[kTileList];
-    uint32_t occ_mask[kTileList / 4]; // one byte per entry: the lights the sphere was kept for
-    uint32_t digits[256];
-    __attribute__((aligned(4))) uint8_t ramp[68];
-    float red[4][6];
-    rtxshadow::Cone cone[rtxlights::kMaxLights];
-    uint32_t cnt;
-};
+// (rtx_tile_pass.inc: LightsShared, the workgroup's LDS)
 
 // diffuse_i and specular_i of one light, as shade_light forms them; res = (res + diffuse_i * od) + specular_i * 1.0f
 __device__ __forceinline__ void add_light(V3& res, V3 point, V3 nn, V3 nv, V3 od, const rtxlights::PackedLight& L, float dpow, float spow)

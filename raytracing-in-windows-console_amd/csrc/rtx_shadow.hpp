@@ -7,14 +7,16 @@
 // The cone is an axis a (the normalised sum of the u_i), a half-angle theta (the largest angle between a and a u_i) and a
 // distance dmax.  A sphere (C, r) seen from L at distance D subtends the half-angle asin(r / D); it can touch the cone only if the
 // angle between a and C - L is at most theta + asin(r / D), and only if D - r < dmax.  Angles are taken with atan2(|x cross y|,
-// x . y), which stays accurate near 0 where acos does not.
+// x . y), which stays accurate near 0 where acos does not.  r is |r| throughout: the exact test squares the radius, so a sphere
+// of negative radius shadows as the one of radius |r| does.
 //
 // Rounding: every quantity is fp32 and the exact test of the shadow pass is fp32 too, so the bound carries margins far above
 // the few ulps either can be off by: the radius is inflated by a relative 1e-4 of itself and of D and by 1e-5 of the coordinate
 // scale (|L| + dmax: what the hit points and the closest points of the exact test are rounded at), the angles by 1e-4 rad and
 // dmax by a relative 1e-4.  Degenerate cones keep everything: a hit point at (or within 1e-6 |P| of) the light, directions that
 // do not add up to a clear axis (L inside the hull of the points), and theta of 90 degrees or more.  tests/host/test_shadow_bound.cpp
-// checks the bound against a float64 segment-to-ball test over millions of random cases.
+// checks the bound against a float64 segment-to-ball test over millions of random cases; tests/test_gpu_tile_bound.py runs it
+// on the device, with the cone as light_cone (rtx_tile_pass.inc) reduces it there.
 #pragma once
 
 #include <math.h>
@@ -97,7 +99,7 @@ RTX_SHADOW_HD inline bool may_occlude(const Cone& c, const float L[3], float cx,
     if (c.all) return true;
     const float vx = cx - L[0], vy = cy - L[1], vz = cz - L[2];
     const float D = sqrtf(vx * vx + vy * vy + vz * vz);
-    const float R = r * (1.0f + kRelMargin) + kRelMargin * D + c.slack;
+    const float R = fabsf(r) * (1.0f + kRelMargin) + kRelMargin * D + c.slack; // (the exact test squares r: a negative radius is |r|)
     if (!(D > R)) return true;        // the light is inside the (inflated) ball, or NaN
     if (D - R > c.dmax) return false; // beyond the farthest hit point
     const float phi = angle_between(c.ax, c.ay, c.az, vx, vy, vz);

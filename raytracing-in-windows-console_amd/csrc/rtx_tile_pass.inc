@@ -238,6 +238,19 @@ __device__ __forceinline__ bool segment_hits_sphere(V3 P, V3 toL, float inv_len2
 
 // ---------------------------------------------------------------- the shadow test of a set of lights
 
+// The LDS of a workgroup of the light-set kernels (rtx_lights_kernels.inc and the files after it): lights_dark_set's list, sums and
+// cones, and the encoder's tables.
+struct LightsShared {
+    float4 occ[kTileList];
+    uint32_t occ_pos[kTileList];
+    uint32_t occ_mask[kTileList / 4]; // one byte per entry: the lights the sphere was kept for
+    uint32_t digits[256];
+    __attribute__((aligned(4))) uint8_t ramp[68];
+    float red[4][6];
+    rtxshadow::Cone cone[rtxlights::kMaxLights];
+    uint32_t cnt;
+};
+
 // The lights (bit i: light i of la.lights) that the point P -- normal `normal`, on object `id` (sphere position, or plane index |
 // bit 31) -- is shadowed from; 0 for a pixel that is not `testable`.  Per light: self-shadow and the planes per pixel
 // (shadowed_before_spheres) and the workgroup's cone from that light over its open points (light_cone), kept in s.cone; a light

@@ -9,6 +9,7 @@
 // nz height), a pair two uint32 (rectangle index, sphere / plane index).  Every entry point returns 0, -1 on a HIP error, -2 on
 // arguments it refuses (an index or a rectangle out of range: nothing is launched).
 #include "../../raytracing-in-windows-console_amd/csrc/rtx_cull.hpp"
+#include "../../raytracing-in-windows-console_amd/csrc/rtx_workgroup.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,9 +21,9 @@ namespace {
 using namespace rtx;
 
 constexpr int kBlock = 256;
-// rtx_kernels.hip: the distance a pixel starts from (RayTracing.h:21).  A test counts as a hit when the trace would take it: it
-// reports one AND its t is below this -- a NaN t, which the tests let through for a NaN ray, is below nothing and wins no pixel.
-constexpr float kNoHit = 99999999.f;
+// kNoHit (rtx_workgroup.hpp) is the distance a pixel starts from (RayTracing.h:21).  A test counts as a hit when the trace would
+// take it: it reports one AND its t is below kNoHit -- a NaN t, which the tests let through for a NaN ray, is below nothing and
+// wins no pixel.
 
 struct Rect {
     uint32_t col0, row0, w, h;
