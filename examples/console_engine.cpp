@@ -3,10 +3,12 @@
 // raw-mode keyboard input where the reference polls Win32 key state, and PrintMachine's printer thread
 // (PrintMachine.cpp:257-306) writing each minimised frame to the terminal after an ANSI cursor-home.
 //
-//   console_engine [W H] [--mode 0..4] [--frames N] [--dt seconds] [--lockstep] [--no-spawn] [--no-status] [--delta] [--trace FILE] [--keys-only]
+//   console_engine [W H] [--mode 0..4] [--frames N] [--dt seconds] [--lockstep] [--no-spawn] [--no-status] [--delta] [--samples N] [--trace FILE] [--keys-only]
 //
 // --delta: the printer receives only the console cells that changed since the frame before, addressed by cursor escapes
 // (RayTracingManager::SetDeltaFrames, rtx_update_delta; no reference counterpart), and a whole frame where one is needed.
+// --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
+// no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
 // Keys (the reference's, as far as a terminal can deliver them -- there are no key-up events and no mouse, so a key
 // counts as held for the frame in which its byte arrives and the arrow keys stand in for mouse motion):
@@ -147,6 +149,7 @@ int main(int argc, char** argv)
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
     bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false;
+    int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
     for (int i = 1; i < argc; i++) {
@@ -158,12 +161,13 @@ int main(int argc, char** argv)
         else if (a == "--no-spawn") spawn = false;
         else if (a == "--no-status") status = false;
         else if (a == "--delta") delta = true; // send only the cells that changed (RayTracingManager::SetDeltaFrames)
+        else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -203,6 +207,7 @@ int main(int argc, char** argv)
         scene->Init();
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
         if (delta) rayTracingManager->SetDeltaFrames(true);
+        if (samples != 1) rayTracingManager->SetSupersampling(samples);
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;
         int bounces = 1;

@@ -234,6 +234,40 @@ enum rtx_option {
                                * path.  Replicated over a device group like every option; every member builds its own grid on its own
                                * device.  RTX_STAT_SHADOW_LONGEST_LIST reads 0 after such a set.  Off by default: where most segments
                                * fall back it is slower.  No reference counterpart (RayTracing.cu:132) */
+    RTX_OPT_SUPERSAMPLE = 30, /* S x S rays per console cell, folded on the GPU: S in {1, 2, 3, 4}, default 1.  Anything else returns
+                               * RTX_ERR_INVALID_ARGUMENT and changes nothing.  At S = 1 every launch is, byte for byte and kernel for
+                               * kernel, what it is without the option.  The value takes effect for launches queued afterwards.
+                               * Replicated over a device group like every option.  The rule, for S > 1 and a call that renders rows
+                               * [row0, row0 + rows) of a W x H frame with params p in one of the five character modes:
+                               * 1. The sample frame is the RTX_RENDER_VALUES output of the existing paths for p', which is p with
+                               *    x = S W and y = S H (ray generation divides by x and y, so p' has exactly p's field of view), over
+                               *    rows [S row0, S (row0 + rows)); scene, light set and every option unchanged; planned exactly as a
+                               *    caller's frame of that size is.  Cell (c, r) with c < W - 1 owns the n = S^2 samples
+                               *    (S c + i, S r + j), numbered k = j S + i; sample (0, 0) is the ray of S = 1.  Sample columns from
+                               *    S (W - 1) on belong to the newline column and are ignored.
+                               * 2. The fold.  vis_k means distance_k <= cam_far; m is the number of visible samples.  m = 0: the
+                               *    cell's values are (99999999.f, 0, 0, 0, 0, 0, 0, 0).  m > 0: distance is the minimum of distance_k
+                               *    over the visible samples, and each of the seven other floats (shadingValue, normal.xyz,
+                               *    colour.xyz) is acc * (1.0f / (float)n), where acc starts at 0.0f and for k = 0 .. n - 1 in order
+                               *    acc = acc + (vis_k ? v_k : 0.0f); every operation rounded to fp32, nothing reassociated or
+                               *    contracted.  Samples that miss, or lie beyond cam_far, count as black: coverage against the
+                               *    console's black background.
+                               * 3. The output is what the record encoder makes of the folded values at (row, col) of the W x H frame:
+                               *    records, pixel words or value floats by the caller's flags; the newline column as always (NUL
+                               *    records, 0xffffffff, eight zeros); out_row_base, the context's own buffer with its zero-fill
+                               *    semantics and RTX_RENDER_ZERO_TAIL unchanged.
+                               * The launches: the existing ones into the render stream's sample buffer (32 S^2 W rows bytes, one per
+                               * render stream for at most 64 streams; it grows on demand, never shrinks, is freed by rtx_destroy;
+                               * RTX_ERR_OUT_OF_MEMORY when it cannot grow), then rtx_resolve<S,mode[,compact|,values]>, which
+                               * rtx_last_kernel_name reports.  Everything that traces through rtx_render_rows inherits the rule:
+                               * rtx_render, rtx_submit_frames / rtx_submit_slabs (queued one by one: no RTX_OPT_BATCH launch while
+                               * S > 1), rtx_update, rtx_update_begin and rtx_update_delta (their pixel words are the folded cells'),
+                               * and device groups (rank g's cell rows are sample rows [S row0_g, S (row0_g + rows_g)) with the global
+                               * row index, so a sharded frame equals the one-device frame).  RTX_SDL writes nothing and is
+                               * unaffected; rtx_pick, rtx_query_*, rtx_expand, rtx_minimize* and rtx_delta_words do not trace.  A
+                               * supersampled launch inside a graph capture returns RTX_ERR_INVALID_ARGUMENT (the sample buffer may
+                               * grow), and so does one with S x or S y of 2^31 or more; otherwise the existing paths' limits apply
+                               * to the sample frame.  No reference counterpart (RayTracing.cu:12-17 traces one ray per cell) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -321,6 +355,9 @@ enum rtx_stat {
     RTX_STAT_DELTA_RUNS = 154,      /* ... and the runs they form: the cursor escapes of that stream.  With RTX_STAT_DELTA_CELLS a caller
                                      * can tell when a key frame would have been shorter.  Reading it waits for the device.
                                      * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+    RTX_STAT_SUPERSAMPLE_FRAMES = 100, /* supersampled launch sets queued so far (RTX_OPT_SUPERSAMPLE > 1): counted as
+                                     * RTX_STAT_SHADOW_FRAMES counts, one per rtx_render_rows call; stays 0 while S = 1.  (Numbered below
+                                     * the other counters: 101 .. 154 are taken.)  No reference counterpart (RayTracing.cu:12-17) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };

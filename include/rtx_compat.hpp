@@ -651,6 +651,9 @@ public:
     void SetLight(const rtx_light* light) { rtx_compat::check(m_ctx, rtx_scene_set_light(m_ctx, light), "rtx_scene_set_light"); }
     void SetLights(const rtx_light* lights, const size_t n) { rtx_compat::check(m_ctx, rtx_scene_set_lights(m_ctx, n, lights), "rtx_scene_set_lights"); }
     void SetShadows(const bool on) { rtx_compat::check(m_ctx, rtx_set_option(m_ctx, RTX_OPT_SHADOWS, on ? 1 : 0), "rtx_set_option(RTX_OPT_SHADOWS)"); }
+    // Extension, no reference counterpart (RayTracing.cu:12-17 traces one ray per console cell): n x n rays per cell, n in 1 .. 4, folded
+    // on the GPU (RTX_OPT_SUPERSAMPLE); Update then hands over the folded cells.  1 by default, and then nothing changes.
+    void SetSupersampling(const int n) { rtx_compat::check(m_ctx, rtx_set_option(m_ctx, RTX_OPT_SUPERSAMPLE, n), "rtx_set_option(RTX_OPT_SUPERSAMPLE)"); }
 
 private:
     rtx_ctx* m_ctx = nullptr;

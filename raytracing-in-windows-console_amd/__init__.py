@@ -50,6 +50,8 @@ OPT_REFLECT_SHADOWS = 28
 OPT_SHADOW_GRID = 29
 STAT_SHADOW_GRID_FRAMES = 146
 STAT_SHADOW_GRID_FALLBACK_POINTS = 147
+OPT_SUPERSAMPLE = 30            # S x S rays per console cell, folded on the GPU: 1 (default) .. 4 (include/rtx.h)
+STAT_SUPERSAMPLE_FRAMES = 100
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH

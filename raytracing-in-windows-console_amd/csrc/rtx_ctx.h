@@ -320,6 +320,17 @@ struct rtx_ctx {
     uint64_t stat_shadow_grid_frames = 0;
     DeviceBuf<uint32_t> d_shadow_grid_fallback; // segments of the last launch set on the path that tested every sphere (one word)
 
+    // supersampling (RTX_OPT_SUPERSAMPLE): with S > 1 rtx_render_rows runs its launches for the S W x S H sample frame in values form
+    // into the render stream's sample buffer (32 S^2 W rows bytes; one per render stream as the hit buffers, for at most
+    // kMaxHitStreams streams; it grows on demand, never shrinks and goes with the context) and rtx_resolve folds it into the target
+    int64_t opt_supersample = 1;
+    uint64_t stat_supersample_frames = 0;
+    struct SampleScratch {
+        hipStream_t stream = nullptr;
+        DeviceBuf<uint8_t> p;
+    };
+    std::vector<SampleScratch> sample_scratch;
+
     // objects edited in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane; rtx_post.hip): rows that
     // come from the host, or from another member of a device group, are staged in d_edit_rows (floats);
     // rtx_write_spheres leaves its two result words in d_edit_result, which the call copies to the pinned pair and waits for

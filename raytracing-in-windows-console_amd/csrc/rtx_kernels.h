@@ -271,6 +271,9 @@ struct TileArgs {
 };
 const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream, int* hip_error);
 const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const TileArgs* t, int mode, void* stream, int* hip_error);
+// The fold of a supersampled launch (RTX_OPT_SUPERSAMPLE): S x S samples of `samples` (the values of the S a->W wide sample frame, its row
+// S a->row0 first) per cell of a's rows, encoded into a->out as `mode` (the five character modes) and a->compact (0 / 1 / 2) say.
+const char* rtx_k_launch_resolve(const KArgs* a, const void* samples, int S, int mode, void* stream, int* hip_error);
 // kind 0: rtx_query_grid, 1: rtx_query_brute.  Returns the hipGetLastError() value.
 int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream);
 // step 0 bounds, 1 count, 2 scan, 3 scatter, 4 sort

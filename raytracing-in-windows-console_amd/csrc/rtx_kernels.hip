@@ -1006,6 +1006,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 #include "rtx_lights_chain_kernels.inc"
 #include "rtx_chain_shadow_kernels.inc"
 #include "rtx_grid_shadow_kernels.inc"
+#include "rtx_resolve_kernels.inc"
 #include "rtx_query_kernels.inc"
 
 } // namespace rtx
@@ -1319,6 +1320,63 @@ extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const Til
             break;
         }
     });
+}
+
+// The fold of a supersampled launch (rtx_resolve_kernels.inc): a->W x (a->row_end - a->row0) cells of S x S samples each, read from
+// `samples` (the sample frame's values, its row S a->row0 first) and written to a->out as `mode`'s records / words / values
+// (a->compact 0 / 1 / 2).  Returns "rtx_resolve<S,RTX_K_mode>" with ",compact" or ",values" as the shade launches do, or nullptr
+// when the launch is refused (S outside 2 .. 4, not a character mode, no cells, more workgroups than a grid holds).
+extern "C" const char* rtx_k_launch_resolve(const KArgs* a, const void* samples, int S, int mode, void* stream_v, int* hip_error)
+{
+    using namespace rtx;
+    struct Names {
+        char s[3][5][3][64];
+        Names()
+        {
+            static const char* const kMode[5] = {"RTX_K_BIT_ASCII", "RTX_K_BIT_PIXEL", "RTX_K_RGB_ASCII", "RTX_K_RGB_PIXEL", "RTX_K_RGB_NORMALS"};
+            static const char* const kSuffix[3] = {"", ",compact", ",values"};
+            for (int n = 0; n < 3; n++) {
+                for (int m = 0; m < 5; m++) {
+                    for (int o = 0; o < 3; o++) snprintf(s[n][m][o], sizeof s[n][m][o], "rtx_resolve<%d,%s%s>", n + 2, kMode[m], kSuffix[o]);
+                }
+            }
+        }
+    };
+    static const Names kNames;
+    static_assert(RTX_K_BIT_ASCII == 0 && RTX_K_RGB_NORMALS == 4 && kOutRecords == 0 && kOutCompact == 1 && kOutValues == 2, "names are indexed by mode and form");
+    *hip_error = 0;
+    const uint64_t cells = (uint64_t)a->W * (uint64_t)(a->row_end - a->row0), blocks = (cells + (uint64_t)kThreads - 1u) / (uint64_t)kThreads;
+    if (S < 2 || S > 4 || mode < RTX_K_BIT_ASCII || mode > RTX_K_RGB_NORMALS || a->compact > 2u || samples == nullptr || a->row_end <= a->row0 || blocks == 0 ||
+        blocks >= (1ull << 31)) {
+        return nullptr;
+    }
+    const dim3 grid((uint32_t)blocks, 1, 1), block(kThreads, 1, 1);
+    const ResolveArgs ra = {static_cast<const float4*>(samples)};
+    hipStream_t st = (hipStream_t)stream_v;
+    const auto with_out = [&](auto n, auto m) {
+        constexpr int N = decltype(n)::value, M = decltype(m)::value;
+        switch (a->compact) {
+        case 0u: hipLaunchKernelGGL((rtx_resolve<N, M, kOutRecords>), grid, block, 0, st, *a, ra); break;
+        case 1u: hipLaunchKernelGGL((rtx_resolve<N, M, kOutCompact>), grid, block, 0, st, *a, ra); break;
+        default: hipLaunchKernelGGL((rtx_resolve<N, M, kOutValues>), grid, block, 0, st, *a, ra); break;
+        }
+    };
+    const auto with_mode = [&](auto n) {
+        switch (mode) {
+        case RTX_K_BIT_ASCII: with_out(n, std::integral_constant<int, RTX_K_BIT_ASCII>{}); break;
+        case RTX_K_BIT_PIXEL: with_out(n, std::integral_constant<int, RTX_K_BIT_PIXEL>{}); break;
+        case RTX_K_RGB_ASCII: with_out(n, std::integral_constant<int, RTX_K_RGB_ASCII>{}); break;
+        case RTX_K_RGB_PIXEL: with_out(n, std::integral_constant<int, RTX_K_RGB_PIXEL>{}); break;
+        default: with_out(n, std::integral_constant<int, RTX_K_RGB_NORMALS>{}); break;
+        }
+    };
+    switch (S) {
+    case 2: with_mode(std::integral_constant<int, 2>{}); break;
+    case 3: with_mode(std::integral_constant<int, 3>{}); break;
+    default: with_mode(std::integral_constant<int, 4>{}); break;
+    }
+    *hip_error = (int)hipGetLastError();
+    return kNames.s[S - 2][mode][a->compact];
 }
 
 extern "C" int rtx_k_launch_query(const QueryArgs* q, int kind, void* stream_v)

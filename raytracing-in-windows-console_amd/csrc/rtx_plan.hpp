@@ -1168,4 +1168,42 @@ static_assert(cup_length(0, 0) == 6 && cup_length(99998, 99998) == kDeltaMaxCup 
 static_assert(delta_block_bound(12, 1024) == 513 * 12 + 512 * 14 && delta_block_bound(20, 1024) == 1024 * 20 + 14,
               "a block inside one long row can need more than 1024 S bytes");
 
+// ------------------------------------------------------------------------------------------------ supersampling
+//
+// RTX_OPT_SUPERSAMPLE (rtx.h): rows [row0, row0 + rows) of a W x H frame of cells at S x S samples per cell are folded from rows
+// [S row0, S (row0 + rows)) of the S W x S H sample frame -- the frame a caller's params with x = S W, y = S H describe, in values
+// form (kSampleBytes per sample).  Cell (c, r) owns samples (S c + i, S r + j); the sample columns from S (W - 1) on are the
+// newline column's and are not read.
+
+constexpr uint64_t kSampleBytes = 32;      // RTX_RENDER_VALUES: eight floats
+constexpr int kMaxSupersample = 4;         // S in 1 .. 4
+constexpr uint64_t kFrameSideLimit = 1ull << 31; // params.x / params.y of any launch are below it
+
+struct SamplePlan {
+    bool ok = false;           // false: refused (S out of range, an empty frame, rows outside it, a sample frame side of 2^31 or more,
+                               // a buffer of 2^63 bytes or more)
+    uint64_t W = 0, H = 0;     // the sample frame: S W x S H
+    uint64_t row0 = 0, rows = 0; // the sample rows of the call
+    uint64_t bytes = 0;        // of the sample buffer: kSampleBytes S^2 W rows (row S row0 of the sample frame at byte 0)
+    uint64_t cells = 0;        // cells folded: W rows, the newline column's included (they are written, not folded)
+};
+
+inline SamplePlan plan_supersample(uint64_t W, uint64_t H, uint64_t row0, uint64_t rows, int S)
+{
+    SamplePlan p;
+    if (S < 1 || S > kMaxSupersample || W == 0 || H == 0 || W >= kFrameSideLimit || H >= kFrameSideLimit) return p;
+    if (row0 > H || rows > H - row0) return p;
+    const uint64_t s = (uint64_t)S;
+    if (s * W >= kFrameSideLimit || s * H >= kFrameSideLimit) return p;
+    if (s * W * (s * rows) > (~0ull >> 1) / kSampleBytes) return p; // (the product is below 2^62; the bytes must not wrap)
+    p.ok = true;
+    p.W = s * W;
+    p.H = s * H;
+    p.row0 = s * row0;
+    p.rows = s * rows;
+    p.cells = W * rows;
+    p.bytes = kSampleBytes * p.W * p.rows;
+    return p;
+}
+
 } // namespace rtxplan

@@ -75,6 +75,9 @@ int check_recordable(rtx_ctx* ctx, hipStream_t stream, int mode, bool* capturing
     RTX_HIP(ctx, hipStreamIsCapturing(stream, &st));
     *capturing = st == hipStreamCaptureStatusActive;
     if (!*capturing) return RTX_OK;
+    if (ctx->opt_supersample > 1 && mode != RTX_SDL) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: supersampled launches cannot be recorded (RTX_OPT_SUPERSAMPLE: the sample buffer may grow)");
+    }
     if (ctx->ns > ctx->ns_uploaded || ctx->np > ctx->np_uploaded) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: the scene has objects that are not uploaded yet (render once before capturing)");
     }
@@ -1004,6 +1007,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
                  hipStream_t stream, unsigned flags, bool* done)
 {
     *done = false;
+    if (ctx->opt_supersample > 1) return RTX_OK; // (every slab has its own sample frame and fold)
     if (rtxplan::shading_path(shading_request(ctx, mode)) != rtxplan::kPathDirect) return RTX_OK; // (several launches per slab)
     if (n < 2 || n > (size_t)kMaxBatch || mode < RTX_BIT_ASCII || mode >= RTX_SDL || (flags & ~(unsigned)RTX_RENDER_COMPACT) != 0u) return RTX_OK;
     if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt_refine == 1) return RTX_OK;
@@ -1079,34 +1083,11 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
     return RTX_OK;
 }
 
-} // namespace
-
-int rtx_frame_zero_semantics(rtx_ctx* ctx, int mode, uint64_t W, uint64_t H, unsigned flags)
+// The launches of rows c.row0 .. of frame `p` into c.d_out, planned (rtx_plan.hpp: tile shape, cell lists, dispatch order, view adaptation) and
+// queued: everything of rtx_render_rows behind validation and the zero-fill decision.
+int render_planned(rtx_ctx* ctx, const rtx_params* p, int mode, const RenderCall& c, hipStream_t stream, bool capturing)
 {
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    return zero_fill_semantics(ctx, mode, W, H, ctx->d_frame.get(), true, false, flags, ctx->stream);
-}
-
-int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, size_t rows, void* d_out,
-                    size_t out_row_base, void* stream_v, unsigned flags)
-{
-    if (!ctx || !p) return RTX_ERR_INVALID_ARGUMENT;
-    RenderCall c;
-    int rc = validate_render_call(ctx, p, mode, row0, rows, d_out, out_row_base, flags, &c);
-    if (rc != RTX_OK) return rc;
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
-    bool capturing = false;
-    if ((rc = check_recordable(ctx, stream, mode, &capturing)) != RTX_OK) return rc;
-    if (capturing && c.own) {
-        // the zero-fill of the context's buffer is decided from what earlier launches left in it (dirty_hi): a recorded
-        // launch would replay that decision whatever the replays in between have written
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: recorded launches need a caller buffer (d_out), not the context's own");
-    }
-    if (!capturing && (rc = scene_up_to_date(ctx, p->cam_pos)) != RTX_OK) return rc;
-    if ((rc = zero_fill_semantics(ctx, mode, c.W, c.H, c.d_out, c.own, c.compact, flags, stream)) != RTX_OK) return rc;
-    if (c.rows == 0) return RTX_OK;
-
+    int rc;
     KArgs a;
     fill_frame_args(ctx, p, c, a);
 
@@ -1145,6 +1126,87 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     if (adapt && (rc = density_feedback_collect(ctx, stream)) != RTX_OK) return rc;
     if (to && (rc = dispatch_order_derive(ctx, stream, shape, a, to, od)) != RTX_OK) return rc;
     return RTX_OK;
+}
+
+// The sample buffer of `stream` with room for `bytes` (rtx_ctx::SampleScratch): one per render stream, as the hit buffers.  Launches
+// that read the outgrown one were queued on this stream.
+int sample_buffer(rtx_ctx* ctx, hipStream_t stream, size_t bytes, void** out)
+{
+    rtx_ctx::SampleScratch* ss = rtxsync::find(ctx->sample_scratch, stream);
+    if (!ss && !(ss = rtxsync::add(ctx->sample_scratch, stream, (size_t)rtx_ctx::kMaxHitStreams))) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "supersampling: more than 64 distinct render streams");
+    }
+    if (ss->p.reserve(bytes, rtxmem::after_stream(stream)) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the sample buffer (RTX_OPT_SUPERSAMPLE)");
+    }
+    *out = ss->p.get();
+    return RTX_OK;
+}
+
+// RTX_OPT_SUPERSAMPLE > 1 (rtx.h): today's launches for the sample frame `sp` -- params p with x = S W, y = S H -- in values form into
+// the stream's sample buffer, planned as a caller's frame of that size is; then the fold (rtx_resolve) into the caller's target.
+int render_supersampled(rtx_ctx* ctx, const rtx_params* p, int mode, const RenderCall& c, const rtxplan::SamplePlan& sp, hipStream_t stream)
+{
+    int rc;
+    void* samples = nullptr;
+    if ((rc = sample_buffer(ctx, stream, (size_t)sp.bytes, &samples)) != RTX_OK) return rc;
+    rtx_params ps = *p;
+    ps.x = sp.W;
+    ps.y = sp.H;
+    RenderCall cs;
+    cs.W = sp.W;
+    cs.H = sp.H;
+    cs.row0 = cs.out_row_base = sp.row0;
+    cs.rows = sp.rows;
+    cs.d_out = samples;
+    cs.compact = cs.values = true;
+    if ((rc = render_planned(ctx, &ps, mode, cs, stream, false)) != RTX_OK) return rc;
+    KArgs a;
+    fill_frame_args(ctx, p, c, a);
+    int herr = 0;
+    const char* name = rtx_k_launch_resolve(&a, samples, (int)ctx->opt_supersample, mode, stream, &herr);
+    if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "supersampling: invalid rendering mode or frame geometry for the fold");
+    if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "fold kernel launch");
+    ctx->last_kernel = name;
+    ctx->stat_supersample_frames++;
+    return RTX_OK;
+}
+
+} // namespace
+
+int rtx_frame_zero_semantics(rtx_ctx* ctx, int mode, uint64_t W, uint64_t H, unsigned flags)
+{
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    return zero_fill_semantics(ctx, mode, W, H, ctx->d_frame.get(), true, false, flags, ctx->stream);
+}
+
+int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, size_t rows, void* d_out,
+                    size_t out_row_base, void* stream_v, unsigned flags)
+{
+    if (!ctx || !p) return RTX_ERR_INVALID_ARGUMENT;
+    RenderCall c;
+    int rc = validate_render_call(ctx, p, mode, row0, rows, d_out, out_row_base, flags, &c);
+    if (rc != RTX_OK) return rc;
+    const bool supersampled = ctx->opt_supersample > 1 && mode != RTX_SDL; // (RTX_SDL writes nothing: as without the option)
+    rtxplan::SamplePlan sp;
+    if (supersampled && !(sp = rtxplan::plan_supersample(c.W, c.H, c.row0, c.rows, (int)ctx->opt_supersample)).ok) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "RTX_OPT_SUPERSAMPLE: S * params.x and S * params.y must be below 2^31");
+    }
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
+    bool capturing = false;
+    if ((rc = check_recordable(ctx, stream, mode, &capturing)) != RTX_OK) return rc;
+    if (capturing && c.own) {
+        // the zero-fill of the context's buffer is decided from what earlier launches left in it (dirty_hi): a recorded
+        // launch would replay that decision whatever the replays in between have written
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: recorded launches need a caller buffer (d_out), not the context's own");
+    }
+    if (!capturing && (rc = scene_up_to_date(ctx, p->cam_pos)) != RTX_OK) return rc;
+    if ((rc = zero_fill_semantics(ctx, mode, c.W, c.H, c.d_out, c.own, c.compact, flags, stream)) != RTX_OK) return rc;
+    if (c.rows == 0) return RTX_OK;
+
+    if (supersampled) return render_supersampled(ctx, p, mode, c, sp, stream);
+    return render_planned(ctx, p, mode, c, stream, capturing);
 }
 
 int rtx_render(rtx_ctx* ctx, const rtx_params* params, int mode)
