@@ -52,7 +52,9 @@
 //    tests/host/test_grid_shadow_bound.cpp checks the claim and the walk against float64.
 //
 // Rays that are not walkable (origin or direction not finite, a = d . d outside [2^-40, 2^40], origin further than `reach` from
-// the box centre on some axis) test every sphere instead.  tests/host/test_grid_bound.cpp checks all of this against float64.
+// the box centre on some axis) test every sphere instead.  tests/host/test_grid_bound.cpp checks all of this against float64;
+// tests/test_gpu_grid_check.py runs the build and the walk on the device and holds them to this header evaluated on the host,
+// bit for bit.
 #pragma once
 
 #include <math.h>
@@ -123,6 +125,28 @@ RTX_GRID_HD inline void cell_range(const Grid& g, int k, float a, float b, int& 
     while (i1 < last && edge(g, k, i1 + 1) < b) i1++;
     while (i1 > 0 && edge(g, k, i1) > b) i1--;
     if (i1 < i0) i1 = i0;
+}
+
+// The cells sphere (c, rw) is listed in (rw: the radius as the scene holds it, of either sign); false: a large sphere (its box is not
+// finite or covers more than kLargeCells cells).  The build's kernels and the host checks share it.
+RTX_GRID_HD inline bool sphere_cells(const Grid& g, float cx, float cy, float cz, float rw, int i0[3], int i1[3])
+{
+    const float r = fabsf(rw);
+    const float h = sphere_half(g, cx, cy, cz, r);
+    const float c[3] = {cx, cy, cz};
+    bool fin = finite_f(h);
+    uint32_t cells = 1u;
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 3; k++) {
+        const float a = c[k] - h, e = c[k] + h;
+        fin = fin && finite_f(a) && finite_f(e);
+        i0[k] = i1[k] = 0;
+        if (fin) cell_range(g, k, a, e, i0[k], i1[k]);
+        cells *= (uint32_t)(i1[k] - i0[k] + 1); // (at most 1024 per axis: no overflow)
+    }
+    return fin && cells <= kLargeCells;
 }
 
 // The planner: the grid of ns spheres whose boxes c +- |r| (finite ones only) span [blo, bhi]; load = spheres per cell aimed at.

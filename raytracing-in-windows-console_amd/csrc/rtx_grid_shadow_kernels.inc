@@ -18,61 +18,7 @@
 // Output: gs.dark0[pixel], bit i set iff light i is dark at level 0 (level 0 keeps its distance <= cam.far condition); cs.dark
 // in rtx_chain_shadow's layout for the deeper levels (no far limit there), and cs.points counted as rtx_chain_shadow counts it.
 
-// Is the open segment from P to L (toL = L - P) within r of the centre of a sphere other than the one of creation index own_gidx
-// (own_pos: its position in a.sph_geom; 0xffffffff for both: none)?  `open`: the lanes that ask.  Adds the lanes that could not
-// walk their segment to n_fallback.
-__device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShadowArgs& gs, V3 P, V3 toL, uint32_t own_gidx, uint32_t own_pos, bool open,
-                                                  uint32_t& n_fallback)
-{
-    const float len2 = dot(toL, toL);
-    const float inv_len2 = len2 > 0.0f ? 1.0f / len2 : 0.0f; // (as lights_dark_set forms it)
-    const float Pf[3] = {P.x, P.y, P.z}, Df[3] = {toL.x, toL.y, toL.z};
-    const bool walk = rtxgrid::segment_walkable(gs.grid, Pf, Df);
-    bool hit = false;
-    bool go = open && walk;
-    // the large list: wave-uniform index (scalar loads)
-    if (__ballot(go) != 0ull) {
-        for (uint32_t j = 0; j < gs.n_large; j++) {
-            const uint32_t i = gs.large[j];
-            const float4 sp = gs.scene_geom[i];
-            const uint32_t gidx = __float_as_uint(gs.scene_od[i].w);
-            if (go && gidx != own_gidx && segment_hits_sphere(P, toL, inv_len2, sp)) {
-                hit = true;
-                go = false;
-            }
-        }
-    }
-    // the walk
-    if (go) {
-        rtxgrid::Walk w;
-        go = rtxgrid::walk_start(gs.grid, Pf, Df, 1.0f, w);
-        while (go) {
-            const uint32_t c = rtxgrid::cell_index(gs.grid, w);
-            const uint32_t b = gs.cell_start[c], e = gs.cell_start[c + 1u];
-            for (uint32_t j = b; j < e; j++) {
-                if (segment_hits_sphere(P, toL, inv_len2, gs.list_geom[j]) && gs.list_gidx[j] != own_gidx) {
-                    hit = true;
-                    break;
-                }
-            }
-            go = !hit && rtxgrid::t_out(w) <= 1.0f && rtxgrid::walk_step(gs.grid, w);
-        }
-    }
-    // not walkable: every sphere of the scene array, by position (wave-uniform index)
-    const bool fb = open && !walk;
-    if (fb) n_fallback++;
-    if (__ballot(fb) != 0ull) {
-        bool pending = fb;
-        for (uint32_t j = 0; j < a.ns && __ballot(pending) != 0ull; j++) {
-            const float4 sp = a.sph_geom[j];
-            if (pending && j != own_pos && segment_hits_sphere(P, toL, inv_len2, sp)) {
-                hit = true;
-                pending = false;
-            }
-        }
-    }
-    return hit;
-}
+#include "rtx_grid_segment.inc" // grid_segment_dark
 
 // The lights (bit i) the point P -- normal `normal`, on object `id` -- is shadowed from: lights_dark_set's answer, per pixel.
 // Called by every lane of the wave (shadowed_before_spheres and the loops above vote).

@@ -128,8 +128,6 @@ __global__ __launch_bounds__(kThreads) void rtx_query_grid(const QueryArgs q)
     const bool walk = rtxgrid::walkable(q.grid, o, r.a);
     const bool live = valid && tmax >= 0.0f; // a hit has 0 <= t <= tmax: nothing to find otherwise (NaN included)
     const bool fallback = valid && !walk;
-    const unsigned long long fb = __ballot(fallback);
-    if (fb != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(q.fallback, (uint32_t)__popcll(fb));
 
     query_planes(q, r, live, tmax, skip, bt, bid);
     if (live && walk) {
@@ -151,6 +149,9 @@ __global__ __launch_bounds__(kThreads) void rtx_query_grid(const QueryArgs q)
             go = !(bt < tout) && tout <= tmax && !(q.any && bid != kQueryNone) && rtxgrid::walk_step(q.grid, w);
         }
     }
+    // the rays the brute loop answers, counted: one that has nothing to find tests nothing, walkable or not, and is not among them
+    const unsigned long long fb = __ballot(fallback && live);
+    if (fb != 0ull && (threadIdx.x & 63u) == 0u) atomicAdd(q.fallback, (uint32_t)__popcll(fb));
     if (__syncthreads_or(fallback && live ? 1 : 0)) query_all_spheres(q, r, fallback && live, tmax, skip, bt, bid, s_geom, s_gidx);
     if (valid) query_store(q, idx, bt, bid);
 }
@@ -205,31 +206,12 @@ __global__ __launch_bounds__(kThreads) void rtx_grid_bounds(const GridBuildArgs 
     }
 }
 
-// The cells sphere i is listed in; false: a large sphere (its box is not finite or covers more than kLargeCells cells).
-__device__ __forceinline__ bool grid_sphere_cells(const rtxgrid::Grid& g, float4 s, int i0[3], int i1[3])
-{
-    const float r = fabsf(s.w);
-    const float h = rtxgrid::sphere_half(g, s.x, s.y, s.z, r);
-    const float c[3] = {s.x, s.y, s.z};
-    bool fin = rtxgrid::finite_f(h);
-    uint32_t cells = 1u;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        const float a = c[k] - h, e = c[k] + h;
-        fin = fin && rtxgrid::finite_f(a) && rtxgrid::finite_f(e);
-        i0[k] = i1[k] = 0;
-        if (fin) rtxgrid::cell_range(g, k, a, e, i0[k], i1[k]);
-        cells *= (uint32_t)(i1[k] - i0[k] + 1); // (at most 1024 per axis: no overflow)
-    }
-    return fin && cells <= rtxgrid::kLargeCells;
-}
-
 __global__ __launch_bounds__(kThreads) void rtx_grid_count(const GridBuildArgs b)
 {
     const uint32_t i = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
     if (i >= b.ns) return;
     int i0[3], i1[3];
-    const bool small = grid_sphere_cells(b.grid, b.sph_geom[i], i0, i1);
+    const bool small = rtxgrid::sphere_cells(b.grid, b.sph_geom[i].x, b.sph_geom[i].y, b.sph_geom[i].z, b.sph_geom[i].w, i0, i1);
     b.is_large[i] = small ? 0 : 1;
     if (!small) return;
     for (int z = i0[2]; z <= i1[2]; z++) {
@@ -308,7 +290,7 @@ __global__ __launch_bounds__(kThreads) void rtx_grid_scatter(const GridBuildArgs
     const uint32_t i = blockIdx.x * (uint32_t)kThreads + threadIdx.x;
     if (i >= b.ns || b.is_large[i]) return;
     int i0[3], i1[3];
-    grid_sphere_cells(b.grid, b.sph_geom[i], i0, i1);
+    rtxgrid::sphere_cells(b.grid, b.sph_geom[i].x, b.sph_geom[i].y, b.sph_geom[i].z, b.sph_geom[i].w, i0, i1);
     for (int z = i0[2]; z <= i1[2]; z++) {
         for (int y = i0[1]; y <= i1[1]; y++) {
             for (int x = i0[0]; x <= i1[0]; x++) {

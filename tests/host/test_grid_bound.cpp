@@ -72,19 +72,8 @@ struct Scene {
 
 bool sphere_cells(const rtxgrid::Grid& g, const Sph& s, int i0[3], int i1[3], float& h)
 {
-    const float r = std::fabs(s.r);
-    h = rtxgrid::sphere_half(g, s.x, s.y, s.z, r);
-    const float c[3] = {s.x, s.y, s.z};
-    bool fin = rtxgrid::finite_f(h);
-    uint32_t n = 1;
-    for (int k = 0; k < 3; k++) {
-        const float a = c[k] - h, e = c[k] + h;
-        fin = fin && rtxgrid::finite_f(a) && rtxgrid::finite_f(e);
-        i0[k] = i1[k] = 0;
-        if (fin) rtxgrid::cell_range(g, k, a, e, i0[k], i1[k]);
-        n *= (uint32_t)(i1[k] - i0[k] + 1);
-    }
-    return fin && n <= rtxgrid::kLargeCells;
+    h = rtxgrid::sphere_half(g, s.x, s.y, s.z, std::fabs(s.r));
+    return rtxgrid::sphere_cells(g, s.x, s.y, s.z, s.r, i0, i1); // (the build kernels' own function)
 }
 
 void build(Scene& sc, float load)
