@@ -3,10 +3,13 @@
 // raw-mode keyboard input where the reference polls Win32 key state, and PrintMachine's printer thread
 // (PrintMachine.cpp:257-306) writing each minimised frame to the terminal after an ANSI cursor-home.
 //
-//   console_engine [W H] [--mode 0..4] [--frames N] [--dt seconds] [--lockstep] [--no-spawn] [--no-status] [--delta] [--samples N] [--trace FILE] [--keys-only]
+//   console_engine [W H] [--mode 0..4] [--frames N] [--dt seconds] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--samples N] [--trace FILE] [--keys-only]
 //
 // --delta: the printer receives only the console cells that changed since the frame before, addressed by cursor escapes
 // (RayTracingManager::SetDeltaFrames, rtx_update_delta; no reference counterpart), and a whole frame where one is needed.
+// --half: two pixel rows per console row -- every cell the upper half block U+2580 with the top pixel's colour in front and the bottom
+// pixel's behind (RayTracingManager::SetHalfBlocks, rtx_update_half; no reference counterpart).  Needs a UTF-8 terminal; made for the
+// two PIXEL modes (--mode 1 or 3); --delta is ignored with it.
 // --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
 // no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
@@ -148,7 +151,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -161,13 +164,14 @@ int main(int argc, char** argv)
         else if (a == "--no-spawn") spawn = false;
         else if (a == "--no-status") status = false;
         else if (a == "--delta") delta = true; // send only the cells that changed (RayTracingManager::SetDeltaFrames)
+        else if (a == "--half") half = true; // W x 2H pixels as half blocks (RayTracingManager::SetHalfBlocks)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -198,7 +202,7 @@ int main(int argc, char** argv)
     try {
         Terminal term;
         // Engine3D::Start (Engine3D.cpp:9-28): printer first (the manager sizes its buffers from it), then the rest
-        PrintMachine::Start(W, H);
+        PrintMachine::Start(W, H, half);
         auto rayTracingManager = std::make_unique<RayTracingManager>();
         auto camera = std::make_unique<Camera3D>();
         auto scene = std::make_unique<Scene3D>();
@@ -207,6 +211,7 @@ int main(int argc, char** argv)
         scene->Init();
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
         if (delta) rayTracingManager->SetDeltaFrames(true);
+        if (half) rayTracingManager->SetHalfBlocks(true);
         if (samples != 1) rayTracingManager->SetSupersampling(samples);
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;

@@ -261,7 +261,7 @@ enum rtx_option {
                                * RTX_ERR_OUT_OF_MEMORY when it cannot grow), then rtx_resolve<S,mode[,compact|,values]>, which
                                * rtx_last_kernel_name reports.  Everything that traces through rtx_render_rows inherits the rule:
                                * rtx_render, rtx_submit_frames / rtx_submit_slabs (queued one by one: no RTX_OPT_BATCH launch while
-                               * S > 1), rtx_update, rtx_update_begin and rtx_update_delta (their pixel words are the folded cells'),
+                               * S > 1), rtx_update, rtx_update_begin, rtx_update_delta and rtx_update_half (their pixel words are the folded cells'),
                                * and device groups (rank g's cell rows are sample rows [S row0_g, S (row0_g + rows_g)) with the global
                                * row index, so a sharded frame equals the one-device frame).  RTX_SDL writes nothing and is
                                * unaffected; rtx_pick, rtx_query_*, rtx_expand, rtx_minimize* and rtx_delta_words do not trace.  A
@@ -358,6 +358,9 @@ enum rtx_stat {
     RTX_STAT_SUPERSAMPLE_FRAMES = 100, /* supersampled launch sets queued so far (RTX_OPT_SUPERSAMPLE > 1): counted as
                                      * RTX_STAT_SHADOW_FRAMES counts, one per rtx_render_rows call; stays 0 while S = 1.  (Numbered below
                                      * the other counters: 101 .. 154 are taken.)  No reference counterpart (RayTracing.cu:12-17) */
+    RTX_STAT_HALF_FRAMES = 99,      /* frames rtx_update_half has handed out so far.  (Numbered below the other counters, as
+                                     * RTX_STAT_SUPERSAMPLE_FRAMES is: 100 .. 154 are taken.)  No reference counterpart
+                                     * (RayTracing.cu:256,476 paint one colour per cell; PrintMachine.cpp:257-306) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -800,6 +803,50 @@ int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cu
  * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
 int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags,
                      void* host_out, size_t host_capacity, size_t* out_bytes, int* kind);
+
+/* ---- half-block frames: two pixel rows per console row.  Every cell is the glyph U+2580 (upper half block, UTF-8 E2 96 80): the
+ * foreground colour paints its top half, the background colour its bottom half, so a W x H console shows W x 2H square pixels.
+ * No reference counterpart: its two PIXEL modes paint one background colour under a space (RayTracing.cu:256,476), one tall
+ * rectangle per cell, and its printer writes what Update hands it (PrintMachine.cpp:257-306).  Needs a UTF-8 terminal.
+ *
+ * THE RULE, on pixel words (RTX_RENDER_COMPACT).  Inputs: one of the five character modes, W, H and W * 2H words, row-major: row 2r is
+ * the top half of console row r, row 2r+1 the bottom half, column W-1 the newline column as everywhere.
+ *   Colour key K(w): a word 0xffffffff outside column W-1 counts as 0 (a miss).  8-bit family (RTX_BIT_ASCII, RTX_BIT_PIXEL):
+ *   K = w & 0xff, and 16 for w == 0.  RGB family (the other three): K = w & 0xffffff, r, g, b in bytes 0, 1, 2.  The glyph byte of a
+ *   word is ignored: the PIXEL modes are what the feature is for, the others are accepted and the family alone decides.
+ *   Escapes SGR(sel, K), sel = '3' for the foreground and '4' for the background, dec() decimal without leading zeros:
+ *   RGB ESC [ sel 8 ; 2 ; dec(r) ; dec(g) ; dec(b) m (13 .. 19 bytes), 8-bit ESC [ sel 8 ; 5 ; dec(K) m (9 .. 11 bytes).
+ *   Slot g = r*W + c, r in [0, H).  For c < W-1: T = K(words[2rW + c]), B = K(words[(2r+1)W + c]).
+ * In slot order: a slot with c == W-1 emits '\n'.  Every other slot is a cell; the cell before it is slot g-1, or g-2 when c == 0 (the
+ * last cell of the row above); the frame's first cell has none.  A cell emits SGR('3', T) if there is no cell before it or T differs
+ * from that cell's T, then SGR('4', B) likewise for B, then the three bytes E2 96 80.  W == 1: H newlines.
+ * The stream is at most H ((W-1)(2E + 3) + 1) bytes, E = 19 for RGB and 11 for 8-bit.  A terminal that keeps the SGR foreground and
+ * background state, fed the stream from the home position, shows (T, B) in every cell.
+ * Out of scope: a pipelined begin / end form, a launch that writes host memory itself (RTX_OPT_UPDATE_HOST_WRITE), a device group's
+ * gather-free direct update (RTX_OPT_GROUP_UPDATE), delta frames of half-block streams, and a space in place of the glyph where
+ * T == B. */
+/* The bound above for a w x h console of `mode`.  0 for anything the other two calls refuse: RTX_SDL or no mode, w == 0 or h == 0,
+ * w or 2h of 2^31 or more, a product that does not fit size_t.  Pure host arithmetic.
+ * No reference counterpart (RayTracing.cu:256,476; its buffers are 20*W*H, PrintMachine.cpp:140). */
+size_t rtx_half_bound(int mode, size_t w, size_t h);
+/* The rule as a pass of its own over the caller's device buffers: d_words w * 2h words (4-byte aligned), d_out the stream (16-byte
+ * aligned, out_capacity bytes; less than rtx_half_bound(mode, w, h) returns RTX_ERR_TOO_LARGE before anything is launched),
+ * *out_bytes its length.  On the context's stream; blocking, like rtx_minimize_words, and with its launches: RTX_OPT_MINIMIZE_FUSED
+ * 0 / 1 / 2 means here what it means there (a launch that gave up is redone as three and counted in RTX_STAT_MINIMIZE_FALLBACKS).
+ * Bytes of d_out past *out_bytes are not written.  On a device group: the root's device alone.
+ * No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306). */
+int rtx_half_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_words,
+                   void* d_out, size_t out_capacity, size_t* out_bytes);
+/* rtx_update for a console of params->x columns and params->y rows shown as half blocks: physics exactly as rtx_update runs it, then
+ * the sample frame -- `params` with y doubled; ray generation divides by y, so the field of view is what it was -- traced as pixel
+ * words by the path rtx_update uses (every shading option and RTX_OPT_SUPERSAMPLE apply; a device group traces sharded and
+ * gathers), the rule over those words into a buffer of the context's own (rtx_half_bound bytes, grown on demand) and the stream
+ * copied to host_out.  20 * W * 2H above the context's capacity: RTX_ERR_TOO_LARGE -- create the context with twice the rows.  A
+ * stream longer than host_capacity: RTX_ERR_TOO_LARGE, and nothing is copied.  Blocking.  Successful or not, the call invalidates
+ * rtx_update_delta's previous frame (the screen shows something else): the next delta call gives a key frame.
+ * Counted in RTX_STAT_HALF_FRAMES.  No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306). */
+int rtx_update_half(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics,
+                    void* host_out, size_t host_capacity, size_t* out_bytes);
 
 /* ---- ansi256_from_rgb (ANSIRGB.h:141-189) on its own: the xterm-256 index (16..255) of each packed 0xRRGGBB
  * value first_rgb, first_rgb+1, ..., first_rgb+count-1 (first_rgb + count <= 2^24), one byte per value into

@@ -160,6 +160,13 @@ struct Device {
         return list;
     }
     static void set_devices(const std::vector<int>& list) { devices() = list; }
+    // Pixel rows per console row the context is created for: 1, or 2 for half-block frames (PrintMachine::Start(x, y, true);
+    // rtx_update_half traces W x 2H pixels).  Read when the context is created.
+    static size_t& rows_per_cell()
+    {
+        static size_t rows = 1;
+        return rows;
+    }
     static std::vector<int> devices_from_environment()
     {
         std::vector<int> list;
@@ -181,8 +188,9 @@ struct Device {
         rtx_ctx*& ctx = slot();
         if (!ctx) {
             std::vector<int> list = devices().empty() ? devices_from_environment() : devices();
-            const int rc = list.empty() ? rtx_create(ordinal(), max_w, max_h, &ctx)
-                                        : rtx_group_create((int)list.size(), list.data(), max_w, max_h, &ctx);
+            const size_t rows = max_h * rows_per_cell();
+            const int rc = list.empty() ? rtx_create(ordinal(), max_w, rows, &ctx)
+                                        : rtx_group_create((int)list.size(), list.data(), max_w, rows, &ctx);
             if (rc != RTX_OK) {
                 throw std::runtime_error(std::string(list.empty() ? "rtx_create: " : "rtx_group_create: ") + rtx_last_error(nullptr));
             }
@@ -209,15 +217,24 @@ struct Device {
 // reference's thread re-prints the same buffer in a busy loop between frames; this one sleeps on a condition
 // variable until SetDataInBackBuffer flags a new frame (a terminal gains nothing from identical bytes), and a frame
 // that arrives while the previous one is still being written replaces it, as in the reference.  With delta frames
-// (SetDeltaInBackBuffer) the cursor is homed in front of key frames only.
+// (SetDeltaInBackBuffer) the cursor is homed in front of key frames only.  Start(x, y, true) prepares for half-block frames
+// (RayTracingManager::SetHalfBlocks; no reference counterpart): the buffers are sized by rtx_half_bound -- 41 bytes per cell
+// where a frame of records has 20 -- and the device context is created for 2 y pixel rows.
 class PrintMachine {
 public:
-    static void Start(const size_t x, const size_t y)
+    static void Start(const size_t x, const size_t y, const bool half_blocks = false)
     {
         State& s = state();
         s.width = x;
         s.height = y;
         s.maxSize = 20 * x * y; // m_charsPerPixel, PrintMachine.h:81
+        s.halfBlocks = half_blocks;
+        if (half_blocks) {
+            const size_t bound = rtx_half_bound(RTX_RGB_PIXEL, x, y); // (the longer family's: the mode may change while running)
+            if (bound == 0) throw std::runtime_error("PrintMachine::Start: no half-block frames of this size");
+            if (bound > s.maxSize) s.maxSize = bound;
+        }
+        rtx_compat::Device::rows_per_cell() = half_blocks ? 2 : 1;
         s.backBuffer.assign(s.maxSize, 0);
         s.printBuffer.assign(s.maxSize, 0);
         s.backBufferPrintSize = 0;
@@ -231,6 +248,7 @@ public:
     static size_t GetWidth() { return state().width; }
     static size_t GetHeight() { return state().height; }
     static size_t GetMaxSize() { return state().maxSize; }
+    static bool HalfBlocks() { return state().halfBlocks; }
     static bool ChangeSize(const size_t x, const size_t y)
     {
         state().width = x;
@@ -381,6 +399,7 @@ private:
         bool shouldSwap = false, terminate = false, statusLines = true;
         bool backIsKey = true;  // the back buffer starts with a whole frame (else with a delta: no cursor home in front of it)
         bool deltaMode = false; // SetDeltaMode
+        bool halfBlocks = false; // Start(x, y, true)
         unsigned long long framesSet = 0, framesPrinted = 0;
         int fd = 1, renderingFps = 0;
         std::thread printer;
@@ -618,6 +637,13 @@ public:
         }
         const rtx_params p = rtx_compat::to_rtx_params(params);
         size_t newSize = 0;
+        if (m_halfBlocks) {
+            // two pixel rows per console row (rtx_update_half): a whole frame every time, handed over as rtx_update's is
+            rtx_compat::check(m_ctx, rtx_update_half(m_ctx, &p, (int)currentRenderingMode, dt, /*run_physics=*/1, m_minimizedResultArray,
+                                                     PrintMachine::GetMaxSize(), &newSize), "rtx_update_half");
+            PrintMachine::SetDataInBackBuffer(m_minimizedResultArray, newSize);
+            return;
+        }
         if (m_deltaFrames) {
             // only the cells that changed (rtx_update_delta): a key frame first, after SetDeltaFrames, and whenever the library
             // decides on one (another size or mode); the printer appends deltas it has not written yet
@@ -645,6 +671,18 @@ public:
         m_wantKey = true;
         PrintMachine::SetDeltaMode(on);
     }
+    // Extension, no reference counterpart (RayTracing.cu:256,476 paint one colour per cell): Update hands over half-block frames --
+    // every cell the glyph U+2580 with the colour of pixel row 2r in front and that of row 2r + 1 behind, W x 2H square pixels on a
+    // W x H console (rtx_update_half; the two PIXEL modes are what it is for, a UTF-8 terminal what it needs).  The printer's buffers
+    // and the device context must have been made for it: PrintMachine::Start(x, y, true) first, else this throws.  While on, delta
+    // frames (SetDeltaFrames) are ignored: every frame is whole; switching off makes the next delta frame a key frame.  Off by
+    // default, and then nothing changes.
+    void SetHalfBlocks(const bool on)
+    {
+        if (on && !PrintMachine::HalfBlocks()) throw std::runtime_error("RayTracingManager::SetHalfBlocks: PrintMachine::Start(x, y, true) must come first");
+        m_halfBlocks = on;
+        m_wantKey = true;
+    }
     void SetRenderingMode(const RenderingMode newRenderMode) { currentRenderingMode = newRenderMode; }
     // Extensions, no reference counterpart (its light is a constant, RayTracing.cu:132,143-157): the point light (nullptr: the
     // reference's) and hard shadows (RTX_OPT_SHADOWS).
@@ -659,5 +697,6 @@ private:
     rtx_ctx* m_ctx = nullptr;
     char* m_minimizedResultArray = nullptr;
     bool m_deltaFrames = false, m_wantKey = true; // SetDeltaFrames
+    bool m_halfBlocks = false;                    // SetHalfBlocks
     RenderingMode currentRenderingMode = BIT_ASCII; // RayTracingManager.h:53
 };

@@ -48,6 +48,8 @@ struct MinInput {
     // a delta (rtx_delta_words): `data` is the current frame's words, `prev` the previous frame's, `counts` the launch's two counters
     const void* prev = nullptr;
     void* counts = nullptr;
+    // a half-block frame (rtx_half_words): `data` is W * 2h pixel words, w x h the cells
+    bool half = false;
 };
 
 // ... and, once launched, where it writes and where its result words are.
@@ -362,6 +364,11 @@ struct rtx_ctx {
     DeviceBuf<unsigned long long> d_delta_counts;
     bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
     uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
+
+    // half-block frames (rtx_update_half; rtx_post.hip): the stream's own buffer, grown on demand to rtx_half_bound bytes (d_min
+    // holds 20 W 2H, a half-block stream can take 41 W H)
+    DeviceBuf<uint8_t> d_half_out;
+    uint64_t stat_half_frames = 0;      // RTX_STAT_HALF_FRAMES
 
     std::string error;
     const char* last_kernel = "";

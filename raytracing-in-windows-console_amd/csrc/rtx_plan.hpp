@@ -1168,6 +1168,38 @@ static_assert(cup_length(0, 0) == 6 && cup_length(99998, 99998) == kDeltaMaxCup 
 static_assert(delta_block_bound(12, 1024) == 513 * 12 + 512 * 14 && delta_block_bound(20, 1024) == 1024 * 20 + 14,
               "a block inside one long row can need more than 1024 S bytes");
 
+// ------------------------------------------------------------------------------------------------ half-block frames
+//
+// rtx_half_words / rtx_update_half (rtx.h) emit, for every cell, at most a foreground and a background escape of at most E bytes each
+// (E = 19: ESC [ 3 8 ; 2 ; r ; g ; b m, E = 11: ESC [ 3 8 ; 5 ; K m) and the 3-byte glyph; a row's last column emits a newline.
+
+constexpr size_t kHalfGlyph = 3;   // U+2580 in UTF-8
+constexpr size_t kHalfEscRgb = 19; // the longest escape of the RGB family ...
+constexpr size_t kHalfEsc8 = 11;   // ... and of the 8-bit family
+
+constexpr size_t half_cell_bound(size_t E) { return 2 * E + kHalfGlyph; }
+
+// a * b + c, or 0 where that does not fit size_t
+constexpr size_t half_mul_add(size_t a, size_t b, size_t c)
+{
+    return (a != 0 && b > (~(size_t)0 - c) / a) ? 0 : a * b + c;
+}
+
+// The longest stream of a W x H frame of cells, H ((W - 1)(2E + 3) + 1); 0 where W or H is 0 or the number does not fit size_t.
+constexpr size_t half_bound(size_t E, size_t W, size_t H)
+{
+    if (W == 0 || H == 0 || E > 64) return 0;
+    const size_t row = half_mul_add(W - 1, half_cell_bound(E), 1);
+    return row == 0 ? 0 : half_mul_add(row, H, 0);
+}
+
+// ... of one block of `slots` consecutive slots anywhere in any frame (a block inside one long row is cells alone): the block's LDS
+// image.  0 where the number does not fit size_t.
+constexpr size_t half_block_bound(size_t E, size_t slots) { return E > 64 ? 0 : half_mul_add(slots, half_cell_bound(E), 0); }
+
+static_assert(half_bound(kHalfEscRgb, 3, 1) == 83 && half_bound(kHalfEsc8, 1, 7) == 7 && half_bound(kHalfEscRgb, ~(size_t)0, 2) == 0, "the half-block bound");
+static_assert(half_block_bound(kHalfEscRgb, 1024) == 1024 * 41 && half_block_bound(kHalfEsc8, 1024) == 1024 * 25, "a block's image");
+
 // ------------------------------------------------------------------------------------------------ supersampling
 //
 // RTX_OPT_SUPERSAMPLE (rtx.h): rows [row0, row0 + rows) of a W x H frame of cells at S x S samples per cell are folded from rows

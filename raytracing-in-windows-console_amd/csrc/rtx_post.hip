@@ -42,6 +42,9 @@ MinInput words_input(int mode, size_t w, size_t h, const void* d_words, uint32_t
 
 MinInput delta_input(int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_counts) { return MinInput{mode, w, h, true, d_cur, 0u, d_prev, d_counts}; }
 
+// (w x h: the cells; d_words: w x 2h pixel words)
+MinInput half_input(int mode, size_t w, size_t h, const void* d_words) { return MinInput{mode, w, h, true, d_words, 0u, nullptr, nullptr, true}; }
+
 // f(Src()) with the slot source (rtx_post_kernels.inc) of `in`: the one place where a mode and an input form pick the kernels.
 template <class F>
 int with_source(rtx_ctx* ctx, const MinInput& in, F f)
@@ -52,6 +55,16 @@ int with_source(rtx_ctx* ctx, const MinInput& in, F f)
             f(rtx::RecordSource<20>());
         } else {
             f(rtx::RecordSource<12>());
+        }
+        return RTX_OK;
+    }
+    if (in.half) {
+        if (in.mode < RTX_BIT_ASCII || in.mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "no pixel words in this mode");
+        // the family alone decides: the glyph byte of a word is ignored
+        if (in.mode >= RTX_RGB_ASCII) {
+            f(rtx::HalfSource<true>());
+        } else {
+            f(rtx::HalfSource<false>());
         }
         return RTX_OK;
     }
@@ -793,6 +806,62 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     if (key) ctx->stat_delta_keyframes++;
     *out_bytes = n;
     *kind = key ? RTX_DELTA_KEY : RTX_DELTA_DIFF;
+    return RTX_OK;
+}
+
+size_t rtx_half_bound(int mode, size_t w, size_t h)
+{
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL || w == 0 || h == 0 || w >= (1ull << 31) || h >= (1ull << 30)) return 0;
+    return rtxplan::half_bound(mode >= RTX_RGB_ASCII ? rtxplan::kHalfEscRgb : rtxplan::kHalfEsc8, w, h); // (0 where it does not fit size_t)
+}
+
+int rtx_half_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_words, void* d_out, size_t out_capacity, size_t* out_bytes)
+{
+    if (!ctx || !out_bytes || !d_words || !d_out) return RTX_ERR_INVALID_ARGUMENT;
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_half_words: not a character mode");
+    const size_t bound = rtx_half_bound(mode, w, h);
+    if (bound == 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_half_words: w and 2 h must be in [1, 2^31)");
+    if (((uintptr_t)d_words & 3u) != 0 || ((uintptr_t)d_out & 15u) != 0) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_half_words: words must be 4-byte, the output 16-byte aligned");
+    }
+    if (out_capacity < bound) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_half_words: the output holds less than rtx_half_bound");
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    return minimize_and_wait(ctx, half_input(mode, w, h, d_words), d_out, out_bytes);
+}
+
+int rtx_update_half(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, size_t host_capacity, size_t* out_bytes)
+{
+    if (!ctx || !params || !host_out || !out_bytes) return RTX_ERR_INVALID_ARGUMENT;
+    ctx->delta_valid = false; // (the consumer's screen is about to show this frame: the next rtx_update_delta gives a key frame)
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_update_half: not a character mode");
+    const size_t W = (size_t)params->x, H = (size_t)params->y;
+    const size_t bound = rtx_half_bound(mode, W, H);
+    if (bound == 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half: x and 2 y must be in [1, 2^31)");
+    if (20 * (uint64_t)W * 2u * (uint64_t)H > ctx->capacity) {
+        return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_half: W x 2H pixels are more than the context was created for (create it with twice the rows)");
+    }
+    int rc;
+    // RayTracingManager.cu:89-107: physics first, as rtx_update
+    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    // the sample frame: two pixel rows per console row, under the same field of view (ray generation divides by y)
+    rtx_params sample = *params;
+    sample.y = 2u * (uint64_t)H;
+    const uint32_t* d_words = nullptr;
+    if ((rc = trace_words(ctx, &sample, mode, ctx->d_words, &d_words)) != RTX_OK) return rc;
+    // (every earlier launch into the buffer has been waited for by the call that queued it)
+    if (ctx->d_half_out.reserve((bound + 15u) & ~(size_t)15u, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the half-block buffer");
+    }
+    size_t n = 0;
+    if ((rc = minimize_and_wait(ctx, half_input(mode, W, H, d_words), ctx->d_half_out.get(), &n)) != RTX_OK) return rc;
+    if (n > host_capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_half: the stream is longer than host_capacity");
+    if (n) {
+        RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_half_out.get(), n, hipMemcpyDeviceToHost, ctx->stream));
+        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    ctx->stat_half_frames++;
+    *out_bytes = n;
     return RTX_OK;
 }
 

@@ -2,7 +2,8 @@
 // of the direction-sorted scene copy, the xterm-256 mapper over a range, and Minimize from records or from pixel words -- as one launch
 // (rtx_min_fused, with the look-back it finds its offsets by) or as the chain rtx_min_count / rtx_min_offsets / rtx_min_scatter.  The
 // host side (buffers, launches, the Update entry points): rtx_post.hip.  Delta frames (rtx_delta_words) are a third slot source of the
-// same Minimize kernels, DeltaSource, over two frames of pixel words.
+// same Minimize kernels, DeltaSource, over two frames of pixel words; half-block frames (rtx_half_words) a fourth, HalfSource, over
+// pairs of pixel rows.
 namespace rtx {
 
 constexpr int kThreads = 256;
@@ -672,6 +673,140 @@ struct DeltaSource {
                 atomicAdd(&in.counts[threadIdx.x], (unsigned long long)mine);
             }
         }
+    }
+};
+
+// ---- half-block frames: W x 2H pixel words as W x H cells of U+2580, the upper half block -- the foreground colour paints pixel
+// row 2r, the background colour row 2r + 1 (rtx_half_words in rtx.h states the rule).  No reference counterpart: its PIXEL modes
+// paint one background colour under a space (RayTracing.cu:256,476).  Slot rules, slot g = r W + c of the W x H cells:
+//   * column W-1 -> '\n'
+//   * any other slot is a cell with T = key(words[2g - c]), B = key(words[2g - c + W]) (a word 0xffffffff counts as 0): the
+//     foreground escape if T differs from the T of the cell before it (slot g-1, or g-2 in column 0; the frame's first cell has
+//     none), the background escape likewise for B, then the glyph's three bytes.
+// Every cell emits, so nothing looks further back than two slots: no walk.  RGB: the family -- r;g;b of the key's three bytes, else
+// the xterm index.
+//
+// The block's buffer, in dwords: [kTop - 2], [kTop - 1] the top words of the two slots before the block's first, [kTop + li] the top
+// word of slot base + li, the same of the bottom words from kBot, the scan's partial sums behind them.  A block's slots may span
+// rows and the two words of a slot lie a row apart: slot li of row r is word base + li + r W, so consecutive lanes read consecutive
+// words along each row and a row's end costs one more memory line.
+template <bool RGB>
+struct HalfSource {
+    typedef uint32_t Elem;
+    typedef const uint32_t* __restrict__ In;
+    struct Item {
+        uint32_t t, b; // the two keys; bit 31: the escape is due
+    };
+    static constexpr uint32_t kDue = 0x80000000u;
+    static constexpr uint32_t kE = RGB ? (uint32_t)rtxplan::kHalfEscRgb : (uint32_t)rtxplan::kHalfEsc8;
+    static constexpr uint32_t kS = 2u * kE + (uint32_t)rtxplan::kHalfGlyph; // the longest slot
+    static constexpr uint32_t kTop = 4, kBot = kTop + kSlotsPerBlock + 4;
+    static constexpr uint32_t kWave = (kBot + kSlotsPerBlock) * 4;
+    static constexpr uint32_t kStage = kWave + (kThreads / 64) * 4;
+    static constexpr uint32_t kBytes = ((uint32_t)rtxplan::half_block_bound(kE, kSlotsPerBlock) + 15u) & ~15u;
+    static_assert(rtxplan::half_block_bound(kE, kSlotsPerBlock) != 0 && kBytes >= rtxplan::half_block_bound(kE, kSlotsPerBlock) && kBytes >= kSlotsPerBlock * kS,
+                  "the image holds the longest stream a block can emit");
+    static_assert(kStage <= kBytes, "words + partial sums fit the image's space");
+
+    static In input(const void* data, const void*, void*) { return (In)data; }
+    static __device__ __forceinline__ void stage_tables() {}
+    static __device__ __forceinline__ void tally_put(const uint32_t*) {}
+    static __device__ __forceinline__ void tally_add(In) {}
+
+    static __device__ __forceinline__ uint32_t key(uint32_t w)
+    {
+        w = w == kNoWord ? 0u : w; // (outside column W-1, which has no key)
+        return colour_key<RGB ? RTX_K_RGB_PIXEL : RTX_K_BIT_PIXEL>(w);
+    }
+
+    static __device__ __forceinline__ uint32_t digits(uint32_t v) { return 1u + (v >= 10u ? 1u : 0u) + (v >= 100u ? 1u : 0u); } // v <= 255
+
+    static __device__ __forceinline__ uint32_t escape_length(uint32_t k)
+    {
+        return RGB ? 10u + digits(k & 255u) + digits((k >> 8) & 255u) + digits((k >> 16) & 255u) : 8u + digits(k);
+    }
+
+    static __device__ __forceinline__ void stage(In words, uint64_t base, uint64_t n_slots, uint32_t, uint8_t* s, uint32_t W)
+    {
+        uint32_t* s_w = reinterpret_cast<uint32_t*>(s);
+        // the block's first row and column by one scalar division (64-bit only where the slot does not fit 32 bits), as first_column
+        const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane((base >> 32) == 0u ? (uint32_t)base / W : (uint32_t)(base / W));
+        const uint32_t col0 = (uint32_t)(base - (uint64_t)row0 * W);
+#pragma unroll
+        for (int k = 0; k < kPerThread; k++) {
+            const uint32_t li = (uint32_t)k * kThreads + threadIdx.x;
+            uint32_t top = kNoWord, bot = kNoWord;
+            if (base + li < n_slots) {
+                const uint32_t row = row0 + (col0 + li) / W; // (32-bit: col0 < W < 2^31 and li < 1024)
+                const uint32_t* p = words + (base + li + (uint64_t)row * W); // = words + 2g - c; the last one read is word 2 n_slots - 1
+                top = p[0];
+                bot = p[W];
+            }
+            s_w[kTop + li] = top;
+            s_w[kBot + li] = bot;
+        }
+        if (threadIdx.x < 2u) {
+            // slot base - 2 + tid: in row row0 if the block's first column is far enough right, else in the row above (whatever W:
+            // a word of the frame, and one that no cell looks at where the slot is not the cell in front of it)
+            const uint32_t back = 2u - threadIdx.x;
+            uint32_t top = kNoWord, bot = kNoWord;
+            if (base >= back) {
+                const uint32_t row = col0 >= back ? row0 : row0 - 1u; // (base >= back and col0 < back: row0 >= 1)
+                const uint32_t* p = words + (base - back + (uint64_t)row * W);
+                top = p[0];
+                bot = p[W];
+            }
+            s_w[kTop - back] = top;
+            s_w[kBot - back] = bot;
+        }
+    }
+
+    // Emitted length of slot g (column col, staged at li): 1 for the newline, else 3 plus the escapes that are due.
+    static __device__ __forceinline__ uint32_t length(In, const uint8_t* s, uint64_t g, int li, uint32_t col, uint32_t W, uint32_t, Item& it)
+    {
+        const uint32_t* s_w = reinterpret_cast<const uint32_t*>(s);
+        const int back = col == 0u ? 2 : 1; // the cell before: slot g-1, or g-2 when g-1 is the row above's last column
+        const uint32_t t = key(s_w[kTop + li]), b = key(s_w[kBot + li]);
+        const uint32_t pt = key(s_w[(int)kTop + li - back]), pb = key(s_w[(int)kBot + li - back]);
+        const bool first = g == 0u, newline = col == W - 1u;
+        const bool due_t = first || t != pt, due_b = first || b != pb;
+        it.t = t | (due_t ? kDue : 0u);
+        it.b = b | (due_b ? kDue : 0u);
+        const uint32_t len = (uint32_t)rtxplan::kHalfGlyph + (due_t ? escape_length(t) : 0u) + (due_b ? escape_length(b) : 0u);
+        return newline ? 1u : len;
+    }
+
+    // ESC [ sel 8 ; 2 ; r ; g ; b m  resp.  ESC [ sel 8 ; 5 ; K m  at dst; returns its length.  The head goes out as two dwords: the
+    // eighth byte is the first digit's place, which is written afterwards (32-bit stores into LDS need no alignment).
+    static __device__ __forceinline__ uint32_t put_escape(uint8_t* dst, uint32_t sel, uint32_t k)
+    {
+        *reinterpret_cast<u32_unaligned*>(dst) = 0x1bu | ((uint32_t)'[' << 8) | (sel << 16) | ((uint32_t)'8' << 24);
+        *reinterpret_cast<u32_unaligned*>(dst + 4) = (uint32_t)';' | ((RGB ? (uint32_t)'2' : (uint32_t)'5') << 8) | ((uint32_t)';' << 16) | ((uint32_t)'0' << 24);
+        uint32_t at = 7u;
+#pragma unroll
+        for (uint32_t q = 0; q < (RGB ? 3u : 1u); q++) {
+            const uint32_t v = (k >> (8u * q)) & 255u, n = digits(v);
+            put_decimal(dst + at, v, n);
+            dst[at + n] = q + 1u < (RGB ? 3u : 1u) ? (uint8_t)';' : (uint8_t)'m';
+            at += n + 1u;
+        }
+        return at;
+    }
+
+    static __device__ __forceinline__ void emit(uint8_t* dst, uint32_t len, bool newline, const Item& it)
+    {
+        if (len == 0u) {
+            return; // a slot past the frame's end
+        }
+        if (newline) {
+            dst[0] = (uint8_t)'\n';
+            return;
+        }
+        if ((it.t & kDue) != 0u) dst += put_escape(dst, (uint32_t)'3', it.t & ~kDue);
+        if ((it.b & kDue) != 0u) dst += put_escape(dst, (uint32_t)'4', it.b & ~kDue);
+        dst[0] = 0xe2u;
+        dst[1] = 0x96u;
+        dst[2] = 0x80u;
     }
 };
 
