@@ -21,6 +21,7 @@
 
 #include "rtx_cull.hpp"
 #include "rtx_device.hpp"
+#include "rtx_far.hpp"
 #include "rtx_kernels.h"
 #include "rtx_records.hpp"
 #include "rtx_reflect.hpp"

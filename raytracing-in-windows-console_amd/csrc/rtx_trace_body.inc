@@ -13,8 +13,13 @@
     __shared__ uint32_t s_idx[kListCap];
     __shared__ float4 s_col[kTable];             // per column: (m0, m4, m8) * vx
     __shared__ float4 s_row[kTable];             // per row:    (m1, m5, m9) * vy
-    // per plane: {n, num} {xlo, xhi, zlo, zhi} {od, gidx} {normalize_gpu(n), its shadingValue} {shade_nn()'s nn, 0}
+    // per plane: {n, num} {xlo, xhi, zlo, zhi} {od, gidx} {normalize_gpu(n), its shadingValue} {shade_nn()'s nn, the direction cut}
     __shared__ float4 s_plane[kPlaneRow * kPlaneTable];
+    // Records and compact words carry nothing of a pixel whose distance exceeds cam.far (encode_and_store's `visible`), so there
+    // a table plane's direction test also drops the lanes whose hit on it provably lies beyond far (rtx_far.hpp: the rule and
+    // its proof).  The value floats and the closest-hit form keep such hits: they compile to the parent's test.
+    constexpr bool kFarCut = (OUT == kOutRecords || OUT == kOutCompact) && MODE != RTX_K_SDL;
+    static_assert(kFarNoHit == kNoHit, "rtx_far.hpp's rule assumes the reference's no-hit distance");
     __shared__ uint32_t s_digits[256];           // three decimal digits of 0..255, NUL padded
     __shared__ uint32_t s_unit[kUnitEntries];    // rescale factors of nearly-unit squared lengths (rtx_unit.hpp)
     // 1 / (2 a) of a ray's nearly-unit a, same slots (rtx_device.hpp: half_recip; the REFINE kernels do not use it).  With these
@@ -255,7 +260,7 @@
             const V3 nrm = normalize_gpu(n);
             const V3 nn = normalize_gpu(nrm);
             s_plane[kPlaneRow * at + 3] = make_float4(nrm.x, nrm.y, nrm.z, nrm.x * 1.0f + nrm.y * 0.0f + nrm.z * 0.0f);
-            s_plane[kPlaneRow * at + 4] = make_float4(nn.x, nn.y, nn.z, 0.0f);
+            s_plane[kPlaneRow * at + 4] = make_float4(nn.x, nn.y, nn.z, kFarCut ? far_dir_cut(num, cam.far) : 0.0f);
             if (OUT == kOutHit) s_plmap[at] = tid;
         }
         if (tid == 0u) {
@@ -396,7 +401,12 @@
         for (uint32_t q = 0; q < np_vis; q++) {
             const float4 pn = s_plane[kPlaneRow * q + 0];
             const float dn = ray.d.x * pn.x + ray.d.y * pn.y + ray.d.z * pn.z;
-            if (dn > 0.0f || fabsf(dn - 0.0f) < 1.1920928955078125e-7f) {
+            if (kFarCut) {
+                // one compare for Plane.cu's two (together dn > -FLT_EPSILON; a NaN takes neither form) and for the far cut
+                if (dn > s_plane[kPlaneRow * q + 4].w) {
+                    continue;
+                }
+            } else if (dn > 0.0f || fabsf(dn - 0.0f) < 1.1920928955078125e-7f) {
                 continue;
             }
             const float t1 = div_cr(pn.w, dn); // = pn.w / dn, bit for bit
@@ -438,11 +448,20 @@
         // ---- shade the winner (RayTracing.cu:123-157).  Values of a missed pixel are never encoded.
         float distance = kNoHit, shadingValue = 0.0f;
         V3 normal = ray.d, colour = ray.d;
+        if (kFarCut && MODE == RTX_K_RGB_NORMALS) {
+            // ... except under cam.far >= kNoHit, where a pixel that hit nothing passes the far test: the reference's initial
+            // normal (0, 0, 0) is then what an RGB_NORMALS record shows (every other byte comes out of ray.d's components,
+            // all below 1, as the 0 the reference has there)
+            normal = v3(0.0f, 0.0f, 0.0f);
+        }
         if (ABL(32u)) {
             distance = b.t; shadingValue = ray.d.x;
         } else if (OUT == kOutHit) {
             distance = b.t; // the shadow path's first launch: the winner only; rtx_shadow_shade shades it
-        } else if (plane_q != 0xffffffffu || b.k != 0xffffffffu) {
+        } else if ((plane_q != 0xffffffffu || b.k != 0xffffffffu) && !(kFarCut && __ballot(in_frame && b.t <= cam.far) == 0ull)) {
+            // (records and compact words: a wave none of whose pixels is visible -- every hit beyond cam.far, as spheres
+            // beyond far and direct-form planes leave them -- skips the stage: its lanes keep distance = kNoHit, which
+            // fails the far test as their b.t <= kNoHit did)
             V3 nn, od;
             if (plane_q < np_tab) {
                 // a plane of the LDS table: normal, shadingValue and nn depend on the plane alone and are in the table (the
