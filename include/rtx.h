@@ -268,6 +268,38 @@ enum rtx_option {
                                * supersampled launch inside a graph capture returns RTX_ERR_INVALID_ARGUMENT (the sample buffer may
                                * grow), and so does one with S x or S y of 2^31 or more; otherwise the existing paths' limits apply
                                * to the sample frame.  No reference counterpart (RayTracing.cu:12-17 traces one ray per cell) */
+    RTX_OPT_REFLECT_GRID = 31, /* mirror rays through the world grid of the ray queries: 0 (default: every launch, byte for byte and
+                               * kernel for kernel, what it is without this option) or 1.  Anything else returns
+                               * RTX_ERR_INVALID_ARGUMENT and changes nothing.  The rule: the test itself is unchanged -- the planes per
+                               * pixel, the reference's sphere test for every sphere other than the one the ray leaves, no far limit,
+                               * the winner the minimum of (t, creation index), at every level 1 .. RTX_OPT_REFLECT_DEPTH (the rule at
+                               * rtx_scene_set_reflectivity) -- only WHICH spheres a secondary ray is tested against changes: the
+                               * grid's large spheres and those listed in the cells the ray passes through, walked with no far limit
+                               * until its best t is below the parameter at which it leaves the cell just tested, or until it leaves
+                               * the grid, exactly as rtx_query_rays walks -- instead of those a bundle over the 16 x 16 tile keeps.
+                               * No sphere the test would report is left out (the queries' proved bound: a mirror ray is a query ray
+                               * with tmax = infinity), so the frames are byte for byte those of the existing path.  It has an effect
+                               * only while the frame is on the mirror path (something reflects), RTX_OPT_REFLECT_CHECK is 0 (checks 1
+                               * and 2 keep today's launches: they are the brute reference), the scene has at least one sphere, and
+                               * the grid is usable (RTX_STAT_QUERY_BRUTE reads 0 after the build); otherwise every launch is what it
+                               * is without it.  The launches, while in effect: closest hits; rtx_grid_reflect -- one pixel per thread,
+                               * every level in one launch, no list in LDS -- in place of rtx_reflect_hit or rtx_reflect_chain; then
+                               * whatever shadow pass and shade family the other options choose, unchanged (they read the hit arrays,
+                               * whose layout and size are unchanged).  The grid is the queries' own, shared with RTX_OPT_SHADOW_GRID
+                               * (one object, one RTX_STAT_QUERY_GRID_BUILDS: a frame with both options on builds once): the first
+                               * frame after rtx_scene_add_*, an edit, a removal, rtx_scene_clear or rtx_update_objects rebuilds it,
+                               * which blocks as a query's build does -- a physics step per frame means a build per frame.  A ray that
+                               * cannot be walked -- its origin further from the spheres' box than three times the box's largest
+                               * half-extent on some axis (a mirror floor far outside the spheres), an origin or direction that is not
+                               * finite, a squared direction length outside [2^-40, 2^40] -- tests every sphere
+                               * (RTX_STAT_REFLECT_GRID_FALLBACK_RAYS).  A launch on this path is refused inside a graph capture with
+                               * RTX_ERR_INVALID_ARGUMENT (the lists change with physics, and the build allocates and waits).
+                               * Replicated over a device group like every option; every member builds its own grid on its own
+                               * device.  Everything that traces through rtx_render_rows inherits it: rtx_update*, slabs,
+                               * RTX_OPT_SUPERSAMPLE, half blocks, delta frames and groups.  RTX_STAT_REFLECT_RAYS counts at any depth
+                               * on this path; RTX_STAT_REFLECT_LONGEST_LIST reads 0 after such a set.  Off by default: there is no
+                               * automatic policy, and where most rays fall back it is slower.  No reference counterpart
+                               * (RayTracing.cu:635) */
     RTX_OPT_REFINE = 5        /* per-wave refinement of the candidate list in the binned kernel: -1 auto (dense scenes), 0 off, 1 on
                                * (needs at most 4 sub-tiles per workgroup and a macro tile of at most 64 x 64 pixels; otherwise it
                                * stays off) */
@@ -304,8 +336,8 @@ enum rtx_stat {
                                      * queued last; with RTX_OPT_REFLECT_DEPTH > 1 the maximum over the levels.  One word per context, as
                                      * RTX_STAT_SHADOW_LONGEST_LIST.  Reading it waits for the device */
     RTX_STAT_REFLECT_RAYS = 138,    /* 138 .. 141: the secondary rays of level 1 .. RTX_MAX_REFLECT_DEPTH that the launch set queued last on
-                                     * the chain kernels (RTX_OPT_REFLECT_DEPTH > 1, or RTX_OPT_REFLECT_DEPTH_CHECK 1) traced; all 0 after a
-                                     * set that took the one-bounce kernels.  One 4-word device array per context, as
+                                     * the chain kernels (RTX_OPT_REFLECT_DEPTH > 1, or RTX_OPT_REFLECT_DEPTH_CHECK 1) or on rtx_grid_reflect
+                                     * (RTX_OPT_REFLECT_GRID in effect: at any depth) traced; all 0 after a set that took rtx_reflect_hit.  One 4-word device array per context, as
                                      * RTX_STAT_REFLECT_LONGEST_LIST.  Reading it waits for the device.
                                      * No reference counterpart (RayTracing.cu:635) */
     RTX_STAT_REFLECT_SHADOW_POINTS = 142, /* 142 .. 145: the hit points of level 1 .. RTX_MAX_REFLECT_DEPTH that the launch set queued last
@@ -318,9 +350,15 @@ enum rtx_stat {
     RTX_STAT_SHADOW_GRID_FALLBACK_POINTS = 147, /* the (point, light) segments of the last such launch set that could not be walked and
                                      * tested every sphere instead, over all levels.  One word per context, as RTX_STAT_SHADOW_LONGEST_LIST.
                                      * Reading it waits for the device, as RTX_STAT_QUERY_FALLBACK_RAYS does */
+    RTX_STAT_REFLECT_GRID_FRAMES = 98, /* launch sets queued with the mirror rays through the world grid (RTX_OPT_REFLECT_GRID in effect):
+                                     * counted as RTX_STAT_SHADOW_FRAMES counts.  (Numbered below the other counters, as
+                                     * RTX_STAT_HALF_FRAMES is) */
+    RTX_STAT_REFLECT_GRID_FALLBACK_RAYS = 97, /* the secondary rays of the last such launch set that could not be walked and tested every
+                                     * sphere instead, over all levels.  One word per context, as RTX_STAT_REFLECT_LONGEST_LIST.
+                                     * Reading it waits for the device, as RTX_STAT_QUERY_FALLBACK_RAYS does */
     RTX_STAT_QUERY_GRID_BUILDS = 122, /* builds of the ray queries' world grid so far: one by the first query after rtx_scene_add_*,
                                      * rtx_scene_clear, rtx_update_objects or a change of RTX_OPT_QUERY_LOAD (or by the first frame after one, under
-                                     * RTX_OPT_SHADOW_GRID: the grid is shared); none by a query or a frame on an unchanged scene */
+                                     * RTX_OPT_SHADOW_GRID or RTX_OPT_REFLECT_GRID: the grid is shared); none by a query or a frame on an unchanged scene */
     RTX_STAT_QUERY_FALLBACK_RAYS = 123, /* rays of the last rtx_query_rays / rtx_query_rays_host / rtx_pick call that the grid kernel answered by
                                      * testing every object because they cannot be walked (see rtx_query_rays).  0 after a call under
                                      * RTX_OPT_QUERY_CHECK 1.  Reading it waits for the device */

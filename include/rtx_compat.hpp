@@ -470,6 +470,9 @@ public:
         check(rtx_get_option(ctx(), RTX_OPT_REFLECT_DEPTH, &v), "RTX_OPT_REFLECT_DEPTH");
         return (int)v;
     }
+    // Mirror rays through the ray queries' world grid instead of the tiles' bundles (RTX_OPT_REFLECT_GRID): the same frames, byte for
+    // byte; off by default.  No reference counterpart (RayTracing.cu:635).
+    void SetReflectGrid(const bool on) { check(rtx_set_option(ctx(), RTX_OPT_REFLECT_GRID, on ? 1 : 0), "RTX_OPT_REFLECT_GRID"); }
     // Objects edited in place, by creation index.  The reference has the seam -- Object3D::SetMiddlePos (Object3D.h:55,
     // Object3D.cu:34) -- and never calls it after upload; here a sphere takes a new centre, radius and colour (rtx_scene_set_spheres:
     // rows of cx cy cz r R G B for first .. first+n-1), a plane all its fields (rtx_scene_set_plane).  Mover, speed, reflectivity

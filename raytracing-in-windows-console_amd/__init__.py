@@ -50,7 +50,10 @@ OPT_REFLECT_SHADOWS = 28
 OPT_SHADOW_GRID = 29
 STAT_SHADOW_GRID_FRAMES = 146
 STAT_SHADOW_GRID_FALLBACK_POINTS = 147
-OPT_SUPERSAMPLE = 30            # S x S rays per console cell, folded on the GPU: 1 (default) .. 4 (include/rtx.h)
+OPT_REFLECT_GRID = 31           # mirror rays through the world grid: 0 (default) or 1 (include/rtx.h)
+STAT_REFLECT_GRID_FRAMES = 98
+STAT_REFLECT_GRID_FALLBACK_RAYS = 97
+OPT_SUPERSAMPLE = 30           # S x S rays per console cell, folded on the GPU: 1 (default) .. 4 (include/rtx.h)
 STAT_SUPERSAMPLE_FRAMES = 100
 STAT_HALF_FRAMES = 99           # frames rtx_update_half has handed out (include/rtx.h)
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149

@@ -322,6 +322,15 @@ struct rtx_ctx {
     uint64_t stat_shadow_grid_frames = 0;
     DeviceBuf<uint32_t> d_shadow_grid_fallback; // segments of the last launch set on the path that tested every sphere (one word)
 
+    // mirror rays through that grid (RTX_OPT_REFLECT_GRID): in effect on the mirror path while RTX_OPT_REFLECT_CHECK is 0, the scene has a
+    // sphere and the build found a usable grid; then rtx_grid_reflect writes the hit arrays in place of rtx_reflect_hit /
+    // rtx_reflect_chain.  d_refl_pos: creation index -> position of the sphere in the scene arrays (words [0, n)) and in the
+    // direction-sorted copy (words [n, 2 n), n = max(objects, 1)), uploaded with the reflectivities (refl_dirty) and valid as they are.
+    int64_t opt_reflect_grid = 0;
+    uint64_t stat_reflect_grid_frames = 0;
+    DeviceBuf<uint32_t> d_refl_pos;
+    DeviceBuf<uint32_t> d_reflect_grid_fallback; // rays of the last launch set on the path that tested every sphere (one word)
+
     // supersampling (RTX_OPT_SUPERSAMPLE): with S > 1 rtx_render_rows runs its launches for the S W x S H sample frame in values form
     // into the render stream's sample buffer (32 S^2 W rows bytes; one per render stream as the hit buffers, for at most
     // kMaxHitStreams streams; it grows on demand, never shrinks and goes with the context) and rtx_resolve folds it into the target

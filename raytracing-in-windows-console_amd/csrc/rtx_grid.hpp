@@ -51,6 +51,12 @@
 //    first hit as well.  segment_walkable() is the classification, for the kernel (rtx_grid_shadow) and the host check alike;
 //    tests/host/test_grid_shadow_bound.cpp checks the claim and the walk against float64.
 //
+// 5. Mirror rays (RTX_OPT_REFLECT_GRID).  A secondary ray of the mirror path is a query ray: mirror_ray and query_ray fill the same Ray
+//    fields from (o, d) with the same operations (a = d . d, fourA = 4a, divTwoA = 1 / (2a)), both are tested with
+//    secondary_sphere_hit, both take the minimum of (t, creation index) and skip the object the ray leaves, and a mirror ray has no
+//    far limit: tmax = infinity.  Steps 1-3 therefore apply verbatim to rtx_grid_reflect's walk, with walkable() as the
+//    classification; nothing new is bounded and no constant is added.
+//
 // Rays that are not walkable (origin or direction not finite, a = d . d outside [2^-40, 2^40], origin further than `reach` from
 // the box centre on some axis) test every sphere instead.  tests/host/test_grid_bound.cpp checks all of this against float64;
 // tests/test_gpu_grid_check.py runs the build and the walk on the device and holds them to this header evaluated on the host,

@@ -192,6 +192,22 @@ struct GridShadowArgs {
     uint32_t* fallback;         // the (point, light) segments that tested every sphere because they cannot be walked (atomicAdd)
 };
 
+// Mirror rays through the world grid (RTX_OPT_REFLECT_GRID): rtx_grid_reflect, in place of rtx_reflect_hit / rtx_reflect_chain, walks
+// every reflective pixel's secondary rays of every level through the ray queries' grid and leaves the hit arrays rtx_reflect_chain
+// leaves (ReflectArgs::hits2, ChainArgs).  The grid's views are the ones GridShadowArgs carries.
+struct GridReflectArgs {
+    rtxgrid::Grid grid;
+    const uint32_t* cell_start; // the build's lists, as QueryArgs has them
+    const float4* list_geom;
+    const uint32_t* list_gidx;
+    const float4* scene_geom;   // the scene arrays in creation order, which the large list indexes
+    const float4* scene_od;
+    const uint32_t* large;
+    uint32_t n_large;
+    const uint32_t* pos_of_gidx; // one word per object: creation index -> the position KArgs::sph_geom knows the sphere by (planes: unused)
+    uint32_t* fallback;         // the rays, over all levels, that tested every sphere because they cannot be walked (atomicAdd)
+};
+
 // Ray queries (rtx_query_rays): n rays of the caller against the scene arrays in creation order (spheres are known by sphere
 // index here, not by the direction-sorted position the trace kernels use), through the world grid or against every sphere.
 struct QueryArgs {
@@ -268,6 +284,7 @@ struct TileArgs {
     const ChainShadowArgs* deep;   // ... with the deeper levels shadow-tested
     const GridShadowArgs* grid;    // rtx_grid_shadow (which takes reflect, chain and deep by value: zero-filled where there is none)
     const uint32_t* dark0;         // the grid families: GridShadowArgs::dark0
+    const GridReflectArgs* grid_reflect; // rtx_grid_reflect
 };
 const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream, int* hip_error);
 const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const TileArgs* t, int mode, void* stream, int* hip_error);

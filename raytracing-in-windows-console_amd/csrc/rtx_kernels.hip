@@ -1002,6 +1002,7 @@ __global__ __launch_bounds__(kThreads) void rtx_expand_words(const ExpandArgs e)
 #include "rtx_tile_pass.inc"
 #include "rtx_reflect_kernels.inc"
 #include "rtx_reflect_chain_kernels.inc"
+#include "rtx_grid_reflect_kernels.inc"
 #include "rtx_shadow_kernels.inc"
 #include "rtx_lights_kernels.inc"
 #include "rtx_lights_chain_kernels.inc"
@@ -1218,6 +1219,7 @@ enum : unsigned {
     kTakesDark0 = 1u << 5,   // t->dark0
     kTakesGrid = 1u << 6,    // t->grid: a usable grid over a scene with spheres, room for level 0's words and the fallback count;
                              // reflect, chain and deep by value (they are read, and then checked, only with GridShadowArgs::deep)
+    kTakesGridReflect = 1u << 7, // t->grid_reflect: a usable grid over a scene with spheres, the position map and the fallback count
 };
 static const unsigned kPassTakes[rtxplan::kShadePasses] = {
     0u,                                                        // kPassNone
@@ -1225,6 +1227,7 @@ static const unsigned kPassTakes[rtxplan::kShadePasses] = {
     kTakesReflect | kTakesChain,                               // rtx_reflect_chain
     kTakesLights | kTakesReflect | kTakesChain | kTakesDeep,   // rtx_chain_shadow
     kTakesLights | kTakesGrid,                                 // rtx_grid_shadow
+    kTakesReflect | kTakesChain | kTakesGridReflect,           // rtx_grid_reflect
 };
 static const unsigned kFamilyTakes[rtxplan::kShadeFamilies] = {
     kTakesShadow,                                              // rtx_shadow_shade
@@ -1257,6 +1260,10 @@ static bool tile_args_ok(const TileArgs* t, unsigned takes)
         if (t->reflect == nullptr || t->chain == nullptr || t->deep == nullptr) return false;
         if (gs->deep != 0u && !tile_args_ok(t, kTakesChain | kTakesDeep)) return false;
     }
+    if (takes & kTakesGridReflect) {
+        const GridReflectArgs* gr = t->grid_reflect;
+        if (gr == nullptr || gr->pos_of_gidx == nullptr || gr->fallback == nullptr || gr->grid.ok == 0u || a->ns == 0u) return false;
+    }
     return true;
 }
 
@@ -1282,9 +1289,13 @@ extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs
         hipLaunchKernelGGL(rtx_chain_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
         name = "rtx_chain_shadow";
         break;
-    default:
+    case rtxplan::kPassGridShadow:
         hipLaunchKernelGGL(rtx_grid_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, *t->grid);
         name = "rtx_grid_shadow";
+        break;
+    default:
+        hipLaunchKernelGGL(rtx_grid_reflect, grid, block, 0, st, *t->a, *t->reflect, *t->chain, *t->grid_reflect);
+        name = "rtx_grid_reflect";
         break;
     }
     *hip_error = (int)hipGetLastError();

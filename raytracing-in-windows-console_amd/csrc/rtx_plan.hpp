@@ -1025,12 +1025,13 @@ inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n,
 //   mirror, not chain   2          rtx_reflect_hit    grid: rtx_grid_shadow (deep 0)               rtx_grid_reflect_shade / several: rtx_lights_reflect_shade, else rtx_reflect_shade
 //   mirror, chain       depth + 1  rtx_reflect_chain  grid: rtx_grid_shadow (deep = deep), else    rtx_grid_chain[_shadow]_shade / rtx_lights_chain[_shadow]_shade
 //                                                     deep: rtx_chain_shadow                       (_shadow: deep)
+//   mirror, RTX_OPT_REFLECT_GRID in effect: the secondary pass of either row is rtx_grid_reflect; nothing else of the row changes
 //
 // The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
 // deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
 
 enum ShadePath { kPathDirect, kPathShaded, kPathMirror };
-enum ShadePass { kPassNone, kPassReflectHit, kPassReflectChain, kPassChainShadow, kPassGridShadow, kShadePasses };
+enum ShadePass { kPassNone, kPassReflectHit, kPassReflectChain, kPassChainShadow, kPassGridShadow, kPassGridReflect, kShadePasses };
 enum ShadeFamily {
     kShadowShade, kLightsShade, kReflectShade, kLightsReflectShade, kLightsChainShade, kLightsChainShadowShade,
     kGridShade, kGridReflectShade, kGridChainShade, kGridChainShadowShade, kShadeFamilies
@@ -1062,6 +1063,7 @@ struct ShadingRequest { // what the decision reads of the call, the options and 
     bool reflect_depth_check = false; // RTX_OPT_REFLECT_DEPTH_CHECK: the chain kernels at depth 1
     bool reflect_shadows = false;    // RTX_OPT_REFLECT_SHADOWS
     bool shadow_grid = false;        // RTX_OPT_SHADOW_GRID
+    bool reflect_grid = false;       // RTX_OPT_REFLECT_GRID
     uint32_t ns = 0;
     bool grid_usable = false;        // the world grid was built and can be walked; known only after its build (shading_wants_grid)
 };
@@ -1076,7 +1078,12 @@ struct ShadingPlan {
     uint32_t levels = 0;               // hit arrays
     uint32_t bytes_per_px = 0;         // of the hit buffer; 0: none
     uint32_t deep_off = 0, dark0_off = 0; // bytes per pixel in front of the deep / dark0 words (level j's hits: 8 j)
-    bool chain() const { return secondary == kPassReflectChain; }
+    // the chain's layout and families: depth + 1 hit arrays, whichever kernel fills them (rtx_reflect_chain, rtx_grid_reflect)
+    bool chain() const
+    {
+        return family == kLightsChainShade || family == kLightsChainShadowShade || family == kGridChainShade || family == kGridChainShadowShade;
+    }
+    bool grid_reflect() const { return secondary == kPassGridReflect; }
 };
 
 inline ShadePath shading_path(const ShadingRequest& q)
@@ -1087,12 +1094,20 @@ inline ShadePath shading_path(const ShadingRequest& q)
     return kPathDirect; // the state the reference has: every launch is the reference's
 }
 
-// Does the frame ask for shadow tests through the world grid?  By the options and the scene alone: the caller then brings the
-// grid up to date (a build blocks, so a capturing stream is refused) and plans with grid_usable set to what came of it.
-inline bool shading_wants_grid(const ShadingRequest& q)
+// Does the frame ask for shadow tests (RTX_OPT_SHADOW_GRID) or for its mirror rays (RTX_OPT_REFLECT_GRID) through the world grid?
+// By the options and the scene alone: the caller then brings the grid up to date, once for both (a build blocks, so a capturing
+// stream is refused), and plans with grid_usable set to what came of it.
+inline bool shadows_want_grid(const ShadingRequest& q)
 {
     return shading_path(q) != kPathDirect && q.shadow_grid && q.shadows && q.shadow_check == 0 && q.ns != 0;
 }
+
+inline bool mirrors_want_grid(const ShadingRequest& q)
+{
+    return shading_path(q) == kPathMirror && q.reflect_grid && q.reflect_check == 0 && q.ns != 0; // (checks 1 and 2: the brute reference)
+}
+
+inline bool shading_wants_grid(const ShadingRequest& q) { return shadows_want_grid(q) || mirrors_want_grid(q); }
 
 inline ShadingPlan plan_shading(const ShadingRequest& q)
 {
@@ -1100,11 +1115,12 @@ inline ShadingPlan plan_shading(const ShadingRequest& q)
     p.path = shading_path(q);
     if (p.path == kPathDirect) return p;
     const bool mirror = p.path == kPathMirror;
-    const bool grid = shading_wants_grid(q) && q.grid_usable;
+    const bool grid = shadows_want_grid(q) && q.grid_usable;
     const bool several = q.n_lights >= 2 || q.lights_check;
     p.deep = mirror && q.reflect_shadows && q.shadows && q.n_reflective != 0;
     const bool chain = mirror && (q.reflect_depth > 1 || q.reflect_depth_check || p.deep);
     p.secondary = chain ? kPassReflectChain : (mirror ? kPassReflectHit : kPassNone);
+    if (mirrors_want_grid(q) && q.grid_usable) p.secondary = kPassGridReflect; // one kernel for both: the hit arrays are the same
     p.shadow_pass = grid ? kPassGridShadow : (p.deep ? kPassChainShadow : kPassNone);
     if (chain) {
         p.family = grid ? (p.deep ? kGridChainShadowShade : kGridChainShade) : (p.deep ? kLightsChainShadowShade : kLightsChainShade);

@@ -63,6 +63,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.reflect_depth_check = ctx->opt_reflect_depth_check != 0;
     q.reflect_shadows = ctx->opt_reflect_shadows != 0;
     q.shadow_grid = ctx->opt_shadow_grid != 0;
+    q.reflect_grid = ctx->opt_reflect_grid != 0;
     q.ns = ctx->ns;
     return q;
 }
@@ -85,8 +86,8 @@ int check_recordable(rtx_ctx* ctx, hipStream_t stream, int mode, bool* capturing
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches with the two-level pre-pass cannot be recorded (its counters alternate per launch)");
     }
     if (rtxplan::shading_wants_grid(shading_request(ctx, mode))) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test through the world grid cannot be recorded (RTX_OPT_SHADOW_GRID: "
-                                                       "the lists change with physics, and their build allocates and waits)");
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: launches that shadow-test or trace mirror rays through the world grid cannot be recorded "
+                                                       "(RTX_OPT_SHADOW_GRID, RTX_OPT_REFLECT_GRID: the lists change with physics, and their build allocates and waits)");
     }
     return RTX_OK;
 }
@@ -512,8 +513,9 @@ rtx_ctx::TileOrder* tile_order_set(rtx_ctx* ctx, hipStream_t stream, const uint6
 
 // ---- the launches of a frame (rtxplan::plan_shading: the light / shadow path, the mirror path, shadow tests through the world grid)
 
-// The grid up to date for a launch set on `stream` (rtx_grid_ensure: a build blocks) and what rtx_grid_shadow reads of it.
-// *in_effect = false: no usable grid (RTX_STAT_QUERY_BRUTE), the frame is planned without one.
+// The grid up to date for a launch set on `stream` (rtx_grid_ensure: a build blocks) and what rtx_grid_shadow and rtx_grid_reflect
+// read of it: once per launch set, whichever of the two options asked.  *in_effect = false: no usable grid (RTX_STAT_QUERY_BRUTE),
+// the frame is planned without one.
 int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool* in_effect)
 {
     *in_effect = false;
@@ -526,6 +528,7 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
         return RTX_OK;
     }
     RTX_HIP(ctx, ctx->d_shadow_grid_fallback.reserve(1, rtxmem::nothing()));
+    RTX_HIP(ctx, ctx->d_reflect_grid_fallback.reserve(1, rtxmem::nothing()));
     gs->grid = g.plan;
     gs->cell_start = g.cell_count.get();
     gs->list_geom = g.list_geom.get();
@@ -602,7 +605,8 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
 }
 
 // The device copies of the reflectivities after a change, a scene edit or a new sort: spheres by index and by sorted position,
-// planes by index (at least one entry each, so that the kernels always get an array).  Waits for the frames in flight first.
+// planes by index (at least one entry each, so that the kernels always get an array); and, valid for the same generation, the
+// creation index -> position map of rtx_grid_reflect (rtx_ctx::d_refl_pos).  Waits for the frames in flight first.
 int upload_reflectivity(rtx_ctx* ctx)
 {
     const size_t ns = ctx->ns, np = ctx->np;
@@ -612,6 +616,14 @@ int upload_reflectivity(rtx_ctx* ctx)
     }
     const bool sorted = ctx->h_sorted_idx.size() == ns && ns > 0;
     for (size_t p = 0; sorted && p < ns; p++) kso[p] = ks[ctx->h_sorted_idx[p]];
+    const size_t no = ctx->refl.size() > 0 ? ctx->refl.size() : 1;
+    std::vector<uint32_t> pos(2 * no, 0u), sorted_pos_of(ns, 0u);
+    for (size_t p = 0; sorted && p < ns; p++) sorted_pos_of[ctx->h_sorted_idx[p]] = (uint32_t)p;
+    for (size_t g = 0; g < ctx->refl.size(); g++) {
+        if (ctx->kind_of[g] != 2) continue;
+        pos[g] = ctx->local_of[g];
+        pos[no + g] = sorted ? sorted_pos_of[ctx->local_of[g]] : ctx->local_of[g];
+    }
     RTX_HIP(ctx, hipDeviceSynchronize());
     for (const auto& pr : {std::make_pair(&ctx->d_refl_sph, &ks), std::make_pair(&ctx->d_refl_sorted, &kso), std::make_pair(&ctx->d_refl_pl, &kp)}) {
         DeviceBuf<float>& d = *pr.first;
@@ -619,6 +631,8 @@ int upload_reflectivity(rtx_ctx* ctx)
         RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing())); // (the device has just been waited for)
         RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
     }
+    RTX_HIP(ctx, ctx->d_refl_pos.reserve(pos.size(), rtxmem::nothing()));
+    RTX_HIP(ctx, hipMemcpy(ctx->d_refl_pos.get(), pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     ctx->refl_dirty = false;
     return RTX_OK;
 }
@@ -657,16 +671,18 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     char* const hits = (char*)hit_base;
     RTX_HIP(ctx, ctx->d_shadow_longest.reserve(1, rtxmem::nothing()));
     if (mirror) RTX_HIP(ctx, ctx->d_reflect_longest.reserve(1, rtxmem::nothing()));
-    if (plan.chain()) RTX_HIP(ctx, ctx->d_reflect_rays.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
+    const bool counts_rays = plan.chain() || plan.grid_reflect(); // (RTX_STAT_REFLECT_RAYS)
+    if (counts_rays) RTX_HIP(ctx, ctx->d_reflect_rays.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
     if (plan.deep) RTX_HIP(ctx, ctx->d_reflect_shadow_points.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
     if (mirror) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest.get(), 0, sizeof(uint32_t), stream));
     RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest.get(), 0, sizeof(uint32_t), stream));
-    if (plan.chain()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays.get(), 0, per_level, stream));
+    if (counts_rays) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays.get(), 0, per_level, stream));
     if (plan.deep) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points.get(), 0, per_level, stream));
     if (plan.dark0) RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback.get(), 0, sizeof(uint32_t), stream));
+    if (plan.grid_reflect()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_grid_fallback.get(), 0, sizeof(uint32_t), stream));
     if (mirror) { // (the other paths leave reflect_rays_valid as it is)
-        ctx->reflect_rays_valid = plan.chain();
+        ctx->reflect_rays_valid = counts_rays;
         ctx->reflect_shadow_points_valid = plan.deep;
     }
 
@@ -676,6 +692,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ReflectArgs ra;
     ChainArgs ca;
     ChainShadowArgs cs;
+    GridReflectArgs gr;
     TileArgs t;
     std::memset(&ra, 0, sizeof ra);
     std::memset(&ca, 0, sizeof ca);
@@ -700,7 +717,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
         ra.longest = ctx->d_reflect_longest.get();
     }
-    if (plan.chain()) {
+    if (counts_rays) { // (rtx_grid_reflect at depth 1: one level into the two-level buffer)
         ca.depth = plan.levels - 1u;
         ca.px = (uint32_t)px;
         ca.rays = ctx->d_reflect_rays.get();
@@ -715,6 +732,21 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         t.grid = &gs;
         t.dark0 = gs.dark0;
     }
+    if (plan.grid_reflect()) {
+        std::memset(&gr, 0, sizeof gr);
+        gr.grid = gs.grid;
+        gr.cell_start = gs.cell_start;
+        gr.list_geom = gs.list_geom;
+        gr.list_gidx = gs.list_gidx;
+        gr.scene_geom = gs.scene_geom;
+        gr.scene_od = gs.scene_od;
+        gr.large = gs.large;
+        gr.n_large = gs.n_large;
+        // (the map's half for the order this launch's a.sph_geom is in)
+        gr.pos_of_gidx = ctx->d_refl_pos.get() + (a.sph_sorted_idx != nullptr ? (ctx->refl.size() > 0 ? ctx->refl.size() : 1) : 0);
+        gr.fallback = ctx->d_reflect_grid_fallback.get();
+        t.grid_reflect = &gr;
+    }
 
     // the passes, the shade launch
     static const struct {
@@ -723,7 +755,8 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
                                  {"mirror pass: invalid frame geometry", "secondary hit kernel launch"},
                                  {"mirror pass: invalid frame geometry or depth", "reflection chain kernel launch"},
                                  {"mirror pass: invalid frame geometry, depth or light set", "chain shadow kernel launch"},
-                                 {"shadow grid pass: invalid frame geometry, depth or light set", "shadow grid kernel launch"}};
+                                 {"shadow grid pass: invalid frame geometry, depth or light set", "shadow grid kernel launch"},
+                                 {"mirror grid pass: invalid frame geometry or depth", "mirror grid kernel launch"}};
     for (const ShadePass pass : {plan.secondary, plan.shadow_pass}) {
         if (pass == kPassNone) continue;
         if (!rtx_k_launch_pass(pass, &t, stream, &herr)) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, kPassText[pass].refused);
@@ -734,10 +767,9 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     if (herr != 0) {
         return rtx_hip_fail(ctx, (hipError_t)herr, plan.chain() ? "chain shading kernel launch" : (mirror ? "mirror shading kernel launch" : "shadow shading kernel launch"));
     }
-    if (plan.dark0) {
-        rtx_grid_read(ctx, stream);
-        ctx->stat_shadow_grid_frames++;
-    }
+    if (plan.dark0 || plan.grid_reflect()) rtx_grid_read(ctx, stream);
+    if (plan.dark0) ctx->stat_shadow_grid_frames++;
+    if (plan.grid_reflect()) ctx->stat_reflect_grid_frames++;
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     return RTX_OK;
