@@ -282,37 +282,7 @@ __device__ __forceinline__ uint32_t stage_chunk(const Camera& cam, const TileFru
     return grown;
 }
 
-// The spheres a workgroup stages: all of them (list == nullptr), or the index list its coarse cell
-// received from rtx_bin_cells (two-level culling for large scenes).
-// A sphere is known to the trace kernels by its POSITION in the arrays they read: the direction-sorted copies when there are
-// some (KArgs::sph_sorted_*), else the scene arrays themselves, where position = sphere index.  Only an exact tie in t needs the
-// creation order (comes_first).
-struct Items {
-    const float4* geom;   // geometry by position
-    const uint32_t* list; // positions (any order), or nullptr: all of [0, count)
-    uint32_t count;       // number of items
-};
-
-__device__ __forceinline__ Items scene_items(const KArgs& a)
-{
-    Items it;
-    it.geom = a.sph_geom;
-    it.list = nullptr;
-    it.count = a.ns;
-    return it;
-}
-
-// Item i: its position and its geometry record.  Past the end any valid record is returned (ignored).
-__device__ __forceinline__ float4 load_item(const Items& it, uint32_t i, uint32_t& k)
-{
-    if (it.count == 0u) {
-        k = 0u;
-        return make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    const uint32_t ii = i < it.count ? i : it.count - 1u;
-    k = it.list ? it.list[ii] : ii;
-    return it.geom[k];
-}
+// (rtx_workgroup.hpp: Items, scene_items, load_item -- the spheres a workgroup stages)
 
 constexpr int kRefineSub = 4;      // REFINE: at most this many sub-tiles (lanes 5 .. 5 + 16 per sub-tile build the pyramids)
 constexpr int kWaveListCap = 128;  // REFINE: candidates a wave keeps for its own 64 pixels; more -> it scans the whole list
@@ -375,211 +345,8 @@ __global__ __launch_bounds__(kThreads, RTX_WAVES_PER_EU) void rtx_trace_batch(co
 #include "rtx_trace_body.inc"
 }
 
-// Level 1 of the two-level culling used for large scenes: the scene is binned into coarse cells (blocks of
-// 2^gx x 2^gy macro tiles, a few hundred to a thousand of them) and every trace workgroup then stages its cell's
-// list instead of the whole scene.  ONE launch, two levels inside it: workgroup (block, split) walks its share of the
-// sphere array against the pyramid of a BLOCK of 4 x 4 cells -- the same conservative test as the per-tile one, on a
-// larger rectangle -- gathers the survivors in LDS (hoisted centre and culling margin, as the REFINE pass of the trace
-// kernel keeps them) and tests each of them against the 16 cell pyramids of the block, one (survivor, cell) pair
-// per thread.  Sound level by level: a sphere that a pixel ray of a cell can hit can be hit by a ray of the
-// cell's block.  Tests: blocks x spheres + 16 x survivors instead of cells x spheres.
-//
-// Lists are compact: cell c owns cell_cap entries (a few times the average; host: rtx_render_rows) and the
-// workgroups append with one reservation per cell and flush -- atomicAdd on the cell's counter, which keeps
-// counting past the capacity.  A trace workgroup that finds count > cell_cap stages the whole scene instead
-// (always a superset), so a list that does not fit costs time, never a pixel.  The order of a list does not
-// matter: the closest hit is the minimum of (t, creation index).
-//
-// The counters alternate between two buffers from launch to launch: this launch accumulates into
-// cell_count_out and zeroes the 16 counters of its block in cell_count_zero, which the next launch on this
-// stream accumulates into -- no memset between frames.
-constexpr int kBlockCells = 16; // cells per block: 4 x 4
-constexpr int kBinCap = 1024;   // block survivors gathered in LDS between cell phases
-
-// Appends the block survivors [0, n) in s_rec / s_idx to the lists of the cells they can touch.
-__device__ __forceinline__ void bin_cells_of_block(const KArgs& a, const float4* s_rec, const uint32_t* s_idx, uint32_t n, const float4 (*s_cellfr)[5],
-                                                   uint32_t* s_cnt, uint32_t* s_base, uint32_t* s_pos, const uint32_t* s_cellid)
-{
-    const uint32_t tid = threadIdx.x;
-    __syncthreads(); // survivors complete
-    if (tid < (uint32_t)kBlockCells) {
-        s_cnt[tid] = 0u;
-        s_pos[tid] = 0u;
-    }
-    __syncthreads();
-    // pass 1: the pairs' verdicts (kept in a bit mask: pair p = tid + 256 i is bit i) and the cells' counts
-    const uint32_t pairs = n * (uint32_t)kBlockCells;
-    unsigned long long keep = 0ull;
-    for (uint32_t p = tid, i = 0; p < pairs; p += (uint32_t)kThreads, i++) {
-        const uint32_t sv = p >> 4, c = p & 15u;
-        if (s_cellid[c] == 0xffffffffu) {
-            continue; // cell beyond the edge of the grid
-        }
-        const float4 r = s_rec[sv];
-        bool out = false;
-#pragma unroll
-        for (int k = 0; k < 4; k++) { // (the four side planes: the block's survivors have passed the camera plane)
-            const float4 nk = s_cellfr[c][k];
-            out = out || (nk.x * r.x + nk.y * r.y + nk.z * r.z > r.w); // as tile_culls, margin in r.w (+inf: never)
-        }
-        if (!out) {
-            keep |= 1ull << i;
-            atomicAdd(&s_cnt[c], 1u);
-        }
-    }
-    __syncthreads();
-    if (tid < (uint32_t)kBlockCells && s_cnt[tid] != 0u) {
-        s_base[tid] = atomicAdd(a.cell_count_out + s_cellid[tid], s_cnt[tid]); // one reservation per cell and flush
-        // capacity feedback for the host (rtx_plan.hpp, cell_capacity_wanted): only lists past half their capacity report
-        const uint32_t need = s_base[tid] + s_cnt[tid];
-        if (a.cell_max_out != nullptr && need > (a.cell_cap >> 1)) atomicMax(a.cell_max_out, need);
-    }
-    __syncthreads();
-    for (uint32_t p = tid, i = 0; p < pairs; p += (uint32_t)kThreads, i++) {
-        if ((keep >> i) & 1ull) {
-            const uint32_t sv = p >> 4, c = p & 15u;
-            const uint32_t at = s_base[c] + atomicAdd(&s_pos[c], 1u);
-            if (at < a.cell_cap) {
-                a.cell_list_out[(size_t)s_cellid[c] * a.cell_cap + at] = a.sph_pos_of != nullptr ? a.sph_pos_of[s_idx[sv]] : s_idx[sv];
-            }
-        }
-    }
-    __syncthreads(); // the survivor buffer may be refilled
-}
-
-__global__ __launch_bounds__(kThreads) void rtx_bin_cells(const KArgs a)
-{
-    static_assert(kBinCap * kBlockCells <= 64 * kThreads, "a thread's pairs must fit the 64-bit verdict mask");
-    __shared__ float4 s_rec[kBinCap];              // ox oy oz margin
-    __shared__ uint32_t s_idx[kBinCap];
-    __shared__ float4 s_cellfr[kBlockCells][5];
-    __shared__ uint32_t s_cellid[kBlockCells];     // global cell number, or 0xffffffff beyond the grid
-    __shared__ uint32_t s_cnt[kBlockCells], s_base[kBlockCells], s_pos[kBlockCells];
-    __shared__ uint32_t s_wcnt[2][8];
-    __shared__ float s_frustum[16];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t tw = 1u << a.tile_log2w, th = (uint32_t)kThreads >> a.tile_log2w;
-    const uint32_t nx = 1u << a.sub_log2nx, ny = a.nsub >> a.sub_log2nx;
-    const uint32_t cw = (tw * nx) << a.cell_log2gx, ch = (th * ny) << a.cell_log2gy; // cell, pixels
-    const uint32_t blocks_x = (a.cells_x + 3u) >> 2;
-    const uint32_t bby = blockIdx.x / blocks_x, bbx = blockIdx.x - bby * blocks_x;   // this workgroup's block of cells
-
-    Camera cam;
-#pragma unroll
-    for (int i = 0; i < 12; i++) {
-        cam.m[i] = a.m[i];
-    }
-    cam.ox = a.ox; cam.oy = a.oy; cam.oz = a.oz;
-    cam.e1 = a.e1; cam.e2 = a.e2; cam.far = a.far;
-    cam.fW = a.fW; cam.fH = a.fH;
-
-    // pyramids: lanes 0..4 the block's five planes, lanes 5..84 plane k of cell c = (lane - 5) / 5
-    if (tid < 5u + 5u * (uint32_t)kBlockCells) {
-        if (tid < 5u) {
-            const V3 n = tile_plane(a, cam, bbx * 4u * cw, a.row0 + bby * 4u * ch, 4u * cw, 4u * ch, tid);
-            s_frustum[3 * tid + 0] = n.x;
-            s_frustum[3 * tid + 1] = n.y;
-            s_frustum[3 * tid + 2] = n.z;
-        } else {
-            const uint32_t q = tid - 5u, c = q / 5u, k = q - c * 5u;
-            const uint32_t cx = bbx * 4u + (c & 3u), cy = bby * 4u + (c >> 2);
-            const V3 n = tile_plane(a, cam, cx * cw, a.row0 + cy * ch, cw, ch, k);
-            s_cellfr[c][k] = make_float4(n.x, n.y, n.z, 0.0f);
-        }
-    }
-    if (tid < (uint32_t)kBlockCells) {
-        const uint32_t cx = bbx * 4u + (tid & 3u), cy = bby * 4u + (tid >> 2);
-        const bool valid = cx < a.cells_x && cy < a.cells_y;
-        s_cellid[tid] = valid ? cy * a.cells_x + cx : 0xffffffffu;
-        // the other counter buffer, for the next launch on this stream (one workgroup per block does it)
-        if (valid && blockIdx.y == 0u && a.cell_count_zero != nullptr) {
-            a.cell_count_zero[cy * a.cells_x + cx] = 0u;
-        }
-    }
-    __syncthreads();
-    TileFrustum fr;
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        fr.n[k].x = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_frustum[3 * k + 0])));
-        fr.n[k].y = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_frustum[3 * k + 1])));
-        fr.n[k].z = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(s_frustum[3 * k + 2])));
-    }
-
-    // The pass walks the scene array in creation order -- in the direction-sorted copy a block's spheres sit in one stretch, i.e.
-    // in one workgroup's share: 36 us instead of 18 -- and translates the survivors to positions when it writes the lists.
-    Items items;
-    items.geom = a.sph_scene_geom;
-    items.list = nullptr;
-    items.count = a.ns;
-    // this workgroup's share of the spheres: [lo, hi), a multiple of the step size except at the end
-    const uint32_t ns = a.ns, splits = gridDim.y;
-    const uint32_t steps = (ns + kChunk - 1) / kChunk;
-    const uint32_t lo = (uint32_t)(((uint64_t)steps * blockIdx.y) / splits) * kChunk;
-    const uint32_t hi_raw = (uint32_t)(((uint64_t)steps * (blockIdx.y + 1)) / splits) * kChunk;
-    const uint32_t hi = hi_raw < ns ? hi_raw : ns;
-
-    uint32_t total = 0, parity = 0;
-    uint32_t k0, k1;
-    float4 g0 = load_item(items, lo + tid, k0), g1 = load_item(items, lo + kThreads + tid, k1);
-    for (uint32_t base = lo; base < hi; base += kChunk, parity ^= 1u) {
-        const float4 g[2] = {g0, g1};
-        const uint32_t kk[2] = {k0, k1};
-        g0 = load_item(items, base + kChunk + tid, k0);
-        g1 = load_item(items, base + kChunk + kThreads + tid, k1);
-        if (total > (uint32_t)(kBinCap - kChunk)) {
-            bin_cells_of_block(a, s_rec, s_idx, total, s_cellfr, s_cnt, s_base, s_pos, s_cellid);
-            total = 0;
-        }
-        bool keep[2];
-        float4 rec[2];
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const uint32_t k = base + (uint32_t)h * kThreads + tid;
-            const float ox = cam.ox - g[h].x, oy = cam.oy - g[h].y, oz = cam.oz - g[h].z;
-            const float oo = ox * ox + oy * oy + oz * oz;
-            const float cc = oo - (g[h].w * g[h].w);
-            float mg;
-            bool inside;
-            const bool culled = tile_culls_moving(fr, ox, oy, oz, oo, g[h].w, a.bin_theta, a.bin_delta, mg, inside);
-            const bool outside = cc > 0.0f && !inside; // every camera the lists are for is strictly outside the sphere
-            keep[h] = (k < hi) && !(outside && culled);
-            // a camera inside or on the sphere: never culled, by any pyramid
-            rec[h] = make_float4(ox, oy, oz, outside ? mg : __builtin_inff());
-        }
-        const unsigned long long m0 = __ballot(keep[0]), m1 = __ballot(keep[1]);
-        if (lane == 0) {
-            s_wcnt[parity][wave] = (uint32_t)__popcll(m0);
-            s_wcnt[parity][4 + wave] = (uint32_t)__popcll(m1);
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        uint32_t before = 0, before1 = 0, first_total = 0, sum = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4u; w++) {
-            const uint32_t c0 = s_wcnt[parity][w], c1 = s_wcnt[parity][4 + w];
-            first_total += c0;
-            sum += c0 + c1;
-            if (w < wave) {
-                before += c0;
-                before1 += c1;
-            }
-        }
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (keep[0]) {
-            const uint32_t pos = total + before + (uint32_t)__popcll(m0 & below);
-            s_rec[pos] = rec[0];
-            s_idx[pos] = kk[0];
-        }
-        if (keep[1]) {
-            const uint32_t pos = total + first_total + before1 + (uint32_t)__popcll(m1 & below);
-            s_rec[pos] = rec[1];
-            s_idx[pos] = kk[1];
-        }
-        total = __builtin_amdgcn_readfirstlane(total + sum);
-    }
-    if (total) {
-        bin_cells_of_block(a, s_rec, s_idx, total, s_cellfr, s_cnt, s_base, s_pos, s_cellid);
-    }
-}
+// Level 1 of the two-level culling used for large scenes: rtx_bin_cells, with the rule it is launched by.
+#include "rtx_bin_cells.inc"
 
 // Zero-fills [begin, end) of the frame (bytes, 4-aligned): the 8-bit modes' unused tail.
 __global__ __launch_bounds__(kThreads) void rtx_zero_fill(uint32_t* p, size_t n_words)
@@ -589,342 +356,8 @@ __global__ __launch_bounds__(kThreads) void rtx_zero_fill(uint32_t* p, size_t n_
     }
 }
 
-// rtx_order_tiles: the dispatch order of the next launches' macro tiles from the work estimates the workgroups of
-// an earlier launch left in tile_cost.  One workgroup; a counting sort over 1024 cost classes (heaviest class first;
-// the order within a class is whatever the atomics give -- any permutation renders the same frame, so only speed
-// depends on it, and every tile receives exactly one rank by construction whatever tile_cost holds).
-//
-// (For grids of several dispatch rounds, and small ones; grids of one round go through rtx_balance_tiles below.)
-// Why order at all: the first 7 workgroups per CU of a launch all become resident at once (1792 of the 2040 that
-// config 2 had with 4 sub-tiles per workgroup), blocks b, b + n_cu, ... on one CU (observed: round-robin; nothing
-// depends on it but speed), and finish when their CU has worked through whatever it was dealt.  In frame order the tiles of a CU differ by 3x in work and the expensive rows come last:
-// the slowest CU takes a third longer than the average and the second-round workgroups start late and run long
-// (profiles/r02_b_stamps_sub4.txt).  So: the tiles go out heaviest first, the first `first_round` of them dealt
-// boustrophedon over the CUs (round k ascending for even k, descending for odd k) so that every CU's share
-// carries the same work, and the light remainder fills the slots as they free up.
-constexpr int kOrderThreads = 1024, kOrderBins = 1024;
-
-// With `base` (the static XCD-aware order of a two-level grid: position -> packed tile, blocks b, b + 8, ... share an XCD and are
-// handed whole cells, rtx_plan.hpp xcd_cell_order) the sort is PER LABEL: the tiles at the positions p = L mod 8 of `base` are
-// put back, heaviest first, at the same positions -- every XCD keeps its cells (and its L2 their lists and spheres: config 5's
-// trace kernel fetches 6 MB per launch this way and 19 MB under a plain heaviest-first order), within an XCD the heavy tiles
-// come first.  1024 classes = 8 labels x 128 cost classes; a tile's position is 8 x (its rank within the label) + label.
-__global__ __launch_bounds__(kOrderThreads) void rtx_order_tiles(const uint32_t* __restrict__ cost, uint32_t n, uint32_t gx, uint32_t n_cu,
-                                                                  uint32_t first_round, const uint32_t* __restrict__ base, uint32_t* __restrict__ order)
-{
-    __shared__ uint32_t s_hist[kOrderBins];
-    __shared__ uint32_t s_lo[kOrderThreads / 64], s_hi[kOrderThreads / 64];
-    __shared__ uint32_t s_start[8];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint32_t lo = 0xffffffffu, hi = 0u;
-    for (uint32_t i = tid; i < n; i += kOrderThreads) {
-        const uint32_t c = cost[i];
-        lo = c < lo ? c : lo;
-        hi = c > hi ? c : hi;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d);
-        lo = l2 < lo ? l2 : lo;
-        hi = h2 > hi ? h2 : hi;
-    }
-    if (lane == 0u) {
-        s_lo[wave] = lo;
-        s_hi[wave] = hi;
-    }
-    s_hist[tid] = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < kOrderThreads / 64; k++) {
-        lo = s_lo[k] < lo ? s_lo[k] : lo;
-        hi = s_hi[k] > hi ? s_hi[k] : hi;
-    }
-    const uint64_t range = (uint64_t)(hi - lo) + 1u;
-    auto bin_of = [&](uint32_t c) { return (uint32_t)(((uint64_t)(hi - c) * (uint64_t)kOrderBins) / range); }; // 0 = heaviest
-    // per label: the class of the tile at position p of `base`
-    auto tile_at = [&](uint32_t p) { const uint32_t packed = base[p]; return (packed >> 16) * gx + (packed & 0xffffu); };
-    auto class_at = [&](uint32_t p) { return ((p & 7u) << 7) | (bin_of(cost[tile_at(p)]) >> 3); };
-    for (uint32_t i = tid; i < n; i += kOrderThreads) {
-        atomicAdd(&s_hist[base != nullptr ? class_at(i) : bin_of(cost[i])], 1u);
-    }
-    __syncthreads();
-    // exclusive prefix sum over the classes (one per thread): wave scan, then the waves' totals
-    const uint32_t mine = s_hist[tid];
-    uint32_t incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = __shfl_up(incl, d);
-        if (lane >= (uint32_t)d) incl += o;
-    }
-    __syncthreads();
-    if (lane == 63u) s_lo[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-#pragma unroll
-    for (int k = 0; k < kOrderThreads / 64; k++) {
-        before += (uint32_t)k < wave ? s_lo[k] : 0u;
-    }
-    s_hist[tid] = before + incl - mine; // now: next free rank of the class
-    if ((tid & 127u) == 0u) s_start[tid >> 7] = before + incl - mine; // (per label: where its ranks begin)
-    __syncthreads();
-    if (base != nullptr) {
-        for (uint32_t p = tid; p < n; p += kOrderThreads) {
-            const uint32_t label = p & 7u;
-            const uint32_t rank = atomicAdd(&s_hist[class_at(p)], 1u) - s_start[label];
-            order[8u * rank + label] = base[p]; // (the label's set has exactly as many tiles as there are positions = label mod 8)
-        }
-        return;
-    }
-    const uint32_t rounds = n_cu ? first_round / n_cu : 0u; // whole rounds dealt boustrophedon
-    for (uint32_t i = tid; i < n; i += kOrderThreads) {
-        const uint32_t rank = atomicAdd(&s_hist[bin_of(cost[i])], 1u);
-        uint32_t blk = rank;
-        if (n_cu && rank < rounds * n_cu) {
-            const uint32_t k = rank / n_cu, c = rank - k * n_cu;
-            blk = (k & 1u) ? k * n_cu + (n_cu - 1u - c) : rank;
-        }
-        const uint32_t by = i / gx, bx = i - by * gx;
-        order[blk] = bx | (by << 16);
-    }
-}
-
-// rtx_balance_tiles: the dispatch order for a tile grid whose workgroups are all resident at once (n <= slots per CU x
-// n_cu; one workgroup, like rtx_order_tiles).  Then the blocks b, b + n_cu, b + 2 n_cu, ... share a compute unit
-// (observed on every launch: profiles/r02_f_cu_balance.md; which physical CU varies, the groups do not), nothing is
-// refilled, and the launch ends when the slowest group does -- in 1080p frame order a third later than the average
-// one.  Two steps:
-//   feedback  The instruction-count estimate ranks tiles well but is off by +-14 % on a group's sum (dependent
-//             chains, the planes, divergence), while a group's duration repeats from launch to launch to 0.3 us.  So the
-//             trace workgroups also leave their start and end times by dispatch position, and every tile carries a
-//             correction factor: the tiles of a group that took longer than the mean group are scaled up, the others
-//             down (damped, clamped), launch after launch.  cost' = (estimate + set-up) x factor.
-//   dealing   The n - (rounds-1) n_cu lightest tiles are the last round (the hardware puts those blocks on groups
-//             0, 1, ...).  The other rounds go heaviest first, and within a round the k-th heaviest tile goes to the
-//             group with the k-th smallest sum so far.
-// Any permutation renders the same frame; every position receives exactly one tile whatever the inputs hold (ranks come
-// from counting, positions from ranks).
-RTX_X_BALANCE_STAMPS();
-// The pass runs beside the next frame's trace launch (a stream of its own), so it is shaped to fit into a slot that
-// launch leaves free: 256 threads, the trace kernel's register budget, under 38 KB of LDS -- a CU holding six trace
-// workgroups has room for exactly that.  (As one 1024-thread workgroup it needed a CU to itself and the frame beside it
-// paid 20 us for the seven workgroups that CU could not take.)
-constexpr int kBalanceMaxTiles = 2048;
-constexpr int kBalanceThreads = 256;
-constexpr int kBalancePerThread = kBalanceMaxTiles / kBalanceThreads;
-constexpr int kBalanceBins = 1024;
-constexpr uint32_t kCostSetup = 1800u; // per workgroup: tables, planes, staging (4 waves x ~4.5 passes' worth of time)
-
-__global__ __launch_bounds__(kBalanceThreads, RTX_WAVES_PER_EU) void rtx_balance_tiles(const uint32_t* __restrict__ cost, uint32_t n, uint32_t gx,
-                                                                                       uint32_t G, const uint32_t* prev_order, float* factor,
-                                                                                       uint32_t have_factor, uint32_t have_times, uint32_t* order,
-                                                                                       float damping, float max_step)
-{
-    // s_a: the estimates by tile, later the corrected costs by rank; s_b: the tile that ran at each position, later the
-    // tile by rank
-    __shared__ uint32_t s_a[kBalanceMaxTiles];
-    __shared__ uint16_t s_b[kBalanceMaxTiles];
-    __shared__ float s_f[kBalanceMaxTiles];        // factor by tile
-    __shared__ float s_c[kBalanceMaxTiles];        // corrected cost by tile; before that, per group: earliest start, latest end
-    int32_t* s_first = reinterpret_cast<int32_t*>(s_c);
-    int32_t* s_last = s_first + kOrderThreads;
-    static_assert(2 * kOrderThreads <= kBalanceMaxTiles, "the groups' times share s_c");
-    __shared__ uint32_t s_hist[kBalanceBins];
-    __shared__ float s_sum[kOrderThreads];         // per group: duration, then the sum dealt so far
-    __shared__ float s_red[kBalanceThreads / 64];
-    __shared__ uint32_t s_lo[kBalanceThreads / 64], s_hi[kBalanceThreads / 64];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    constexpr int kWaves = kBalanceThreads / 64;
-
-    BSTAMP(0);
-    for (uint32_t g = tid; g < (uint32_t)kOrderThreads; g += kBalanceThreads) {
-        s_first[g] = 0x7fffffff;
-        s_last[g] = (int32_t)0x80000000;
-        s_hist[g] = 0u;
-    }
-    const uint32_t ref = have_times ? cost[n] : 0u;
-    __syncthreads();
-    // ---- everything this needs from memory, requested before anything is used (clamped indices instead of branches:
-    // one round trip instead of eight); then the groups' first start and last end (a group's clocks are one XCD's:
-    // only differences within a group are used)
-    uint32_t c_in[kBalancePerThread], t0[kBalancePerThread], t1[kBalancePerThread], pk[kBalancePerThread];
-    float f_in[kBalancePerThread];
-#pragma unroll
-    for (int q = 0; q < kBalancePerThread; q++) {
-        const uint32_t i = tid + (uint32_t)q * kBalanceThreads;
-        const uint32_t ii = i < n ? i : n - 1u;
-        c_in[q] = cost[ii];
-        t0[q] = have_times ? cost[n + ii] : 0u;
-        t1[q] = have_times ? cost[2u * n + ii] : 0u;
-        pk[q] = prev_order != nullptr ? prev_order[ii] : 0u;
-        f_in[q] = have_factor ? factor[ii] : 1.0f;
-    }
-#pragma unroll
-    for (int q = 0; q < kBalancePerThread; q++) {
-        const uint32_t i = tid + (uint32_t)q * kBalanceThreads;
-        if (i < n) {
-            const uint32_t po = prev_order != nullptr ? (pk[q] >> 16) * gx + (pk[q] & 0xffffu) : i;
-            s_a[i] = c_in[q];
-            s_b[i] = (uint16_t)(po < n ? po : i);
-            s_f[i] = (f_in[q] >= 0.5f && f_in[q] <= 2.0f) ? f_in[q] : 1.0f;
-            if (have_times) {
-                atomicMin(&s_first[i % G], (int32_t)(t0[q] - ref));
-                atomicMax(&s_last[i % G], (int32_t)(t1[q] - ref));
-            }
-        }
-    }
-    __syncthreads();
-    BSTAMP(1);
-    // ---- feedback: how long each group took, against the mean
-    float tot = 0.0f;
-    for (uint32_t g = tid; g < G; g += kBalanceThreads) {
-        float dur = 0.0f;
-        if (have_times) {
-            dur = (float)(s_last[g] - s_first[g]);
-            dur = (dur > 0.0f && dur < 1.0e8f) ? dur : 0.0f; // (a second: nonsense)
-        }
-        s_sum[g] = dur;
-        tot += dur;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) tot += __shfl_xor(tot, d);
-    if (lane == 0u) s_red[wave] = tot;
-    __syncthreads();
-    tot = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kWaves; k++) tot += s_red[k];
-    const float mean = tot / (float)G;
-    if (have_times && mean > 0.0f) {
-        for (uint32_t p = tid; p < n; p += kBalanceThreads) { // a dispatch position; s_b: the tile that ran there
-            const float d = s_sum[p % G];
-            if (d > 0.0f) {
-                float r = 1.0f + damping * (d / mean - 1.0f);
-                r = r < 1.0f - max_step ? 1.0f - max_step : (r > 1.0f + max_step ? 1.0f + max_step : r);
-                const uint32_t t = s_b[p];                      // (a permutation: every tile once)
-                const float f = s_f[t] * r;
-                s_f[t] = f < 0.5f ? 0.5f : (f > 2.0f ? 2.0f : f);
-            }
-        }
-    }
-    __syncthreads();
-    BSTAMP(2);
-    // ---- corrected costs; ranks by a counting sort over 1024 classes, heaviest first
-    uint32_t lo = 0xffffffffu, hi = 0u;
-    float total = 0.0f;
-    for (uint32_t i = tid; i < n; i += kBalanceThreads) {
-        const float f = s_f[i];
-        factor[i] = f;
-        const uint32_t c_in = s_a[i];
-        const float c = (float)(c_in < (1u << 24) ? c_in + kCostSetup : (1u << 24)) * f;
-        s_c[i] = c;
-        total += c;
-        const uint32_t u = (uint32_t)c;
-        lo = u < lo ? u : lo;
-        hi = u > hi ? u : hi;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d);
-        lo = l2 < lo ? l2 : lo;
-        hi = h2 > hi ? h2 : hi;
-        total += __shfl_xor(total, d);
-    }
-    if (lane == 0u) {
-        s_lo[wave] = lo;
-        s_hi[wave] = hi;
-        s_red[wave] = total;
-    }
-    __syncthreads();
-    total = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kWaves; k++) {
-        lo = s_lo[k] < lo ? s_lo[k] : lo;
-        hi = s_hi[k] > hi ? s_hi[k] : hi;
-        total += s_red[k];
-    }
-    const float to_bin = (float)kBalanceBins / ((float)(hi - lo) + 1.0f);
-    auto bin_of = [&](float c) { // 0 = heaviest
-        const uint32_t b = (uint32_t)((float)(hi - (uint32_t)c) * to_bin);
-        return b < (uint32_t)kBalanceBins ? b : (uint32_t)kBalanceBins - 1u;
-    };
-    // exclusive prefix sums over the 1024 classes in s_hist: four consecutive classes per thread, wave scan, wave totals
-    auto scan_hist = [&]() {
-        const uint32_t h0 = s_hist[4u * tid], h1 = s_hist[4u * tid + 1u], h2 = s_hist[4u * tid + 2u], h3 = s_hist[4u * tid + 3u];
-        const uint32_t mine = h0 + h1 + h2 + h3;
-        uint32_t incl = mine;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t o = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += o;
-        }
-        if (lane == 63u) s_lo[wave] = incl;
-        __syncthreads();
-        uint32_t before = incl - mine;
-#pragma unroll
-        for (int k = 0; k < kWaves; k++) {
-            before += (uint32_t)k < wave ? s_lo[k] : 0u;
-        }
-        s_hist[4u * tid] = before;
-        s_hist[4u * tid + 1u] = before + h0;
-        s_hist[4u * tid + 2u] = before + h0 + h1;
-        s_hist[4u * tid + 3u] = before + h0 + h1 + h2;
-        __syncthreads();
-    };
-    for (uint32_t i = tid; i < n; i += kBalanceThreads) {
-        atomicAdd(&s_hist[bin_of(s_c[i])], 1u);
-    }
-    __syncthreads();
-    scan_hist();
-    BSTAMP(3);
-    for (uint32_t i = tid; i < n; i += kBalanceThreads) {
-        const float c = s_c[i];
-        const uint32_t rank = atomicAdd(&s_hist[bin_of(c)], 1u);
-        s_a[rank] = __float_as_uint(c); // (the estimates are not needed any more, nor the positions)
-        s_b[rank] = (uint16_t)i;
-    }
-    __syncthreads();
-    BSTAMP(4);
-    // ---- dealing
-    auto put = [&](uint32_t pos, uint32_t rank) {
-        const uint32_t t = s_b[rank];
-        const uint32_t ty = t / gx, tx = t - ty * gx;
-        order[pos] = tx | (ty << 16);
-    };
-    const uint32_t rounds = (n + G - 1u) / G, tail0 = (rounds - 1u) * G;
-    for (uint32_t g = tid; g < G; g += kBalanceThreads) {
-        float sum0 = 0.0f;
-        if (tail0 + g < n) {
-            sum0 = __uint_as_float(s_a[tail0 + g]);
-            put(tail0 + g, tail0 + g);
-        }
-        s_sum[g] = sum0;
-    }
-    // Per round: rank the groups by their sums with the same counting sort (1024 classes over [0, 1.25 x the mean final
-    // sum]: a class is 0.12 % of a group's work wide, far below what the estimates are good for; ties take the order the
-    // atomics give), then the group with the k-th smallest sum takes the k-th heaviest tile of the round.
-    const float sum_to_bin = total > 0.0f ? (float)kBalanceBins * (float)G / (1.25f * total) : 0.0f;
-    auto sum_bin = [&](float v) {
-        const uint32_t b = (uint32_t)(v * sum_to_bin);
-        return b < (uint32_t)kBalanceBins ? b : (uint32_t)kBalanceBins - 1u;
-    };
-    BSTAMP(5);
-    for (uint32_t r = 0; r + 1u < rounds; r++) {
-        for (uint32_t k = tid; k < (uint32_t)kBalanceBins; k += kBalanceThreads) s_hist[k] = 0u;
-        __syncthreads();
-        for (uint32_t g = tid; g < G; g += kBalanceThreads) {
-            atomicAdd(&s_hist[sum_bin(s_sum[g])], 1u);
-        }
-        __syncthreads();
-        scan_hist();
-        for (uint32_t g = tid; g < G; g += kBalanceThreads) {
-            const float v = s_sum[g];
-            const uint32_t k = atomicAdd(&s_hist[sum_bin(v)], 1u); // < G: the classes hold G groups in all
-            put(r * G + g, r * G + k);
-            s_sum[g] = v + __uint_as_float(s_a[r * G + k]);
-        }
-        __syncthreads();
-    }
-    BSTAMP(6);
-}
+// The passes that write a dispatch order, rtx_order_tiles and rtx_balance_tiles, with the rules they are launched by.
+#include "rtx_order_kernels.inc"
 
 // rtx_expand: compact pixel words -> records, for up to kMaxExpandSeg segments (a segment = a run of pixels that
 // is contiguous in both buffers: one rank's rows of one frame).  Pure streaming: 4 bytes read, S written per pixel.
@@ -1431,35 +864,19 @@ extern "C" int rtx_k_launch_pick_ray(const KArgs* a, uint32_t col, uint32_t row,
 
 extern "C" int rtx_k_launch_bin_cells(const KArgs* a, unsigned splits, void* stream_v)
 {
-    const unsigned blocks = ((a->cells_x + 3u) >> 2) * ((a->cells_y + 3u) >> 2);
-    hipLaunchKernelGGL(rtx::rtx_bin_cells, dim3(blocks, splits, 1), dim3(rtx::kThreads), 0, (hipStream_t)stream_v, *a);
-    return (int)hipGetLastError();
+    return rtx::launch_bin_cells(a, splits, (hipStream_t)stream_v);
 }
 
 extern "C" int rtx_k_launch_order_tiles(const uint32_t* tile_cost, uint32_t n_tiles, uint32_t gx, uint32_t n_cu, uint32_t first_round,
                                         const uint32_t* base_order, uint32_t* tile_order, void* stream_v)
 {
-    if (n_tiles == 0 || gx == 0 || gx > 0xffffu || (n_tiles + gx - 1u) / gx > 0xffffu) {
-        return (int)hipErrorInvalidValue;
-    }
-    if (first_round > n_tiles) first_round = n_tiles;
-    hipLaunchKernelGGL(rtx::rtx_order_tiles, dim3(1), dim3(rtx::kOrderThreads), 0, (hipStream_t)stream_v, tile_cost, n_tiles, gx, n_cu, first_round, base_order, tile_order);
-    return (int)hipGetLastError();
+    return rtx::launch_order_tiles(tile_cost, n_tiles, gx, n_cu, first_round, base_order, tile_order, (hipStream_t)stream_v);
 }
 
 extern "C" int rtx_k_launch_balance_tiles(const uint32_t* tile_cost, uint32_t n_tiles, uint32_t gx, uint32_t n_cu, const uint32_t* prev_order,
                                           float* factor, int have_factor, int have_times, uint32_t* tile_order, void* stream_v)
 {
-    if (n_tiles == 0 || n_tiles > (uint32_t)rtx::kBalanceMaxTiles || gx == 0 || n_cu == 0 || n_cu > (uint32_t)rtx::kOrderThreads) {
-        return (int)hipErrorInvalidValue;
-    }
-    RTX_X_BALANCE_DEBUG();
-    // how much of a group's deviation from the mean duration goes into its tiles' factors per pass, and the largest step
-    float damping = 0.7f, max_step = 0.18f;
-    RTX_X_BALANCE_PARAMS(damping, max_step);
-    hipLaunchKernelGGL(rtx::rtx_balance_tiles, dim3(1), dim3(rtx::kBalanceThreads), 0, (hipStream_t)stream_v, tile_cost, n_tiles, gx, n_cu, prev_order,
-                       factor, (uint32_t)have_factor, (uint32_t)have_times, tile_order, damping, max_step);
-    return (int)hipGetLastError();
+    return rtx::launch_balance_tiles(tile_cost, n_tiles, gx, n_cu, prev_order, factor, have_factor, have_times, tile_order, (hipStream_t)stream_v);
 }
 
 extern "C" int rtx_k_launch_zero(void* p, size_t bytes, void* stream_v)
