@@ -513,7 +513,7 @@ def test_per_wave_refinement_gives_the_same_frame(R, ctx, mode, sub, tile):
 
 
 def test_refinement_with_more_survivors_than_a_wave_keeps(R, ctx):
-    """Hundreds of spheres stacked on the same pixels: a wave's refined list overflows its 192 slots and the
+    """Hundreds of spheres stacked on the same pixels: a wave's refined list overflows its 128 slots and the
     wave must fall back to the whole list."""
     rng = np.random.default_rng(11)
     n = 600
