@@ -1,4 +1,4 @@
-// rtx_ctx.h -- the context behind the C ABI, shared by rtx_api.cpp and rtx_post.hip.
+// rtx_ctx.h -- the context behind the C ABI, shared by rtx_api.cpp, rtx_post.hip, rtx_update.cpp and the other host files.
 #pragma once
 
 #include "../../include/rtx.h"
@@ -60,6 +60,15 @@ struct MinRun {
     uint64_t* d_total = nullptr; // [0] the stream's length, [1] the failure word of a fused launch
     uint32_t epoch = 0;          // not 0: a fused launch under this epoch
 };
+
+inline MinInput records_input(int mode, size_t w, size_t h, const void* d_records) { return MinInput{mode, w, h, false, d_records, 0u}; }
+
+inline MinInput words_input(int mode, size_t w, size_t h, const void* d_words, uint32_t lead = 0) { return MinInput{mode, w, h, true, d_words, lead}; }
+
+inline MinInput delta_input(int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_counts) { return MinInput{mode, w, h, true, d_cur, 0u, d_prev, d_counts}; }
+
+// (w x h: the cells; d_words: w x 2h pixel words)
+inline MinInput half_input(int mode, size_t w, size_t h, const void* d_words) { return MinInput{mode, w, h, true, d_words, 0u, nullptr, nullptr, true}; }
 
 // bit casts (the creation index of an object travels in the .w of its float4s)
 inline float bits_to_float(uint32_t u)
@@ -224,7 +233,7 @@ struct rtx_ctx {
     };
     std::vector<JoinEvent> join_events;
 
-    // pipelined Update (rtx_update_begin / rtx_update_end): two slots, each with its own frame, minimise
+    // pipelined Update (rtx_update_begin / rtx_update_end; rtx_update.cpp): two slots, each with its own frame, minimise
     // buffer, scan scratch and events; the copy of slot k's stream to the host runs on copy_stream while slot
     // k^1 is being traced
     struct UpdateSlot {
@@ -361,7 +370,7 @@ struct rtx_ctx {
     PinnedBuf<uint8_t> h_remove_marks;
     uint64_t stat_scene_removed = 0;    // RTX_STAT_SCENE_REMOVED
 
-    // delta frames (rtx_delta_words, rtx_update_delta; rtx_post.hip): the previous and the current frame's pixel words in two
+    // delta frames (rtx_delta_words: rtx_post.hip; rtx_update_delta: rtx_update.cpp): the previous and the current frame's pixel words in two
     // buffers that swap roles (delta_at: the one the last successful call handed out), the delta's own output buffer (sized by
     // rtx_delta_bound at first use) and the two counters of the last delta launch (changed cells, runs)
     DeviceBuf<uint32_t> d_delta_words[2];
@@ -374,7 +383,7 @@ struct rtx_ctx {
     bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
     uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
 
-    // half-block frames (rtx_update_half; rtx_post.hip): the stream's own buffer, grown on demand to rtx_half_bound bytes (d_min
+    // half-block frames (rtx_update_half; rtx_update.cpp): the stream's own buffer, grown on demand to rtx_half_bound bytes (d_min
     // holds 20 W 2H, a half-block stream can take 41 W H)
     DeviceBuf<uint8_t> d_half_out;
     uint64_t stat_half_frames = 0;      // RTX_STAT_HALF_FRAMES
@@ -390,6 +399,15 @@ int rtx_hip_fail(rtx_ctx* ctx, hipError_t e, const char* what);
 int rtx_sync_scene(rtx_ctx* ctx);
 void rtx_scene_edited(rtx_ctx* ctx);
 int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip
+// rtx_post.hip: Minimize as rtx_update.cpp drives it.  launch_minimize queues the Minimize of `in` into d_out on the context's stream
+// (scratch d_scan: min_scan_bytes of it; `pair`: pinned host words, as the device addresses them, that receive the result instead of
+// d_scan); settle_minimize takes the two result words as the host read them after a wait and redoes a launch whose blocks gave up;
+// minimize_and_wait is both with the context's scratch, the wait in between, d_out = nullptr being the context's d_min.
+size_t min_scan_bytes(uint64_t n_slots);
+int ensure_min_buffers(rtx_ctx* ctx, uint64_t n_slots, bool need_out);
+int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_out, MinRun* run, uint64_t* pair = nullptr);
+int settle_minimize(rtx_ctx* ctx, const MinRun& run, const uint64_t got[2], uint64_t* total);
+int minimize_and_wait(rtx_ctx* ctx, const MinInput& in, void* d_out, size_t* out_bytes);
 // rtx_post.hip: the rows of an edit in place -> spheres first .. first+n-1 of THIS context alone (a validated range of creation
 // indices, n > 0, not inside a capture), blocking.  `rows` is host memory (src_device < 0; h_centres follows) or device memory of
 // src_device: read in place, or copied into the context's scratch first (`stage`: a group member's copy of the root's rows).

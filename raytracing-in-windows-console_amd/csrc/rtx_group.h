@@ -1,5 +1,5 @@
 // rtx_group.h -- a context that renders on several devices (rtx_group_create): what the entry points of rtx_api.cpp /
-// rtx_post.hip call when the context they are handed is the root of a device group.
+// rtx_post.hip / rtx_update.cpp call when the context they are handed is the root of a device group.
 //
 // One process, one member context (scene replica, streams, slab buffer) per logical rank, rank 0 = the root = the context
 // the caller holds.  Frames shard by pixel rows -- rank g traces rows [g H / N, (g + 1) H / N) with the GLOBAL row index in ray
@@ -61,7 +61,7 @@ bool threads_active(rtx_ctx* root); // the ranks other than the root have submis
 // (the ranks wait side by side); on the caller's thread alone everything is queued first, so that the ranks' device work still
 // overlaps, and then awaited on every rank -- also after a failure: nothing may still be running on a rank's buffers.
 int run_phases(rtx_ctx* root, const std::function<int(int, rtx_ctx*)>& queue, const std::function<int(int, rtx_ctx*)>& await);
-// rtx_update without a gather (RTX_OPT_GROUP_UPDATE): wanted for this group?  ... and what rtx_post.hip reports back
+// rtx_update without a gather (RTX_OPT_GROUP_UPDATE): wanted for this group?  ... and what rtx_update.cpp reports back
 bool update_direct_wanted(const rtx_ctx* root);
 void update_direct_done(rtx_ctx* root, bool ok); // ok: counted; not ok: the group gathers on its root from now on
 

@@ -10,6 +10,8 @@
 // grid) and fills in the culling the reference only sketches in comments (RayTracingManager.cu:21-24, 109-117).
 #pragma once
 
+#include "../../include/rtx.h" // the statuses and modes the Update family's plan speaks in
+
 #include <algorithm>
 #include <cmath>
 #include <limits>
@@ -1251,6 +1253,89 @@ inline SamplePlan plan_supersample(uint64_t W, uint64_t H, uint64_t row0, uint64
     p.rows = s * rows;
     p.cells = W * rows;
     p.bytes = kSampleBytes * p.W * p.rows;
+    return p;
+}
+
+// ------------------------------------------------------------------------------------------------ the Update family
+//
+// rtx_update, rtx_update_begin, rtx_update_delta and rtx_update_half (rtx.h) run one sequence -- physics step, trace, encode, deliver
+// to the host -- and differ in what they refuse, in what they trace and encode, and in which ways of delivering they try.  All of
+// that is decided here, from the call, the options and the context; rtx_update.cpp executes it.  Where the entry points differ
+// without a reason anybody wrote down, they differ here, line by line: DESIGN.md 4.12, "Known divergences".
+
+enum UpdateEntry { kUpdateBlocking, kUpdatePipelined, kUpdateDelta, kUpdateHalf };
+enum UpdateSource { kUpdateWords, kUpdateRecords };
+enum UpdateEncoder { kEncodeMinimize, kEncodeDelta, kEncodeHalf }; // (a delta call minimises instead where the context owes a key frame)
+
+constexpr uint64_t kHostWriteAutoSlots = 1ull << 17; // a pipelined frame takes the host-write form unasked up to this many slots
+
+// What the decision reads of the call, the options and the context: W, H = params.x, params.y (a half-block call's console cells);
+// capacity: the context's, 20 bytes per pixel of the frame it was created for; unknown_flags: rtx_update_delta was given flag bits it
+// does not know; the options RTX_OPT_UPDATE_WORDS, RTX_OPT_MINIMIZE_FUSED, RTX_OPT_UPDATE_HOST_WRITE; group: the context is the root
+// of a device group, group_direct: ... whose ranks deliver their own rows (RTX_OPT_GROUP_UPDATE, and no failure so far);
+// host_aligned: host_out is 16-byte aligned.
+struct UpdateRequest {
+    UpdateEntry entry = kUpdateBlocking;
+    int mode = 0;
+    uint64_t W = 0, H = 0, capacity = 0;
+    bool unknown_flags = false;
+    int64_t opt_update_words = -1, opt_min_fused = -1, opt_update_host_write = -1;
+    bool group = false, group_direct = false, host_aligned = false;
+};
+
+// refusal: not RTX_OK, the call is refused with this status and `message`; physics_first: the physics step precedes the refusal (else
+// a refused call steps nothing).  The ways of delivering that are tried, in this order: try_group_direct, every rank minimises its
+// rows and copies them over its own link; try_host_write, the Minimize launch writes host_out and the length itself; and the one that
+// is always there, the copy of the encoded stream.  A way that turns out not to work when it is tried (the direct update fails,
+// host_out is not device-addressable) falls through to the next at run time.
+struct UpdatePlan {
+    int refusal = RTX_OK;
+    const char* message = "";
+    bool physics_first = false;
+    UpdateSource source = kUpdateWords;
+    UpdateEncoder encoder = kEncodeMinimize;
+    bool try_group_direct = false, try_host_write = false;
+};
+
+inline UpdatePlan update_refused(UpdatePlan p, int status, const char* message) { return p.refusal = status, p.message = message, p; }
+
+inline UpdatePlan plan_update(const UpdateRequest& q)
+{
+    UpdatePlan p;
+    const bool character = q.mode >= RTX_BIT_ASCII && q.mode < RTX_SDL, empty = q.W == 0 || q.H == 0;
+    if (q.entry == kUpdateDelta) {
+        p.encoder = kEncodeDelta;
+        if (!character) return update_refused(p, RTX_ERR_INVALID_MODE, "rtx_update_delta: not a character mode");
+        if (q.unknown_flags) return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: unknown flag bits");
+        if (empty || q.W - 1 > kDeltaMaxIndex || q.H > kDeltaMaxIndex) return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: x - 1 and y must be in [0, 99999], x and y at least 1");
+        if (20 * q.W * q.H > q.capacity) return update_refused(p, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
+        return p;
+    }
+    if (q.entry == kUpdateHalf) {
+        p.encoder = kEncodeHalf;
+        if (!character) return update_refused(p, RTX_ERR_INVALID_MODE, "rtx_update_half: not a character mode");
+        if (empty || q.W >= kFrameSideLimit || q.H >= kFrameSideLimit / 2 || half_bound(q.mode >= RTX_RGB_ASCII ? kHalfEscRgb : kHalfEsc8, (size_t)q.W, (size_t)q.H) == 0) {
+            return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half: x and 2 y must be in [1, 2^31)");
+        }
+        if (20 * q.W * 2u * q.H > q.capacity) return update_refused(p, RTX_ERR_TOO_LARGE, "rtx_update_half: W x 2H pixels are more than the context was created for (create it with twice the rows)");
+        return p;
+    }
+    // the plain frame, blocking or pipelined
+    const bool pipelined = q.entry == kUpdatePipelined, any_mode = q.mode >= RTX_BIT_ASCII && q.mode <= RTX_SDL, too_large = 20 * q.W * q.H > q.capacity;
+    p.physics_first = !pipelined;
+    p.source = q.mode != RTX_SDL && q.opt_update_words != 0 ? kUpdateWords : kUpdateRecords;
+    if (pipelined) {
+        if (!any_mode) return update_refused(p, RTX_ERR_INVALID_MODE, "invalid rendering mode");
+        if (empty || too_large) return update_refused(p, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
+    } else if (p.source == kUpdateWords) { // (the blocking record form refuses nothing itself: rtx_render does)
+        if (!any_mode) return update_refused(p, RTX_ERR_INVALID_MODE, "invalid rendering mode");
+        if (empty || too_large) return update_refused(p, empty ? RTX_ERR_INVALID_ARGUMENT : RTX_ERR_TOO_LARGE, "frame larger than the context was created for, or empty");
+    }
+    if (p.source == kUpdateRecords) return p; // records are minimised into a device buffer and copied
+    p.try_group_direct = q.group_direct;
+    const bool host_writable = q.opt_min_fused != 0 && q.host_aligned; // (only the one-launch Minimize takes a host target)
+    p.try_host_write = host_writable && (pipelined ? !q.group && (q.opt_update_host_write > 0 || (q.opt_update_host_write < 0 && q.W * q.H <= kHostWriteAutoSlots))
+                                                   : q.opt_update_host_write != 0);
     return p;
 }
 

@@ -1,6 +1,6 @@
 // rtx_post.hip -- what RayTracingManager::Update runs around the trace kernel, on the GPU:
-// UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319),
-// plus rtx_update, the whole of Update in one call.
+// UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319) with its delta and half-block
+// encoders.  (The whole of Update in one call -- rtx_update and its family -- is rtx_update.cpp, which drives the launches here.)
 // Also the edits of scene objects in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane) and their removal
 // (rtx_scene_remove_objects, rtx_scene_remove_marked_device): their kernels sit beside the physics step's, which moves the same arrays.
 #include "rtx_ctx.h"
@@ -20,6 +20,8 @@ namespace {
 
 uint64_t min_blocks(uint64_t n_slots) { return (n_slots + rtx::kSlotsPerBlock - 1) / rtx::kSlotsPerBlock; }
 
+} // namespace
+
 // Bytes of Minimize scratch for a frame of n_slots: [total u64 x 8][offsets u64 x blocks][sums u32 x blocks]
 size_t min_scan_bytes(uint64_t n_slots) { return (size_t)min_blocks(n_slots) * (sizeof(uint32_t) + sizeof(uint64_t)) + 64; }
 
@@ -36,14 +38,7 @@ int ensure_min_buffers(rtx_ctx* ctx, uint64_t n_slots, bool need_out)
     return RTX_OK;
 }
 
-MinInput records_input(int mode, size_t w, size_t h, const void* d_records) { return MinInput{mode, w, h, false, d_records, 0u}; }
-
-MinInput words_input(int mode, size_t w, size_t h, const void* d_words, uint32_t lead = 0) { return MinInput{mode, w, h, true, d_words, lead}; }
-
-MinInput delta_input(int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_counts) { return MinInput{mode, w, h, true, d_cur, 0u, d_prev, d_counts}; }
-
-// (w x h: the cells; d_words: w x 2h pixel words)
-MinInput half_input(int mode, size_t w, size_t h, const void* d_words) { return MinInput{mode, w, h, true, d_words, 0u, nullptr, nullptr, true}; }
+namespace {
 
 // f(Src()) with the slot source (rtx_post_kernels.inc) of `in`: the one place where a mode and an input form pick the kernels.
 template <class F>
@@ -126,12 +121,14 @@ int ensure_look_tables(rtx_ctx* ctx, size_t n_blocks)
     return RTX_OK;
 }
 
+} // namespace
+
 // Minimize of `in` into d_out on the context's stream (scratch d_scan: min_scan_bytes): one launch (rtx_min_fused,
 // RTX_OPT_MINIMIZE_FUSED) or the chain.  run->d_total[0] will hold the stream's length; after a fused launch (run->epoch != 0)
 // run->d_total[1] == run->epoch says that blocks gave up: settle_minimize then redoes the frame as the chain.
 // (`pair`: where the one-launch form leaves the two result words instead of at d_scan -- pinned host memory as the device addresses it,
 // for a caller that reads them after a synchronisation without a copy; the chain does not take it)
-int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_out, MinRun* run, uint64_t* pair = nullptr)
+int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_out, MinRun* run, uint64_t* pair)
 {
     *run = MinRun{in, d_out, d_scan, (uint64_t*)d_scan, 0u};
     const uint64_t n_slots = (uint64_t)in.w * in.h;
@@ -193,145 +190,7 @@ int minimize_and_wait(rtx_ctx* ctx, const MinInput& in, void* d_out, size_t* out
     return RTX_OK;
 }
 
-// Update traces pixel words and minimises from them (the records of the frame are never written) unless the caller asked for
-// the record form (RTX_OPT_UPDATE_WORDS = 0) or the mode has no words (RTX_SDL).
-bool update_from_words(const rtx_ctx* ctx, int mode) { return mode != RTX_SDL && ctx->opt_update_words != 0; }
-
-int ensure_words_buffer(rtx_ctx* ctx, DeviceBuf<uint32_t>& buf, size_t need)
-{
-    if (buf.reserve(need, rtxmem::after_stream(ctx->stream)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the pixel-word buffer");
-    return RTX_OK;
-}
-
-// The frame of `p` as W*H pixel words in *d_words, complete in stream order on the context's stream: sharded over the
-// group's devices and gathered, or one launch into `own` (grown as needed).
-int trace_words(rtx_ctx* ctx, const rtx_params* p, int mode, DeviceBuf<uint32_t>& own, const uint32_t** d_words)
-{
-    if (ctx->group) return rtxgroup::render_words(ctx, p, mode, d_words);
-    int rc = ensure_words_buffer(ctx, own, (size_t)p->x * (size_t)p->y);
-    if (rc != RTX_OK) return rc;
-    if ((rc = rtx_render_rows(ctx, p, mode, 0, (size_t)p->y, own.get(), 0, ctx->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc;
-    *d_words = own.get();
-    return RTX_OK;
-}
-
-// The blocking Update with ONE host wait: the Minimize launch stores the stream straight into the caller's buffer (pinned
-// host memory, addressed by the device) and its length into a pinned word, so that no copy is queued and nothing is waited for twice.
-// A console-sized frame's Update is three launches, two small copies and two waits -- 45 us of which the kernels are 11 -- and this
-// takes a copy, the stream's copy and a wait out of it.  *done = false: not this way (the buffer is not device-addressable, or the
-// one-launch Minimize is off): the caller goes the usual way.
-int update_host_write(rtx_ctx* ctx, const rtx_params* p, int mode, void* host_out, size_t* out_bytes, bool* done)
-{
-    *done = false;
-    if (ctx->opt_min_fused == 0 || ((uintptr_t)host_out & 15u) != 0) return RTX_OK;
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    void* d_host = nullptr;
-    if (hipHostGetDevicePointer(&d_host, host_out, 0) != hipSuccess || d_host == nullptr) {
-        (void)hipGetLastError(); // pageable memory: the usual way
-        return RTX_OK;
-    }
-    if (ctx->h_pair.reserve(2, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for the stream's length");
-    }
-    void* d_pair = nullptr;
-    RTX_HIP(ctx, hipHostGetDevicePointer(&d_pair, ctx->h_pair.get(), 0));
-    const size_t W = (size_t)p->x, H = (size_t)p->y;
-    const uint32_t* d_words = nullptr;
-    int rc = trace_words(ctx, p, mode, ctx->d_words, &d_words);
-    if (rc != RTX_OK) return rc;
-    if ((rc = ensure_min_buffers(ctx, (uint64_t)W * H, false)) != RTX_OK) return rc;
-    ctx->h_pair.get()[0] = 0;
-    ctx->h_pair.get()[1] = 0;
-    MinRun run;
-    if ((rc = launch_minimize(ctx, ctx->d_scan.get(), words_input(mode, W, H, d_words), (uint8_t*)d_host, &run, (uint64_t*)d_pair)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t total = 0;
-    // (blocks that gave up: the chain, into the same buffer, its length read back the usual way)
-    if ((rc = settle_minimize(ctx, run, ctx->h_pair.get(), &total)) != RTX_OK) return rc;
-    ctx->stat_host_writes++;
-    *out_bytes = (size_t)total;
-    *done = true;
-    return RTX_OK;
-}
-
-// rtx_update on a device group WITHOUT a gather (RTX_OPT_GROUP_UPDATE): the whole Update is bound by the copy of the minimised
-// stream over one PCIe link, and a group has one link per device.  Every rank traces its rows as pixel words -- and the row above
-// them, whose last pixel is the colour its first pixel is compared with (RayTracingManager.cu:181-319 carries the last emitted colour
-// across rows) -- minimises its own rows (launch_minimize with `lead` = W) and, once the lengths of the ranks before it are
-// known on the host, copies its part of the stream to its place in host_out from its own device.  The ranks' parts, in rank
-// order, are the bytes the root would have made of the gathered frame.  false in *done: nothing was delivered, gather instead.
-int update_group_direct(rtx_ctx* root, const rtx_params* p, int mode, void* host_out, size_t* out_bytes)
-{
-    const int N = rtx_group_size(root);
-    const size_t W = (size_t)p->x, H = (size_t)p->y;
-    struct Part {
-        size_t row0 = 0, rows = 0, bytes = 0, offset = 0;
-    };
-    std::vector<Part> part((size_t)N);
-    for (int r = 0; r < N; r++) {
-        const rtxplan::Slab s = rtxplan::slab_of(H, r, N);
-        part[(size_t)r].row0 = (size_t)s.row0;
-        part[(size_t)r].rows = (size_t)s.rows;
-    }
-    std::vector<MinRun> runs((size_t)N);
-    // a rank's device work: trace (its rows and the one above), minimise, the two words of the result on their way to the host
-    auto queue_rows = [&](int r, rtx_ctx* m) -> int {
-        Part& q = part[(size_t)r];
-        if (q.rows == 0) return RTX_OK;
-        RTX_HIP(m, hipSetDevice(m->device));
-        const size_t above = q.row0 > 0 ? 1u : 0u;
-        int rc2 = ensure_words_buffer(m, m->d_words, (q.rows + above) * W);
-        if (rc2 != RTX_OK) return rc2;
-        if (m->h_pair.reserve(2, rtxmem::nothing()) != hipSuccess) {
-            return rtx_fail(m, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for a rank's stream length");
-        }
-        if ((rc2 = rtx_render_rows(m, p, mode, q.row0 - above, q.rows + above, m->d_words.get(), q.row0 - above, m->stream, RTX_RENDER_COMPACT)) != RTX_OK) return rc2;
-        if ((rc2 = ensure_min_buffers(m, (uint64_t)W * q.rows, true)) != RTX_OK) return rc2;
-        MinRun& run = runs[(size_t)r];
-        if ((rc2 = launch_minimize(m, m->d_scan.get(), words_input(mode, W, q.rows, m->d_words.get() + above * W, (uint32_t)(above * W)), m->d_min.get(), &run)) != RTX_OK) return rc2;
-        RTX_HIP(m, hipMemcpyAsync(m->h_pair.get(), run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, m->stream));
-        return RTX_OK;
-    };
-    auto await_rows = [&](int r, rtx_ctx* m) -> int {
-        Part& q = part[(size_t)r];
-        if (q.rows == 0) return RTX_OK;
-        RTX_HIP(m, hipSetDevice(m->device));
-        RTX_HIP(m, hipStreamSynchronize(m->stream));
-        uint64_t total = 0;
-        const int rc2 = settle_minimize(m, runs[(size_t)r], m->h_pair.get(), &total);
-        if (rc2 != RTX_OK) return rc2;
-        q.bytes = (size_t)total;
-        return RTX_OK;
-    };
-    auto queue_copy = [&](int r, rtx_ctx* m) -> int {
-        const Part& q = part[(size_t)r];
-        if (q.bytes == 0) return RTX_OK;
-        RTX_HIP(m, hipSetDevice(m->device));
-        RTX_HIP(m, hipMemcpyAsync((uint8_t*)host_out + q.offset, m->d_min.get(), q.bytes, hipMemcpyDeviceToHost, m->stream));
-        return RTX_OK;
-    };
-    auto await_copy = [&](int r, rtx_ctx* m) -> int {
-        if (part[(size_t)r].bytes == 0) return RTX_OK;
-        RTX_HIP(m, hipSetDevice(m->device));
-        RTX_HIP(m, hipStreamSynchronize(m->stream));
-        return RTX_OK;
-    };
-    int rc = rtxgroup::run_phases(root, queue_rows, await_rows);
-    if (rc != RTX_OK) {
-        (void)hipSetDevice(root->device);
-        return rc;
-    }
-    size_t at = 0;
-    for (int r = 0; r < N; r++) {
-        part[(size_t)r].offset = at;
-        at += part[(size_t)r].bytes;
-    }
-    rc = rtxgroup::run_phases(root, queue_copy, await_copy);
-    RTX_HIP(root, hipSetDevice(root->device));
-    if (rc != RTX_OK) return rc;
-    *out_bytes = at;
-    return RTX_OK;
-}
+namespace {
 
 // rtx_scene_set_spheres*: is [first, first + n) a run of spheres?  (Then it is a run of consecutive sphere indices too.)
 int check_sphere_range(rtx_ctx* ctx, const char* who, unsigned first, size_t n)
@@ -755,60 +614,6 @@ int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cu
     return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts.get()), d_out, out_bytes);
 }
 
-int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags, void* host_out, size_t host_capacity,
-                     size_t* out_bytes, int* kind)
-{
-    if (!ctx || !params || !host_out || !out_bytes || !kind) return RTX_ERR_INVALID_ARGUMENT;
-    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_update_delta: not a character mode");
-    if ((flags & ~(unsigned)RTX_DELTA_KEYFRAME) != 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: unknown flag bits");
-    const size_t W = (size_t)params->x, H = (size_t)params->y;
-    if (W == 0 || H == 0 || W - 1 > rtxplan::kDeltaMaxIndex || H > rtxplan::kDeltaMaxIndex) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_delta: x - 1 and y must be in [0, 99999], x and y at least 1");
-    }
-    if (20 * (uint64_t)W * (uint64_t)H > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
-    int rc;
-    // RayTracingManager.cu:89-107: physics first, as rtx_update
-    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    const bool key = !ctx->delta_valid || ctx->delta_w != W || ctx->delta_h != H || ctx->delta_mode != mode || (flags & RTX_DELTA_KEYFRAME) != 0;
-    const unsigned at = ctx->delta_at ^ 1u; // the buffer that does NOT hold the frame handed out last: nothing of this call reads it before it is written
-    ctx->delta_valid = false;               // until this call has handed its frame out
-    // the words: traced straight into the pair's buffer; a group's gathered words are copied into it
-    const uint32_t* d_words = nullptr;
-    if ((rc = ensure_words_buffer(ctx, ctx->d_delta_words[at], W * H)) != RTX_OK) return rc;
-    if ((rc = trace_words(ctx, params, mode, ctx->d_delta_words[at], &d_words)) != RTX_OK) return rc;
-    if (d_words != ctx->d_delta_words[at].get()) {
-        RTX_HIP(ctx, hipMemcpyAsync(ctx->d_delta_words[at].get(), d_words, W * H * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    size_t n = 0;
-    const uint8_t* d_stream = nullptr;
-    if (key) {
-        // what rtx_update makes of the frame: Minimize of the words into the context's buffer
-        if ((rc = rtx_minimize_words(ctx, mode, W, H, ctx->d_delta_words[at].get(), nullptr, &n)) != RTX_OK) return rc;
-        d_stream = ctx->d_min.get();
-    } else {
-        const size_t bound = rtx_delta_bound(mode, W, H);
-        if (ctx->d_delta_out.reserve(bound, rtxmem::after_stream(ctx->stream)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta buffer");
-        if ((rc = rtx_delta_words(ctx, mode, W, H, ctx->d_delta_words[at].get(), ctx->d_delta_words[at ^ 1u].get(), ctx->d_delta_out.get(), ctx->d_delta_out.capacity(), &n)) != RTX_OK) return rc;
-        d_stream = ctx->d_delta_out.get();
-    }
-    if (n > host_capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_delta: the stream is longer than host_capacity (the next call gives a key frame)");
-    if (n) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, d_stream, n, hipMemcpyDeviceToHost, ctx->stream));
-        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->delta_at = at;
-    ctx->delta_valid = true;
-    ctx->delta_w = W;
-    ctx->delta_h = H;
-    ctx->delta_mode = mode;
-    ctx->stat_delta_frames++;
-    if (key) ctx->stat_delta_keyframes++;
-    *out_bytes = n;
-    *kind = key ? RTX_DELTA_KEY : RTX_DELTA_DIFF;
-    return RTX_OK;
-}
-
 size_t rtx_half_bound(int mode, size_t w, size_t h)
 {
     if (mode < RTX_BIT_ASCII || mode >= RTX_SDL || w == 0 || h == 0 || w >= (1ull << 31) || h >= (1ull << 30)) return 0;
@@ -827,245 +632,6 @@ int rtx_half_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_wor
     if (out_capacity < bound) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_half_words: the output holds less than rtx_half_bound");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     return minimize_and_wait(ctx, half_input(mode, w, h, d_words), d_out, out_bytes);
-}
-
-int rtx_update_half(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, size_t host_capacity, size_t* out_bytes)
-{
-    if (!ctx || !params || !host_out || !out_bytes) return RTX_ERR_INVALID_ARGUMENT;
-    ctx->delta_valid = false; // (the consumer's screen is about to show this frame: the next rtx_update_delta gives a key frame)
-    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_update_half: not a character mode");
-    const size_t W = (size_t)params->x, H = (size_t)params->y;
-    const size_t bound = rtx_half_bound(mode, W, H);
-    if (bound == 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half: x and 2 y must be in [1, 2^31)");
-    if (20 * (uint64_t)W * 2u * (uint64_t)H > ctx->capacity) {
-        return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_half: W x 2H pixels are more than the context was created for (create it with twice the rows)");
-    }
-    int rc;
-    // RayTracingManager.cu:89-107: physics first, as rtx_update
-    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    // the sample frame: two pixel rows per console row, under the same field of view (ray generation divides by y)
-    rtx_params sample = *params;
-    sample.y = 2u * (uint64_t)H;
-    const uint32_t* d_words = nullptr;
-    if ((rc = trace_words(ctx, &sample, mode, ctx->d_words, &d_words)) != RTX_OK) return rc;
-    // (every earlier launch into the buffer has been waited for by the call that queued it)
-    if (ctx->d_half_out.reserve((bound + 15u) & ~(size_t)15u, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the half-block buffer");
-    }
-    size_t n = 0;
-    if ((rc = minimize_and_wait(ctx, half_input(mode, W, H, d_words), ctx->d_half_out.get(), &n)) != RTX_OK) return rc;
-    if (n > host_capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_update_half: the stream is longer than host_capacity");
-    if (n) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_half_out.get(), n, hipMemcpyDeviceToHost, ctx->stream));
-        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    ctx->stat_half_frames++;
-    *out_bytes = n;
-    return RTX_OK;
-}
-
-int rtx_update(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, size_t* out_bytes)
-{
-    if (!ctx || !params || !host_out || !out_bytes) return RTX_ERR_INVALID_ARGUMENT;
-    ctx->delta_valid = false; // (the consumer's screen is about to show this frame: the next rtx_update_delta gives a key frame)
-    int rc;
-    // RayTracingManager.cu:89-107: physics first
-    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
-    size_t n = 0;
-    if (update_from_words(ctx, mode)) {
-        // :120-134 + :146 on 4-byte pixel words: the trace stores words, the minimise pass reads them and writes the very
-        // stream it would have made of the records (which are never written: the context's frame buffer keeps what it held)
-        if (mode < RTX_BIT_ASCII || mode > RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode");
-        if (params->x == 0 || params->y == 0 || 20 * (uint64_t)params->x * (uint64_t)params->y > ctx->capacity) {
-            return rtx_fail(ctx, params->x && params->y ? RTX_ERR_TOO_LARGE : RTX_ERR_INVALID_ARGUMENT, "frame larger than the context was created for, or empty");
-        }
-        if (rtxgroup::update_direct_wanted(ctx)) {
-            // no gather: every rank minimises its own rows and copies them over its own PCIe link
-            rc = update_group_direct(ctx, params, mode, host_out, &n);
-            rtxgroup::update_direct_done(ctx, rc == RTX_OK);
-            if (rc == RTX_OK) {
-                *out_bytes = n;
-                return RTX_OK;
-            }
-            (void)hipGetLastError(); // (the group gathers on its root from now on; this frame too)
-        }
-        if (ctx->opt_update_host_write != 0) { // (a group that gathers on its root: the root's Minimize launch writes the host buffer)
-            // the Minimize launch writes the stream into the caller's pinned buffer itself (RTX_OPT_UPDATE_HOST_WRITE): one host wait.  At
-            // any size in this blocking form -- 1080p: 0.370 ms against 0.395 with the copy queued after a wait for the length
-            bool done = false;
-            if ((rc = update_host_write(ctx, params, mode, host_out, &n, &done)) != RTX_OK) return rc;
-            if (done) {
-                *out_bytes = n;
-                return RTX_OK;
-            }
-        }
-        const uint32_t* d_words = nullptr;
-        if ((rc = trace_words(ctx, params, mode, ctx->d_words, &d_words)) != RTX_OK) return rc;
-        if ((rc = rtx_minimize_words(ctx, mode, (size_t)params->x, (size_t)params->y, d_words, nullptr, &n)) != RTX_OK) return rc;
-        if (n) {
-            RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min.get(), n, hipMemcpyDeviceToHost, ctx->stream));
-            RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-        *out_bytes = n;
-        return RTX_OK;
-    }
-    // :86 + :120-134: zero semantics and trace
-    if ((rc = rtx_render(ctx, params, mode)) != RTX_OK) return rc;
-    // :146: minimise on the device; :143 then only moves the minimised stream across PCIe
-    if ((rc = rtx_minimize(ctx, mode, (size_t)params->x, (size_t)params->y, nullptr, nullptr, &n)) != RTX_OK) return rc;
-    if (n) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, ctx->d_min.get(), n, hipMemcpyDeviceToHost, ctx->stream));
-        RTX_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    *out_bytes = n;
-    return RTX_OK;
-}
-
-// ---- pipelined Update: the frame sequence of RayTracingManager::Update split in two calls so
-// that the copy of frame k's minimised stream to the host overlaps the trace of frame k+1.
-int rtx_update_begin(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, void* host_out, int* ticket)
-{
-    if (!ctx || !params || !host_out || !ticket) return RTX_ERR_INVALID_ARGUMENT;
-    ctx->delta_valid = false; // (as rtx_update: the next rtx_update_delta gives a key frame)
-    if (mode < RTX_BIT_ASCII || mode > RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode");
-    const size_t w = (size_t)params->x, h = (size_t)params->y;
-    if (w == 0 || h == 0 || 20 * w * h > ctx->capacity) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "frame larger than the context was created for");
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned si = ctx->upd_next;
-    rtx_ctx::UpdateSlot& sl = ctx->upd[si];
-    if (sl.busy) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_begin: both slots are in flight; call rtx_update_end first");
-    if (!ctx->copy_stream) {
-        // A stream of another priority than the render streams': the runtime spreads a process's streams of one priority over four
-        // hardware queues, and a copy that lands in the queue of the context's own stream holds back the next frame's kernels until
-        // it is done -- the pipelined Update then costs copy + kernels (0.376 ms) instead of the copy alone (0.326), which is what
-        // bench.py's default line measured whenever four render streams had been created first.
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest ||
-            ctx->copy_stream.ensure_with_priority(hipStreamNonBlocking, greatest) != hipSuccess) {
-            (void)hipGetLastError();
-            RTX_HIP(ctx, ctx->copy_stream.ensure(hipStreamNonBlocking));
-        }
-    }
-    // every member under its own null check: a call that fails half-way (out of memory) leaves a slot the next
-    // call completes, instead of one that looks initialised with null buffers behind it
-    const bool from_words = update_from_words(ctx, mode);
-    if (!from_words && !sl.d_frame.get()) {
-        if (sl.d_frame.reserve(ctx->capacity, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for an update slot's frame");
-        const hipError_t me = hipMemsetAsync(sl.d_frame.get(), 0, ctx->capacity, ctx->stream);
-        if (me != hipSuccess) {
-            sl.d_frame.release();
-            return rtx_hip_fail(ctx, me, "hipMemsetAsync(update slot frame)");
-        }
-    }
-    if (!sl.d_min.get() && sl.d_min.reserve(ctx->capacity, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for an update slot's minimise buffer");
-    }
-    if (sl.h_total.reserve(2, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipHostMalloc failed for an update slot");
-    }
-    RTX_HIP(ctx, sl.ev_ready.ensure());
-    RTX_HIP(ctx, sl.ev_copied.ensure());
-    // (the slot is not busy: the launch that used the old scratch has been waited for)
-    RTX_HIP(ctx, sl.d_scan.reserve(min_scan_bytes((uint64_t)w * h), rtxmem::nothing()));
-    int rc;
-    if (run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
-    if (from_words && rtxgroup::update_direct_wanted(ctx)) {
-        // a group whose ranks minimise and copy their own rows (RTX_OPT_GROUP_UPDATE): N links carry the stream at once, which is
-        // worth more than the overlap of one link's copy with the next trace -- the frame is complete when this call returns
-        size_t n = 0;
-        rc = update_group_direct(ctx, params, mode, host_out, &n);
-        rtxgroup::update_direct_done(ctx, rc == RTX_OK);
-        if (rc == RTX_OK) {
-            sl.bytes = n;
-            RTX_HIP(ctx, hipEventRecord(sl.ev_copied, ctx->copy_stream));
-            sl.busy = true;
-            *ticket = (int)si;
-            ctx->upd_next = si ^ 1u;
-            return RTX_OK;
-        }
-        (void)hipGetLastError(); // (the group gathers on its root from now on; this frame too)
-    }
-    const uint32_t* d_words = nullptr;
-    sl.host_write = false;
-    if (from_words && !ctx->group && ctx->opt_min_fused != 0 && ((uintptr_t)host_out & 15u) == 0 &&
-        (ctx->opt_update_host_write > 0 || (ctx->opt_update_host_write < 0 && (uint64_t)w * h <= (1u << 17)))) {
-        // a small frame: the Minimize launch stores the stream and its length in host memory itself, and NOTHING is waited for here --
-        // rtx_update_end waits for the frame.  (At console sizes the copy form's two waits per frame were what the pipelined Update cost.)
-        void *d_host = nullptr, *d_pair = nullptr;
-        if (hipHostGetDevicePointer(&d_host, host_out, 0) == hipSuccess && d_host != nullptr && hipHostGetDevicePointer(&d_pair, sl.h_total.get(), 0) == hipSuccess) {
-            if ((rc = trace_words(ctx, params, mode, sl.d_words, &d_words)) != RTX_OK) return rc;
-            sl.h_total.get()[0] = 0;
-            sl.h_total.get()[1] = 0;
-            if ((rc = launch_minimize(ctx, sl.d_scan.get(), words_input(mode, w, h, d_words), (uint8_t*)d_host, &sl.run, (uint64_t*)d_pair)) != RTX_OK) return rc;
-            RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
-            sl.host_write = true;
-            ctx->stat_host_writes++;
-            sl.busy = true;
-            *ticket = (int)si;
-            ctx->upd_next = si ^ 1u;
-            return RTX_OK;
-        }
-        (void)hipGetLastError(); // pageable memory: the copy form
-    }
-    if (from_words) {
-        // pixel words into the slot's own buffer (a group: into the group's, gathered), minimised from there
-        if ((rc = trace_words(ctx, params, mode, sl.d_words, &d_words)) != RTX_OK) return rc;
-        if ((rc = launch_minimize(ctx, sl.d_scan.get(), words_input(mode, w, h, d_words), sl.d_min.get(), &sl.run)) != RTX_OK) return rc;
-    } else {
-    // the slot's frame buffer is caller-style memory for rtx_render_rows: whole frame, with the zero
-    // semantics of the per-frame memset (the buffer starts zeroed; SDL frames write nothing, so clear)
-    const bool rgb = mode >= RTX_RGB_ASCII;
-    if (mode == RTX_SDL) {
-        RTX_HIP(ctx, hipMemsetAsync(sl.d_frame.get(), 0, 20 * w * h, ctx->stream));
-    }
-    if (ctx->group) {
-        if ((rc = rtxgroup::render_frame(ctx, params, mode, sl.d_frame.get(), rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) return rc;
-    } else if ((rc = rtx_render_rows(ctx, params, mode, 0, h, sl.d_frame.get(), 0, ctx->stream, rgb ? RTX_RENDER_DEFAULT : RTX_RENDER_ZERO_TAIL)) != RTX_OK) {
-        return rc;
-    }
-    if ((rc = launch_minimize(ctx, sl.d_scan.get(), records_input(mode, w, h, sl.d_frame.get()), sl.d_min.get(), &sl.run)) != RTX_OK) return rc;
-    }
-    RTX_HIP(ctx, hipMemcpyAsync(sl.h_total.get(), sl.run.d_total, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    RTX_HIP(ctx, hipEventRecord(sl.ev_ready, ctx->stream));
-    // the length is needed on the host to size the copy: wait for this frame's kernels (the previous frame's
-    // copy keeps running on the copy stream meanwhile)
-    RTX_HIP(ctx, hipEventSynchronize(sl.ev_ready));
-    {
-        uint64_t total = 0;
-        if ((rc = settle_minimize(ctx, sl.run, sl.h_total.get(), &total)) != RTX_OK) return rc;
-        sl.bytes = (size_t)total;
-    }
-    if (sl.bytes) {
-        RTX_HIP(ctx, hipMemcpyAsync(host_out, sl.d_min.get(), sl.bytes, hipMemcpyDeviceToHost, ctx->copy_stream));
-    }
-    RTX_HIP(ctx, hipEventRecord(sl.ev_copied, ctx->copy_stream));
-    sl.busy = true;
-    *ticket = (int)si;
-    ctx->upd_next = si ^ 1u;
-    return RTX_OK;
-}
-
-int rtx_update_end(rtx_ctx* ctx, int ticket, size_t* out_bytes)
-{
-    if (!ctx || !out_bytes || ticket < 0 || ticket > 1) return RTX_ERR_INVALID_ARGUMENT;
-    rtx_ctx::UpdateSlot& sl = ctx->upd[ticket];
-    if (!sl.busy) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_update_end: no frame in flight under this ticket");
-    RTX_HIP(ctx, hipSetDevice(ctx->device));
-    if (sl.host_write) {
-        RTX_HIP(ctx, hipEventSynchronize(sl.ev_ready));
-        sl.host_write = false;
-        sl.busy = false;
-        uint64_t total = 0;
-        const int rc = settle_minimize(ctx, sl.run, sl.h_total.get(), &total);
-        if (rc != RTX_OK) return rc;
-        *out_bytes = (size_t)total;
-        return RTX_OK;
-    }
-    RTX_HIP(ctx, hipEventSynchronize(sl.ev_copied));
-    *out_bytes = sl.bytes;
-    sl.busy = false;
-    return RTX_OK;
 }
 
 } // extern "C"
