@@ -9,7 +9,9 @@
 // (RayTracingManager::SetDeltaFrames, rtx_update_delta; no reference counterpart), and a whole frame where one is needed.
 // --half: two pixel rows per console row -- every cell the upper half block U+2580 with the top pixel's colour in front and the bottom
 // pixel's behind (RayTracingManager::SetHalfBlocks, rtx_update_half; no reference counterpart).  Needs a UTF-8 terminal; made for the
-// two PIXEL modes (--mode 1 or 3); --delta is ignored with it.
+// two PIXEL modes (--mode 1 or 3).
+// --half --delta: half blocks of which, after the first frame, only the cells whose two colours changed are sent, each run behind a
+// cursor escape (RayTracingManager::SetHalfDeltaFrames, rtx_update_half_delta; no reference counterpart).
 // --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
 // no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
@@ -210,8 +212,12 @@ int main(int argc, char** argv)
         camera->Update();
         scene->Init();
         rayTracingManager->SetRenderingMode((RenderingMode)mode0);
-        if (delta) rayTracingManager->SetDeltaFrames(true);
-        if (half) rayTracingManager->SetHalfBlocks(true);
+        if (half && delta) {
+            rayTracingManager->SetHalfDeltaFrames(true); // half blocks, and only the cells whose colours changed
+        } else {
+            if (delta) rayTracingManager->SetDeltaFrames(true);
+            if (half) rayTracingManager->SetHalfBlocks(true);
+        }
         if (samples != 1) rayTracingManager->SetSupersampling(samples);
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;

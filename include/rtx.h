@@ -261,7 +261,7 @@ enum rtx_option {
                                * RTX_ERR_OUT_OF_MEMORY when it cannot grow), then rtx_resolve<S,mode[,compact|,values]>, which
                                * rtx_last_kernel_name reports.  Everything that traces through rtx_render_rows inherits the rule:
                                * rtx_render, rtx_submit_frames / rtx_submit_slabs (queued one by one: no RTX_OPT_BATCH launch while
-                               * S > 1), rtx_update, rtx_update_begin, rtx_update_delta and rtx_update_half (their pixel words are the folded cells'),
+                               * S > 1), rtx_update, rtx_update_begin, rtx_update_delta, rtx_update_half and rtx_update_half_delta (their pixel words are the folded cells'),
                                * and device groups (rank g's cell rows are sample rows [S row0_g, S (row0_g + rows_g)) with the global
                                * row index, so a sharded frame equals the one-device frame).  RTX_SDL writes nothing and is
                                * unaffected; rtx_pick, rtx_query_*, rtx_expand, rtx_minimize* and rtx_delta_words do not trace.  A
@@ -389,9 +389,12 @@ enum rtx_stat {
                                      * (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
     RTX_STAT_DELTA_CELLS = 153,     /* cells the last delta launch (rtx_delta_words, or an rtx_update_delta that returned RTX_DELTA_DIFF)
                                      * found changed; 0 before the first.  Two words per context, counted on the device.  Reading it
-                                     * waits for the device.  No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+                                     * waits for the device.  A delta launch of either kind: rtx_half_delta_words and an
+                                     * rtx_update_half_delta that returned RTX_DELTA_DIFF write the same two words.
+                                     * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
     RTX_STAT_DELTA_RUNS = 154,      /* ... and the runs they form: the cursor escapes of that stream.  With RTX_STAT_DELTA_CELLS a caller
                                      * can tell when a key frame would have been shorter.  Reading it waits for the device.
+                                     * Of the last delta launch of either kind, as RTX_STAT_DELTA_CELLS.
                                      * No reference counterpart (PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
     RTX_STAT_SUPERSAMPLE_FRAMES = 100, /* supersampled launch sets queued so far (RTX_OPT_SUPERSAMPLE > 1): counted as
                                      * RTX_STAT_SHADOW_FRAMES counts, one per rtx_render_rows call; stays 0 while S = 1.  (Numbered below
@@ -399,6 +402,12 @@ enum rtx_stat {
     RTX_STAT_HALF_FRAMES = 99,      /* frames rtx_update_half has handed out so far.  (Numbered below the other counters, as
                                      * RTX_STAT_SUPERSAMPLE_FRAMES is: 100 .. 154 are taken.)  No reference counterpart
                                      * (RayTracing.cu:256,476 paint one colour per cell; PrintMachine.cpp:257-306) */
+    RTX_STAT_HALF_DELTA_FRAMES = 96, /* frames rtx_update_half_delta has handed out so far, key frames included; they count neither in
+                                     * RTX_STAT_HALF_FRAMES nor in RTX_STAT_DELTA_FRAMES.  (Numbered below the other counters: 97 .. 154
+                                     * are taken.)  No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306,
+                                     * RayTracingManager.cu:150) */
+    RTX_STAT_HALF_DELTA_KEYFRAMES = 95, /* ... of which were key frames (RTX_DELTA_KEY).  No reference counterpart
+                                     * (RayTracing.cu:256,476, PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -861,8 +870,8 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
  * The stream is at most H ((W-1)(2E + 3) + 1) bytes, E = 19 for RGB and 11 for 8-bit.  A terminal that keeps the SGR foreground and
  * background state, fed the stream from the home position, shows (T, B) in every cell.
  * Out of scope: a pipelined begin / end form, a launch that writes host memory itself (RTX_OPT_UPDATE_HOST_WRITE), a device group's
- * gather-free direct update (RTX_OPT_GROUP_UPDATE), delta frames of half-block streams, and a space in place of the glyph where
- * T == B. */
+ * gather-free direct update (RTX_OPT_GROUP_UPDATE), and a space in place of the glyph where T == B.  Not part of these three calls:
+ * delta frames of half-block streams, which are a call family of their own (rtx_update_half_delta, below). */
 /* The bound above for a w x h console of `mode`.  0 for anything the other two calls refuse: RTX_SDL or no mode, w == 0 or h == 0,
  * w or 2h of 2^31 or more, a product that does not fit size_t.  Pure host arithmetic.
  * No reference counterpart (RayTracing.cu:256,476; its buffers are 20*W*H, PrintMachine.cpp:140). */
@@ -885,6 +894,63 @@ int rtx_half_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_wor
  * Counted in RTX_STAT_HALF_FRAMES.  No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306). */
 int rtx_update_half(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics,
                     void* host_out, size_t host_capacity, size_t* out_bytes);
+
+/* ---- delta frames of half-block streams: only the half-block cells whose two colours changed since the previous frame, addressed
+ * by cursor escapes.  The delta frames' two-frame memory and runs with the half-block frames' (T, B) keys and escapes.
+ * No reference counterpart: its PIXEL modes paint one colour per cell (RayTracing.cu:256,476) and its printer homes the cursor and
+ * rewrites the whole screen every frame (PrintMachine.cpp:257-306) from the stream Update hands it (RayTracingManager.cu:150).
+ *
+ * THE RULE, on pixel words (RTX_RENDER_COMPACT).  Inputs: one of the five character modes, W, H and two arrays cur and prev of W * 2H
+ * words each, laid out as rtx_half_words lays them out: row 2r is the top half of console row r, row 2r+1 the bottom half, column W-1
+ * the newline column.  K(w), SGR(sel, K), the two families and the glyph E2 96 80 are those of the half-block rule: a word 0xffffffff
+ * outside column W-1 counts as 0, the glyph byte of a word is ignored.
+ *   Slot g = r*W + c.  For c < W-1: T = K(cur[2rW + c]), B = K(cur[(2r+1)W + c]); Tp, Bp the same of prev.
+ *   changed(g)  iff  c < W-1 and (T, B) != (Tp, Bp) -- the displayed keys, not the words: a glyph-only difference is no change, 0
+ *                    against 0xffffffff is no change, and in the 8-bit family 0 against a word whose byte 0 is 16 is no change
+ *   start(g)    iff  changed(g) and (c == 0 or not changed(g-1))
+ * A changed slot emits, in this order: if start(g), the cursor escape ESC [ <r+1> ; <c+1> H (decimal, no leading zeros, as in the
+ * delta rule) and then SGR('3', T) and SGR('4', B), both unconditionally; otherwise SGR('3', T) iff T differs from the T of slot g-1
+ * in cur, and SGR('4', B) likewise; then the three glyph bytes.  Every other slot emits nothing, the newline column included: a
+ * delta addresses its own cells.  The stream is the concatenation in slot order; two frames with equal keys give 0 bytes.
+ * A terminal that shows the (T, B) grid of prev and is fed the stream shows the (T, B) grid of cur in every cell afterwards,
+ * whatever SGR state it had on entry: every run sets both colours itself.
+ * With C = 2E + 3 (41 for RGB, 25 for 8-bit), c changed cells in r runs cost at most C c + cup r, cup the cursor escape's length.
+ * Limits: W-1 <= 99999 and H <= 99999; anything larger is RTX_ERR_INVALID_ARGUMENT.  RTX_SDL and anything that is no mode:
+ * RTX_ERR_INVALID_MODE.
+ * Out of scope: tracking the terminal's SGR state across runs to elide a run's first escapes, bridging short unchanged gaps between
+ * runs, choosing a key frame automatically when it would be shorter (RTX_STAT_DELTA_CELLS and RTX_STAT_DELTA_RUNS let a caller
+ * decide), a pipelined begin / end form, a launch that writes host memory itself (RTX_OPT_UPDATE_HOST_WRITE), and a device group's
+ * gather-free direct update (RTX_OPT_GROUP_UPDATE). */
+/* The largest stream either kind can be for a w x h console of `mode`: the larger of the rule's maximum (per row C c + cup r) and
+ * the key frame's rtx_half_bound(mode, w, h).  0 for arguments the other two calls refuse.  Pure host arithmetic.
+ * No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
+size_t rtx_half_delta_bound(int mode, size_t w, size_t h);
+/* The rule as a pass of its own over the caller's device buffers: d_cur and d_prev w * 2h words each (4-byte aligned), d_out the
+ * stream (16-byte aligned, out_capacity bytes; less than rtx_half_delta_bound(mode, w, h) returns RTX_ERR_TOO_LARGE before anything
+ * is launched), *out_bytes its length.  On the context's stream; blocking, like rtx_delta_words, and with its launches:
+ * RTX_OPT_MINIMIZE_FUSED 0 / 1 / 2 means here what it means there (a launch that gave up is redone as three and counted in
+ * RTX_STAT_MINIMIZE_FALLBACKS).  Bytes of d_out past *out_bytes are not written.  RTX_STAT_DELTA_CELLS and RTX_STAT_DELTA_RUNS read
+ * the launch's changed cells and runs.  On a device group: the root's device alone.
+ * No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
+int rtx_half_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cur, const void* d_prev,
+                         void* d_out, size_t out_capacity, size_t* out_bytes);
+/* rtx_update_half with a memory of the frame before.  Refusals are rtx_update_half's (a character mode; 20 * W * 2H within the
+ * context's capacity, else RTX_ERR_TOO_LARGE: create it with twice the rows) with rtx_update_delta's limits and its check of
+ * `flags`, in rtx_update_delta's order, and physics runs where rtx_update_delta runs it.  The sample frame -- `params` with y
+ * doubled -- is traced as pixel words by the path rtx_update uses (every shading option and RTX_OPT_SUPERSAMPLE apply; a device
+ * group traces sharded and gathers), then
+ *   a KEY frame (*kind = RTX_DELTA_KEY: byte for byte what rtx_update_half returns for the frame) when the context holds no valid
+ *   previous half-block frame, when that frame's W, H or mode differ, when `flags` has RTX_DELTA_KEYFRAME, or when any other entry
+ *   point of the family (rtx_update, rtx_update_begin, rtx_update_delta, rtx_update_half) ran on the context since the last call;
+ *   otherwise the rule's stream against the frame the last successful call handed out (*kind = RTX_DELTA_DIFF).
+ * The context remembers one frame as "what the consumer's screen shows", of one kind: a call of rtx_update_half_delta makes the next
+ * rtx_update_delta a key frame as well.  The two frames live in rtx_update_delta's pair of word buffers, grown to W * 2H.  A stream
+ * longer than host_capacity returns RTX_ERR_TOO_LARGE, copies nothing, and the next call gives a key frame (so does a call that
+ * failed for any other reason).  Blocking.  Counted in RTX_STAT_HALF_DELTA_FRAMES and RTX_STAT_HALF_DELTA_KEYFRAMES, not in
+ * RTX_STAT_HALF_FRAMES or RTX_STAT_DELTA_FRAMES.
+ * No reference counterpart (RayTracing.cu:256,476, PrintMachine.cpp:257-306, RayTracingManager.cu:150). */
+int rtx_update_half_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags,
+                          void* host_out, size_t host_capacity, size_t* out_bytes, int* kind);
 
 /* ---- ansi256_from_rgb (ANSIRGB.h:141-189) on its own: the xterm-256 index (16..255) of each packed 0xRRGGBB
  * value first_rgb, first_rgb+1, ..., first_rgb+count-1 (first_rgb + count <= 2^24), one byte per value into

@@ -640,6 +640,23 @@ public:
         }
         const rtx_params p = rtx_compat::to_rtx_params(params);
         size_t newSize = 0;
+        if (m_halfDeltaFrames) {
+            // two pixel rows per console row, and only the cells whose colours changed (rtx_update_half_delta): a key frame first, after
+            // SetHalfDeltaFrames, and whenever the library decides on one; the printer appends deltas it has not written yet
+            int kind = RTX_DELTA_KEY;
+            const int rc = rtx_update_half_delta(m_ctx, &p, (int)currentRenderingMode, dt, /*run_physics=*/1, m_wantKey ? RTX_DELTA_KEYFRAME : RTX_DELTA_DEFAULT,
+                                                 m_minimizedResultArray, PrintMachine::GetMaxSize(), &newSize, &kind);
+            if (rc != RTX_ERR_TOO_LARGE) rtx_compat::check(m_ctx, rc, "rtx_update_half_delta");
+            m_wantKey = false;
+            if (rc == RTX_ERR_TOO_LARGE || !PrintMachine::SetDeltaInBackBuffer(m_minimizedResultArray, newSize, kind == RTX_DELTA_KEY)) {
+                // a delta longer than the buffers (rtx_half_delta_bound is above rtx_half_bound), or unprinted deltas that have outgrown
+                // the back buffer: the same frame once more (no physics), whole, replaces them
+                rtx_compat::check(m_ctx, rtx_update_half_delta(m_ctx, &p, (int)currentRenderingMode, 0.0, /*run_physics=*/0, RTX_DELTA_KEYFRAME,
+                                                               m_minimizedResultArray, PrintMachine::GetMaxSize(), &newSize, &kind), "rtx_update_half_delta");
+                PrintMachine::SetDeltaInBackBuffer(m_minimizedResultArray, newSize, true);
+            }
+            return;
+        }
         if (m_halfBlocks) {
             // two pixel rows per console row (rtx_update_half): a whole frame every time, handed over as rtx_update's is
             rtx_compat::check(m_ctx, rtx_update_half(m_ctx, &p, (int)currentRenderingMode, dt, /*run_physics=*/1, m_minimizedResultArray,
@@ -678,13 +695,25 @@ public:
     // every cell the glyph U+2580 with the colour of pixel row 2r in front and that of row 2r + 1 behind, W x 2H square pixels on a
     // W x H console (rtx_update_half; the two PIXEL modes are what it is for, a UTF-8 terminal what it needs).  The printer's buffers
     // and the device context must have been made for it: PrintMachine::Start(x, y, true) first, else this throws.  While on, delta
-    // frames (SetDeltaFrames) are ignored: every frame is whole; switching off makes the next delta frame a key frame.  Off by
-    // default, and then nothing changes.
+    // frames (SetDeltaFrames) are ignored: every frame is whole (half-block frames have a delta form of their own,
+    // SetHalfDeltaFrames); switching off makes the next delta frame a key frame.  Off by default, and then nothing changes.
     void SetHalfBlocks(const bool on)
     {
         if (on && !PrintMachine::HalfBlocks()) throw std::runtime_error("RayTracingManager::SetHalfBlocks: PrintMachine::Start(x, y, true) must come first");
         m_halfBlocks = on;
         m_wantKey = true;
+    }
+    // Extension, no reference counterpart (RayTracing.cu:256,476; PrintMachine.cpp:257-306; RayTracingManager.cu:150): Update hands over
+    // half-block frames as SetHalfBlocks does, but after the first only the cells whose two colours changed, each run behind a cursor
+    // escape (rtx_update_half_delta).  Needs PrintMachine::Start(x, y, true), as SetHalfBlocks does, else this throws; switches the
+    // printer to delta mode.  While on it decides what Update sends, whatever SetHalfBlocks and SetDeltaFrames say; switching it off
+    // leaves the printer's delta mode to SetDeltaFrames.  Off by default, and then nothing changes.
+    void SetHalfDeltaFrames(const bool on)
+    {
+        if (on && !PrintMachine::HalfBlocks()) throw std::runtime_error("RayTracingManager::SetHalfDeltaFrames: PrintMachine::Start(x, y, true) must come first");
+        m_halfDeltaFrames = on;
+        m_wantKey = true;
+        PrintMachine::SetDeltaMode(on || m_deltaFrames);
     }
     void SetRenderingMode(const RenderingMode newRenderMode) { currentRenderingMode = newRenderMode; }
     // Extensions, no reference counterpart (its light is a constant, RayTracing.cu:132,143-157): the point light (nullptr: the
@@ -701,5 +730,6 @@ private:
     char* m_minimizedResultArray = nullptr;
     bool m_deltaFrames = false, m_wantKey = true; // SetDeltaFrames
     bool m_halfBlocks = false;                    // SetHalfBlocks
+    bool m_halfDeltaFrames = false;               // SetHalfDeltaFrames
     RenderingMode currentRenderingMode = BIT_ASCII; // RayTracingManager.h:53
 };

@@ -56,6 +56,7 @@ STAT_REFLECT_GRID_FALLBACK_RAYS = 97
 OPT_SUPERSAMPLE = 30           # S x S rays per console cell, folded on the GPU: 1 (default) .. 4 (include/rtx.h)
 STAT_SUPERSAMPLE_FRAMES = 100
 STAT_HALF_FRAMES = 99           # frames rtx_update_half has handed out (include/rtx.h)
+STAT_HALF_DELTA_FRAMES, STAT_HALF_DELTA_KEYFRAMES = 96, 95  # frames rtx_update_half_delta has handed out, and its key frames
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
@@ -188,6 +189,10 @@ _SIGNATURES = [
     ("rtx_half_bound", C.c_size_t, [C.c_int, C.c_size_t, C.c_size_t]),
     ("rtx_half_words", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("rtx_update_half", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_double, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("rtx_half_delta_bound", C.c_size_t, [C.c_int, C.c_size_t, C.c_size_t]),
+    ("rtx_half_delta_words", C.c_int, [_P, C.c_int, C.c_size_t, C.c_size_t, _P, _P, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("rtx_update_half_delta", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_double, C.c_int, C.c_uint, _P, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_int)]),
     ("rtx_ansi256_map", C.c_int, [_P, C.c_uint32, C.c_size_t, _P, _P]),
     ("rtx_host_alloc", _P, [_P, C.c_size_t]),
     ("rtx_host_free", None, [_P, _P]),
@@ -259,6 +264,12 @@ def delta_bound(mode, w, h):
 def half_bound(mode, w, h):
     """rtx_half_bound: the most bytes a half-block stream of a w x h console can take (0 for arguments the half-block calls refuse)."""
     return lib().rtx_half_bound(mode, w, h)
+
+
+def half_delta_bound(mode, w, h):
+    """rtx_half_delta_bound: the most bytes a delta or a key frame of a w x h half-block console can take (0 for arguments the
+    half-block delta calls refuse)."""
+    return lib().rtx_half_delta_bound(mode, w, h)
 
 
 # BASELINE.json configs: (W, H, spheres, planes, LCG seed)  (SURVEY.md Appendix D)
@@ -697,6 +708,24 @@ class Context:
         self._check(lib().rtx_update_half(self._h, C.byref(params), mode, dt, 1 if run_physics else 0, ptr,
                                           need if capacity is None else capacity, C.byref(n)))
         return arr[:n.value]  # a view of the pinned buffer: valid until the next update() / update_half()
+
+    def half_delta_words(self, mode, w, h, d_cur, d_prev, d_out, out_capacity):
+        """rtx_half_delta_words: the delta of two half-block frames of w x 2h pixel words (device pointers) into d_out; returns the
+        stream's length."""
+        n = C.c_size_t()
+        self._check(lib().rtx_half_delta_words(self._h, mode, w, h, d_cur, d_prev, d_out, out_capacity, C.byref(n)))
+        return n.value
+
+    def update_half_delta(self, params, mode, dt=0.0, run_physics=False, flags=DELTA_DEFAULT, capacity=None):
+        """rtx_update_half_delta: (stream, kind) -- the whole half-block frame as update_half() returns it (DELTA_KEY) or only the
+        cells whose colours changed since the frame the last call handed out (DELTA_DIFF).  `capacity`: the host_capacity passed
+        (default: half_delta_bound's)."""
+        need = half_delta_bound(mode, int(params.x), int(params.y))
+        ptr, _, arr = self._pinned_buffer(max(need, 16))
+        n, kind = C.c_size_t(), C.c_int(-1)
+        self._check(lib().rtx_update_half_delta(self._h, C.byref(params), mode, dt, 1 if run_physics else 0, flags, ptr,
+                                                need if capacity is None else capacity, C.byref(n), C.byref(kind)))
+        return arr[:n.value], kind.value  # a view of the pinned buffer: valid until the next update call of any kind
 
     def ansi256_map(self, first_rgb, count, d_out, stream=None):
         """rtx_ansi256_map: xterm-256 indices of packed 0xRRGGBB values first_rgb .. first_rgb+count-1 into d_out."""

@@ -70,6 +70,9 @@ inline MinInput delta_input(int mode, size_t w, size_t h, const void* d_cur, con
 // (w x h: the cells; d_words: w x 2h pixel words)
 inline MinInput half_input(int mode, size_t w, size_t h, const void* d_words) { return MinInput{mode, w, h, true, d_words, 0u, nullptr, nullptr, true}; }
 
+// (a delta of two half-block frames, rtx_half_delta_words: both marks -- `half` with `prev` and `counts`)
+inline MinInput half_delta_input(int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_counts) { return MinInput{mode, w, h, true, d_cur, 0u, d_prev, d_counts, true}; }
+
 // bit casts (the creation index of an object travels in the .w of its float4s)
 inline float bits_to_float(uint32_t u)
 {
@@ -375,13 +378,15 @@ struct rtx_ctx {
     // rtx_delta_bound at first use) and the two counters of the last delta launch (changed cells, runs)
     DeviceBuf<uint32_t> d_delta_words[2];
     unsigned delta_at = 0;
-    bool delta_valid = false;           // delta_words[delta_at] is the frame the consumer shows: W, H and mode as below
+    bool delta_valid = false;           // delta_words[delta_at] is the frame the consumer shows: W, H, mode and kind as below
+    bool delta_half = false;            // ... as a half-block frame (rtx_update_half_delta: W x 2H words), else as plain cells (rtx_update_delta)
     size_t delta_w = 0, delta_h = 0;
     int delta_mode = -1;
     DeviceBuf<uint8_t> d_delta_out;
     DeviceBuf<unsigned long long> d_delta_counts;
     bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
     uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
+    uint64_t stat_half_delta_frames = 0, stat_half_delta_keyframes = 0; // RTX_STAT_HALF_DELTA_FRAMES, _KEYFRAMES
 
     // half-block frames (rtx_update_half; rtx_update.cpp): the stream's own buffer, grown on demand to rtx_half_bound bytes (d_min
     // holds 20 W 2H, a half-block stream can take 41 W H)

@@ -1218,6 +1218,38 @@ constexpr size_t half_block_bound(size_t E, size_t slots) { return E > 64 ? 0 : 
 static_assert(half_bound(kHalfEscRgb, 3, 1) == 83 && half_bound(kHalfEsc8, 1, 7) == 7 && half_bound(kHalfEscRgb, ~(size_t)0, 2) == 0, "the half-block bound");
 static_assert(half_block_bound(kHalfEscRgb, 1024) == 1024 * 41 && half_block_bound(kHalfEsc8, 1024) == 1024 * 25, "a block's image");
 
+// ------------------------------------------------------------------------------------------------ delta frames of half-block streams
+//
+// rtx_half_delta_words / rtx_update_half_delta (rtx.h) emit, for every run of changed cells of a row, the cursor escape of a delta
+// frame and then each cell as a half-block frame does: at most two colour escapes of E bytes and the glyph, 2E + 3 bytes a cell.  So
+// the delta frames' expression holds with S = 2E + 3: c changed cells in r runs cost at most (2E + 3) c + cup r.
+
+// ... of one block of `slots` consecutive slots anywhere in any frame within the limits: the block's LDS image.  More than
+// half_block_bound: a run may start on the block's first slot, and a block inside one long row is cells alone.
+constexpr size_t half_delta_block_bound(size_t E, size_t slots) { return E > 64 ? 0 : delta_run_bound(half_cell_bound(E), kDeltaMaxCup, slots); }
+
+// ... of a W x H frame of cells: the rows' sums as in delta_bound, or the key frame rtx_update_half_delta sends instead (half_bound:
+// it has a newline per row, so it is the larger one for narrow frames).  0 for what the calls refuse -- W or H 0, W - 1 or H above
+// kDeltaMaxIndex -- and where a number does not fit size_t.
+inline size_t half_delta_bound(size_t E, size_t W, size_t H)
+{
+    if (W == 0 || H == 0 || E > 64 || W - 1 > kDeltaMaxIndex || H > kDeltaMaxIndex) return 0;
+    const size_t key = half_bound(E, W, H);
+    if (key == 0) return 0;
+    size_t total = 0;
+    for (size_t lo = 0, hi = 9; W >= 2 && lo < H; lo = hi, hi = hi * 10 + 9) { // rows lo .. hi - 1: row + 1 has the digits of lo + 1
+        const size_t rows = (hi < H ? hi : H) - lo;
+        // (a row: at most (W - 1)(2E + 3 + 14) <= 1e5 * 145; the frame: at most 1e5 times that -- checked all the same)
+        const size_t sum = half_mul_add(rows, delta_run_bound(half_cell_bound(E), cup_length(lo, W - 2), W - 1), total);
+        if (sum == 0) return 0;
+        total = sum;
+    }
+    return total > key ? total : key;
+}
+
+static_assert(half_delta_block_bound(kHalfEscRgb, 1024) == 41998 && half_delta_block_bound(kHalfEsc8, 1024) == 25614,
+              "a run that starts on a block's first slot: more than half_block_bound");
+
 // ------------------------------------------------------------------------------------------------ supersampling
 //
 // RTX_OPT_SUPERSAMPLE (rtx.h): rows [row0, row0 + rows) of a W x H frame of cells at S x S samples per cell are folded from rows
@@ -1258,20 +1290,23 @@ inline SamplePlan plan_supersample(uint64_t W, uint64_t H, uint64_t row0, uint64
 
 // ------------------------------------------------------------------------------------------------ the Update family
 //
-// rtx_update, rtx_update_begin, rtx_update_delta and rtx_update_half (rtx.h) run one sequence -- physics step, trace, encode, deliver
+// rtx_update, rtx_update_begin, rtx_update_delta, rtx_update_half and rtx_update_half_delta (rtx.h) run one sequence -- physics step, trace, encode, deliver
 // to the host -- and differ in what they refuse, in what they trace and encode, and in which ways of delivering they try.  All of
 // that is decided here, from the call, the options and the context; rtx_update.cpp executes it.  Where the entry points differ
 // without a reason anybody wrote down, they differ here, line by line: DESIGN.md 4.12, "Known divergences".
 
-enum UpdateEntry { kUpdateBlocking, kUpdatePipelined, kUpdateDelta, kUpdateHalf };
+enum UpdateEntry : int { kUpdateBlocking, kUpdatePipelined, kUpdateDelta, kUpdateHalf };
+// rtx_update_half_delta.  A value of the type and no enumerator: a switch over the four entries above (tests/host/test_update_plan.cpp
+// has one, compiled with -Wswitch -Werror) stays complete.
+constexpr UpdateEntry kUpdateHalfDelta = static_cast<UpdateEntry>(4);
 enum UpdateSource { kUpdateWords, kUpdateRecords };
-enum UpdateEncoder { kEncodeMinimize, kEncodeDelta, kEncodeHalf }; // (a delta call minimises instead where the context owes a key frame)
+enum UpdateEncoder { kEncodeMinimize, kEncodeDelta, kEncodeHalf, kEncodeHalfDelta }; // (a delta call minimises instead where the context owes a key frame, a half-block delta call encodes a whole half-block frame)
 
 constexpr uint64_t kHostWriteAutoSlots = 1ull << 17; // a pipelined frame takes the host-write form unasked up to this many slots
 
 // What the decision reads of the call, the options and the context: W, H = params.x, params.y (a half-block call's console cells);
-// capacity: the context's, 20 bytes per pixel of the frame it was created for; unknown_flags: rtx_update_delta was given flag bits it
-// does not know; the options RTX_OPT_UPDATE_WORDS, RTX_OPT_MINIMIZE_FUSED, RTX_OPT_UPDATE_HOST_WRITE; group: the context is the root
+// capacity: the context's, 20 bytes per pixel of the frame it was created for; unknown_flags: rtx_update_delta or
+// rtx_update_half_delta was given flag bits it does not know; the options RTX_OPT_UPDATE_WORDS, RTX_OPT_MINIMIZE_FUSED, RTX_OPT_UPDATE_HOST_WRITE; group: the context is the root
 // of a device group, group_direct: ... whose ranks deliver their own rows (RTX_OPT_GROUP_UPDATE, and no failure so far);
 // host_aligned: host_out is 16-byte aligned.
 struct UpdateRequest {
@@ -1318,6 +1353,15 @@ inline UpdatePlan plan_update(const UpdateRequest& q)
             return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half: x and 2 y must be in [1, 2^31)");
         }
         if (20 * q.W * 2u * q.H > q.capacity) return update_refused(p, RTX_ERR_TOO_LARGE, "rtx_update_half: W x 2H pixels are more than the context was created for (create it with twice the rows)");
+        return p;
+    }
+    if (q.entry == kUpdateHalfDelta) {
+        // rtx_update_delta's checks in its order, with rtx_update_half's frame: W x 2H pixels within the capacity
+        p.encoder = kEncodeHalfDelta;
+        if (!character) return update_refused(p, RTX_ERR_INVALID_MODE, "rtx_update_half_delta: not a character mode");
+        if (q.unknown_flags) return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half_delta: unknown flag bits");
+        if (empty || q.W - 1 > kDeltaMaxIndex || q.H > kDeltaMaxIndex) return update_refused(p, RTX_ERR_INVALID_ARGUMENT, "rtx_update_half_delta: x - 1 and y must be in [0, 99999], x and y at least 1");
+        if (20 * q.W * 2u * q.H > q.capacity) return update_refused(p, RTX_ERR_TOO_LARGE, "rtx_update_half_delta: W x 2H pixels are more than the context was created for (create it with twice the rows)");
         return p;
     }
     // the plain frame, blocking or pipelined

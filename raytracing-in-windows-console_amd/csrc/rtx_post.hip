@@ -1,6 +1,6 @@
 // rtx_post.hip -- what RayTracingManager::Update runs around the trace kernel, on the GPU:
-// UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319) with its delta and half-block
-// encoders.  (The whole of Update in one call -- rtx_update and its family -- is rtx_update.cpp, which drives the launches here.)
+// UpdateObjects (RayTracingManager.cu:10-44, 89-107) and Minimize (RayTracingManager.cu:167-319) with its delta, half-block and
+// half-block delta encoders.  (The whole of Update in one call -- rtx_update and its family -- is rtx_update.cpp, which drives the launches here.)
 // Also the edits of scene objects in place (rtx_scene_set_spheres, rtx_scene_set_spheres_device, rtx_scene_set_plane) and their removal
 // (rtx_scene_remove_objects, rtx_scene_remove_marked_device): their kernels sit beside the physics step's, which moves the same arrays.
 #include "rtx_ctx.h"
@@ -56,7 +56,13 @@ int with_source(rtx_ctx* ctx, const MinInput& in, F f)
     if (in.half) {
         if (in.mode < RTX_BIT_ASCII || in.mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "no pixel words in this mode");
         // the family alone decides: the glyph byte of a word is ignored
-        if (in.mode >= RTX_RGB_ASCII) {
+        if (in.prev) {
+            if (in.mode >= RTX_RGB_ASCII) {
+                f(rtx::HalfDeltaSource<true>());
+            } else {
+                f(rtx::HalfDeltaSource<false>());
+            }
+        } else if (in.mode >= RTX_RGB_ASCII) {
             f(rtx::HalfSource<true>());
         } else {
             f(rtx::HalfSource<false>());
@@ -632,6 +638,30 @@ int rtx_half_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_wor
     if (out_capacity < bound) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_half_words: the output holds less than rtx_half_bound");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     return minimize_and_wait(ctx, half_input(mode, w, h, d_words), d_out, out_bytes);
+}
+
+size_t rtx_half_delta_bound(int mode, size_t w, size_t h)
+{
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return 0;
+    return rtxplan::half_delta_bound(mode >= RTX_RGB_ASCII ? rtxplan::kHalfEscRgb : rtxplan::kHalfEsc8, w, h); // (0 for what the calls refuse)
+}
+
+int rtx_half_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cur, const void* d_prev, void* d_out, size_t out_capacity, size_t* out_bytes)
+{
+    if (!ctx || !out_bytes || !d_cur || !d_prev || !d_out) return RTX_ERR_INVALID_ARGUMENT;
+    if (mode < RTX_BIT_ASCII || mode >= RTX_SDL) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "rtx_half_delta_words: not a character mode");
+    const size_t bound = rtx_half_delta_bound(mode, w, h);
+    if (bound == 0) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_half_delta_words: w - 1 and h must be in [0, 99999], h and w at least 1");
+    if ((((uintptr_t)d_cur | (uintptr_t)d_prev) & 3u) != 0 || ((uintptr_t)d_out & 15u) != 0) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_half_delta_words: words must be 4-byte, the output 16-byte aligned");
+    }
+    if (out_capacity < bound) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_half_delta_words: the output holds less than rtx_half_delta_bound");
+    RTX_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) {
+        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
+    }
+    ctx->delta_counts_valid = true;
+    return minimize_and_wait(ctx, half_delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts.get()), d_out, out_bytes);
 }
 
 } // extern "C"

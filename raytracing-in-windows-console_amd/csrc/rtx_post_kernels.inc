@@ -3,7 +3,7 @@
 // (rtx_min_fused, with the look-back it finds its offsets by) or as the chain rtx_min_count / rtx_min_offsets / rtx_min_scatter.  The
 // host side (buffers, launches, the Update entry points): rtx_post.hip.  Delta frames (rtx_delta_words) are a third slot source of the
 // same Minimize kernels, DeltaSource, over two frames of pixel words; half-block frames (rtx_half_words) a fourth, HalfSource, over
-// pairs of pixel rows.
+// pairs of pixel rows; their delta frames (rtx_half_delta_words) a fifth, HalfDeltaSource, over two such frames.
 namespace rtx {
 
 constexpr int kThreads = 256;
@@ -807,6 +807,178 @@ struct HalfSource {
         dst[0] = 0xe2u;
         dst[1] = 0x96u;
         dst[2] = 0x80u;
+    }
+};
+
+// ---- delta frames of half-block streams: two frames of W x 2H pixel words, `cur` and the one before it, `prev`; only the cells whose
+// (T, B) keys changed are emitted, each run of them addressed by a cursor escape (rtx_half_delta_words in rtx.h states the rule).  No
+// reference counterpart (RayTracing.cu:256,476; PrintMachine.cpp:257-306).  Slot rules, slot g = r W + c of the W x H cells:
+//   * column W-1, a cell whose keys (T, B) are those of prev                -> nothing
+//   * a changed cell whose left neighbour in the row did not change (or column 0): a run starts -> ESC [ row+1 ; col+1 H, then
+//     both colour escapes (whatever the terminal's colours were: a run relies on nothing before it) and the glyph
+//   * any other changed cell -> the foreground escape if T differs from the T of the cell to its left in cur, the background escape
+//     likewise for B, then the glyph
+// Column 0 always starts a run, so a cell looks at slot g-1 of its own row and no further: one slot of halo, no walk.
+//
+// The block's buffer, in dwords: [0] the row and [1] the column of the block's first slot; four arrays of the block's slots, each
+// with the slot in front of the block at [k - 1] (0xffffffff where that slot is not in the block's first row: nothing looks at
+// it then) -- top and bottom words of cur from kCurTop and kCurBot, of prev from kPrevTop and kPrevBot -- and the scan's partial
+// sums behind them.  Words are addressed as HalfSource::stage addresses them: consecutive lanes read consecutive words along each
+// row.  The image is built over all of it once every thread holds its own slots.
+template <bool RGB>
+struct HalfDeltaSource {
+    typedef HalfSource<RGB> Half;
+    typedef uint32_t Elem;
+    typedef DeltaInput In;
+    struct Item {
+        uint32_t t, b;       // the two keys; bit 31: the escape is due
+        uint32_t row1, col1; // row + 1 and column + 1 where a run starts, else 0: a start cannot be told from a length (35 .. 55
+                             // bytes in the RGB family against 3 .. 41 of a cell inside a run)
+    };
+    static constexpr uint32_t kDue = Half::kDue;
+    static constexpr uint32_t kE = Half::kE;
+    static constexpr uint32_t kS = Half::kS; // the longest cell inside a run
+    static constexpr uint32_t kCurTop = 4, kCurBot = kCurTop + kSlotsPerBlock + 4, kPrevTop = kCurBot + kSlotsPerBlock + 4, kPrevBot = kPrevTop + kSlotsPerBlock + 4;
+    static constexpr uint32_t kWave = (kPrevBot + kSlotsPerBlock) * 4;
+    static constexpr uint32_t kStage = kWave + (kThreads / 64) * 4;
+    // the image: 1024 cells of 2E + 3 bytes behind one escape when a run starts on the block's first slot
+    static constexpr uint32_t kBytes = ((uint32_t)rtxplan::half_delta_block_bound(kE, kSlotsPerBlock) + 15u) & ~15u;
+    static_assert(rtxplan::half_delta_block_bound(kE, kSlotsPerBlock) != 0 && kBytes >= rtxplan::half_delta_block_bound(kE, kSlotsPerBlock) &&
+                      kBytes > kSlotsPerBlock * kS,
+                  "the image holds the longest stream a block can emit");
+    static_assert(kStage <= kBytes, "words + partial sums fit the image's space");
+
+    static In input(const void* cur, const void* prev, void* counts) { return In{(const uint32_t*)cur, (const uint32_t*)prev, (unsigned long long*)counts}; }
+    static __device__ __forceinline__ void stage_tables() {}
+
+    // changed cells | runs << 16 of each wave: the cells from the lengths (tally_put), the runs from the items as they are emitted
+    static __device__ __forceinline__ uint32_t* tally()
+    {
+        __shared__ uint32_t s_tally[kThreads / 64];
+        return s_tally;
+    }
+
+    static __device__ __forceinline__ void stage(In in, uint64_t base, uint64_t n_slots, uint32_t, uint8_t* s, uint32_t W)
+    {
+        uint32_t* s_w = reinterpret_cast<uint32_t*>(s);
+        // the block's first row and column by one scalar division (64-bit only where the slot does not fit 32 bits), as first_column
+        const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane((base >> 32) == 0u ? (uint32_t)base / W : (uint32_t)(base / W));
+        const uint32_t col0 = (uint32_t)(base - (uint64_t)row0 * W);
+#pragma unroll
+        for (int k = 0; k < kPerThread; k++) {
+            const uint32_t li = (uint32_t)k * kThreads + threadIdx.x;
+            uint32_t ct = kNoWord, cb = kNoWord, pt = kNoWord, pb = kNoWord;
+            if (base + li < n_slots) {
+                const uint32_t row = row0 + (col0 + li) / W; // (32-bit: col0 < W <= 100000 and li < 1024)
+                const uint64_t at = base + li + (uint64_t)row * W; // = 2g - c; the last word read is word 2 n_slots - 1
+                ct = in.cur[at];
+                cb = in.cur[at + W];
+                pt = in.prev[at];
+                pb = in.prev[at + W];
+            }
+            s_w[kCurTop + li] = ct;
+            s_w[kCurBot + li] = cb;
+            s_w[kPrevTop + li] = pt;
+            s_w[kPrevBot + li] = pb;
+        }
+        if (threadIdx.x == 0u) {
+            uint32_t ct = kNoWord, cb = kNoWord, pt = kNoWord, pb = kNoWord;
+            if (col0 >= 1u) { // slot base - 1 is the cell to the left of the block's first, in row row0 (base >= col0 >= 1)
+                const uint64_t at = base - 1u + (uint64_t)row0 * W;
+                ct = in.cur[at];
+                cb = in.cur[at + W];
+                pt = in.prev[at];
+                pb = in.prev[at + W];
+            }
+            s_w[0] = row0;
+            s_w[1] = col0;
+            s_w[kCurTop - 1] = ct;
+            s_w[kCurBot - 1] = cb;
+            s_w[kPrevTop - 1] = pt;
+            s_w[kPrevBot - 1] = pb;
+        }
+        if (threadIdx.x < (uint32_t)(kThreads / 64)) {
+            tally()[threadIdx.x] = 0u;
+        }
+    }
+
+    // Emitted length of slot g (column col, staged at li): 0, or 3 plus the escapes that are due plus, where a run starts, the
+    // cursor escape's 6 .. 14 bytes.
+    static __device__ __forceinline__ uint32_t length(In, const uint8_t* s, uint64_t, int li, uint32_t col, uint32_t W, uint32_t, Item& it)
+    {
+        const uint32_t* s_w = reinterpret_cast<const uint32_t*>(s);
+        const uint32_t t = Half::key(s_w[(int)kCurTop + li]), b = Half::key(s_w[(int)kCurBot + li]);
+        const uint32_t lt = Half::key(s_w[(int)kCurTop + li - 1]), lb = Half::key(s_w[(int)kCurBot + li - 1]); // (staged whatever li: the halo)
+        const bool changed = col != W - 1u && (t != Half::key(s_w[(int)kPrevTop + li]) || b != Half::key(s_w[(int)kPrevBot + li]));
+        const bool left_changed = col != 0u && (lt != Half::key(s_w[(int)kPrevTop + li - 1]) || lb != Half::key(s_w[(int)kPrevBot + li - 1])); // (column col - 1 < W - 1: a cell)
+        const bool start = changed && !left_changed;
+        const bool due_t = start || t != lt, due_b = start || b != lb;
+        it.t = t | (due_t ? kDue : 0u);
+        it.b = b | (due_b ? kDue : 0u);
+        it.row1 = it.col1 = 0u;
+        uint32_t len = (uint32_t)rtxplan::kHalfGlyph + (due_t ? Half::escape_length(t) : 0u) + (due_b ? Half::escape_length(b) : 0u);
+        if (start) {
+            it.row1 = s_w[0] + (s_w[1] + (uint32_t)li) / W + 1u; // (32-bit: column + 1024 < 2^31)
+            it.col1 = col + 1u;
+            len += 4u + decimal_length(it.row1) + decimal_length(it.col1);
+        }
+        return changed ? len : 0u;
+    }
+
+    static __device__ __forceinline__ void emit(uint8_t* dst, uint32_t len, bool, const Item& it)
+    {
+        if (len == 0u) {
+            return; // an unchanged cell, a row's last column, a slot past the frame's end
+        }
+        if (it.row1 != 0u) {
+            const uint32_t nr = decimal_length(it.row1), nc = decimal_length(it.col1);
+            dst[0] = 0x1bu;
+            dst[1] = (uint8_t)'[';
+            put_decimal(dst + 2, it.row1, nr);
+            dst[2u + nr] = (uint8_t)';';
+            put_decimal(dst + 3u + nr, it.col1, nc);
+            dst[3u + nr + nc] = (uint8_t)'H';
+            dst += 4u + nr + nc;
+            atomicAdd(&tally()[threadIdx.x >> 6], 0x10000u); // a run of the launch (LDS, no return value; zeroed by stage())
+        }
+        if ((it.t & kDue) != 0u) dst += Half::put_escape(dst, (uint32_t)'3', it.t & ~kDue);
+        if ((it.b & kDue) != 0u) dst += Half::put_escape(dst, (uint32_t)'4', it.b & ~kDue);
+        dst[0] = 0xe2u;
+        dst[1] = 0x96u;
+        dst[2] = 0x80u;
+    }
+
+    // The launch's counts, as DeltaSource's: each wave's sum before a barrier of the caller's, then one atomic instruction of two
+    // lanes per block.  The lengths give the changed cells; the runs were counted as their escapes were written (emit).
+    static __device__ __forceinline__ void tally_put(const uint32_t* len)
+    {
+        uint32_t v = 0u;
+#pragma unroll
+        for (int k = 0; k < kPerThread; k++) {
+            v += len[k] != 0u ? 1u : 0u;
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            v += (uint32_t)__shfl_xor((int)v, d);
+        }
+        if ((threadIdx.x & 63u) == 0u && v != 0u) {
+            atomicAdd(&tally()[threadIdx.x >> 6], v);
+        }
+    }
+
+    static __device__ __forceinline__ void tally_add(In in)
+    {
+        if (threadIdx.x < 2u) {
+            uint32_t v = 0u;
+#pragma unroll
+            for (int k = 0; k < kThreads / 64; k++) {
+                v += tally()[k];
+            }
+            const uint32_t mine = threadIdx.x == 0u ? (v & 0xffffu) : (v >> 16); // (at most 1024 cells and 512 runs per block)
+            if (v != 0u) {
+                atomicAdd(&in.counts[threadIdx.x], (unsigned long long)mine);
+            }
+        }
     }
 };
 

@@ -1,5 +1,5 @@
 // rtx_update.cpp -- RayTracingManager::Update (RayTracingManager.cu:76-154) in one call, and its family: rtx_update, the pipelined
-// rtx_update_begin / rtx_update_end, rtx_update_delta and rtx_update_half.  Every one of them is the same sequence:
+// rtx_update_begin / rtx_update_end, rtx_update_delta, rtx_update_half and rtx_update_half_delta.  Every one of them is the same sequence:
 //   0. the call's plan (rtxplan::plan_update, rtx_plan.hpp): its refusal, what it traces and encodes, how it tries to deliver
 //   1. the physics step (rtx_update_objects)
 //   2. trace: pixel words or records into a buffer of the context's, of an update slot's or of the delta pair's
@@ -350,7 +350,8 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     int rc = enter(ctx, rtxplan::kUpdateDelta, params, mode, host_out, dt, run_physics, &plan, (flags & ~(unsigned)RTX_DELTA_KEYFRAME) != 0);
     if (rc != RTX_OK) return rc;
     const size_t W = (size_t)params->x, H = (size_t)params->y;
-    const bool key = !ctx->delta_valid || ctx->delta_w != W || ctx->delta_h != H || ctx->delta_mode != mode || (flags & RTX_DELTA_KEYFRAME) != 0;
+    // (delta_half: the consumer's screen shows a half-block frame, rtx_update_half_delta's)
+    const bool key = !ctx->delta_valid || ctx->delta_half || ctx->delta_w != W || ctx->delta_h != H || ctx->delta_mode != mode || (flags & RTX_DELTA_KEYFRAME) != 0;
     const unsigned at = ctx->delta_at ^ 1u; // the buffer that does NOT hold the frame handed out last: nothing of this call reads it before it is written
     ctx->delta_valid = false;               // until this call has handed its frame out
     // the words: traced straight into the pair's buffer; a group's gathered words are copied into it.  A key frame is what rtx_update
@@ -368,6 +369,7 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     if ((rc = encode_copy_wait(ctx, in, d_stream, host_out, host_capacity, "rtx_update_delta: the stream is longer than host_capacity (the next call gives a key frame)", out_bytes)) != RTX_OK) return rc;
     ctx->delta_at = at;
     ctx->delta_valid = true;
+    ctx->delta_half = false;
     ctx->delta_w = W;
     ctx->delta_h = H;
     ctx->delta_mode = mode;
@@ -395,6 +397,45 @@ int rtx_update_half(rtx_ctx* ctx, const rtx_params* params, int mode, double dt,
     rc = encode_copy_wait(ctx, half_input(mode, W, H, in.data), ctx->d_half_out.get(), host_out, host_capacity, "rtx_update_half: the stream is longer than host_capacity", out_bytes);
     if (rc == RTX_OK) ctx->stat_half_frames++;
     return rc;
+}
+
+// rtx_update_delta's sequence over rtx_update_half's frame: the delta pair holds W x 2H words, a key frame is rtx_update_half's stream.
+int rtx_update_half_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt, int run_physics, unsigned flags, void* host_out, size_t host_capacity,
+                          size_t* out_bytes, int* kind)
+{
+    if (!ctx || !params || !host_out || !out_bytes || !kind) return RTX_ERR_INVALID_ARGUMENT;
+    UpdatePlan plan;
+    int rc = enter(ctx, rtxplan::kUpdateHalfDelta, params, mode, host_out, dt, run_physics, &plan, (flags & ~(unsigned)RTX_DELTA_KEYFRAME) != 0);
+    if (rc != RTX_OK) return rc;
+    const size_t W = (size_t)params->x, H = (size_t)params->y;
+    const bool key = !ctx->delta_valid || !ctx->delta_half || ctx->delta_w != W || ctx->delta_h != H || ctx->delta_mode != mode || (flags & RTX_DELTA_KEYFRAME) != 0;
+    const unsigned at = ctx->delta_at ^ 1u; // the buffer that does NOT hold the frame handed out last
+    ctx->delta_valid = false;               // until this call has handed its frame out
+    // the sample frame: two pixel rows per console row, under the same field of view (ray generation divides by y)
+    rtx_params sample = *params;
+    sample.y = 2u * (uint64_t)H;
+    MinInput in;
+    if ((rc = trace_words(ctx, &sample, mode, ctx->d_delta_words[at], true, &in)) != RTX_OK) return rc;
+    // (every earlier launch into the buffer has been waited for by the call that queued it)
+    if (ctx->d_half_out.reserve((rtx_half_delta_bound(mode, W, H) + 15u) & ~(size_t)15u, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the half-block buffer");
+    if (key) {
+        in = half_input(mode, W, H, in.data);
+    } else {
+        if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
+        ctx->delta_counts_valid = true;
+        in = half_delta_input(mode, W, H, in.data, ctx->d_delta_words[at ^ 1u].get(), ctx->d_delta_counts.get());
+    }
+    if ((rc = encode_copy_wait(ctx, in, ctx->d_half_out.get(), host_out, host_capacity, "rtx_update_half_delta: the stream is longer than host_capacity (the next call gives a key frame)", out_bytes)) != RTX_OK) return rc;
+    ctx->delta_at = at;
+    ctx->delta_valid = true;
+    ctx->delta_half = true;
+    ctx->delta_w = W;
+    ctx->delta_h = H;
+    ctx->delta_mode = mode;
+    ctx->stat_half_delta_frames++;
+    if (key) ctx->stat_half_delta_keyframes++;
+    *kind = key ? RTX_DELTA_KEY : RTX_DELTA_DIFF;
+    return RTX_OK;
 }
 
 } // extern "C"
