@@ -153,7 +153,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -167,13 +167,14 @@ int main(int argc, char** argv)
         else if (a == "--no-status") status = false;
         else if (a == "--delta") delta = true; // send only the cells that changed (RayTracingManager::SetDeltaFrames)
         else if (a == "--half") half = true; // W x 2H pixels as half blocks (RayTracingManager::SetHalfBlocks)
+        else if (a == "--checker") checker = true; // a two-axis checker on the floor plane (Scene3D::SetPatterns, SetPlanePattern)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -219,6 +220,12 @@ int main(int argc, char** argv)
             if (half) rayTracingManager->SetHalfBlocks(true);
         }
         if (samples != 1) rayTracingManager->SetSupersampling(samples);
+        if (checker) {
+            // dark cells of four world units across x and z; y does not count, so the pattern lies flat on the floor
+            const rtx_pattern floor_checker = {{0.0f, 0.0f, 0.0f}, {0.25f, 0.0f, 0.25f}, {30.0f, 30.0f, 30.0f}};
+            scene->SetPatterns(&floor_checker, 1);
+            scene->SetPlanePattern(1);
+        }
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;
         int bounces = 1;

@@ -408,6 +408,10 @@ enum rtx_stat {
                                      * RayTracingManager.cu:150) */
     RTX_STAT_HALF_DELTA_KEYFRAMES = 95, /* ... of which were key frames (RTX_DELTA_KEY).  No reference counterpart
                                      * (RayTracing.cu:256,476, PrintMachine.cpp:257-306, RayTracingManager.cu:150) */
+    RTX_STAT_PATTERNED_OBJECTS = 94, /* objects with a pattern slot above 0 (rtx_scene_set_object_pattern).  (Numbered below the other
+                                     * counters: 95 .. 154 are taken.)  No reference counterpart (RayTracing.cu:144) */
+    RTX_STAT_PATTERN_FRAMES = 93,   /* launch sets queued while that count is not 0: counted as RTX_STAT_SHADOW_FRAMES counts, on whichever
+                                     * of the two paths the frame takes.  No reference counterpart (RayTracing.cu:144) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -568,6 +572,45 @@ int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, si
 int rtx_scene_set_reflectivity(rtx_ctx* ctx, unsigned first, size_t n, const float* k);
 /* The reflectivity of object `index`.  No reference counterpart. */
 int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);
+/* Checker patterns: a second colour per object, chosen by the parity of the lattice cell the hit point lies in.  The table holds
+ * up to RTX_MAX_PATTERNS entries, slots 1 .. n; an object carries a slot (0: none, what every new object has).  36 bytes. */
+#define RTX_MAX_PATTERNS 16
+typedef struct rtx_pattern {
+    float origin[3]; /* a corner of the cell lattice, world space */
+    float freq[3];   /* cells per world unit along x, y, z; 0 = that axis does not count */
+    float rgb[3];    /* the second colour, 0..255 as the add calls take colours */
+} rtx_pattern;
+/* The rule.  An object with slot s in 1 .. n is shaded (the character modes; RGB_NORMALS and SDL are unaffected) at its hit point
+ * P, the point the shading already lights, P_q = r.o_q + r.d_q * t (one multiply, one add), with the colour od chosen by entry s:
+ *   u_q = (P_q - origin_q) * freq_q                  q = x, y, z
+ *   f   = (floorf(u_x) + floorf(u_y)) + floorf(u_z)
+ *   h   = f - 2.0f * floorf(f * 0.5f)
+ *   od  = (h != 0.0f) ? od2 : od_object              od2 = rgb / 255.0f, the IEEE division the add calls use
+ * every operation rounded to fp32, nothing reassociated, no contraction.  A NaN h selects od2; for |f| >= 2^24 every float is even
+ * and the object keeps its own colour; freq_q = 0 with a finite P gives floorf(+-0) = 0, so two zero axes make stripes and one zero
+ * axis makes the checker of a floor.  The rule holds at every level of a mirror chain (rtx_scene_set_reflectivity): local_j is
+ * shaded with the pattern of o_j at P_j.  Distance, glyph, normal, the shadow tests, the fold of the chain and the record encoders
+ * are untouched: only the three od floats that enter Blinn-Phong change.  While no object has a slot above 0 every launch is what
+ * it is without these calls, whatever the table holds; otherwise a frame takes the closest-hit launch and a shade launch (the
+ * light / shadow path's, or the mirror path's), which read the slots and the table.
+ * rtx_scene_set_patterns replaces the table: n in 0 .. RTX_MAX_PATTERNS, n == 0 (patterns may be NULL) clears it.  All or nothing:
+ * a non-finite float among an entry's nine, n > RTX_MAX_PATTERNS, patterns == NULL with n > 0, or an n below the slot of some
+ * object (rtx_last_error names the object) changes nothing and returns RTX_ERR_INVALID_ARGUMENT.  rtx_scene_set_object_pattern
+ * gives objects first .. first+n-1 (creation indices, spheres and planes alike) the slot; it refuses a range past rtx_scene_count
+ * and a slot above the table's count.  On a device group both are validated before any rank is touched, then applied to every
+ * rank.  The table is context state like the light set: rtx_scene_clear leaves it.  The slots belong to the objects like the
+ * reflectivities: rtx_scene_clear forgets them, rtx_scene_set_spheres and rtx_scene_set_plane keep them, and after
+ * rtx_scene_remove_objects the survivors keep theirs under the renumbering rule.  Geometry is unchanged, so sorted copies, cell
+ * lists and the world grid stay valid; a graph recorded before a change of table or slots is refused by rtx_graph_launch
+ * (re-capture).  The device copies are uploaded with the reflectivities' by the next launch that needs them, at the cost stated at
+ * rtx_scene_set_reflectivity; recording right after a change fails with RTX_ERR_INVALID_ARGUMENT ("render once before capturing").
+ * No reference counterpart (RayTracing.cu:144 reads the one colour an object has). */
+int rtx_scene_set_patterns(rtx_ctx* ctx, size_t n, const rtx_pattern* patterns);
+/* The table in use: writes min(capacity, n) entries to out (which may be NULL when capacity is 0) and always *n_out = n. */
+int rtx_scene_get_patterns(const rtx_ctx* ctx, size_t capacity, rtx_pattern* out, size_t* n_out);
+int rtx_scene_set_object_pattern(rtx_ctx* ctx, unsigned first, size_t n, unsigned slot);
+/* The slot of object `index` (0: none).  No reference counterpart. */
+int rtx_scene_get_object_pattern(const rtx_ctx* ctx, unsigned index, unsigned* slot);
 /* Bulk append: n records of 7 floats (cx cy cz r R G B). */
 int rtx_scene_add_spheres(rtx_ctx* ctx, size_t n, const float* xyzr_rgb);
 unsigned rtx_scene_count(const rtx_ctx* ctx);

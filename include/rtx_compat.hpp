@@ -461,6 +461,16 @@ public:
         for (const unsigned i : m_planes) v[i - first] = k;
         check(rtx_scene_set_reflectivity(ctx(), first, v.size(), v.data()), "rtx_scene_set_reflectivity");
     }
+    // Extensions, no reference counterpart (RayTracing.cu:144 reads the one colour an object has): checker patterns.  The table of
+    // up to RTX_MAX_PATTERNS entries (rtx_scene_set_patterns; entry i serves slot i + 1), the slot of the object of creation index
+    // `index` (0: none), or of every plane this scene created (rtx_scene_set_object_pattern, a call per plane: the objects between
+    // them keep theirs).
+    void SetPatterns(const rtx_pattern* patterns, const size_t n) { check(rtx_scene_set_patterns(ctx(), n, patterns), "rtx_scene_set_patterns"); }
+    void SetPattern(const unsigned index, const unsigned slot) { check(rtx_scene_set_object_pattern(ctx(), index, 1, slot), "rtx_scene_set_object_pattern"); }
+    void SetPlanePattern(const unsigned slot)
+    {
+        for (const unsigned i : m_planes) check(rtx_scene_set_object_pattern(ctx(), i, 1, slot), "rtx_scene_set_object_pattern");
+    }
     // Mirrors that see mirrors: levels of secondary rays, 1 .. RTX_MAX_REFLECT_DEPTH (RTX_OPT_REFLECT_DEPTH).
     // No reference counterpart (RayTracing.cu:635).
     void SetReflectDepth(const int depth) { check(rtx_set_option(ctx(), RTX_OPT_REFLECT_DEPTH, depth), "RTX_OPT_REFLECT_DEPTH"); }

@@ -57,6 +57,8 @@ OPT_SUPERSAMPLE = 30           # S x S rays per console cell, folded on the GPU:
 STAT_SUPERSAMPLE_FRAMES = 100
 STAT_HALF_FRAMES = 99           # frames rtx_update_half has handed out (include/rtx.h)
 STAT_HALF_DELTA_FRAMES, STAT_HALF_DELTA_KEYFRAMES = 96, 95  # frames rtx_update_half_delta has handed out, and its key frames
+STAT_PATTERNED_OBJECTS, STAT_PATTERN_FRAMES = 94, 93  # objects with a pattern slot, and launch sets queued while there are some
+MAX_PATTERNS = 16
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
@@ -100,6 +102,11 @@ class Light(C.Structure):
                 ("specular_rgb", C.c_float * 3), ("specular_power", C.c_float)]
 
 
+class Pattern(C.Structure):
+    """struct rtx_pattern: one entry of the checker-pattern table (include/rtx.h, rtx_scene_set_patterns).  36 bytes."""
+    _fields_ = [("origin", C.c_float * 3), ("freq", C.c_float * 3), ("rgb", C.c_float * 3)]
+
+
 # struct rtx_ray (32 bytes) and struct rtx_ray_hit (8 bytes) as numpy structured types: what Context.query_rays takes and returns
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("skip", np.uint32)])
 RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.uint32)])
@@ -124,6 +131,11 @@ def make_rays(origins, directions, tmax=np.inf, skip=NO_OBJECT):
 def make_light(pos=(1.0, 50.0, 0.0), diffuse_rgb=(1.0, 1.0, 1.0), diffuse_power=2000.0, specular_rgb=(1.0, 1.0, 1.0), specular_power=3000.0):
     """A Light; the defaults are the reference's light."""
     return Light((C.c_float * 3)(*pos), (C.c_float * 3)(*diffuse_rgb), diffuse_power, (C.c_float * 3)(*specular_rgb), specular_power)
+
+
+def make_pattern(origin=(0.0, 0.0, 0.0), freq=(1.0, 0.0, 1.0), rgb=(0.0, 0.0, 0.0)):
+    """A Pattern; the defaults are a black one-unit checker for a floor."""
+    return Pattern((C.c_float * 3)(*origin), (C.c_float * 3)(*freq), (C.c_float * 3)(*rgb))
 
 
 # every symbol include/rtx.h declares: (name, restype, argtypes)
@@ -158,6 +170,10 @@ _SIGNATURES = [
     ("rtx_scene_get_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_reflectivity", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
     ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
+    ("rtx_scene_set_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern)]),
+    ("rtx_scene_get_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern), C.POINTER(C.c_size_t)]),
+    ("rtx_scene_set_object_pattern", C.c_int, [_P, C.c_uint, C.c_size_t, C.c_uint]),
+    ("rtx_scene_get_object_pattern", C.c_int, [_P, C.c_uint, C.POINTER(C.c_uint)]),
     ("rtx_render", C.c_int, [_P, C.POINTER(Params), C.c_int]),
     ("rtx_render_rows", C.c_int, [_P, C.POINTER(Params), C.c_int, C.c_size_t, C.c_size_t, _P, C.c_size_t, _P, C.c_uint]),
     ("rtx_submit_frames", C.c_int, [_P, C.c_size_t, C.POINTER(Params), C.c_int, C.POINTER(_P), C.POINTER(_P)]),
@@ -500,6 +516,35 @@ class Context:
     def get_reflectivity(self, index):
         out = C.c_float()
         self._check(lib().rtx_scene_get_reflectivity(self._h, index, C.byref(out)))
+        return out.value
+
+    def set_patterns(self, patterns):
+        """rtx_scene_set_patterns: the whole table, 0 .. MAX_PATTERNS Pattern values; entry i serves slot i + 1."""
+        patterns = list(patterns)
+        arr = (Pattern * max(len(patterns), 1))()
+        for i, p in enumerate(patterns):
+            C.memmove(C.byref(arr[i]), C.byref(p), C.sizeof(Pattern))
+        self._check(lib().rtx_scene_set_patterns(self._h, len(patterns), arr if patterns else None))
+
+    def get_patterns(self):
+        """rtx_scene_get_patterns: the table in use, as a list of Pattern."""
+        arr = (Pattern * MAX_PATTERNS)()
+        n = C.c_size_t()
+        self._check(lib().rtx_scene_get_patterns(self._h, MAX_PATTERNS, arr, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            p = Pattern()
+            C.memmove(C.byref(p), C.byref(arr[i]), C.sizeof(Pattern))
+            out.append(p)
+        return out
+
+    def set_object_pattern(self, first, slot, n=1):
+        """rtx_scene_set_object_pattern: slot (0: none) for objects first .. first+n-1 (creation indices)."""
+        self._check(lib().rtx_scene_set_object_pattern(self._h, first, n, slot))
+
+    def get_object_pattern(self, index):
+        out = C.c_uint()
+        self._check(lib().rtx_scene_get_object_pattern(self._h, index, C.byref(out)))
         return out.value
 
     # -- ray queries

@@ -289,6 +289,19 @@ struct rtx_ctx {
     bool refl_dirty = true;
     uint64_t refl_gen = 0;
     DeviceBuf<float> d_refl_sph, d_refl_sorted, d_refl_pl;
+    // checker patterns (rtx_scene_set_patterns, rtx_scene_set_object_pattern): the table (context state, like the lights), the slot
+    // of every object by creation index (with the objects, like refl) and how many objects have a slot above 0 -- while that is
+    // not 0 a frame that would be direct takes the light / shadow path, and every shade launch gets the device copies (PatternArgs).
+    // Those -- slots of the spheres by index and by sorted position, of the planes by index, and the packed table -- are uploaded
+    // with the reflectivities' (refl_dirty, upload_reflectivity); pat_gen tells recorded graphs they are stale.
+    rtx_pattern patterns[RTX_MAX_PATTERNS] = {};
+    size_t n_patterns = 0;
+    std::vector<uint8_t> pat_slot;
+    uint32_t n_patterned = 0;
+    uint64_t pat_gen = 0;
+    uint64_t stat_pattern_frames = 0;
+    DeviceBuf<uint8_t> d_pat_sph, d_pat_sorted, d_pat_pl;
+    DeviceBuf<rtxpattern::Entry> d_pat_table;
     std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
     int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;

@@ -513,6 +513,16 @@ int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float*
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_reflectivity(m, first, n, k); });
 }
 
+int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_patterns(m, n, patterns); });
+}
+
+int scene_set_object_pattern(rtx_ctx* root, unsigned first, size_t n, unsigned slot)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_object_pattern(m, first, n, slot); });
+}
+
 int scene_set_spheres(rtx_ctx* root, unsigned first, size_t n, const float* rows)
 {
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_spheres(m, first, n, rows); });

@@ -28,6 +28,8 @@ int scene_add_plane(rtx_ctx* root, const float pos[3], const float normal[3], co
 int scene_set_sphere_motion(rtx_ctx* root, unsigned index, int mover, float speed);
 int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights);
 int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k); // (the root has validated and applied it)
+int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns);        // (likewise, both)
+int scene_set_object_pattern(rtx_ctx* root, unsigned first, size_t n, unsigned slot);
 // edits in place (the root has validated the range and applied the edit to itself): the host form calls every member; the device
 // form copies the rows from the root's device into every other member's scratch, behind `after` (an event on the caller's stream),
 // and runs the kernel there -- logical ranks on the root's own GPU take the same path

@@ -7,6 +7,7 @@
 
 #include "rtx_grid.hpp"
 #include "rtx_lights.hpp"
+#include "rtx_pattern.hpp"
 #include "rtx_plan.hpp"
 
 // Kernel-side mode numbers = enum RenderingMode (RayTracingManager.h:21).
@@ -156,6 +157,15 @@ struct ReflectArgs {
     uint32_t* longest;   // atomicMax of the longest candidate list a workgroup held, or nullptr
 };
 
+// Checker patterns (rtx_scene_set_patterns), for the shade launches alone: the slot of every object and the table.  table ==
+// nullptr (no object has a slot): nothing is loaded and od is the object's.  The device copies travel with the reflectivities'.
+struct PatternArgs {
+    const uint8_t* slot_sph;          // slot of the spheres, by the position the trace kernels index them by (KArgs::sph_geom's order)
+    const uint8_t* slot_pl;           // ... of the planes, by plane index
+    const rtxpattern::Entry* table;   // entry s - 1 serves slot s
+    uint32_t n;                       // entries; a slot above it (none is stored) counts as 0
+};
+
 // Mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade
 // folds the chain.  The hit buffer holds depth + 1 hit arrays of px entries: level j's at ReflectArgs::hits + j * px (hits2 is
 // level 1's).  By value, so a recorded graph keeps its depth.
@@ -285,6 +295,7 @@ struct TileArgs {
     const GridShadowArgs* grid;    // rtx_grid_shadow (which takes reflect, chain and deep by value: zero-filled where there is none)
     const uint32_t* dark0;         // the grid families: GridShadowArgs::dark0
     const GridReflectArgs* grid_reflect; // rtx_grid_reflect
+    const PatternArgs* pattern;    // every shade family, by value (NULL: none, as a zero-filled one)
 };
 const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream, int* hip_error);
 const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const TileArgs* t, int mode, void* stream, int* hip_error);

@@ -745,23 +745,24 @@ extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const Til
     }();
     *hip_error = 0;
     if ((unsigned)family >= (unsigned)kShadeFamilies || !tile_args_ok(t, kFamilyTakes[family])) return nullptr;
+    const PatternArgs pa = t->pattern != nullptr ? *t->pattern : PatternArgs{nullptr, nullptr, nullptr, 0u};
     return launch_shade(t->a, mode, kNames[family], hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
         constexpr int M = decltype(m)::value, O = decltype(o)::value;
         hipStream_t st = (hipStream_t)stream_v;
         switch (family) {
-        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow); break;
-        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O>), grid, block, 0, st, *t->a, *t->lights); break;
-        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect); break;
-        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect); break;
-        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain); break;
+        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, pa); break;
+        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, pa); break;
+        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect, pa); break;
+        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, pa); break;
+        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, pa); break;
         case kLightsChainShadowShade:
-            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
+            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, pa);
             break;
-        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, t->dark0); break;
-        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0); break;
-        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0); break;
+        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, t->dark0, pa); break;
+        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0, pa); break;
+        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0, pa); break;
         default:
-            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0);
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0, pa);
             break;
         }
     });

@@ -18,8 +18,8 @@
 // constant word 0 (the compiler folds the mask away: rtx_lights_chain_shade's code is what it was), rtx_lights_chain_shadow_shade
 // the same body with the pixel's word.
 
-__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
-                                                      float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark)
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+                                                      const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark)
 {
     V3 local[kMaxReflectDepth + 1];
     float kk[kMaxReflectDepth];
@@ -46,7 +46,7 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
                 if (alive) {
                     t = __uint_as_float(h.x);
                     o = h.y;
-                    const Surface sf = surface_of(a, h.y, add(r.o, mulf(r.d, t)));
+                    const Surface sf = surface_of(a, pa, h.y, add(r.o, mulf(r.d, t)));
                     n = sf.normal;
                     local[j + 1] = shade_lights(r, t, n, sf.od, la.lights, (deep_dark >> (8 * j)) & 0xffu);
                 }
@@ -67,22 +67,22 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
     return C;
 }
 
-__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
-                                                 float distance, V3 normal, uint32_t id, V3 cl, size_t at)
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+                                                 const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at)
 {
-    return lights_chain_blend_dark(a, la, ra, ca, ray, distance, normal, id, cl, at, 0u);
+    return lights_chain_blend_dark(a, la, ra, ca, pa, ray, distance, normal, id, cl, at, 0u);
 }
 
 template <int MODE, int OUT>
-__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca)
+__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const PatternArgs pa)
 {
-    lights_shade_body<MODE, OUT, 2>(a, la, ra, ca);
+    lights_shade_body<MODE, OUT, 2>(a, la, ra, ca, pa);
 }
 
 // The chain's shade launch under RTX_OPT_REFLECT_SHADOWS: rtx_lights_chain_shade with the deeper levels' dark lights (cs.dark).
 template <int MODE, int OUT>
 __global__ __launch_bounds__(kThreads) void rtx_lights_chain_shadow_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca,
-                                                                          const ChainShadowArgs cs)
+                                                                          const ChainShadowArgs cs, const PatternArgs pa)
 {
-    lights_shade_body<MODE, OUT, 3>(a, la, ra, ca, cs.dark);
+    lights_shade_body<MODE, OUT, 3>(a, la, ra, ca, pa, cs.dark);
 }

@@ -61,10 +61,10 @@ __device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 norm
 
 // (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels; deep_dark: byte j - 1 the lights
 // level j is shadowed from)
-__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
-                                                      float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark);
-__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const Ray& ray,
-                                                 float distance, V3 normal, uint32_t id, V3 cl, size_t at);
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+                                                      const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark);
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+                                                 const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at);
 
 // What the shade family of the grid path keeps of LightsShared (RTX_OPT_SHADOW_GRID, rtx_grid_shadow_kernels.inc): the encoder's tables.
 struct ShadeTablesShared {
@@ -78,7 +78,7 @@ struct ShadeTablesShared {
 // hits: rtx_grid_shadow's output) instead of computed here -- no cone, no walk, no list in LDS.  What a value does not use is not
 // compiled.
 template <int MODE, int OUT, int REFLECT, bool DARK0 = false>
-__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca,
+__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                   const uint32_t* deep_dark = nullptr, const uint32_t* dark0 = nullptr)
 {
     __shared__ std::conditional_t<DARK0, ShadeTablesShared, LightsShared> s;
@@ -105,7 +105,7 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
     V3 normal = ray.d, colour = ray.d, od = ray.d;
     if (any_hit) {
         distance = __uint_as_float(px.hit.x);
-        const Surface sf = surface_of(a, id, add(ray.o, mulf(ray.d, distance)));
+        const Surface sf = surface_of(a, pa, id, add(ray.o, mulf(ray.d, distance)));
         normal = sf.normal;
         od = sf.od;
         shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // RayTracing.cu:133
@@ -127,30 +127,30 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
         colour = shade_lights(ray, distance, normal, od, la.lights, dark);
         if constexpr (REFLECT == 1) {
             if (distance <= cam.far) {
-                colour = reflect_blend(a, ra, ray, distance, normal, id, colour, px.at(a),
+                colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a),
                                        [&](const Ray& r2, float t2, V3 n2, V3 od2) { return shade_lights(r2, t2, n2, od2, la.lights, 0u); });
             }
         } else if constexpr (REFLECT == 2) {
-            if (distance <= cam.far) colour = lights_chain_blend(a, la, ra, ca, ray, distance, normal, id, colour, px.at(a));
+            if (distance <= cam.far) colour = lights_chain_blend(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a));
         } else if constexpr (REFLECT == 3) {
-            if (distance <= cam.far) colour = lights_chain_blend_dark(a, la, ra, ca, ray, distance, normal, id, colour, px.at(a), deep_dark[px.at(a)]);
+            if (distance <= cam.far) colour = lights_chain_blend_dark(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a), deep_dark[px.at(a)]);
         }
     }
     encode_and_store<MODE, OUT>(a, cam, s.digits, s.ramp, px.in_frame, px.newline_col, px.row, px.col, distance, normal, colour, shadingValue);
 }
 
 template <int MODE, int OUT>
-__global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgs la)
+__global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgs la, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
     const ChainArgs ca = {};
-    lights_shade_body<MODE, OUT, 0>(a, la, ra, ca);
+    lights_shade_body<MODE, OUT, 0>(a, la, ra, ca, pa);
 }
 
 // The mirror path's third launch for a set of several lights: rtx_lights_shade's shading, then the blend.
 template <int MODE, int OUT>
-__global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra)
+__global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const PatternArgs pa)
 {
     const ChainArgs ca = {}; // (read only by the chain's blend, which is not compiled here)
-    lights_shade_body<MODE, OUT, 1>(a, la, ra, ca);
+    lights_shade_body<MODE, OUT, 1>(a, la, ra, ca, pa);
 }

@@ -987,6 +987,24 @@ inline RemovalPlan plan_removal(const std::vector<uint8_t>& kind_of, const std::
     return p;
 }
 
+// What is kept per object by creation index beside kind_of / local_of (reflectivities, pattern slots) after the removal: the
+// survivors' values in their order, which is the order of RemovalPlan::kind_of.
+template <class T>
+inline std::vector<T> survivors_of(const std::vector<T>& per_object, const std::vector<uint32_t>& ascending)
+{
+    std::vector<T> kept;
+    kept.reserve(per_object.size() - std::min(per_object.size(), ascending.size()));
+    size_t next = 0;
+    for (size_t i = 0; i < per_object.size(); i++) {
+        if (next < ascending.size() && ascending[next] == i) {
+            next++;
+            continue;
+        }
+        kept.push_back(per_object[i]);
+    }
+    return kept;
+}
+
 // ------------------------------------------------------------------------------------------------ row partition of a device group
 
 // Rank r of n traces rows [H r / n, H (r + 1) / n) of a frame of H rows (sharding.row_bounds states the same
@@ -1028,6 +1046,8 @@ inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n,
 //   mirror, chain       depth + 1  rtx_reflect_chain  grid: rtx_grid_shadow (deep = deep), else    rtx_grid_chain[_shadow]_shade / rtx_lights_chain[_shadow]_shade
 //                                                     deep: rtx_chain_shadow                       (_shadow: deep)
 //   mirror, RTX_OPT_REFLECT_GRID in effect: the secondary pass of either row is rtx_grid_reflect; nothing else of the row changes
+//   checker patterns (n_patterned != 0): a frame that would be direct takes the `shaded` row; nothing of any row changes -- the
+//   shade launches read the slots and the table (PatternArgs, rtx_kernels.h)
 //
 // The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
 // deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
@@ -1068,6 +1088,7 @@ struct ShadingRequest { // what the decision reads of the call, the options and 
     bool reflect_grid = false;       // RTX_OPT_REFLECT_GRID
     uint32_t ns = 0;
     bool grid_usable = false;        // the world grid was built and can be walked; known only after its build (shading_wants_grid)
+    uint32_t n_patterned = 0;        // objects with a pattern slot above 0 (rtx_scene_set_object_pattern)
 };
 
 struct ShadingPlan {
@@ -1093,6 +1114,7 @@ inline ShadePath shading_path(const ShadingRequest& q)
     if (q.mode < kShadedModeLo || q.mode > kShadedModeHi) return kPathDirect;
     if (q.n_reflective != 0 || q.reflect_check == 2) return kPathMirror; // (takes precedence, and runs the shadow test itself)
     if (q.shadows || q.n_lights != 1 || q.lights_check || !q.light0_is_reference) return kPathShaded;
+    if (q.n_patterned != 0) return kPathShaded; // (a pattern is read by the shade launches alone: it adds no pass and no bytes)
     return kPathDirect; // the state the reference has: every launch is the reference's
 }
 

@@ -360,8 +360,14 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
     }
     ctx->refl.swap(refl);
     ctx->n_reflective = n_reflective; // (0: the mirror path is simply not taken any more)
+    // the pattern slots move with the survivors, as the reflectivities do
+    std::vector<uint8_t> slots = rtxplan::survivors_of(ctx->pat_slot, ascending);
+    ctx->pat_slot.swap(slots);
+    ctx->n_patterned = 0;
+    for (const uint8_t s : ctx->pat_slot) ctx->n_patterned += s != 0 ? 1u : 0u;
     ctx->refl_dirty = true;
     ctx->refl_gen++;
+    ctx->pat_gen++;
     if (ctx->h_centres.size() == ctx->ns) {
         // the sort's input at the next re-sort, by sphere index
         size_t kept = 0, gone = 0;

@@ -65,6 +65,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.shadow_grid = ctx->opt_shadow_grid != 0;
     q.reflect_grid = ctx->opt_reflect_grid != 0;
     q.ns = ctx->ns;
+    q.n_patterned = ctx->n_patterned;
     return q;
 }
 
@@ -633,6 +634,23 @@ int upload_reflectivity(rtx_ctx* ctx)
     }
     RTX_HIP(ctx, ctx->d_refl_pos.reserve(pos.size(), rtxmem::nothing()));
     RTX_HIP(ctx, hipMemcpy(ctx->d_refl_pos.get(), pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    // the pattern slots in the same three orders, and the packed table (rtx_pattern.hpp): always all kMaxPatterns entries
+    std::vector<uint8_t> ss(ks.size(), 0), sso(ks.size(), 0), sp(kp.size(), 0);
+    for (size_t g = 0; g < ctx->pat_slot.size(); g++) {
+        (ctx->kind_of[g] == 2 ? ss : sp)[ctx->local_of[g]] = ctx->pat_slot[g];
+    }
+    for (size_t p = 0; sorted && p < ns; p++) sso[p] = ss[ctx->h_sorted_idx[p]];
+    for (const auto& pr : {std::make_pair(&ctx->d_pat_sph, &ss), std::make_pair(&ctx->d_pat_sorted, &sso), std::make_pair(&ctx->d_pat_pl, &sp)}) {
+        DeviceBuf<uint8_t>& d = *pr.first;
+        const std::vector<uint8_t>& h = *pr.second;
+        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing()));
+        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size(), hipMemcpyHostToDevice));
+    }
+    rtxpattern::Entry table[rtxpattern::kMaxPatterns];
+    std::memset(table, 0, sizeof table);
+    for (size_t i = 0; i < ctx->n_patterns; i++) table[i] = rtxpattern::pack_entry(ctx->patterns[i]);
+    RTX_HIP(ctx, ctx->d_pat_table.reserve(rtxpattern::kMaxPatterns, rtxmem::nothing()));
+    RTX_HIP(ctx, hipMemcpy(ctx->d_pat_table.get(), table, sizeof table, hipMemcpyHostToDevice));
     ctx->refl_dirty = false;
     return RTX_OK;
 }
@@ -646,9 +664,11 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ShadingRequest req = shading_request(ctx, mode);
     const bool mirror = shading_path(req) == kPathMirror;
     if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
-    if (mirror && ctx->refl_dirty) {
+    const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
+    if ((mirror || patterned) && ctx->refl_dirty) {
         if (capturing) {
-            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: the reflectivities are not uploaded yet (render once before capturing)");
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
+                                                                  : "graph capture: the pattern slots are not uploaded yet (render once before capturing)");
         }
         if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
     }
@@ -693,7 +713,9 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ChainArgs ca;
     ChainShadowArgs cs;
     GridReflectArgs gr;
+    PatternArgs pa;
     TileArgs t;
+    std::memset(&pa, 0, sizeof pa);
     std::memset(&ra, 0, sizeof ra);
     std::memset(&ca, 0, sizeof ca);
     std::memset(&cs, 0, sizeof cs);
@@ -702,6 +724,13 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     t.reflect = &ra;
     t.chain = &ca;
     t.deep = &cs;
+    t.pattern = &pa;
+    if (patterned) {
+        pa.slot_sph = a.sph_sorted_idx != nullptr ? ctx->d_pat_sorted.get() : ctx->d_pat_sph.get();
+        pa.slot_pl = ctx->d_pat_pl.get();
+        pa.table = ctx->d_pat_table.get();
+        pa.n = (uint32_t)ctx->n_patterns;
+    }
     if (shade_takes_light_set(plan.family)) {
         la = lights_args(ctx, hits);
         t.lights = &la;
@@ -772,6 +801,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     if (plan.grid_reflect()) ctx->stat_reflect_grid_frames++;
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
+    if (patterned) ctx->stat_pattern_frames++;
     return RTX_OK;
 }
 
@@ -1396,6 +1426,7 @@ struct rtx_graph_handle {
     hipGraphExec_t exec = nullptr;
     uint64_t scene_gen = 0;
     uint64_t refl_gen = 0; // ... and the reflectivities (the mirror path's launches read their device copies)
+    uint64_t pat_gen = 0;  // ... and the pattern table and slots (a change alters which launches make a frame and what they read)
     std::vector<uint64_t> frozen; // dispatch-order sets its launches read (released by rtx_graph_destroy)
 };
 
@@ -1430,6 +1461,7 @@ int rtx_graph_end(rtx_ctx* ctx, void* stream_v, void** graph_out)
     h->exec = exec;
     h->scene_gen = ctx->scene_gen;
     h->refl_gen = ctx->refl_gen;
+    h->pat_gen = ctx->pat_gen;
     h->frozen.swap(frozen);
     *graph_out = h;
     return RTX_OK;
@@ -1446,6 +1478,10 @@ int rtx_graph_launch(rtx_ctx* ctx, void* graph, void* stream_v)
     if (h->refl_gen != ctx->refl_gen) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the reflectivities changed after this graph was recorded (its launches read "
                                                        "the device copies, which the next launch replaces): re-capture");
+    }
+    if (h->pat_gen != ctx->pat_gen) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the pattern table or the objects' slots changed after this graph was recorded (its "
+                                                       "launches read the device copies, which the next launch replaces): re-capture");
     }
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     RTX_HIP(ctx, hipGraphLaunch(h->exec, stream_v ? (hipStream_t)stream_v : ctx->stream));

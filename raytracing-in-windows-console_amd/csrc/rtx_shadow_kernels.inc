@@ -14,7 +14,7 @@
 // With REFLECT (the mirror path's third launch) each reflective pixel's secondary hit (ra.hits2) is shaded and blended into the
 // colour before it is encoded (reflect_blend); without, nothing of it is compiled.
 template <int MODE, int OUT, bool REFLECT>
-__device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa, const ReflectArgs& ra)
+__device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa, const ReflectArgs& ra, const PatternArgs& pa)
 {
     __shared__ float4 s_occ[kTileList];
     __shared__ uint32_t s_occ_pos[kTileList];
@@ -43,7 +43,7 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
     V3 normal = ray.d, colour = ray.d, od = ray.d;
     if (any_hit) {
         distance = __uint_as_float(px.hit.x);
-        const Surface s = surface_of(a, id, add(ray.o, mulf(ray.d, distance)));
+        const Surface s = surface_of(a, pa, id, add(ray.o, mulf(ray.d, distance)));
         normal = s.normal;
         od = s.od;
         shadingValue = normal.x * 1.0f + normal.y * 0.0f + normal.z * 0.0f; // RayTracing.cu:133
@@ -87,7 +87,7 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
         colour = shade_light(ray, distance, normal, od, sa.light, shadowed ? 0.0f : sa.light.dpow, shadowed ? 0.0f : sa.light.spow);
         if constexpr (REFLECT) {
             if (distance <= cam.far) {
-                colour = reflect_blend(a, ra, ray, distance, normal, id, colour, px.at(a), [&](const Ray& r2, float t2, V3 n2, V3 od2) {
+                colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a), [&](const Ray& r2, float t2, V3 n2, V3 od2) {
                     return shade_light(r2, t2, n2, od2, sa.light, sa.light.dpow, sa.light.spow);
                 });
             }
@@ -97,15 +97,15 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
 }
 
 template <int MODE, int OUT>
-__global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, const ShadowArgs sa)
+__global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, const ShadowArgs sa, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
-    shade_body<MODE, OUT, false>(a, sa, ra);
+    shade_body<MODE, OUT, false>(a, sa, ra, pa);
 }
 
 // The mirror path's third launch: rtx_shadow_shade's shading, then the blend.
 template <int MODE, int OUT>
-__global__ __launch_bounds__(kThreads) void rtx_reflect_shade(const KArgs a, const ShadowArgs sa, const ReflectArgs ra)
+__global__ __launch_bounds__(kThreads) void rtx_reflect_shade(const KArgs a, const ShadowArgs sa, const ReflectArgs ra, const PatternArgs pa)
 {
-    shade_body<MODE, OUT, true>(a, sa, ra);
+    shade_body<MODE, OUT, true>(a, sa, ra, pa);
 }

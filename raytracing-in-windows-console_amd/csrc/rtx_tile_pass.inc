@@ -81,6 +81,23 @@ __device__ __forceinline__ Surface surface_of(const KArgs& a, uint32_t id, V3 P)
     return s;
 }
 
+// The same for the shade launches, with the checker pattern of the object (rtx_scene_set_patterns, the rule in rtx_pattern.hpp)
+// applied to od: after everything above, and feeding od alone.  One byte per shaded lane, by the index the od load used; then, for
+// the lanes of a patterned object, 48 bytes of a table of at most 768 that stays in cache.  No table: no load and no arithmetic.
+__device__ __forceinline__ Surface surface_of(const KArgs& a, const PatternArgs& pa, uint32_t id, V3 P)
+{
+    Surface s = surface_of(a, id, P);
+    if (pa.table != nullptr) { // (a kernel argument: uniform)
+        const uint32_t slot = (id & 0x80000000u) ? pa.slot_pl[id & 0x7fffffffu] : pa.slot_sph[id];
+        if (slot != 0u && slot <= pa.n) {
+            const rtxpattern::Entry e = pa.table[slot - 1u];
+            const float Pf[3] = {P.x, P.y, P.z};
+            if (rtxpattern::pattern_odd(Pf, e)) s.od = v3(e.od2.x, e.od2.y, e.od2.z);
+        }
+    }
+    return s;
+}
+
 // ---------------------------------------------------------------- the walk over the scene's spheres
 
 // The scene is walked 512 spheres a step: two coalesced loads per thread, the next step's requested ahead.  keep(in0, c0, in1,
@@ -513,8 +530,8 @@ struct MayMeetBundles {
 // od) -- the light or lights at full powers, no shadow test there (the chain's launches have one: RTX_OPT_REFLECT_SHADOWS), no
 // further bounce; black without a hit -- and blended with the local colour cl.  Pixels whose winner does not reflect keep cl.
 template <class Shade>
-__device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& ra, const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at,
-                                            Shade shade)
+__device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& ra, const PatternArgs& pa, const Ray& ray, float distance, V3 normal, uint32_t id,
+                                            V3 cl, size_t at, Shade shade)
 {
     const float k = reflectivity_of(ra, id);
     if (!(k > 0.0f)) return cl;
@@ -523,7 +540,7 @@ __device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& r
     V3 cr = v3(0.0f, 0.0f, 0.0f);
     if (h.y != 0xffffffffu) {
         const float t2 = __uint_as_float(h.x);
-        const Surface s2 = surface_of(a, h.y, add(r2.o, mulf(r2.d, t2)));
+        const Surface s2 = surface_of(a, pa, h.y, add(r2.o, mulf(r2.d, t2)));
         cr = shade(r2, t2, s2.normal, s2.od);
     }
     const float w = 1.0f - k;
