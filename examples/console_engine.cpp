@@ -12,6 +12,8 @@
 // two PIXEL modes (--mode 1 or 3).
 // --half --delta: half blocks of which, after the first frame, only the cells whose two colours changed are sent, each run behind a
 // cursor escape (RayTracingManager::SetHalfDeltaFrames, rtx_update_half_delta; no reference counterpart).
+// --glass: the mirror key (see below) then also gives every other sphere k = 0.85 and an index of refraction of 1.5
+// (Scene3D::SetRefraction, rtx_scene_set_refraction; no reference counterpart): glass balls over the floor.
 // --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
 // no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
@@ -153,7 +155,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -168,13 +170,14 @@ int main(int argc, char** argv)
         else if (a == "--delta") delta = true; // send only the cells that changed (RayTracingManager::SetDeltaFrames)
         else if (a == "--half") half = true; // W x 2H pixels as half blocks (RayTracingManager::SetHalfBlocks)
         else if (a == "--checker") checker = true; // a two-axis checker on the floor plane (Scene3D::SetPatterns, SetPlanePattern)
+        else if (a == "--glass") glass = true; // the mirror key also turns every other sphere into glass (Scene3D::SetRefraction)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -271,6 +274,18 @@ int main(int argc, char** argv)
                 case K_MIRRORS:
                     mirrors = !mirrors;
                     scene->SetPlaneReflectivity(mirrors ? 0.5f : 0.0f);
+                    if (glass) {
+                        // every other sphere of the scene as it is now: k = 0.85 of what is seen through it, ior = 1.5
+                        rtx_ctx* const c = rtx_compat::Device::get(PrintMachine::GetWidth(), PrintMachine::GetHeight());
+                        unsigned nth = 0;
+                        for (unsigned i = 0; i < rtx_scene_count(c); i++) {
+                            int type = 0;
+                            float row[11];
+                            if (rtx_scene_get_object(c, i, &type, row) != RTX_OK || type != 2 || nth++ % 2u != 0u) continue;
+                            scene->SetReflectivity(i, mirrors ? 0.85f : 0.0f);
+                            scene->SetRefraction(i, mirrors ? 1.5f : 0.0f);
+                        }
+                    }
                     break;
                 case K_BOUNCES:
                     bounces = bounces % RTX_MAX_REFLECT_DEPTH + 1;

@@ -412,6 +412,10 @@ enum rtx_stat {
                                      * counters: 95 .. 154 are taken.)  No reference counterpart (RayTracing.cu:144) */
     RTX_STAT_PATTERN_FRAMES = 93,   /* launch sets queued while that count is not 0: counted as RTX_STAT_SHADOW_FRAMES counts, on whichever
                                      * of the two paths the frame takes.  No reference counterpart (RayTracing.cu:144) */
+    RTX_STAT_REFRACTIVE_OBJECTS = 92, /* objects with ior > 0 (rtx_scene_set_refraction).  (Numbered below the other counters: 93 .. 154
+                                     * are taken.)  No reference counterpart (RayTracing.cu:635) */
+    RTX_STAT_REFRACT_FRAMES = 91,   /* launch sets queued on the mirror path while that count is not 0: counted as RTX_STAT_SHADOW_FRAMES
+                                     * counts.  No reference counterpart (RayTracing.cu:635) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -572,6 +576,47 @@ int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, si
 int rtx_scene_set_reflectivity(rtx_ctx* ctx, unsigned first, size_t n, const float* k);
 /* The reflectivity of object `index`.  No reference counterpart. */
 int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);
+/* Glass: the index of refraction ior of objects first .. first+n-1 (creation indices, spheres and planes alike).  It belongs to an
+ * object as k does: every new object has ior = 0, which means mirror -- today's behaviour; rtx_scene_clear forgets the values,
+ * rtx_scene_set_spheres and rtx_scene_set_plane keep them, and after rtx_scene_remove_objects the survivors keep theirs under the
+ * renumbering rule.  Accepted: 0, or a finite value in [1, 4].  All or nothing: a NaN, a value in (0, 1), a value above 4, a
+ * negative value, a range past rtx_scene_count or ior == NULL with n > 0 changes nothing and returns RTX_ERR_INVALID_ARGUMENT (on a
+ * device group: validated before any rank is touched, then applied to every rank).  ior only matters where k > 0: an object with
+ * k = 0 has no chain.  While no object has ior > 0 every launch is what it is without this call, and the mirror path's kernels
+ * load nothing more.  Geometry is unchanged, so sorted copies, cell lists and the world grid stay valid; a graph recorded before
+ * a change is refused by rtx_graph_launch (re-capture).  The device copies are uploaded with the reflectivities', in the same three
+ * orders, at the cost of the one device wait stated at rtx_scene_set_reflectivity; recording right after a change fails with
+ * RTX_ERR_INVALID_ARGUMENT ("render once before capturing").  No new option and no new launch: RTX_OPT_REFLECT_DEPTH,
+ * RTX_OPT_REFLECT_SHADOWS, RTX_OPT_REFLECT_GRID, RTX_OPT_SHADOW_GRID, light sets, patterns, supersampling, half blocks, delta
+ * frames and device groups apply as they do to mirrors.
+ * The rule.  In the rule of rtx_scene_set_reflectivity one sentence gains a second case: how r_{j+1} is formed from r_j, its hit
+ * (t_j, o_j) and normal_j.  With ior(o_j) = 0 it is the mirror ray, bit for bit.  Otherwise take P = r_j.o + r_j.d * t_j,
+ * N = normalize(normal_j) and V = normalize(-r_j.d) (the library's normalize, exactly as the mirror ray forms them), with
+ * dot(a, b) = (a_x b_x + a_y b_y) + a_z b_z, every operation rounded to fp32, nothing reassociated, no contraction.
+ * o_j a sphere of radius r (the stored float), q = x, y, z:
+ *   ci  = dot(N, V)
+ *   eta = 1.0f / ior
+ *   s2  = (eta * eta) * (1.0f - ci * ci)
+ *   c2  = 1.0f - s2
+ *   ct  = sqrtf(c2 > 0.0f ? c2 : 0.0f)               a NaN c2 gives ct = 0
+ *   g   = eta * ci - ct
+ *   T_q = N_q * g - V_q * eta                        the unit direction inside
+ *   L   = (2.0f * r) * ct                            the chord
+ *   o_q = P_q + T_q * L                              the exit point
+ *   m   = 2.0f * dot(T, V)
+ *   d_q = V_q - T_q * m                              the exit direction
+ * with the root and the division correctly rounded.  The exit direction comes from symmetry: reflecting the path in the plane
+ * through the centre perpendicular to T maps it onto its own reverse, so there is no second Snell step and no intersection
+ * test; with ior >= 1 total internal reflection cannot occur.  o_j a plane (a thin sheet): o = P, d = r_j.d.  In both cases
+ * a = dot(d, d), fourA = 4a and divTwoA = 1/(2a), as the mirror ray forms them.  The ray is tested against every object but
+ * o_j, exactly as the mirror ray is.  Everything else is unchanged: the existence rule k(o_j) > 0, the fold, the shadow tests at
+ * P_j, distance, glyph and normal of the pixel.  As code, once: csrc/rtx_refract.hpp.
+ * Out of scope: Fresnel weighting; an object that both mirrors and transmits (a ray tree); anything inside a glass sphere (the
+ * interior is treated as empty); attenuated or coloured shadows (glass occludes like any object); a slab of finite thickness;
+ * ior < 1.  No reference counterpart (RayTracing.cu:635 plans a recursive RayTrace). */
+int rtx_scene_set_refraction(rtx_ctx* ctx, unsigned first, size_t n, const float* ior);
+/* The index of refraction of object `index` (0: a mirror).  No reference counterpart. */
+int rtx_scene_get_refraction(const rtx_ctx* ctx, unsigned index, float* ior);
 /* Checker patterns: a second colour per object, chosen by the parity of the lattice cell the hit point lies in.  The table holds
  * up to RTX_MAX_PATTERNS entries, slots 1 .. n; an object carries a slot (0: none, what every new object has).  36 bytes. */
 #define RTX_MAX_PATTERNS 16

@@ -461,6 +461,9 @@ public:
         for (const unsigned i : m_planes) v[i - first] = k;
         check(rtx_scene_set_reflectivity(ctx(), first, v.size(), v.data()), "rtx_scene_set_reflectivity");
     }
+    // Extension, no reference counterpart (RayTracing.cu:635): glass.  The index of refraction of the object of creation index `index`
+    // (rtx_scene_set_refraction: 0 a mirror, else in [1, 4]); it shows where the object's reflectivity is above 0.
+    void SetRefraction(const unsigned index, const float ior) { check(rtx_scene_set_refraction(ctx(), index, 1, &ior), "rtx_scene_set_refraction"); }
     // Extensions, no reference counterpart (RayTracing.cu:144 reads the one colour an object has): checker patterns.  The table of
     // up to RTX_MAX_PATTERNS entries (rtx_scene_set_patterns; entry i serves slot i + 1), the slot of the object of creation index
     // `index` (0: none), or of every plane this scene created (rtx_scene_set_object_pattern, a call per plane: the objects between

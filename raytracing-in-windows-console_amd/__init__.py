@@ -59,6 +59,7 @@ STAT_HALF_FRAMES = 99           # frames rtx_update_half has handed out (include
 STAT_HALF_DELTA_FRAMES, STAT_HALF_DELTA_KEYFRAMES = 96, 95  # frames rtx_update_half_delta has handed out, and its key frames
 STAT_PATTERNED_OBJECTS, STAT_PATTERN_FRAMES = 94, 93  # objects with a pattern slot, and launch sets queued while there are some
 MAX_PATTERNS = 16
+STAT_REFRACTIVE_OBJECTS, STAT_REFRACT_FRAMES = 92, 91  # objects with ior > 0, and launch sets queued on the mirror path while there are some
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
@@ -170,6 +171,8 @@ _SIGNATURES = [
     ("rtx_scene_get_lights", C.c_int, [_P, C.c_size_t, C.POINTER(Light), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_reflectivity", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
     ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
+    ("rtx_scene_set_refraction", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
+    ("rtx_scene_get_refraction", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
     ("rtx_scene_set_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern)]),
     ("rtx_scene_get_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_object_pattern", C.c_int, [_P, C.c_uint, C.c_size_t, C.c_uint]),
@@ -516,6 +519,16 @@ class Context:
     def get_reflectivity(self, index):
         out = C.c_float()
         self._check(lib().rtx_scene_get_reflectivity(self._h, index, C.byref(out)))
+        return out.value
+
+    def set_refraction(self, first, ior):
+        """rtx_scene_set_refraction: ior (a number or a sequence; 0: a mirror, else in [1, 4]) for objects first, first+1, ..."""
+        v = np.ascontiguousarray(np.atleast_1d(np.asarray(ior, dtype=np.float32)))
+        self._check(lib().rtx_scene_set_refraction(self._h, first, v.size, v.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def get_refraction(self, index):
+        out = C.c_float()
+        self._check(lib().rtx_scene_get_refraction(self._h, index, C.byref(out)))
         return out.value
 
     def set_patterns(self, patterns):

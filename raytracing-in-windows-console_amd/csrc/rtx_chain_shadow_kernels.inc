@@ -4,7 +4,7 @@
 //
 // Level j (1 .. depth) of a pixel's chain that hit an object o_j has the hit point P_j = r_j.o + r_j.d * t_j (as shade_lights
 // forms `point`) and the normal n_j = surface_of(o_j, P_j).  Every thread walks its pixel's chain forward from the hits
-// rtx_reflect_chain stored (level j at ra.hits + j * ca.px) exactly as lights_chain_blend does -- reflectivity_of, mirror_ray,
+// rtx_reflect_chain stored (level j at ra.hits + j * ca.px) exactly as lights_chain_blend does -- reflectivity_of, secondary_ray,
 // surface_of, the same operations on the same bits, so P_j and n_j are the shade launch's -- and per level the workgroup runs
 // level 0's shadow test (lights_dark_set: per light self-shadow, planes and the cone over the tile's pending level-j points, one
 // walk of the scene for all lights with 8-bit light masks, segment tests at each flush) with P_j, n_j, o_j and no far limit.  The
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kThreads, RTX_CHAIN_SHADOW_WAVES) void rtx_chain_sh
         if (alive) {
             alive = reflectivity_of(ra, o) > 0.0f;
             if (alive) {
-                r = mirror_ray(r, t, n);
+                r = secondary_ray(a, ra, r, t, n, o);
                 const uint2 h = ra.hits[(size_t)(j + 1u) * ca.px + at];
                 alive = h.y != 0xffffffffu;
                 if (alive) {

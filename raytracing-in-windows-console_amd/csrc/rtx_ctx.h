@@ -302,6 +302,15 @@ struct rtx_ctx {
     uint64_t stat_pattern_frames = 0;
     DeviceBuf<uint8_t> d_pat_sph, d_pat_sorted, d_pat_pl;
     DeviceBuf<rtxpattern::Entry> d_pat_table;
+    // glass (rtx_scene_set_refraction): the index of refraction of every object by creation index (with the objects, like refl;
+    // 0: a mirror) and how many are above 0 -- while that is not 0 the mirror path's launches get the device copies
+    // (ReflectArgs::ior_sph / ior_pl), uploaded with the reflectivities' in their three orders; ior_gen tells recorded graphs they
+    // are stale.
+    std::vector<float> ior;
+    uint32_t n_refractive = 0;
+    uint64_t ior_gen = 0;
+    uint64_t stat_refract_frames = 0;
+    DeviceBuf<float> d_ior_sph, d_ior_sorted, d_ior_pl;
     std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
     int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;

@@ -4,7 +4,7 @@
 // rtx_grid_reflect: one instantiation, in place of rtx_reflect_hit and rtx_reflect_chain.  A 256-thread workgroup owns a 16 x 16
 // tile as the other tile passes do, so that neighbouring pixels walk neighbouring cells, but there is no list in LDS and no
 // barrier: every pixel is on its own.  Level 0 is set up exactly as rtx_reflect_chain does it (tile_pixel, the chain condition,
-// reflectivity_of, surface_of, mirror_ray: the same operations on the same bits), then the level loop runs with the ray, the
+// reflectivity_of, surface_of, secondary_ray: the same operations on the same bits), then the level loop runs with the ray, the
 // object left and the pending flag in registers.  A level is closest_of_planes unchanged, then secondary_sphere_hit against the
 // spheres of the grid's large list, then against the lists of the cells the ray's walk visits (rtx_grid.hpp: walk_start /
 // walk_step with tmax = infinity), stopping when the best t is below t_out of the cell just tested or the ray leaves the grid,
@@ -39,7 +39,11 @@
 #else
 #define RTX_GRID_REFLECT_BOUNDS __launch_bounds__(kThreads)
 #endif
-__global__ RTX_GRID_REFLECT_BOUNDS void rtx_grid_reflect(const KArgs a, const ReflectArgs ra, const ChainArgs ca, const GridReflectArgs gr)
+// GLASS: some object is refractive (ra.ior_sph is not null).  The kernel tests that once, outside the level loop, and runs one of two
+// copies of the body: without glass the parent's instructions, with the rays formed by mirror_ray alone (measured: with the test
+// inside the loop the frames without a refractive object were 4-5 % longer, profiles/r33_glass_cost.txt).
+template <bool GLASS>
+__device__ __forceinline__ void grid_reflect_body(const KArgs& a, const ReflectArgs& ra, const ChainArgs& ca, const GridReflectArgs& gr)
 {
     constexpr uint32_t kNone = 0xffffffffu;
     const uint32_t tid = threadIdx.x;
@@ -56,7 +60,7 @@ __global__ RTX_GRID_REFLECT_BOUNDS void rtx_grid_reflect(const KArgs a, const Re
     const bool chain = pending; // the pixel has a chain: every level up to the depth gets an entry
     V3 normal = ray.d;
     if (pending) normal = surface_of(a, hit.y, add(ray.o, mulf(ray.d, __uint_as_float(hit.x)))).normal;
-    Ray cur = mirror_ray(ray, pending ? __uint_as_float(hit.x) : 0.0f, normal); // the ray of the level being traced
+    Ray cur = secondary_ray<GLASS>(a, ra, ray, pending ? __uint_as_float(hit.x) : 0.0f, normal, hit.y); // the ray of the level being traced
     uint32_t id = hit.y;                                                          // the object it leaves, by position ...
     uint32_t own = kNone;                                                         // ... and by creation index
     if (pending) own = creation_index(a, id);
@@ -147,7 +151,7 @@ __global__ RTX_GRID_REFLECT_BOUNDS void rtx_grid_reflect(const KArgs a, const Re
         if (__ballot(next) != 0ull) {
             V3 n = cur.d;
             if (next) n = surface_of(a, bid, add(cur.o, mulf(cur.d, bt))).normal;
-            cur = mirror_ray(cur, next ? bt : 0.0f, n);
+            cur = secondary_ray<GLASS>(a, ra, cur, next ? bt : 0.0f, n, bid);
         }
         id = bid;
         own = bg;
@@ -163,4 +167,13 @@ __global__ RTX_GRID_REFLECT_BOUNDS void rtx_grid_reflect(const KArgs a, const Re
 #pragma unroll
     for (int k = 32; k >= 1; k >>= 1) n_fallback += (uint32_t)__shfl_xor((int)n_fallback, k);
     if (lane == 0u && n_fallback != 0u) atomicAdd(gr.fallback, n_fallback);
+}
+
+__global__ RTX_GRID_REFLECT_BOUNDS void rtx_grid_reflect(const KArgs a, const ReflectArgs ra, const ChainArgs ca, const GridReflectArgs gr)
+{
+    if (ra.ior_sph != nullptr) { // (a kernel argument: uniform)
+        grid_reflect_body<true>(a, ra, ca, gr);
+    } else {
+        grid_reflect_body<false>(a, ra, ca, gr);
+    }
 }

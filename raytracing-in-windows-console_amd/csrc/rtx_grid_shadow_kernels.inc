@@ -5,7 +5,7 @@
 // rtx_grid_shadow: one instantiation, nothing shaded or encoded.  A 256-thread workgroup owns a 16 x 16 tile as the other tile
 // passes do, so that neighbouring pixels walk neighbouring cells, but there is no list in LDS and no barrier: every pixel is on
 // its own.  Each thread rebuilds its pixel exactly as lights_shade_body and rtx_chain_shadow do (tile_pixel, surface_of, the
-// forward walk of the chain with reflectivity_of / mirror_ray: the same operations on the same bits, so P_j, n_j, o_j are theirs)
+// forward walk of the chain with reflectivity_of / secondary_ray: the same operations on the same bits, so P_j, n_j, o_j are theirs)
 // and decides for level 0 -- and for the levels 1 .. depth when gs.deep is set (RTX_OPT_REFLECT_SHADOWS in effect) -- and every
 // light of the set whether the point is dark: shadowed_before_spheres unchanged (self-shadow and planes), then segment_hits_sphere
 // against the spheres of the grid's large list, then against the lists of the cells the segment's walk visits (rtx_grid.hpp:
@@ -89,7 +89,7 @@ __global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const Ligh
             if (alive) {
                 alive = reflectivity_of(ra, o) > 0.0f;
                 if (alive) {
-                    r = mirror_ray(r, t, n);
+                    r = secondary_ray(a, ra, r, t, n, o);
                     const uint2 h = ra.hits[(size_t)(j + 1u) * ca.px + at];
                     alive = h.y != 0xffffffffu;
                     if (alive) {

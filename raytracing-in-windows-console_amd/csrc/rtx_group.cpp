@@ -513,6 +513,11 @@ int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float*
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_reflectivity(m, first, n, k); });
 }
 
+int scene_set_refraction(rtx_ctx* root, unsigned first, size_t n, const float* ior)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_refraction(m, first, n, ior); });
+}
+
 int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns)
 {
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_patterns(m, n, patterns); });

@@ -30,6 +30,7 @@ int scene_set_lights(rtx_ctx* root, size_t n, const rtx_light* lights);
 int scene_set_reflectivity(rtx_ctx* root, unsigned first, size_t n, const float* k); // (the root has validated and applied it)
 int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns);        // (likewise, both)
 int scene_set_object_pattern(rtx_ctx* root, unsigned first, size_t n, unsigned slot);
+int scene_set_refraction(rtx_ctx* root, unsigned first, size_t n, const float* ior);
 // edits in place (the root has validated the range and applied the edit to itself): the host form calls every member; the device
 // form copies the rows from the root's device into every other member's scratch, behind `after` (an event on the caller's stream),
 // and runs the kernel there -- logical ranks on the root's own GPU take the same path

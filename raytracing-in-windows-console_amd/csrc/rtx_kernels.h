@@ -8,6 +8,7 @@
 #include "rtx_grid.hpp"
 #include "rtx_lights.hpp"
 #include "rtx_pattern.hpp"
+#include "rtx_refract.hpp"
 #include "rtx_plan.hpp"
 
 // Kernel-side mode numbers = enum RenderingMode (RayTracingManager.h:21).
@@ -155,6 +156,10 @@ struct ReflectArgs {
     const float* k_pl;   // ... of the planes, by plane index
     uint32_t brute;      // 1: no culling, every sphere tested (RTX_OPT_REFLECT_CHECK 1)
     uint32_t* longest;   // atomicMax of the longest candidate list a workgroup held, or nullptr
+    // glass (rtx_scene_set_refraction): the index of refraction of the spheres and of the planes, ordered as k_sph and k_pl are;
+    // both nullptr while no object is refractive -- nothing is loaded then and every secondary ray is the mirror's
+    const float* ior_sph;
+    const float* ior_pl;
 };
 
 // Checker patterns (rtx_scene_set_patterns), for the shade launches alone: the slot of every object and the table.  table ==

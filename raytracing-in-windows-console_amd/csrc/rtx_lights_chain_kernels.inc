@@ -6,7 +6,7 @@
 //
 // Level 0 is lights_shade_body's work: the shadow test per light, one walk of the scene, local_0 = shade_lights with the pixel's
 // dark lights at powers 0.  lights_chain_blend then walks the chain forward from the hits rtx_reflect_chain stored (level j at
-// ra.hits + j * ca.px), rebuilding r_j with mirror_ray; local_j (j >= 1) = shade_lights of r_j at t_j with full powers for every
+// ra.hits + j * ca.px), rebuilding r_j with secondary_ray; local_j (j >= 1) = shade_lights of r_j at t_j with full powers for every
 // light, in order, no shadow test (under RTX_OPT_REFLECT_SHADOWS: see below), black when level j hit nothing.  It keeps local_j and k_j for the at most 5 levels in
 // registers (loops unrolled: no indexed array, no scratch), then folds from the deepest level inwards:
 // C_j = local_j where level j + 1 does not exist, else minf(255.0f, local_j * (1.0f - k_j) + C_{j+1} * k_j) per component --
@@ -40,7 +40,7 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
             if (alive) {
                 kk[j] = k;
                 deepest = (uint32_t)j + 1u;
-                r = mirror_ray(r, t, n);
+                r = secondary_ray(a, ra, r, t, n, o);
                 const uint2 h = ra.hits[(size_t)(j + 1) * ca.px + at];
                 alive = h.y != 0xffffffffu;
                 if (alive) {

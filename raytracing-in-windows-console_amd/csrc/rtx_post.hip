@@ -365,9 +365,14 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
     ctx->pat_slot.swap(slots);
     ctx->n_patterned = 0;
     for (const uint8_t s : ctx->pat_slot) ctx->n_patterned += s != 0 ? 1u : 0u;
+    // ... and the indices of refraction
+    std::vector<float> iors = rtxplan::survivors_of(ctx->ior, ascending);
+    ctx->ior.swap(iors);
+    ctx->n_refractive = rtxrefract::count_refractive(ctx->ior);
     ctx->refl_dirty = true;
     ctx->refl_gen++;
     ctx->pat_gen++;
+    ctx->ior_gen++;
     if (ctx->h_centres.size() == ctx->ns) {
         // the sort's input at the next re-sort, by sphere index
         size_t kept = 0, gone = 0;

@@ -3,7 +3,7 @@
 // function it calls.  rtx_reflect_hit (rtx_reflect_kernels.inc) stays the depth-1 launch.
 //
 // Level 0 is the primary ray and its hit.  Level j + 1 exists for a pixel iff j + 1 <= depth, level j hit an object o_j and
-// k(o_j) > 0; its ray is mirror_ray(r_j, t_j, normal_j) with normal_j = surface_of(o_j) at the hit (sphere:
+// k(o_j) > 0; its ray is secondary_ray(r_j, t_j, normal_j, o_j) -- the mirror's, or the glass's -- with normal_j = surface_of(o_j) at the hit (sphere:
 // normalize_gpu(normalize_gpu(P - C)), plane: normalize_gpu(n)), tested against every object but o_j with the reference's tests and
 // no far limit, winner the lexicographic minimum of (t, creation index).  Level j's hits go to ra.hits + j * ca.px.
 //
@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kThreads, 6) void rtx_reflect_chain(const KArgs a, 
     const bool chain = pending; // the pixel has a chain: every level up to the depth gets an entry
     V3 normal = ray.d;
     if (pending) normal = surface_of(a, hit.y, add(ray.o, mulf(ray.d, __uint_as_float(hit.x)))).normal;
-    Ray cur = mirror_ray(ray, pending ? __uint_as_float(hit.x) : 0.0f, normal); // the ray of the level being traced
+    Ray cur = secondary_ray(a, ra, ray, pending ? __uint_as_float(hit.x) : 0.0f, normal, hit.y); // the ray of the level being traced
     uint32_t id = hit.y;                                                          // the object it leaves
 
     const uint32_t ns = a.ns;
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(kThreads, 6) void rtx_reflect_chain(const KArgs a, 
         if (__ballot(next) != 0ull) {
             V3 n = cur.d;
             if (next) n = surface_of(a, bid, add(cur.o, mulf(cur.d, bt))).normal;
-            cur = mirror_ray(cur, next ? bt : 0.0f, n);
+            cur = secondary_ray(a, ra, cur, next ? bt : 0.0f, n, bid);
         }
         id = bid;
         pending = next;

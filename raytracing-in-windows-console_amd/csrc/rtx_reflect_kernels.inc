@@ -3,7 +3,7 @@
 // kOutHit form (every pixel's closest hit), rtx_reflect_hit (the closest hit of each reflective pixel's secondary ray) and
 // rtx_reflect_shade (rtx_shadow_kernels.inc: the shading, then the blend).
 //
-// A pixel reflects when it is visible (t <= cam_far, not column W-1) and its winner o has k > 0.  Its secondary ray (mirror_ray) is
+// A pixel reflects when it is visible (t <= cam_far, not column W-1) and its winner o has k > 0.  Its secondary ray (secondary_ray) is
 // tested against every sphere and plane but o; the winner is the lexicographic minimum of (t, creation index).
 //
 // rtx_reflect_hit: every thread of a tile rebuilds its primary and forms its secondary ray; the planes are tested per pixel
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(kThreads) void rtx_reflect_hit(const KArgs a, const
     if (pending) pending = reflectivity_of(ra, id) > 0.0f;
     V3 normal = ray.d;
     if (pending) normal = surface_of(a, id, add(ray.o, mulf(ray.d, distance))).normal;
-    const Ray r2 = mirror_ray(ray, pending ? distance : 0.0f, normal);
+    const Ray r2 = secondary_ray(a, ra, ray, pending ? distance : 0.0f, normal, id);
     float bt = kNoHit;
     uint32_t bid = 0xffffffffu;
     closest_of_planes(a, r2, pending, id, bt, bid);

@@ -634,6 +634,18 @@ int upload_reflectivity(rtx_ctx* ctx)
     }
     RTX_HIP(ctx, ctx->d_refl_pos.reserve(pos.size(), rtxmem::nothing()));
     RTX_HIP(ctx, hipMemcpy(ctx->d_refl_pos.get(), pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    // the indices of refraction in the same three orders
+    std::vector<float> is(ks.size(), 0.0f), iso(ks.size(), 0.0f), ip(kp.size(), 0.0f);
+    for (size_t g = 0; g < ctx->ior.size(); g++) {
+        (ctx->kind_of[g] == 2 ? is : ip)[ctx->local_of[g]] = ctx->ior[g];
+    }
+    for (size_t p = 0; sorted && p < ns; p++) iso[p] = is[ctx->h_sorted_idx[p]];
+    for (const auto& pr : {std::make_pair(&ctx->d_ior_sph, &is), std::make_pair(&ctx->d_ior_sorted, &iso), std::make_pair(&ctx->d_ior_pl, &ip)}) {
+        DeviceBuf<float>& d = *pr.first;
+        const std::vector<float>& h = *pr.second;
+        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing()));
+        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     // the pattern slots in the same three orders, and the packed table (rtx_pattern.hpp): always all kMaxPatterns entries
     std::vector<uint8_t> ss(ks.size(), 0), sso(ks.size(), 0), sp(kp.size(), 0);
     for (size_t g = 0; g < ctx->pat_slot.size(); g++) {
@@ -745,6 +757,10 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         ra.k_pl = ctx->d_refl_pl.get();
         ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
         ra.longest = ctx->d_reflect_longest.get();
+        if (ctx->n_refractive != 0) { // (else both stay nullptr: every secondary ray is the mirror's)
+            ra.ior_sph = a.sph_sorted_idx != nullptr ? ctx->d_ior_sorted.get() : ctx->d_ior_sph.get();
+            ra.ior_pl = ctx->d_ior_pl.get();
+        }
     }
     if (counts_rays) { // (rtx_grid_reflect at depth 1: one level into the two-level buffer)
         ca.depth = plan.levels - 1u;
@@ -802,6 +818,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     if (patterned) ctx->stat_pattern_frames++;
+    if (mirror && ctx->n_refractive != 0) ctx->stat_refract_frames++;
     return RTX_OK;
 }
 
@@ -1427,6 +1444,7 @@ struct rtx_graph_handle {
     uint64_t scene_gen = 0;
     uint64_t refl_gen = 0; // ... and the reflectivities (the mirror path's launches read their device copies)
     uint64_t pat_gen = 0;  // ... and the pattern table and slots (a change alters which launches make a frame and what they read)
+    uint64_t ior_gen = 0;  // ... and the indices of refraction (the mirror path's launches read their device copies, or none)
     std::vector<uint64_t> frozen; // dispatch-order sets its launches read (released by rtx_graph_destroy)
 };
 
@@ -1462,6 +1480,7 @@ int rtx_graph_end(rtx_ctx* ctx, void* stream_v, void** graph_out)
     h->scene_gen = ctx->scene_gen;
     h->refl_gen = ctx->refl_gen;
     h->pat_gen = ctx->pat_gen;
+    h->ior_gen = ctx->ior_gen;
     h->frozen.swap(frozen);
     *graph_out = h;
     return RTX_OK;
@@ -1482,6 +1501,10 @@ int rtx_graph_launch(rtx_ctx* ctx, void* graph, void* stream_v)
     if (h->pat_gen != ctx->pat_gen) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the pattern table or the objects' slots changed after this graph was recorded (its "
                                                        "launches read the device copies, which the next launch replaces): re-capture");
+    }
+    if (h->ior_gen != ctx->ior_gen) {
+        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the indices of refraction changed after this graph was recorded (its launches "
+                                                       "read the device copies, which the next launch replaces): re-capture");
     }
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     RTX_HIP(ctx, hipGraphLaunch(h->exec, stream_v ? (hipStream_t)stream_v : ctx->stream));

@@ -371,6 +371,48 @@ __device__ __forceinline__ Ray mirror_ray(const Ray& ray, float distance, V3 nor
     return r;
 }
 
+// The next ray of a chain: `ray` hit object `id` (sphere position, or plane index | bit 31; 0xffffffff: none, a lane whose ray
+// nobody reads) at `distance` with normal `normal`.  While no object is refractive (ra.ior_sph == nullptr, a kernel argument: the
+// test is uniform) it is mirror_ray and nothing is loaded.  Otherwise ior(id) picks the case per lane (rtx_scene_set_refraction,
+// the rule in include/rtx.h): 0, the mirror's ray, bit for bit; a sphere, the ray that leaves its far side (rtx_refract.hpp:
+// through_sphere, with P, N and V formed as mirror_ray forms them and the stored radius); a plane, a thin sheet: the ray goes on
+// from P in its direction.  a, fourA and divTwoA as mirror_ray forms them.
+// (secondary_ray<GLASS>: for a caller that has made the uniform test itself, outside its level loop -- GLASS = ra.ior_sph != nullptr.)
+template <bool GLASS>
+__device__ __forceinline__ Ray secondary_ray(const KArgs& a, const ReflectArgs& ra, const Ray& ray, float distance, V3 normal, uint32_t id)
+{
+    Ray r = mirror_ray(ray, distance, normal);
+    if constexpr (GLASS) {
+        const bool plane = (id & 0x80000000u) != 0u;
+        float ior = 0.0f;
+        if (id != 0xffffffffu) ior = plane ? ra.ior_pl[id & 0x7fffffffu] : ra.ior_sph[id];
+        if (ior > 0.0f) {
+            if (plane) {
+                r.d = ray.d; // (r.o is P already)
+            } else {
+                const V3 N = normalize_gpu(normal);
+                const V3 V = normalize_gpu(mulf(ray.d, -1.0f));
+                const float Pf[3] = {r.o.x, r.o.y, r.o.z}, Nf[3] = {N.x, N.y, N.z}, Vf[3] = {V.x, V.y, V.z};
+                float of[3], df[3];
+                rtxrefract::through_sphere(
+                    Pf, Nf, Vf, a.sph_geom[id].w, ior, [](float x) { return sqrt_cr(x); }, [](float x) { return rcp_cr(x); }, of, df);
+                r.o = v3(of[0], of[1], of[2]);
+                r.d = v3(df[0], df[1], df[2]);
+            }
+            r.a = dot(r.d, r.d);
+            r.fourA = 4.0f * r.a;
+            r.divTwoA = rcp_cr(2.0f * r.a);
+        }
+    }
+    return r;
+}
+
+__device__ __forceinline__ Ray secondary_ray(const KArgs& a, const ReflectArgs& ra, const Ray& ray, float distance, V3 normal, uint32_t id)
+{
+    if (ra.ior_sph != nullptr) return secondary_ray<true>(a, ra, ray, distance, normal, id);
+    return mirror_ray(ray, distance, normal);
+}
+
 // Creation index of an object (sphere position, or plane index | bit 31): looked up only to break an exact tie in t.
 __device__ __forceinline__ uint32_t creation_index(const KArgs& a, uint32_t id)
 {
@@ -535,7 +577,7 @@ __device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& r
 {
     const float k = reflectivity_of(ra, id);
     if (!(k > 0.0f)) return cl;
-    const Ray r2 = mirror_ray(ray, distance, normal);
+    const Ray r2 = secondary_ray(a, ra, ray, distance, normal, id);
     const uint2 h = ra.hits2[at];
     V3 cr = v3(0.0f, 0.0f, 0.0f);
     if (h.y != 0xffffffffu) {
