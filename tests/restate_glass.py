@@ -4,7 +4,8 @@ csrc/rtx_refract.hpp::through_sphere and of secondary_ray (csrc/rtx_tile_pass.in
     restate.shade_chain, values8, encode_records and encode_words serve unchanged;
   * dark_sets: the shadow test of RTX_OPT_SHADOWS / RTX_OPT_REFLECT_SHADOWS in fp32 as the kernels' exact tests state it
     (shadowed_before_spheres and segment_hits_sphere of csrc/rtx_tile_pass.inc), so that shadowed frames compare on every pixel;
-  * scene_a, scene_b: the two scenes.
+  * scene_a, scene_b: the two scenes; scene_c, scene_d: those of tests/test_gpu_glass_edges.py, where glass spheres overlap other
+    objects, sink into the floor and hold other spheres, and edge_classes, which counts the rays that start there.
 tests/test_host_restate_glass.py states the input conditions of the GPU tests on this file alone."""
 import numpy as np
 
@@ -31,10 +32,14 @@ def refract_sphere(P, N, V, r, ior):
     return o, d
 
 
-def trace_chain_glass(p, sph, pl, ks, iors, pix, max_depth=4):
+def trace_chain_glass(p, sph, pl, ks, iors, pix, max_depth=4, wrong=None):
     """restate.trace_chain with ior per object (a dict {creation index: ior} or an array; 0: a mirror).  Level j + 1's ray is the
     mirror ray of level j where ior(o_j) = 0, the ray through the sphere where o_j is a sphere, and the ray going on from P_j where
-    o_j is a plane.  Each level >= 1 also carries `glass`: the ray was refracted, not mirrored."""
+    o_j is a plane.  Each level >= 1 also carries `glass`: the ray was refracted, not mirrored.
+    `wrong` restates one bug a kernel could have, for tests/test_host_restate_glass.py to show that the scenes would let it be seen:
+    "origin" (the ray through a sphere starts at P_j, not at the exit point), "own" (a secondary ray is tested against the object
+    it left as well), "radius" (the chord is taken with the radius of the sphere created before)."""
+    assert wrong in (None, "origin", "own", "radius")
     sph = np.asarray(sph, dtype=np.float32).reshape(-1, 7)
     pl = RS.host_planes(pl)
     W = int(p.x)
@@ -42,7 +47,7 @@ def trace_chain_glass(p, sph, pl, ks, iors, pix, max_depth=4):
     ns = len(sph)
     kk = RS.k_array(ks, ns + len(pl))
     ii = RS.k_array(iors, ns + len(pl))
-    radius = np.concatenate([sph[:, 3], np.zeros(len(pl), np.float32)]).astype(np.float32)
+    radius = np.concatenate([np.roll(sph[:, 3], 1) if wrong == "radius" else sph[:, 3], np.zeros(len(pl), np.float32)]).astype(np.float32)
     odall = np.concatenate([sph[:, 4:7], pl[:, 6:9]]).astype(np.float32) / f32(255.0)
     with np.errstate(all="ignore"):
         O3, D = RS.primary_rays(p, pix)
@@ -76,10 +81,11 @@ def trace_chain_glass(p, sph, pl, ks, iors, pix, max_depth=4):
                 go_, gd = refract_sphere(Pj, N, V, radius[cur["gid"]], np.where(glass, ior, f32(1.0)).astype(np.float32))
                 through = glass & is_sphere
                 sheet = glass & ~is_sphere
-                Ro = tuple(np.where(through, go_[q], Pj[q]).astype(np.float32) for q in range(3))
+                if wrong != "origin":
+                    Ro = tuple(np.where(through, go_[q], Pj[q]).astype(np.float32) for q in range(3))
                 Rd = tuple(np.where(through, gd[q], np.where(sheet, cur["D"][q], Rd[q])).astype(np.float32) for q in range(3))
             a2 = RS._dot(Rd, Rd)
-            t2, g2 = RS._closest(Ro, Rd, sph, pl, a2, f32(4.0) * a2, f32(1.0) / (f32(2.0) * a2), exclude=cur["gid"])
+            t2, g2 = RS._closest(Ro, Rd, sph, pl, a2, f32(4.0) * a2, f32(1.0) / (f32(2.0) * a2), exclude=None if wrong == "own" else cur["gid"])
             P2 = tuple(Ro[q] + Rd[q] * t2 for q in range(3))
             n2 = RS._normal(P2, sph, pl, g2)
         od2 = odall[np.maximum(g2, 0)]
@@ -200,3 +206,78 @@ def scene_b():
         pix = np.arange(GW * GH)
         _cache["b"] = (p, sph, pl, ks, iors, pix, trace_chain_glass(p, sph, pl, ks, iors, pix))
     return _cache["b"]
+
+
+# scene C: glass where objects do not stand clear of each other (scene A's camera).  Sphere 0 (glass) stands in front of and
+# overlaps sphere 1 (glass, ior 1.0); sphere 3, a mirror, covers the far side of sphere 2 (glass); sphere 4 (glass) is sunk into the
+# floor; sphere 5 (glass), in the free corner of the frame, overlaps sphere 6, a mirror behind it; sphere 7 (glass, ior 4.0) stands
+# free.  The floor (patterned by the GPU tests, as scene A's) is a weak mirror, the upright sheet glass.
+C_SPH = np.array([[-4, 4, 28, 4, 230, 40, 40], [-3, 4.5, 33, 4, 40, 230, 40], [6, 4, 27, 4, 40, 40, 230], [6.5, 4, 30.5, 3, 230, 230, 40],
+                  [0.5, 0, 19, 3, 200, 120, 60], [-3.5, 10, 40, 2.5, 90, 200, 200], [-2, 10, 42, 2.5, 220, 220, 220],
+                  [3, 10, 36, 3, 180, 60, 200]], dtype=np.float32)
+C_PL = np.array([[0, -1, 30, 0, 1, 0, 120, 120, 120, 80, 80], [2, 3, 14, 0, 0, -1, 90, 140, 160, 6, 10]], dtype=np.float32)
+C_KS = {0: 1.0, 1: 0.7, 2: 0.9, 3: 0.5, 4: 0.8, 5: 1.0, 6: 0.6, 7: 0.5, 8: 0.4, 9: 0.7}
+C_IORS = {0: 1.5, 1: 1.0, 2: 1.3, 4: 2.0, 5: 1.5, 7: 4.0, 9: 1.3}
+C_FLOOR, C_SHEET, C_SUNK = 8, 9, 4
+C_GLASS = (0, 1, 2, 4, 5, 7, C_SHEET)
+
+
+def scene_c():
+    """(params, spheres, planes, ks, iors, pixels, trace) of scene C at 41 x 23."""
+    if "c" not in _cache:
+        p = scene_a_params()
+        pix = np.arange(GW * GH)
+        _cache["c"] = (p, C_SPH, C_PL, C_KS, C_IORS, pix, trace_chain_glass(p, C_SPH, C_PL, C_KS, C_IORS, pix))
+    return _cache["c"]
+
+
+# scene D: 300 spheres over scene C's floor (the direction-sorted copies exist), scene B's pattern of glass and mirrors, and sphere 8
+# (glass) so large that it holds dozens of the others and goes to the world grid's large list
+D_NS, D_BIG, D_FLOOR = 300, 8, 300
+
+
+def scene_d_objects():
+    """(spheres, planes, ks, iors) of scene D."""
+    rng = np.random.default_rng(11)
+    sph = np.zeros((D_NS, 7), dtype=np.float32)
+    for q, (lo, hi) in enumerate(((-12.0, 12.0), (0.0, 8.0), (20.0, 44.0), (0.8, 2.0))):  # x of every sphere, then y, z and r
+        sph[:, q] = rng.uniform(lo, hi, D_NS)
+    sph[:, 4:] = rng.integers(40, 231, (D_NS, 3))
+    sph[D_BIG] = [0, 5, 34, 9, 200, 200, 230]
+    ks = np.zeros(D_NS + 1, dtype=np.float32)
+    iors = np.zeros(D_NS + 1, dtype=np.float32)
+    ks[0:D_NS:4] = 0.85
+    iors[0:D_NS:4] = 1.5
+    ks[1:D_NS:4] = 0.5
+    ks[D_FLOOR] = 0.4
+    return sph, C_PL[:1].copy(), ks, iors
+
+
+def scene_d():
+    """(params, spheres, planes, ks, iors, pixels, trace) of scene D at 41 x 23."""
+    if "d" not in _cache:
+        p = scene_a_params()
+        sph, pl, ks, iors = scene_d_objects()
+        pix = np.arange(GW * GH)
+        _cache["d"] = (p, sph, pl, ks, iors, pix, trace_chain_glass(p, sph, pl, ks, iors, pix))
+    return _cache["d"]
+
+
+def edge_classes(trace, floor):
+    """Per level j >= 1 of a trace (None at 0) the classes of its refracted rays that tests/test_host_restate_glass.py and
+    tests/test_gpu_glass_edges.py count, as masks over the level's rays, decided in float64 on the fp32 origins:
+      glass   the ray was refracted (it left a glass sphere or went on through a glass plane);
+      inside  ... and starts strictly inside a sphere other than the one it left;
+      beyond  ... and starts on the far side of the plane `floor` (creation index): below it, where its normal points up;
+      hit     the ray hit an object."""
+    sph = trace["sph"].astype(np.float64)
+    pf = trace["pl"][floor - len(sph)].astype(np.float64)
+    out = [None]
+    for lev in trace["levels"][1:]:
+        o = np.stack([lev["O"][q] for q in range(3)], axis=1).astype(np.float64)
+        d2 = ((o[:, None, :] - sph[None, :, :3]) ** 2).sum(-1)
+        within = d2 < sph[None, :, 3] ** 2
+        within[np.arange(len(o)), np.clip(lev["left"], 0, len(sph) - 1)] &= lev["left"] >= len(sph)
+        glass = lev["glass"].copy()
+        out.append(dict(glass=glass, inside=glass & within.any(1), beyond=glass & (((o - pf[:3]) * pf[3:6]).sum(1) < 0.0), hit=lev["gid"] >= 0))
+    return out

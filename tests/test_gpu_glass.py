@@ -10,7 +10,8 @@ kernels' exact shadow tests in fp32.
   3. scene B (300 spheres, a quarter glass): the direction-sorted store on and off;
   4. neutrality: mirrors with every ior 0 give the bytes they give before any call, and again after the values are set back;
   5. inheritance: RTX_OPT_SUPERSAMPLE 2, rtx_update, a device group of two logical ranks;
-  6. lifecycle: an edited radius, removal, clear, a recorded graph, both counters."""
+  6. lifecycle: an edited radius, removal, clear, a recorded graph, both counters.
+Here every object stands clear of every other; tests/test_gpu_glass_edges.py: glass that overlaps, sinks, nests and moves."""
 import numpy as np
 import pytest
 

@@ -1,13 +1,18 @@
 """tests/restate_glass.py judged on the CPU, so that tests/test_gpu_glass.py cannot pass vacuously: with every ior 0 it is
 restate.trace_chain bit for bit; the two scenes of the GPU tests have refracted rays at levels 1 to 3, glass rays that reach the
 (patterned) floor and a mirror, a glass sphere seen in a mirror, chords that depend on the radius, and shadows at every level; and
-the closed form of the rule agrees with two float64 Snell refractions along the chains of scene A."""
+the closed form of the rule agrees with two float64 Snell refractions along the chains of scene A.
+For tests/test_gpu_glass_edges.py: scenes C and D have refracted rays that start inside another sphere, beyond the floor and in a
+large-list sphere; float64 picks the restatement's winner for every secondary ray it decides; four restated bugs would each change
+the picture; shadows reach the points beyond the floor; the restatement follows the rule in float64 on its own fp32 inputs."""
 import numpy as np
 import pytest
 
+import grid_cases as GC
 import restate as RS
 import restate_glass as RG
 import restate_pattern as RP
+import tile_cases as TCS
 
 f32 = np.float32
 
@@ -119,7 +124,8 @@ def test_shadows_are_in_the_picture_at_every_level(nl):
 def test_the_closed_form_agrees_with_two_snell_refractions_in_float64():
     """Along scene A's chains: every ray that leaves a glass sphere against float64 -- refract at entry, intersect the sphere,
     refract at exit.  The fp32 inputs (P, N, V) are taken as exact; the bound is the issue's figures for fp32 (3.1e-6 of r for the
-    exit point, 2.0e-6 for the direction) times four."""
+    exit point, 2.0e-6 for the direction) times four.
+    The bound is scene A's: scene C's rays at ci 0.05 .. 0.07 into its ior-4 sphere leave with k2 = 0.003 and give 1.47e-5 (see below)."""
     p, sph, pl, ks, iors, pix, trace = RG.scene_a()
     ii = RS.k_array(iors, len(sph) + len(pl))
     worst_o = worst_d = 0.0
@@ -161,3 +167,188 @@ def test_the_closed_form_agrees_with_two_snell_refractions_in_float64():
     print("checked %d rays: exit point %.3g of r, direction %.3g" % (n_checked, worst_o, worst_d))
     assert n_checked >= 200
     assert worst_o <= 4 * 3.1e-6 and worst_d <= 4 * 2.0e-6
+
+
+# ---------------------------------------------------------------- scenes C and D: glass where objects do not stand clear
+
+SCENES = {"c": (RG.scene_c, RG.C_FLOOR), "d": (RG.scene_d, RG.D_FLOOR)}
+REF = [RS.reference_light()]
+
+
+def class_counts(trace, floor):
+    """What the edge tests count, over the levels 1 .. max_depth of a trace: refracted rays, those that start inside another sphere
+    and beyond the floor (and how many of each hit something), the levels either kind appears at, the objects left."""
+    ec = RG.edge_classes(trace, floor)
+    c = dict(glass=0, inside=0, inside_hit=0, beyond=0, beyond_hit=0, levels=[], left=set(), left_at_edge={})
+    for j, (e, lev) in enumerate(zip(ec[1:], trace["levels"][1:]), 1):
+        for key in ("glass", "inside", "beyond"):
+            c[key] += int(e[key].sum())
+        c["inside_hit"] += int((e["inside"] & e["hit"]).sum())
+        c["beyond_hit"] += int((e["beyond"] & e["hit"]).sum())
+        if (e["inside"] | e["beyond"]).any():
+            c["levels"].append(j)
+        c["left"] |= set(np.unique(lev["left"][e["glass"]]).tolist())
+        for o in lev["left"][e["inside"] | e["beyond"]].tolist():
+            c["left_at_edge"][o] = c["left_at_edge"].get(o, 0) + 1
+    return c
+
+
+def test_scene_c_input_conditions():
+    trace = RG.scene_c()[6]
+    c = class_counts(trace, RG.C_FLOOR)
+    print("scene C: rays", trace["rays"], c)
+    assert c["inside"] >= 75 and c["inside_hit"] >= 35
+    assert c["beyond"] >= 85 and c["beyond_hit"] >= 5
+    assert set(c["levels"]) >= {1, 2, 3}
+    assert c["left"] == set(RG.C_GLASS)
+    # the sunk sphere is the one whose rays start beyond the floor
+    ec = RG.edge_classes(trace, RG.C_FLOOR)
+    assert all((lev["left"][e["beyond"]] == RG.C_SUNK).all() for e, lev in zip(ec[1:], trace["levels"][1:]))
+
+
+def test_scene_d_input_conditions():
+    p, sph, pl, ks, iors, pix, trace = RG.scene_d()
+    c = class_counts(trace, RG.D_FLOOR)
+    big = sum(int((lev["glass"] & (lev["left"] == RG.D_BIG)).sum()) for lev in trace["levels"][1:])
+    print("scene D: rays", trace["rays"], "leave the big sphere", big, c)
+    assert c["inside"] >= 45 and big >= 75 and c["glass"] >= 150
+    assert len(sph) >= 256  # (the direction-sorted copies exist)
+    # the big sphere, and no other, is in the world grid's large list at the default load of 1 sphere per cell
+    g = GC.plan_of(sph[:, :4], 1.0)
+    large = GC.large64(g, sph[:, :4])
+    assert g["ok"] == 1 and large[RG.D_BIG] == 1 and (np.delete(large, RG.D_BIG) == 0).all(), (g["n"], np.nonzero(large)[0])
+
+
+@pytest.mark.parametrize("scene", ["c", "d"])
+def test_float64_agrees_with_the_restatement_on_every_secondary_ray(scene):
+    """Each level's fp32 ray taken as exact, tile_cases.closest64 (the production rules, own object excluded, ties to the lower
+    creation index): the winner is the restatement's wherever float64 decides, and it leaves at most 2 % undecided."""
+    trace = SCENES[scene][0]()[6]
+    sph, pl = trace["sph"], trace["pl"]
+    ns = len(sph)
+    n = wrong = undecided = 0
+    for lev in trace["levels"][1:]:
+        if len(lev["idx"]) == 0:
+            continue
+        O3 = np.stack(lev["O"], axis=1).astype(np.float64)
+        D = np.stack(lev["D"], axis=1).astype(np.float64)
+        ids = np.where(lev["left"] < ns, lev["left"], 0x80000000 | (lev["left"] - ns)).astype(np.uint32)
+        win, _, decided = TCS.closest64(O3, D, ids, sph[:, :4].astype(np.float64), np.arange(ns), pl.astype(np.float64))
+        gid = np.where(win == 0xffffffff, -1, np.where(win & 0x80000000, ns + (win & 0x7fffffff).astype(np.int64), win.astype(np.int64)))
+        n += len(gid)
+        undecided += int((~decided).sum())
+        wrong += int((decided & (gid != lev["gid"])).sum())
+    print("scene %s: %d secondary rays, float64 leaves %d undecided (%.2f %%), %d winners differ" % (scene.upper(), n, undecided, 100.0 * undecided / n, wrong))
+    assert n == sum(trace["rays"]) and wrong == 0
+    assert undecided <= 0.02 * n
+
+
+def _changed_pixels(trace, other):
+    a, b = RS.shade_chain(trace, REF)[4], RS.shade_chain(other, REF)[4]
+    return int((np.logical_or.reduce([~RS.same_floats(a[q], b[q]) for q in range(3)]) & trace["vis"]).sum())
+
+
+D_IOR_PERMUTATION = 7  # (sphere i takes the ior of sphere i + 7: a glass sphere's value goes to a plain one)
+
+
+@pytest.mark.parametrize("bug,scene", [("origin", "c"), ("own", "c"), ("ior", "d"), ("radius", "d")])
+def test_a_kernel_with_this_bug_would_be_seen(bug, scene):
+    """Four bugs restated in numpy (restate_glass.trace_chain_glass's `wrong`; the ior of another sphere, as a kernel that looks
+    it up by creation index where the sorted position is meant would take it): the depth-4 colours are other ones on 20 visible
+    pixels at least."""
+    p, sph, pl, ks, iors, pix, trace = SCENES[scene][0]()
+    if bug == "ior":
+        other_iors = np.concatenate([np.roll(iors[:len(sph)], -D_IOR_PERMUTATION), iors[len(sph):]])
+        assert (other_iors != iors).sum() >= 100
+        other = RG.trace_chain_glass(p, sph, pl, ks, other_iors, pix)
+    else:
+        other = RG.trace_chain_glass(p, sph, pl, ks, iors, pix, wrong=bug)
+    changed = _changed_pixels(trace, other)
+    print("bug '%s' on scene %s: %d visible pixels change" % (bug, scene.upper(), changed))
+    assert changed >= 20
+
+
+@pytest.mark.parametrize("nl", [1, 3])
+def test_scene_c_shadows_are_in_the_picture_at_every_level(nl):
+    trace = RG.scene_c()[6]
+    dark = RG.dark_sets(trace, RG.lights_a(nl), True)
+    for j in (0, 1, 2):
+        lev = trace["levels"][j]
+        tested = np.zeros(trace["n"], dtype=bool)
+        tested[lev["idx"][lev["gid"] >= 0]] = True
+        if j == 0:
+            tested &= trace["vis"] & (trace["t"] <= f32(trace["p"].cam_far))
+        n_dark, n_lit = int((dark[j][tested] != 0).sum()), int((dark[j][tested] == 0).sum())
+        print("%d lights, level %d: %d dark, %d lit" % (nl, j, n_dark, n_lit))
+        assert n_dark >= 10 and n_lit >= 10, j
+        assert not dark[j][~tested].any()
+    # points beyond the floor: hits of rays of level >= 1, under the floor's plane
+    pf = trace["pl"][RG.C_FLOOR - len(trace["sph"])].astype(np.float64)
+    under = 0
+    for j in (1, 2, 3, 4):
+        lev = trace["levels"][j]
+        ok = lev["gid"] >= 0
+        P = np.stack([(lev["O"][q] + lev["D"][q] * lev["t"]) for q in range(3)], axis=1).astype(np.float64)
+        below = ok & (((P - pf[:3]) * pf[3:6]).sum(1) < 0.0)
+        under += int((dark[j][lev["idx"][below]] != 0).sum())
+    print("%d lights: %d dark points beyond the floor" % (nl, under))
+    assert under >= 5
+
+
+def rule64(P, N, V, r, ior):
+    """THE RULE (csrc/rtx_refract.hpp, through_sphere) in float64."""
+    ci = (N * V).sum(1)
+    eta = 1.0 / ior
+    ct = np.sqrt(np.maximum(1.0 - eta * eta * (1.0 - ci * ci), 0.0))
+    T = N * (eta * ci - ct)[:, None] - V * eta[:, None]
+    o = P + T * (2.0 * r * ct)[:, None]
+    d = V - T * (2.0 * (T * V).sum(1))[:, None]
+    return o, d
+
+
+# The worst over both scenes, measured on the CPU: exit point 9.91e-7 of r (scene D), direction 4.32e-7 (scene C).  Times four, as
+# the margins of tests/host/test_refract.cpp are.
+RULE_BOUND_O, RULE_BOUND_D = 4 * 9.91e-7, 4 * 4.32e-7
+
+
+def rule_errors(trace, iors):
+    """(rays, worst exit point / r, worst direction) of the restatement against rule64 on the same fp32 N, V, P, r and ior, over
+    every ray of the trace that leaves a glass sphere."""
+    sph = trace["sph"]
+    ii = RS.k_array(iors, len(sph) + len(trace["pl"]))
+    n, worst_o, worst_d = 0, 0.0, 0.0
+    for j in range(1, len(trace["levels"])):
+        prev, lev = trace["levels"][j - 1], trace["levels"][j]
+        sel = lev["glass"] & (lev["left"] < len(sph))
+        if not sel.any():
+            continue
+        pos = np.searchsorted(prev["idx"], lev["idx"][sel])
+        with np.errstate(all="ignore"):
+            Nf = RS._nrm(*(prev["normal"][q][pos] for q in range(3)))
+            Vf = RS._nrm(*(prev["D"][q][pos] * f32(-1.0) for q in range(3)))
+            Pf = tuple(prev["O"][q][pos] + prev["D"][q][pos] * prev["t"][pos] for q in range(3))
+        N, V, P = (np.stack(x, axis=1).astype(np.float64) for x in (Nf, Vf, Pf))
+        obj = lev["left"][sel]
+        r = sph[obj, 3].astype(np.float64)
+        o, d = rule64(P, N, V, r, ii[obj].astype(np.float64))
+        got_o = np.stack([lev["O"][q][sel] for q in range(3)], axis=1).astype(np.float64)
+        got_d = np.stack([lev["D"][q][sel] for q in range(3)], axis=1).astype(np.float64)
+        worst_o = max(worst_o, float((np.linalg.norm(got_o - o, axis=1) / r).max()))
+        worst_d = max(worst_d, float(np.linalg.norm(got_d - d, axis=1).max()))
+        n += int(sel.sum())
+    return n, worst_o, worst_d
+
+
+def test_the_rule_in_float64_on_the_fp32_inputs():
+    """Scenes C and D, every ray that leaves a glass sphere, grazing entries included: the rule evaluated in float64 from the same
+    fp32 P, N, V, r and ior against the restatement.  (Two Snell steps in float64, as the test above takes them on scene A, are no
+    measure here: the exit step is ill-conditioned in the fp32 inputs where k2 is small -- 0.003 for scene C's rays at ci 0.05 .. 0.07
+    into the ior-4 sphere, which give 1.47e-5 and 1.36e-5 in direction there, the next sphere's rays 4.4e-6 -- while the rule itself
+    stays within 4.3e-7.)  Measured on the CPU: scene C 9.16e-7 of r for the exit point and 4.32e-7 for
+    the direction over 576 rays, scene D 9.91e-7 and 3.96e-7 over 323; the bounds are four times the worst of the two."""
+    for scene in ("c", "d"):
+        s = SCENES[scene][0]()
+        n, worst_o, worst_d = rule_errors(s[6], s[4])
+        print("scene %s: %d rays through a sphere: exit point %.3g of r, direction %.3g" % (scene.upper(), n, worst_o, worst_d))
+        assert n >= 150
+        assert worst_o <= RULE_BOUND_O and worst_d <= RULE_BOUND_D
