@@ -3,6 +3,7 @@
 
 #include "../../include/rtx.h"
 #include "rtx_kernels.h"
+#include "rtx_materials.hpp"
 #include "rtx_mem.hpp"
 #include "rtx_plan.hpp"
 #include "rtx_sync.hpp"
@@ -279,38 +280,20 @@ struct rtx_ctx {
     std::vector<HitScratch> hit_scratch;
     std::vector<DeviceBuf<uint8_t>> hit_retired; // outgrown buffers that a recorded graph may still read
 
-    // one-bounce mirrors (rtx_scene_set_reflectivity): k by creation index, and how many objects have k > 0 (the path is taken
-    // while that is not 0, or under RTX_OPT_REFLECT_CHECK 2).  Then rtx_render_rows traces the closest hits, rtx_reflect_hit the
-    // secondary hits of the reflective pixels and rtx_reflect_shade shades and blends: 16 bytes per pixel of the stream's hit
-    // buffer.  The device copies -- spheres by index and by sorted position (rtx_sort_scene keeps h_sorted_idx), planes by index
-    // -- are uploaded at the next launch on the path after a change (refl_dirty); refl_gen tells recorded graphs they are stale.
-    std::vector<float> refl;
-    uint32_t n_reflective = 0;
-    bool refl_dirty = true;
-    uint64_t refl_gen = 0;
-    DeviceBuf<float> d_refl_sph, d_refl_sorted, d_refl_pl;
-    // checker patterns (rtx_scene_set_patterns, rtx_scene_set_object_pattern): the table (context state, like the lights), the slot
-    // of every object by creation index (with the objects, like refl) and how many objects have a slot above 0 -- while that is
-    // not 0 a frame that would be direct takes the light / shadow path, and every shade launch gets the device copies (PatternArgs).
-    // Those -- slots of the spheres by index and by sorted position, of the planes by index, and the packed table -- are uploaded
-    // with the reflectivities' (refl_dirty, upload_reflectivity); pat_gen tells recorded graphs they are stale.
-    rtx_pattern patterns[RTX_MAX_PATTERNS] = {};
+    // surface attributes by creation index (rtx_materials.hpp): the reflectivity k, the slot in the pattern table and the index of
+    // refraction, with their counts, the upload flag and the generations that tell recorded graphs they are stale.  While an object
+    // has k > 0 (or under RTX_OPT_REFLECT_CHECK 2) rtx_render_rows traces the closest hits, rtx_reflect_hit the secondary hits of the
+    // reflective pixels and rtx_reflect_shade shades and blends: 16 bytes per pixel of the stream's hit buffer.
+    rtxmat::Book materials;
+    rtx_pattern patterns[RTX_MAX_PATTERNS] = {}; // the table (rtx_scene_set_patterns): context state, like the lights
     size_t n_patterns = 0;
-    std::vector<uint8_t> pat_slot;
-    uint32_t n_patterned = 0;
-    uint64_t pat_gen = 0;
-    uint64_t stat_pattern_frames = 0;
-    DeviceBuf<uint8_t> d_pat_sph, d_pat_sorted, d_pat_pl;
-    DeviceBuf<rtxpattern::Entry> d_pat_table;
-    // glass (rtx_scene_set_refraction): the index of refraction of every object by creation index (with the objects, like refl;
-    // 0: a mirror) and how many are above 0 -- while that is not 0 the mirror path's launches get the device copies
-    // (ReflectArgs::ior_sph / ior_pl), uploaded with the reflectivities' in their three orders; ior_gen tells recorded graphs they
-    // are stale.
-    std::vector<float> ior;
-    uint32_t n_refractive = 0;
-    uint64_t ior_gen = 0;
-    uint64_t stat_refract_frames = 0;
-    DeviceBuf<float> d_ior_sph, d_ior_sorted, d_ior_pl;
+    uint64_t stat_pattern_frames = 0, stat_refract_frames = 0;
+    struct MaterialBufs { // the device copies, all uploaded at the next launch that reads any of them after a change (upload_materials)
+        rtxmat::Orders<DeviceBuf<float>> k, ior;
+        rtxmat::Orders<DeviceBuf<uint8_t>> slot;
+        DeviceBuf<rtxpattern::Entry> table;
+        DeviceBuf<uint32_t> pos; // rtxmat::position_map, for rtx_grid_reflect (RTX_OPT_REFLECT_GRID)
+    } d_mat;
     std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
     int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;
@@ -358,11 +341,9 @@ struct rtx_ctx {
 
     // mirror rays through that grid (RTX_OPT_REFLECT_GRID): in effect on the mirror path while RTX_OPT_REFLECT_CHECK is 0, the scene has a
     // sphere and the build found a usable grid; then rtx_grid_reflect writes the hit arrays in place of rtx_reflect_hit /
-    // rtx_reflect_chain.  d_refl_pos: creation index -> position of the sphere in the scene arrays (words [0, n)) and in the
-    // direction-sorted copy (words [n, 2 n), n = max(objects, 1)), uploaded with the reflectivities (refl_dirty) and valid as they are.
+    // rtx_reflect_chain, finding spheres through d_mat.pos.
     int64_t opt_reflect_grid = 0;
     uint64_t stat_reflect_grid_frames = 0;
-    DeviceBuf<uint32_t> d_refl_pos;
     DeviceBuf<uint32_t> d_reflect_grid_fallback; // rays of the last launch set on the path that tested every sphere (one word)
 
     // supersampling (RTX_OPT_SUPERSAMPLE): with S > 1 rtx_render_rows runs its launches for the S W x S H sample frame in values form

@@ -346,33 +346,7 @@ int rtx_remove_objects_here(rtx_ctx* ctx, const std::vector<uint32_t>& ascending
         if (moves[a / 4]) live[a]->swap(ctx->d_spare[a]);
     }
     // the books, all in one place: what a context holds to which the survivors were added in their order
-    std::vector<float> refl;
-    refl.reserve(plan.kind_of.size());
-    uint32_t n_reflective = 0;
-    size_t next = 0;
-    for (size_t i = 0; i < ctx->refl.size(); i++) {
-        if (next < n && ascending[next] == i) {
-            next++;
-            continue;
-        }
-        refl.push_back(ctx->refl[i]);
-        n_reflective += ctx->refl[i] > 0.0f ? 1u : 0u;
-    }
-    ctx->refl.swap(refl);
-    ctx->n_reflective = n_reflective; // (0: the mirror path is simply not taken any more)
-    // the pattern slots move with the survivors, as the reflectivities do
-    std::vector<uint8_t> slots = rtxplan::survivors_of(ctx->pat_slot, ascending);
-    ctx->pat_slot.swap(slots);
-    ctx->n_patterned = 0;
-    for (const uint8_t s : ctx->pat_slot) ctx->n_patterned += s != 0 ? 1u : 0u;
-    // ... and the indices of refraction
-    std::vector<float> iors = rtxplan::survivors_of(ctx->ior, ascending);
-    ctx->ior.swap(iors);
-    ctx->n_refractive = rtxrefract::count_refractive(ctx->ior);
-    ctx->refl_dirty = true;
-    ctx->refl_gen++;
-    ctx->pat_gen++;
-    ctx->ior_gen++;
+    ctx->materials.remove(ascending); // (no reflective object left: the mirror path is simply not taken any more)
     if (ctx->h_centres.size() == ctx->ns) {
         // the sort's input at the next re-sort, by sphere index
         size_t kept = 0, gone = 0;
@@ -704,7 +678,7 @@ int rtx_sort_scene(rtx_ctx* ctx, const float origin[3])
     RTX_HIP(ctx, hipGetLastError());
     RTX_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the staging vectors go out of scope; other streams may render next)
     ctx->sorted_gen = ctx->scene_gen;
-    ctx->h_sorted_idx.swap(order); // the reflectivities by sorted position follow this order (rtx_render.cpp, upload_reflectivity)
-    ctx->refl_dirty = true;
+    ctx->h_sorted_idx.swap(order);
+    ctx->materials.order_changed(); // the attributes by sorted position follow this order (rtx_render.cpp, upload_materials)
     return RTX_OK;
 }

@@ -9,8 +9,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <vector>
-
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #include <hip/hip_runtime.h>
 #define RTX_REFRACT_HD __host__ __device__
@@ -37,28 +35,6 @@ inline const char* values_fault(size_t n, const float* ior, size_t* bad = nullpt
         }
     }
     return nullptr;
-}
-
-// The host's books: the values by creation index (one per object, 0 for a new one) and how many of them are above 0.
-// call_fault: NULL, or why rtx_scene_set_refraction refuses objects first .. first+n-1 of `count`; store: a call that passed it.
-inline const char* call_fault(size_t count, unsigned first, size_t n, const float* ior, size_t* bad = nullptr)
-{
-    if (bad) *bad = n;
-    if (first > count || n > count - first) return "the range goes past rtx_scene_count";
-    return values_fault(n, ior, bad);
-}
-
-inline uint32_t count_refractive(const std::vector<float>& book)
-{
-    uint32_t c = 0;
-    for (const float v : book) c += v > 0.0f ? 1u : 0u;
-    return c;
-}
-
-inline void store(std::vector<float>& book, uint32_t& n_refractive, unsigned first, size_t n, const float* ior)
-{
-    for (size_t i = 0; i < n; i++) book[first + i] = ior[i] > 0.0f ? ior[i] : 0.0f; // (-0 is stored as 0)
-    n_refractive = count_refractive(book);
 }
 
 RTX_REFRACT_HD inline float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }

@@ -57,7 +57,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.lights_check = ctx->opt_lights_check != 0;
     q.n_lights = ctx->n_lights;
     q.light0_is_reference = std::memcmp(&ctx->lights[0], &ref, sizeof ref) == 0;
-    q.n_reflective = ctx->n_reflective;
+    q.n_reflective = ctx->materials.n_reflective();
     q.reflect_check = (int)ctx->opt_reflect_check;
     q.reflect_depth = (uint32_t)ctx->opt_reflect_depth;
     q.reflect_depth_check = ctx->opt_reflect_depth_check != 0;
@@ -65,7 +65,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.shadow_grid = ctx->opt_shadow_grid != 0;
     q.reflect_grid = ctx->opt_reflect_grid != 0;
     q.ns = ctx->ns;
-    q.n_patterned = ctx->n_patterned;
+    q.n_patterned = ctx->materials.n_patterned();
     return q;
 }
 
@@ -605,65 +605,29 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     return la;
 }
 
-// The device copies of the reflectivities after a change, a scene edit or a new sort: spheres by index and by sorted position,
-// planes by index (at least one entry each, so that the kernels always get an array); and, valid for the same generation, the
-// creation index -> position map of rtx_grid_reflect (rtx_ctx::d_refl_pos).  Waits for the frames in flight first.
-int upload_reflectivity(rtx_ctx* ctx)
+// The device copies of the book after a change, a scene edit or a new sort (rtx_materials.hpp: the three attributes in their three
+// orders), the packed pattern table and, valid for the same generation, rtx_grid_reflect's map.  Waits for the frames in flight first.
+int upload_materials(rtx_ctx* ctx)
 {
-    const size_t ns = ctx->ns, np = ctx->np;
-    std::vector<float> ks(ns > 0 ? ns : 1, 0.0f), kso(ks.size(), 0.0f), kp(np > 0 ? np : 1, 0.0f);
-    for (size_t g = 0; g < ctx->refl.size(); g++) {
-        (ctx->kind_of[g] == 2 ? ks : kp)[ctx->local_of[g]] = ctx->refl[g];
-    }
-    const bool sorted = ctx->h_sorted_idx.size() == ns && ns > 0;
-    for (size_t p = 0; sorted && p < ns; p++) kso[p] = ks[ctx->h_sorted_idx[p]];
-    const size_t no = ctx->refl.size() > 0 ? ctx->refl.size() : 1;
-    std::vector<uint32_t> pos(2 * no, 0u), sorted_pos_of(ns, 0u);
-    for (size_t p = 0; sorted && p < ns; p++) sorted_pos_of[ctx->h_sorted_idx[p]] = (uint32_t)p;
-    for (size_t g = 0; g < ctx->refl.size(); g++) {
-        if (ctx->kind_of[g] != 2) continue;
-        pos[g] = ctx->local_of[g];
-        pos[no + g] = sorted ? sorted_pos_of[ctx->local_of[g]] : ctx->local_of[g];
-    }
-    RTX_HIP(ctx, hipDeviceSynchronize());
-    for (const auto& pr : {std::make_pair(&ctx->d_refl_sph, &ks), std::make_pair(&ctx->d_refl_sorted, &kso), std::make_pair(&ctx->d_refl_pl, &kp)}) {
-        DeviceBuf<float>& d = *pr.first;
-        const std::vector<float>& h = *pr.second;
-        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing())); // (the device has just been waited for)
-        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    RTX_HIP(ctx, ctx->d_refl_pos.reserve(pos.size(), rtxmem::nothing()));
-    RTX_HIP(ctx, hipMemcpy(ctx->d_refl_pos.get(), pos.data(), pos.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    // the indices of refraction in the same three orders
-    std::vector<float> is(ks.size(), 0.0f), iso(ks.size(), 0.0f), ip(kp.size(), 0.0f);
-    for (size_t g = 0; g < ctx->ior.size(); g++) {
-        (ctx->kind_of[g] == 2 ? is : ip)[ctx->local_of[g]] = ctx->ior[g];
-    }
-    for (size_t p = 0; sorted && p < ns; p++) iso[p] = is[ctx->h_sorted_idx[p]];
-    for (const auto& pr : {std::make_pair(&ctx->d_ior_sph, &is), std::make_pair(&ctx->d_ior_sorted, &iso), std::make_pair(&ctx->d_ior_pl, &ip)}) {
-        DeviceBuf<float>& d = *pr.first;
-        const std::vector<float>& h = *pr.second;
-        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing()));
-        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    // the pattern slots in the same three orders, and the packed table (rtx_pattern.hpp): always all kMaxPatterns entries
-    std::vector<uint8_t> ss(ks.size(), 0), sso(ks.size(), 0), sp(kp.size(), 0);
-    for (size_t g = 0; g < ctx->pat_slot.size(); g++) {
-        (ctx->kind_of[g] == 2 ? ss : sp)[ctx->local_of[g]] = ctx->pat_slot[g];
-    }
-    for (size_t p = 0; sorted && p < ns; p++) sso[p] = ss[ctx->h_sorted_idx[p]];
-    for (const auto& pr : {std::make_pair(&ctx->d_pat_sph, &ss), std::make_pair(&ctx->d_pat_sorted, &sso), std::make_pair(&ctx->d_pat_pl, &sp)}) {
-        DeviceBuf<uint8_t>& d = *pr.first;
-        const std::vector<uint8_t>& h = *pr.second;
-        RTX_HIP(ctx, d.reserve(h.size(), rtxmem::nothing()));
-        RTX_HIP(ctx, hipMemcpy(d.get(), h.data(), h.size(), hipMemcpyHostToDevice));
-    }
-    rtxpattern::Entry table[rtxpattern::kMaxPatterns];
-    std::memset(table, 0, sizeof table);
+    std::vector<rtxpattern::Entry> table(rtxpattern::kMaxPatterns); // (always all of them, zeros past the table's count)
     for (size_t i = 0; i < ctx->n_patterns; i++) table[i] = rtxpattern::pack_entry(ctx->patterns[i]);
-    RTX_HIP(ctx, ctx->d_pat_table.reserve(rtxpattern::kMaxPatterns, rtxmem::nothing()));
-    RTX_HIP(ctx, hipMemcpy(ctx->d_pat_table.get(), table, sizeof table, hipMemcpyHostToDevice));
-    ctx->refl_dirty = false;
+    const auto upload = [](auto& to, const auto& h) { // host values -> a device buffer that holds at least as many (the device has just been waited for)
+        const hipError_t e = to.reserve(h.size(), rtxmem::nothing());
+        return e != hipSuccess ? e : hipMemcpy(to.get(), h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice);
+    };
+    const auto upload_orders = [&](auto& to, auto field) { // one attribute in its three orders
+        const auto h = rtxmat::layout_of(ctx->materials.column(field), ctx->kind_of, ctx->local_of, ctx->ns, ctx->np, ctx->h_sorted_idx);
+        hipError_t e = upload(to.sph, h.sph);
+        if (e == hipSuccess) e = upload(to.sph_sorted, h.sph_sorted);
+        return e != hipSuccess ? e : upload(to.pl, h.pl);
+    };
+    RTX_HIP(ctx, hipDeviceSynchronize());
+    RTX_HIP(ctx, upload_orders(ctx->d_mat.k, &rtxmat::Surface::k));
+    RTX_HIP(ctx, upload_orders(ctx->d_mat.ior, &rtxmat::Surface::ior));
+    RTX_HIP(ctx, upload_orders(ctx->d_mat.slot, &rtxmat::Surface::slot));
+    RTX_HIP(ctx, upload(ctx->d_mat.table, table));
+    RTX_HIP(ctx, upload(ctx->d_mat.pos, rtxmat::position_map(ctx->kind_of, ctx->local_of, ctx->ns, ctx->h_sorted_idx)));
+    ctx->materials.uploaded();
     return RTX_OK;
 }
 
@@ -677,12 +641,12 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     const bool mirror = shading_path(req) == kPathMirror;
     if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
     const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
-    if ((mirror || patterned) && ctx->refl_dirty) {
+    if ((mirror || patterned) && ctx->materials.stale()) {
         if (capturing) {
             return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
                                                                   : "graph capture: the pattern slots are not uploaded yet (render once before capturing)");
         }
-        if ((rc = upload_reflectivity(ctx)) != RTX_OK) return rc;
+        if ((rc = upload_materials(ctx)) != RTX_OK) return rc;
     }
     GridShadowArgs gs; // (never while capturing: check_recordable has refused)
     if (shading_wants_grid(req) && (rc = grid_shadow_args(ctx, stream, &gs, &req.grid_usable)) != RTX_OK) return rc;
@@ -737,10 +701,11 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     t.chain = &ca;
     t.deep = &cs;
     t.pattern = &pa;
+    const bool sorted_staging = a.sph_sorted_idx != nullptr; // the order this launch's a.sph_geom is in
     if (patterned) {
-        pa.slot_sph = a.sph_sorted_idx != nullptr ? ctx->d_pat_sorted.get() : ctx->d_pat_sph.get();
-        pa.slot_pl = ctx->d_pat_pl.get();
-        pa.table = ctx->d_pat_table.get();
+        pa.slot_sph = ctx->d_mat.slot.spheres(sorted_staging).get();
+        pa.slot_pl = ctx->d_mat.slot.pl.get();
+        pa.table = ctx->d_mat.table.get();
         pa.n = (uint32_t)ctx->n_patterns;
     }
     if (shade_takes_light_set(plan.family)) {
@@ -753,13 +718,13 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     if (mirror) {
         ra.hits = (const uint2*)hits;
         ra.hits2 = (uint2*)(hits + 8u * px); // level 1's
-        ra.k_sph = a.sph_sorted_idx != nullptr ? ctx->d_refl_sorted.get() : ctx->d_refl_sph.get();
-        ra.k_pl = ctx->d_refl_pl.get();
+        ra.k_sph = ctx->d_mat.k.spheres(sorted_staging).get();
+        ra.k_pl = ctx->d_mat.k.pl.get();
         ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
         ra.longest = ctx->d_reflect_longest.get();
-        if (ctx->n_refractive != 0) { // (else both stay nullptr: every secondary ray is the mirror's)
-            ra.ior_sph = a.sph_sorted_idx != nullptr ? ctx->d_ior_sorted.get() : ctx->d_ior_sph.get();
-            ra.ior_pl = ctx->d_ior_pl.get();
+        if (ctx->materials.n_refractive() != 0) { // (else both stay nullptr: every secondary ray is the mirror's)
+            ra.ior_sph = ctx->d_mat.ior.spheres(sorted_staging).get();
+            ra.ior_pl = ctx->d_mat.ior.pl.get();
         }
     }
     if (counts_rays) { // (rtx_grid_reflect at depth 1: one level into the two-level buffer)
@@ -787,8 +752,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         gr.scene_od = gs.scene_od;
         gr.large = gs.large;
         gr.n_large = gs.n_large;
-        // (the map's half for the order this launch's a.sph_geom is in)
-        gr.pos_of_gidx = ctx->d_refl_pos.get() + (a.sph_sorted_idx != nullptr ? (ctx->refl.size() > 0 ? ctx->refl.size() : 1) : 0);
+        gr.pos_of_gidx = ctx->d_mat.pos.get() + (sorted_staging ? rtxmat::map_stride(ctx->materials.size()) : 0); // (the map's half for that order)
         gr.fallback = ctx->d_reflect_grid_fallback.get();
         t.grid_reflect = &gr;
     }
@@ -818,7 +782,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     if (patterned) ctx->stat_pattern_frames++;
-    if (mirror && ctx->n_refractive != 0) ctx->stat_refract_frames++;
+    if (mirror && ctx->materials.n_refractive() != 0) ctx->stat_refract_frames++;
     return RTX_OK;
 }
 
@@ -1442,9 +1406,7 @@ void release_frozen_orders(rtx_ctx* ctx, const std::vector<uint64_t>& ids)
 struct rtx_graph_handle {
     hipGraphExec_t exec = nullptr;
     uint64_t scene_gen = 0;
-    uint64_t refl_gen = 0; // ... and the reflectivities (the mirror path's launches read their device copies)
-    uint64_t pat_gen = 0;  // ... and the pattern table and slots (a change alters which launches make a frame and what they read)
-    uint64_t ior_gen = 0;  // ... and the indices of refraction (the mirror path's launches read their device copies, or none)
+    rtxmat::Generations materials; // ... and the surface attributes: a change alters which launches make a frame and what they read
     std::vector<uint64_t> frozen; // dispatch-order sets its launches read (released by rtx_graph_destroy)
 };
 
@@ -1478,9 +1440,7 @@ int rtx_graph_end(rtx_ctx* ctx, void* stream_v, void** graph_out)
     }
     h->exec = exec;
     h->scene_gen = ctx->scene_gen;
-    h->refl_gen = ctx->refl_gen;
-    h->pat_gen = ctx->pat_gen;
-    h->ior_gen = ctx->ior_gen;
+    h->materials = ctx->materials.generations();
     h->frozen.swap(frozen);
     *graph_out = h;
     return RTX_OK;
@@ -1494,18 +1454,7 @@ int rtx_graph_launch(rtx_ctx* ctx, void* graph, void* stream_v)
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the scene was edited after this graph was recorded (its launches keep the old object "
                                                        "counts and array addresses): re-capture after a scene edit");
     }
-    if (h->refl_gen != ctx->refl_gen) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the reflectivities changed after this graph was recorded (its launches read "
-                                                       "the device copies, which the next launch replaces): re-capture");
-    }
-    if (h->pat_gen != ctx->pat_gen) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the pattern table or the objects' slots changed after this graph was recorded (its "
-                                                       "launches read the device copies, which the next launch replaces): re-capture");
-    }
-    if (h->ior_gen != ctx->ior_gen) {
-        return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "rtx_graph_launch: the indices of refraction changed after this graph was recorded (its launches "
-                                                       "read the device copies, which the next launch replaces): re-capture");
-    }
+    if (const char* stale = rtxmat::stale_fault(h->materials, ctx->materials.generations())) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, std::string("rtx_graph_launch: ") + stale);
     RTX_HIP(ctx, hipSetDevice(ctx->device));
     RTX_HIP(ctx, hipGraphLaunch(h->exec, stream_v ? (hipStream_t)stream_v : ctx->stream));
     return RTX_OK;

@@ -1,4 +1,4 @@
-// test_refract.cpp -- the glass of rtx_scene_set_refraction on the host (csrc/rtx_refract.hpp, csrc/rtx_plan.hpp):
+// test_refract.cpp -- the glass of rtx_scene_set_refraction on the host (csrc/rtx_refract.hpp):
 //   g++ -std=c++17 -O1 -g -ffp-contract=off -fsanitize=address,undefined tests/host/test_refract.cpp -o test_refract
 //   1. through_sphere -- the very expressions secondary_ray runs on the device, here with sqrtf and 1.0f / x -- against float64:
 //      Snell's refraction at entry, the intersection of the inner ray with the sphere, Snell's refraction at exit.  The fp32
@@ -11,8 +11,7 @@
 //   2. normal incidence gives d within the bound of -V; ior = 1 gives d within the bound of -V and o within the bound (of r) of
 //      the far side of the sphere, P - V (2 r ci);
 //   3. NaN inputs trap nowhere (the sanitizers see every operation), and a NaN c2 takes ct = 0;
-//   4. the host books: which values a call accepts, a range past the count, the count of refractive objects, clear, and the
-//      values under rtxplan::plan_removal's renumbering (survivors_of, as rtx_scene_remove_objects keeps them).
+//   4. which values a call accepts (the book they are stored in: csrc/rtx_materials.hpp, tests/host/test_materials.cpp).
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -20,10 +19,8 @@
 #include <random>
 #include <vector>
 
-#include "../../raytracing-in-windows-console_amd/csrc/rtx_plan.hpp"
 #include "../../raytracing-in-windows-console_amd/csrc/rtx_refract.hpp"
 
-using namespace rtxplan;
 using rtxrefract::through_sphere;
 
 static int g_failures = 0;
@@ -229,68 +226,23 @@ static void test_nan()
     CHECK(!rtxrefract::ior_ok(nan) && !rtxrefract::ior_ok(inf) && !rtxrefract::ior_ok(-inf));
 }
 
-// ---------------------------------------------------------------- 4. the host books
+// ---------------------------------------------------------------- 4. accepted values
 
-static void test_books()
+static void test_values()
 {
     const float nan = std::numeric_limits<float>::quiet_NaN();
     // values
     for (const float v : {0.0f, 1.0f, 1.5f, 4.0f, 1.0000001f}) CHECK(rtxrefract::ior_ok(v));
     for (const float v : {nan, 0.5f, 0.99999994f, 1.0e-30f, 4.0000005f, 100.0f, -1.0f, -1.5f, -1.0e-30f}) CHECK(!rtxrefract::ior_ok(v));
-    // a call: all or nothing
-    std::vector<float> book(5, 0.0f);
-    uint32_t n_refractive = 0;
-    const float two[2] = {1.5f, 0.0f}, with_nan[2] = {1.5f, nan}, low[1] = {0.5f};
+    // a call's values: all or nothing
+    const float two[2] = {1.5f, 0.0f}, with_nan[2] = {1.5f, nan}, low[1] = {0.5f}, minus_zero[1] = {-0.0f};
     size_t bad = 99;
-    CHECK(rtxrefract::call_fault(5, 0, 2, two, &bad) == nullptr);
-    CHECK(rtxrefract::call_fault(5, 3, 2, two) == nullptr);
-    CHECK(rtxrefract::call_fault(5, 5, 0, nullptr) == nullptr);
-    CHECK(rtxrefract::call_fault(5, 4, 2, two) != nullptr);          // a range past the count
-    CHECK(rtxrefract::call_fault(5, 6, 0, nullptr) != nullptr);
-    CHECK(rtxrefract::call_fault(5, 0, (size_t)-1, two) != nullptr); // (no overflow in first + n)
-    CHECK(rtxrefract::call_fault(5, 0, 2, nullptr) != nullptr);
-    CHECK(rtxrefract::call_fault(5, 0, 2, with_nan, &bad) != nullptr && bad == 1);
-    CHECK(rtxrefract::call_fault(5, 2, 1, low, &bad) != nullptr && bad == 0);
-    rtxrefract::store(book, n_refractive, 0, 2, two);
-    rtxrefract::store(book, n_refractive, 3, 2, two);
-    CHECK((book == std::vector<float>{1.5f, 0.0f, 0.0f, 1.5f, 0.0f}) && n_refractive == 2);
-    const float back[1] = {0.0f}, minus_zero[1] = {-0.0f};
-    rtxrefract::store(book, n_refractive, 0, 1, back);
-    CHECK(n_refractive == 1 && book[0] == 0.0f);
-    CHECK(rtxrefract::call_fault(5, 1, 1, minus_zero) == nullptr);
-    rtxrefract::store(book, n_refractive, 1, 1, minus_zero);
-    CHECK(n_refractive == 1 && !std::signbit(book[1]));
-    // removal: the values move with the survivors under the renumbering rule
-    std::mt19937_64 rng(5u);
-    for (int round = 0; round < 200; round++) {
-        const size_t n = 1 + rng() % 40;
-        std::vector<uint8_t> kind_of(n);
-        std::vector<float> iors(n);
-        for (size_t i = 0; i < n; i++) {
-            kind_of[i] = rng() % 4 == 0 ? 1 : 2;
-            iors[i] = rng() % 3 == 0 ? 1.0f + (float)(rng() % 300) * 0.01f : 0.0f;
-        }
-        std::vector<uint32_t> removed;
-        for (size_t i = 0; i < n; i++) {
-            if (rng() % 3 == 0) removed.push_back((uint32_t)i);
-        }
-        const RemovalPlan plan = plan_removal(kind_of, removed);
-        const std::vector<float> kept = survivors_of(iors, removed);
-        CHECK(kept.size() == plan.kind_of.size() && kept.size() == n - removed.size());
-        uint32_t want = 0;
-        for (size_t i = 0; i < n; i++) {
-            const uint32_t j = index_after_removal(removed, (uint32_t)i);
-            if (j == kNoIndex) continue;
-            CHECK(j < kept.size() && kept[j] == iors[i] && plan.kind_of[j] == kind_of[i]);
-            want += iors[i] > 0.0f ? 1u : 0u;
-        }
-        CHECK(rtxrefract::count_refractive(kept) == want);
-    }
-    CHECK((survivors_of(std::vector<float>{0.0f, 1.5f, 0.0f, 4.0f}, std::vector<uint32_t>{0}) == std::vector<float>{1.5f, 0.0f, 4.0f}));
-    // clear: no object, no value, nothing refractive; a range past the (empty) count is refused
-    book.clear();
-    CHECK(rtxrefract::count_refractive(book) == 0);
-    CHECK(rtxrefract::call_fault(0, 0, 1, two) != nullptr && rtxrefract::call_fault(0, 0, 0, nullptr) == nullptr);
+    CHECK(rtxrefract::values_fault(2, two, &bad) == nullptr && bad == 2);
+    CHECK(rtxrefract::values_fault(0, nullptr) == nullptr);
+    CHECK(rtxrefract::values_fault(2, nullptr) != nullptr);
+    CHECK(rtxrefract::values_fault(2, with_nan, &bad) != nullptr && bad == 1);
+    CHECK(rtxrefract::values_fault(1, low, &bad) != nullptr && bad == 0);
+    CHECK(rtxrefract::values_fault(1, minus_zero) == nullptr);
 }
 
 int main()
@@ -298,7 +250,7 @@ int main()
     const Worst w = test_against_float64();
     test_special_cases();
     test_nan();
-    test_books();
+    test_values();
     if (g_failures != 0) {
         std::printf("%d check(s) failed\n", g_failures);
         return 1;

@@ -1,6 +1,6 @@
 """Glass on the host (tests/host/test_refract.cpp under ASan + UBSan): csrc/rtx_refract.hpp's through_sphere -- the expressions
 secondary_ray runs on the device -- against two float64 Snell refractions with a real chord intersection, normal incidence and
-ior = 1, NaN inputs, and the host's books: accepted values, a range past the count, clear, and rtxplan::plan_removal's renumbering."""
+ior = 1, NaN inputs, and the values a call accepts (the book they are stored in: tests/host/test_materials.cpp)."""
 import os
 import shutil
 import subprocess
