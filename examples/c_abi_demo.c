@@ -23,6 +23,14 @@ int main(int argc, char** argv)
     rtx_scene_add_spheres(ctx, 5, &spheres[0][0]);
     const float pos[3] = {0.0f, -3.0f, 30.0f}, nrm[3] = {0.0f, 1.0f, 0.0f}, grey[3] = {100.0f, 100.0f, 100.0f};
     rtx_scene_add_plane(ctx, pos, nrm, grey, 10.0f, 20.0f);
+    {
+        /* the surface finish of sphere 0, here the one every object has (the reference's constants): the frame stays the reference's */
+        const rtx_finish finish = {0.2f, 1.0f, 1.0f, 5u};
+        if (rtx_scene_set_finish(ctx, 0, 1, &finish) != RTX_OK) {
+            fprintf(stderr, "rtx_scene_set_finish: %s\n", rtx_last_error(ctx));
+            return 1;
+        }
+    }
 
     rtx_params params;
     if (rtx_camera_params(W, H, NULL, NULL, &params) != RTX_OK) {

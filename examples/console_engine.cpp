@@ -14,6 +14,8 @@
 // cursor escape (RayTracingManager::SetHalfDeltaFrames, rtx_update_half_delta; no reference counterpart).
 // --glass: the mirror key (see below) then also gives every other sphere k = 0.85 and an index of refraction of 1.5
 // (Scene3D::SetRefraction, rtx_scene_set_refraction; no reference counterpart): glass balls over the floor.
+// --finish: the spheres cycle through four finishes as they are created -- matt, the default, glossy (exponent 2^7), glowing (0.8 of
+// their own colour under no light) -- and the floor is matt (Scene3D::SetFinish, rtx_scene_set_finish; no reference counterpart).
 // --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
 // no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
@@ -155,7 +157,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false, finish = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -171,13 +173,14 @@ int main(int argc, char** argv)
         else if (a == "--half") half = true; // W x 2H pixels as half blocks (RayTracingManager::SetHalfBlocks)
         else if (a == "--checker") checker = true; // a two-axis checker on the floor plane (Scene3D::SetPatterns, SetPlanePattern)
         else if (a == "--glass") glass = true; // the mirror key also turns every other sphere into glass (Scene3D::SetRefraction)
+        else if (a == "--finish") finish = true; // matt, default, glossy and glowing spheres over a matt floor (Scene3D::SetFinish)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--finish] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -229,6 +232,26 @@ int main(int argc, char** argv)
             scene->SetPatterns(&floor_checker, 1);
             scene->SetPlanePattern(1);
         }
+        unsigned finished = 0; // objects that have their finish (--finish)
+        const auto finish_new_objects = [&] {
+            rtx_ctx* const c = rtx_compat::Device::get(PrintMachine::GetWidth(), PrintMachine::GetHeight());
+            for (; finished < rtx_scene_count(c); finished++) {
+                int type = 0;
+                float row[11];
+                if (rtx_scene_get_object(c, finished, &type, row) != RTX_OK) continue;
+                if (type != 2) {
+                    scene->SetFinish(finished, 0.2f, 1.0f, 0.0f, 5u); // a plane: matt
+                    continue;
+                }
+                switch (finished % 4u) {
+                case 0: scene->SetFinish(finished, 0.2f, 1.0f, 0.0f, 5u); break; // matt
+                case 1: break;                                                   // the default
+                case 2: scene->SetFinish(finished, 0.2f, 1.0f, 1.5f, 7u); break; // glossy
+                default: scene->SetFinish(finished, 0.8f, 0.6f, 0.3f, 5u); break; // glowing
+                }
+            }
+        };
+        if (finish) finish_new_objects();
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;
         int bounces = 1;
@@ -359,6 +382,7 @@ int main(int argc, char** argv)
                     const MyMath::Vector3 pos(rand() % 100 - 50, rand() % 100 - 50, rand() % 100 - 50);
                     const MyMath::Vector3 col(rand() % 255, rand() % 255, rand() % 255);
                     scene->CreateSphere(radius, pos, col);
+                    if (finish) finish_new_objects();
                     if (trace) {
                         std::fprintf(trace, "spawn %a %a %a %a %a %a %a\n", (double)radius, (double)pos.x, (double)pos.y, (double)pos.z, (double)col.x,
                                      (double)col.y, (double)col.z);

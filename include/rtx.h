@@ -416,6 +416,10 @@ enum rtx_stat {
                                      * are taken.)  No reference counterpart (RayTracing.cu:635) */
     RTX_STAT_REFRACT_FRAMES = 91,   /* launch sets queued on the mirror path while that count is not 0: counted as RTX_STAT_SHADOW_FRAMES
                                      * counts.  No reference counterpart (RayTracing.cu:635) */
+    RTX_STAT_FINISHED_OBJECTS = 90, /* objects whose finish is not the default's 16 bytes (rtx_scene_set_finish).  (Numbered below the
+                                     * other counters: 91 .. 154 are taken.)  No reference counterpart (RayTracing.cu:143-157) */
+    RTX_STAT_FINISH_FRAMES = 89,    /* launch sets queued while that count is not 0: counted as RTX_STAT_PATTERN_FRAMES counts.  No
+                                     * reference counterpart (RayTracing.cu:143-157) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -617,6 +621,50 @@ int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);
 int rtx_scene_set_refraction(rtx_ctx* ctx, unsigned first, size_t n, const float* ior);
 /* The index of refraction of object `index` (0: a mirror).  No reference counterpart. */
 int rtx_scene_get_refraction(const rtx_ctx* ctx, unsigned index, float* ior);
+/* Surface finish: how strongly an object shows its own colour under no light, every light's diffuse term and every light's
+ * highlight, and how tight that highlight is.  The reference shades every object with its call-site constants (RayTracing.cu:73,
+ * 143-157): the default here.  16 bytes. */
+typedef struct rtx_finish {
+    float ambient;           /* ka: weight of the object colour under no light      (reference: 0.2f) */
+    float diffuse;           /* kd: weight of every light's diffuse term            (reference: 1)    */
+    float specular;          /* ks: weight of every light's specular term           (reference: 1)    */
+    uint32_t shininess_log2; /* m:  the Blinn-Phong exponent is 2^m, m in 0 .. 8    (reference: 5)    */
+} rtx_finish;
+/* The finish of objects first .. first+n-1 (creation indices, spheres and planes alike).  It belongs to an object as k and ior do:
+ * every new object has {0.2f, 1.0f, 1.0f, 5}; rtx_scene_clear forgets the values, rtx_scene_set_spheres and rtx_scene_set_plane
+ * keep them, and after rtx_scene_remove_objects the survivors keep theirs under the renumbering rule.  Accepted: ambient, diffuse
+ * and specular finite and in [0, 16] (-0.0f is stored as +0.0f), shininess_log2 <= 8.  All or nothing: a NaN or infinity, a
+ * negative value, a value above 16, m > 8, a range past rtx_scene_count or finishes == NULL with n > 0 changes nothing and returns
+ * RTX_ERR_INVALID_ARGUMENT, and rtx_last_error names the first offending object (on a device group: validated before any rank is
+ * touched, then applied to every rank).  While every object has the default finish every launch is what it is without this call,
+ * and the shade kernels load nothing more.  Otherwise a frame that would be one trace launch takes the closest-hit launch and
+ * rtx_shadow_shade, as a patterned frame does; every other frame keeps its launches, and the shade launch reads 16 more bytes per
+ * shaded hit.  Geometry is unchanged, so sorted copies, cell lists and the world grid stay valid; a graph recorded before a change
+ * is refused by rtx_graph_launch (re-capture).  The device copies are uploaded with the reflectivities', in the same three orders,
+ * at the cost of the one device wait stated at rtx_scene_set_reflectivity; recording right after a change fails with
+ * RTX_ERR_INVALID_ARGUMENT ("render once before capturing").  No new option and no new launch: shadows, light sets, mirrors and
+ * glass at any depth, the grid options, supersampling, half blocks, delta frames and device groups apply as they do without.
+ * The rule, for a visible pixel in the character modes (RGB_NORMALS and SDL are unaffected), at every level j of a mirror or glass
+ * chain with the finish (ka, kd, ks, m) of o_j.  In the rule of rtx_scene_set_lights three literals and one function give way to
+ * the object's values (q = r, g, b):
+ *   x_i   = clampf(dot(nn, h_i), 0, 1)                      as without a finish
+ *   si_i  = (float) sq^m((double) x_i)                      m squarings in double, rounded once to float (m = 5: the reference's
+ *                                                           pinned pow(x, 32); m = 0: x_i)
+ *   res_q = ka * od_q
+ *   for each light i, in the order given:
+ *   res_q = (res_q + (diffuse_iq * kd) * od_q) + specular_iq * ks
+ *   res_q * 255.0f ; minf(255.0f, .)
+ * diffuse_iq = ((colour_iq * diffuseIntensity_i) * dpow_i) * divDistance_i and specular_iq = ((colour_iq * si_i) * spow_i) *
+ * divDistance_i are formed as without a finish, with si_i in place of the 32nd power.  Every operation is rounded to fp32, nothing
+ * is reassociated or contracted; a light the pixel is shadowed from still enters with both powers 0; od is the object's colour
+ * after the checker pattern.  With the default finish the expression is the one without, operation for operation (x * 1.0f is
+ * exact, five squarings are the 32nd power).  Distance, glyph, normal, the shadow tests, which rays exist, the chain's fold with k
+ * and the record encoders do not depend on the finish.  As code, once: csrc/rtx_finish.hpp.
+ * Out of scope: a specular colour per object, emission that lights other objects, textures on the coefficients, Fresnel weighting,
+ * exponents that are not powers of two.  No reference counterpart (RayTracing.cu:73,143-157). */
+int rtx_scene_set_finish(rtx_ctx* ctx, unsigned first, size_t n, const rtx_finish* finishes);
+/* The finish of object `index`.  No reference counterpart. */
+int rtx_scene_get_finish(const rtx_ctx* ctx, unsigned index, rtx_finish* out);
 /* Checker patterns: a second colour per object, chosen by the parity of the lattice cell the hit point lies in.  The table holds
  * up to RTX_MAX_PATTERNS entries, slots 1 .. n; an object carries a slot (0: none, what every new object has).  36 bytes. */
 #define RTX_MAX_PATTERNS 16

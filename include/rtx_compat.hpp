@@ -464,6 +464,14 @@ public:
     // Extension, no reference counterpart (RayTracing.cu:635): glass.  The index of refraction of the object of creation index `index`
     // (rtx_scene_set_refraction: 0 a mirror, else in [1, 4]); it shows where the object's reflectivity is above 0.
     void SetRefraction(const unsigned index, const float ior) { check(rtx_scene_set_refraction(ctx(), index, 1, &ior), "rtx_scene_set_refraction"); }
+    // Extension, no reference counterpart (RayTracing.cu:73,143-157 shade every object with the same constants): the surface finish of
+    // the object of creation index `index` (rtx_scene_set_finish: the weights of its own colour under no light, of the lights'
+    // diffuse terms and of their highlights, each in [0, 16], and the Blinn-Phong exponent 2^shininess_log2, at most 2^8).
+    void SetFinish(const unsigned index, const float ambient, const float diffuse, const float specular, const unsigned shininess_log2)
+    {
+        const rtx_finish f = {ambient, diffuse, specular, shininess_log2};
+        check(rtx_scene_set_finish(ctx(), index, 1, &f), "rtx_scene_set_finish");
+    }
     // Extensions, no reference counterpart (RayTracing.cu:144 reads the one colour an object has): checker patterns.  The table of
     // up to RTX_MAX_PATTERNS entries (rtx_scene_set_patterns; entry i serves slot i + 1), the slot of the object of creation index
     // `index` (0: none), or of every plane this scene created (rtx_scene_set_object_pattern, a call per plane: the objects between

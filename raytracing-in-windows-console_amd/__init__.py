@@ -60,6 +60,7 @@ STAT_HALF_DELTA_FRAMES, STAT_HALF_DELTA_KEYFRAMES = 96, 95  # frames rtx_update_
 STAT_PATTERNED_OBJECTS, STAT_PATTERN_FRAMES = 94, 93  # objects with a pattern slot, and launch sets queued while there are some
 MAX_PATTERNS = 16
 STAT_REFRACTIVE_OBJECTS, STAT_REFRACT_FRAMES = 92, 91  # objects with ior > 0, and launch sets queued on the mirror path while there are some
+STAT_FINISHED_OBJECTS, STAT_FINISH_FRAMES = 90, 89  # objects whose finish is not the default, and launch sets queued while there are some
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
 STAT_REFLECT_SHADOW_POINTS = 142  # 142 .. 145: level 1 .. MAX_REFLECT_DEPTH
@@ -108,6 +109,12 @@ class Pattern(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("freq", C.c_float * 3), ("rgb", C.c_float * 3)]
 
 
+class Finish(C.Structure):
+    """struct rtx_finish: ambient, diffuse and specular weight and log2 of the Blinn-Phong exponent of one object (include/rtx.h,
+    rtx_scene_set_finish).  16 bytes."""
+    _fields_ = [("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("shininess_log2", C.c_uint32)]
+
+
 # struct rtx_ray (32 bytes) and struct rtx_ray_hit (8 bytes) as numpy structured types: what Context.query_rays takes and returns
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("skip", np.uint32)])
 RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.uint32)])
@@ -137,6 +144,11 @@ def make_light(pos=(1.0, 50.0, 0.0), diffuse_rgb=(1.0, 1.0, 1.0), diffuse_power=
 def make_pattern(origin=(0.0, 0.0, 0.0), freq=(1.0, 0.0, 1.0), rgb=(0.0, 0.0, 0.0)):
     """A Pattern; the defaults are a black one-unit checker for a floor."""
     return Pattern((C.c_float * 3)(*origin), (C.c_float * 3)(*freq), (C.c_float * 3)(*rgb))
+
+
+def make_finish(ambient=0.2, diffuse=1.0, specular=1.0, shininess_log2=5):
+    """A Finish; the defaults are the reference's call-site constants, which every new object has."""
+    return Finish(ambient, diffuse, specular, shininess_log2)
 
 
 # every symbol include/rtx.h declares: (name, restype, argtypes)
@@ -173,6 +185,8 @@ _SIGNATURES = [
     ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
     ("rtx_scene_set_refraction", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
     ("rtx_scene_get_refraction", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
+    ("rtx_scene_set_finish", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(Finish)]),
+    ("rtx_scene_get_finish", C.c_int, [_P, C.c_uint, C.POINTER(Finish)]),
     ("rtx_scene_set_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern)]),
     ("rtx_scene_get_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_object_pattern", C.c_int, [_P, C.c_uint, C.c_size_t, C.c_uint]),
@@ -530,6 +544,22 @@ class Context:
         out = C.c_float()
         self._check(lib().rtx_scene_get_refraction(self._h, index, C.byref(out)))
         return out.value
+
+    def set_finish(self, first, finishes):
+        """rtx_scene_set_finish: a Finish, or a sequence of them (or of (ambient, diffuse, specular, shininess_log2) tuples), for
+        objects first, first+1, ... (creation indices)."""
+        finishes = [finishes] if isinstance(finishes, Finish) else list(finishes)
+        arr = (Finish * max(len(finishes), 1))()
+        for i, f in enumerate(finishes):
+            f = f if isinstance(f, Finish) else make_finish(*f)
+            C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(Finish))
+        self._check(lib().rtx_scene_set_finish(self._h, first, len(finishes), arr if finishes else None))
+
+    def get_finish(self, index):
+        """rtx_scene_get_finish: the Finish of object `index`."""
+        out = Finish()
+        self._check(lib().rtx_scene_get_finish(self._h, index, C.byref(out)))
+        return out
 
     def set_patterns(self, patterns):
         """rtx_scene_set_patterns: the whole table, 0 .. MAX_PATTERNS Pattern values; entry i serves slot i + 1."""

@@ -280,17 +280,18 @@ struct rtx_ctx {
     std::vector<HitScratch> hit_scratch;
     std::vector<DeviceBuf<uint8_t>> hit_retired; // outgrown buffers that a recorded graph may still read
 
-    // surface attributes by creation index (rtx_materials.hpp): the reflectivity k, the slot in the pattern table and the index of
-    // refraction, with their counts, the upload flag and the generations that tell recorded graphs they are stale.  While an object
+    // surface attributes by creation index (rtx_materials.hpp): the reflectivity k, the slot in the pattern table, the index of
+    // refraction and the finish, with their counts, the upload flag and the generations that tell recorded graphs they are stale.  While an object
     // has k > 0 (or under RTX_OPT_REFLECT_CHECK 2) rtx_render_rows traces the closest hits, rtx_reflect_hit the secondary hits of the
     // reflective pixels and rtx_reflect_shade shades and blends: 16 bytes per pixel of the stream's hit buffer.
     rtxmat::Book materials;
     rtx_pattern patterns[RTX_MAX_PATTERNS] = {}; // the table (rtx_scene_set_patterns): context state, like the lights
     size_t n_patterns = 0;
-    uint64_t stat_pattern_frames = 0, stat_refract_frames = 0;
+    uint64_t stat_pattern_frames = 0, stat_refract_frames = 0, stat_finish_frames = 0;
     struct MaterialBufs { // the device copies, all uploaded at the next launch that reads any of them after a change (upload_materials)
         rtxmat::Orders<DeviceBuf<float>> k, ior;
         rtxmat::Orders<DeviceBuf<uint8_t>> slot;
+        rtxmat::Orders<DeviceBuf<rtx_finish>> finish;
         DeviceBuf<rtxpattern::Entry> table;
         DeviceBuf<uint32_t> pos; // rtxmat::position_map, for rtx_grid_reflect (RTX_OPT_REFLECT_GRID)
     } d_mat;

@@ -6,6 +6,7 @@
 // sqrt and division (hipcc's default), no reassociation, denormals kept.
 #pragma once
 
+#include "rtx_finish.hpp"
 #include "rtx_unit.hpp"
 
 #include <hip/hip_runtime.h>
@@ -376,6 +377,41 @@ __device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 norma
     res.x = 0.2f * od.x + diffuse.x * od.x + specular.x * 1.0f;
     res.y = 0.2f * od.y + diffuse.y * od.y + specular.y * 1.0f;
     res.z = 0.2f * od.z + diffuse.z * od.z + specular.z * 1.0f;
+    res = mulf(res, 255.0f);
+    return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
+}
+
+// shade_light() for an object with a finish (rtx_scene_set_finish; the rule: rtx_finish.hpp): the object's ka, kd and ks where
+// shade_light() has 0.2f, no factor and 1.0f, and the 2^m-th power where it has pow32.  With the default finish the result is
+// shade_light()'s bit for bit.
+template <class LightT>
+__device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 normal, V3 od, const LightT& L, float dpow, float spow, const rtx_finish& f)
+{
+    const V3 point = add(r.o, mulf(r.d, distance));
+    const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
+
+    V3 lightDir = sub(v3(L.px, L.py, L.pz), point);
+    float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
+    dist = dist * dist;
+    const float divDistance = rcp_cr(dist);
+    lightDir = normalize_gpu(lightDir);
+
+    const V3 nn = normalize_gpu(normal);
+    const V3 nv = normalize_gpu(viewDir);
+
+    const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
+    const V3 diffuse = v3(((L.dr * diffuseIntensity) * dpow) * divDistance, ((L.dg * diffuseIntensity) * dpow) * divDistance,
+                          ((L.db * diffuseIntensity) * dpow) * divDistance);
+
+    const V3 h = normalize_gpu(add(lightDir, nv));
+    const float specularIntensity = rtxfinish::power(clampf(dot(nn, h), 0.0f, 1.0f), f.shininess_log2);
+    const V3 specular = v3(((L.sr * specularIntensity) * spow) * divDistance, ((L.sg * specularIntensity) * spow) * divDistance,
+                           ((L.sb * specularIntensity) * spow) * divDistance);
+
+    V3 res;
+    res.x = rtxfinish::add_terms(rtxfinish::ambient(f.ambient, od.x), diffuse.x, f.diffuse, od.x, specular.x, f.specular);
+    res.y = rtxfinish::add_terms(rtxfinish::ambient(f.ambient, od.y), diffuse.y, f.diffuse, od.y, specular.y, f.specular);
+    res.z = rtxfinish::add_terms(rtxfinish::ambient(f.ambient, od.z), diffuse.z, f.diffuse, od.z, specular.z, f.specular);
     res = mulf(res, 255.0f);
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }

@@ -119,31 +119,31 @@ __global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const Ligh
 // The shade family of the grid path: lights_shade_body with level 0's dark set read from gs.dark0 instead of computed -- no cone,
 // no walk of the scene, no list in LDS -- for any set of 1 .. 8 lights.  REFLECT as there: 0 rtx_grid_shade, 1
 // rtx_grid_reflect_shade (one bounce), 2 rtx_grid_chain_shade, 3 rtx_grid_chain_shadow_shade (the deeper levels' words).
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_grid_shade(const KArgs a, const LightsArgs la, const uint32_t* dark0, const PatternArgs pa)
 {
     const ReflectArgs ra = {};
     const ChainArgs ca = {};
-    lights_shade_body<MODE, OUT, 0, true>(a, la, ra, ca, pa, nullptr, dark0);
+    lights_shade_body<MODE, OUT, 0, true, FIN>(a, la, ra, ca, pa, nullptr, dark0);
 }
 
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_grid_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const uint32_t* dark0, const PatternArgs pa)
 {
     const ChainArgs ca = {};
-    lights_shade_body<MODE, OUT, 1, true>(a, la, ra, ca, pa, nullptr, dark0);
+    lights_shade_body<MODE, OUT, 1, true, FIN>(a, la, ra, ca, pa, nullptr, dark0);
 }
 
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_grid_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const uint32_t* dark0,
                                                                  const PatternArgs pa)
 {
-    lights_shade_body<MODE, OUT, 2, true>(a, la, ra, ca, pa, nullptr, dark0);
+    lights_shade_body<MODE, OUT, 2, true, FIN>(a, la, ra, ca, pa, nullptr, dark0);
 }
 
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_grid_chain_shadow_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca,
                                                                         const ChainShadowArgs cs, const uint32_t* dark0, const PatternArgs pa)
 {
-    lights_shade_body<MODE, OUT, 3, true>(a, la, ra, ca, pa, cs.dark, dark0);
+    lights_shade_body<MODE, OUT, 3, true, FIN>(a, la, ra, ca, pa, cs.dark, dark0);
 }

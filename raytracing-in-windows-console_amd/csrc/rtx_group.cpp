@@ -518,6 +518,11 @@ int scene_set_refraction(rtx_ctx* root, unsigned first, size_t n, const float* i
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_refraction(m, first, n, ior); });
 }
 
+int scene_set_finish(rtx_ctx* root, unsigned first, size_t n, const rtx_finish* finishes)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_finish(m, first, n, finishes); });
+}
+
 int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns)
 {
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_patterns(m, n, patterns); });

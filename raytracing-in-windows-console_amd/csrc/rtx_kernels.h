@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "rtx_finish.hpp"
 #include "rtx_grid.hpp"
 #include "rtx_lights.hpp"
 #include "rtx_pattern.hpp"
@@ -162,13 +163,17 @@ struct ReflectArgs {
     const float* ior_pl;
 };
 
-// Checker patterns (rtx_scene_set_patterns), for the shade launches alone: the slot of every object and the table.  table ==
+// Checker patterns (rtx_scene_set_patterns) and finishes, for the shade launches alone: the slot of every object and the table.  table ==
 // nullptr (no object has a slot): nothing is loaded and od is the object's.  The device copies travel with the reflectivities'.
 struct PatternArgs {
     const uint8_t* slot_sph;          // slot of the spheres, by the position the trace kernels index them by (KArgs::sph_geom's order)
     const uint8_t* slot_pl;           // ... of the planes, by plane index
     const rtxpattern::Entry* table;   // entry s - 1 serves slot s
     uint32_t n;                       // entries; a slot above it (none is stored) counts as 0
+    // surface finishes (rtx_scene_set_finish): 16 bytes per object, ordered as slot_sph and slot_pl are; both nullptr while every
+    // object has the default finish -- then the launch is the family's kernel without finishes, which never reads them, else its FIN form
+    const rtx_finish* fin_sph;
+    const rtx_finish* fin_pl;
 };
 
 // Mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade

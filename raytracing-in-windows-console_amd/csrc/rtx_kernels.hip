@@ -745,25 +745,37 @@ extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const Til
     }();
     *hip_error = 0;
     if ((unsigned)family >= (unsigned)kShadeFamilies || !tile_args_ok(t, kFamilyTakes[family])) return nullptr;
-    const PatternArgs pa = t->pattern != nullptr ? *t->pattern : PatternArgs{nullptr, nullptr, nullptr, 0u};
-    return launch_shade(t->a, mode, kNames[family], hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+    const PatternArgs pa = t->pattern != nullptr ? *t->pattern : PatternArgs{nullptr, nullptr, nullptr, 0u, nullptr, nullptr};
+    if ((pa.fin_sph == nullptr) != (pa.fin_pl == nullptr)) return nullptr; // (finishes: both orders or none)
+    // the family's FIN form while some object has a finish of its own (rtx_scene_set_finish), else the form without: two kernels, not
+    // one with a uniform test -- a kernel's registers are those of its hungrier path, and with both paths in one the chain's grid
+    // families lost an occupancy step for every frame, finished or not (profiles/r36_finish_resource_usage.txt)
+    const auto launch = [&](auto m, auto o, auto fin, dim3 grid, dim3 block) {
         constexpr int M = decltype(m)::value, O = decltype(o)::value;
+        constexpr bool F = decltype(fin)::value;
         hipStream_t st = (hipStream_t)stream_v;
         switch (family) {
-        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, pa); break;
-        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, pa); break;
-        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect, pa); break;
-        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, pa); break;
-        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, pa); break;
+        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->shadow, pa); break;
+        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, pa); break;
+        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect, pa); break;
+        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, pa); break;
+        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, pa); break;
         case kLightsChainShadowShade:
-            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, pa);
+            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, pa);
             break;
-        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, t->dark0, pa); break;
-        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0, pa); break;
-        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0, pa); break;
+        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, t->dark0, pa); break;
+        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0, pa); break;
+        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0, pa); break;
         default:
-            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0, pa);
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0, pa);
             break;
+        }
+    };
+    return launch_shade(t->a, mode, kNames[family], hip_error, [&](auto m, auto o, dim3 grid, dim3 block) {
+        if (pa.fin_sph != nullptr) {
+            launch(m, o, std::true_type{}, grid, block);
+        } else {
+            launch(m, o, std::false_type{}, grid, block);
         }
     });
 }

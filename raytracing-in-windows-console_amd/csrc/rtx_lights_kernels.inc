@@ -59,10 +59,65 @@ __device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 norm
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 
+// add_light for an object with a finish (rtx_scene_set_finish; the rule: rtx_finish.hpp): kd and ks where add_light has no factor
+// and 1.0f, the 2^m-th power where it has pow32.
+__device__ __forceinline__ void add_light(V3& res, V3 point, V3 nn, V3 nv, V3 od, const rtxlights::PackedLight& L, float dpow, float spow, const rtx_finish& f)
+{
+    V3 lightDir = sub(v3(L.px, L.py, L.pz), point);
+    float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
+    dist = dist * dist;
+    const float divDistance = rcp_cr(dist);
+    lightDir = normalize_gpu(lightDir);
+
+    const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
+    const V3 diffuse = v3(((L.dr * diffuseIntensity) * dpow) * divDistance, ((L.dg * diffuseIntensity) * dpow) * divDistance,
+                          ((L.db * diffuseIntensity) * dpow) * divDistance);
+
+    const V3 h = normalize_gpu(add(lightDir, nv));
+    const float specularIntensity = rtxfinish::power(clampf(dot(nn, h), 0.0f, 1.0f), f.shininess_log2);
+    const V3 specular = v3(((L.sr * specularIntensity) * spow) * divDistance, ((L.sg * specularIntensity) * spow) * divDistance,
+                           ((L.sb * specularIntensity) * spow) * divDistance);
+
+    res.x = rtxfinish::add_terms(res.x, diffuse.x, f.diffuse, od.x, specular.x, f.specular);
+    res.y = rtxfinish::add_terms(res.y, diffuse.y, f.diffuse, od.y, specular.y, f.specular);
+    res.z = rtxfinish::add_terms(res.z, diffuse.z, f.diffuse, od.z, specular.z, f.specular);
+}
+
+// shade_lights for an object with a finish.
+__device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 normal, V3 od, const rtxlights::Block& ls, uint32_t shadowed, const rtx_finish& f)
+{
+    const V3 point = add(r.o, mulf(r.d, distance));
+    const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
+    const V3 nn = normalize_gpu(normal);
+    const V3 nv = normalize_gpu(viewDir);
+    V3 res = v3(rtxfinish::ambient(f.ambient, od.x), rtxfinish::ambient(f.ambient, od.y), rtxfinish::ambient(f.ambient, od.z));
+    for (uint32_t i = 0; i < ls.n; i++) {
+        const bool dark = ((shadowed >> i) & 1u) != 0u;
+        add_light(res, point, nn, nv, od, ls.light[i], dark ? 0.0f : ls.light[i].dpow, dark ? 0.0f : ls.light[i].spow, f);
+    }
+    res = mulf(res, 255.0f);
+    return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
+}
+
+// FIN (rtx_scene_set_finish: the forms launched while some object has a finish of its own): every shade_lights takes the finish of
+// the object it shades; without, nothing of it is compiled and the code is what it was before there were finishes.
+template <bool FIN>
+__device__ __forceinline__ V3 shade_lights_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const rtxlights::Block& ls,
+                                              uint32_t shadowed)
+{
+    if constexpr (FIN) {
+        return shade_lights(r, distance, normal, od, ls, shadowed, finish_of(pa, id));
+    } else {
+        return shade_lights(r, distance, normal, od, ls, shadowed);
+    }
+}
+
 // (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels; deep_dark: byte j - 1 the lights
 // level j is shadowed from)
+template <bool FIN>
 __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                       const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark);
+template <bool FIN>
 __device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                  const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at);
 
@@ -76,8 +131,8 @@ struct ShadeTablesShared {
 // lights_chain_blend); 3: a chain whose deeper levels were shadow-tested (RTX_OPT_REFLECT_SHADOWS: deep_dark, the words
 // rtx_chain_shadow left, laid out as the hits).  DARK0: level 0's dark set is read from dark0 (a word per pixel, laid out as the
 // hits: rtx_grid_shadow's output) instead of computed here -- no cone, no walk, no list in LDS.  What a value does not use is not
-// compiled.
-template <int MODE, int OUT, int REFLECT, bool DARK0 = false>
+// compiled.  FIN: the objects' finishes are read (shade_lights_of).
+template <int MODE, int OUT, int REFLECT, bool DARK0 = false, bool FIN = false>
 __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                   const uint32_t* deep_dark = nullptr, const uint32_t* dark0 = nullptr)
 {
@@ -124,33 +179,33 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
 
     // ---- shade with every light (both powers 0 for the lights the pixel is shadowed from) and encode
     if (any_hit) {
-        colour = shade_lights(ray, distance, normal, od, la.lights, dark);
+        colour = shade_lights_of<FIN>(pa, id, ray, distance, normal, od, la.lights, dark);
         if constexpr (REFLECT == 1) {
             if (distance <= cam.far) {
                 colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a),
-                                       [&](const Ray& r2, float t2, V3 n2, V3 od2) { return shade_lights(r2, t2, n2, od2, la.lights, 0u); });
+                                       [&](const Ray& r2, float t2, V3 n2, V3 od2, uint32_t id2) { return shade_lights_of<FIN>(pa, id2, r2, t2, n2, od2, la.lights, 0u); });
             }
         } else if constexpr (REFLECT == 2) {
-            if (distance <= cam.far) colour = lights_chain_blend(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a));
+            if (distance <= cam.far) colour = lights_chain_blend<FIN>(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a));
         } else if constexpr (REFLECT == 3) {
-            if (distance <= cam.far) colour = lights_chain_blend_dark(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a), deep_dark[px.at(a)]);
+            if (distance <= cam.far) colour = lights_chain_blend_dark<FIN>(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a), deep_dark[px.at(a)]);
         }
     }
     encode_and_store<MODE, OUT>(a, cam, s.digits, s.ramp, px.in_frame, px.newline_col, px.row, px.col, distance, normal, colour, shadingValue);
 }
 
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgs la, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
     const ChainArgs ca = {};
-    lights_shade_body<MODE, OUT, 0>(a, la, ra, ca, pa);
+    lights_shade_body<MODE, OUT, 0, false, FIN>(a, la, ra, ca, pa);
 }
 
 // The mirror path's third launch for a set of several lights: rtx_lights_shade's shading, then the blend.
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const PatternArgs pa)
 {
     const ChainArgs ca = {}; // (read only by the chain's blend, which is not compiled here)
-    lights_shade_body<MODE, OUT, 1>(a, la, ra, ca, pa);
+    lights_shade_body<MODE, OUT, 1, false, FIN>(a, la, ra, ca, pa);
 }

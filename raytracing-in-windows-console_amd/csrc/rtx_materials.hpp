@@ -1,9 +1,10 @@
 // rtx_materials.hpp -- the surface attributes every object carries by creation index (reflectivity, pattern slot, index of
-// refraction), stated once for the host: the book that holds them with their counts, the one upload flag and the generations
+// refraction, finish), stated once for the host: the book that holds them with their counts, the one upload flag and the generations
 // recorded graphs are checked against, and the layout of their device copies.  The book's operations are the only way the library
 // changes any of it.  Host only, no HIP header: g++ compiles it on its own (tests/host/test_materials.cpp).
 #pragma once
 
+#include "rtx_finish.hpp"
 #include "rtx_plan.hpp"
 #include "rtx_refract.hpp"
 
@@ -14,15 +15,16 @@ namespace rtxmat {
 
 // What a recorded graph is stale against, beside the scene generation: a change alters which launches make a frame and what they read.
 struct Generations {
-    uint64_t reflectivity = 0, pattern = 0, refraction = 0;
+    uint64_t reflectivity = 0, pattern = 0, refraction = 0, finish = 0;
 };
 
-// NULL, or why a graph recorded at `then` must not be replayed `now`: the first of the three that moved, in this order.
+// NULL, or why a graph recorded at `then` must not be replayed `now`: the first of the four that moved, in this order.
 inline const char* stale_fault(const Generations& then, const Generations& now)
 {
     if (then.reflectivity != now.reflectivity) return "the reflectivities changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     if (then.pattern != now.pattern) return "the pattern table or the objects' slots changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     if (then.refraction != now.refraction) return "the indices of refraction changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
+    if (then.finish != now.finish) return "the finishes changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     return nullptr;
 }
 
@@ -33,7 +35,13 @@ struct Surface {
     float k = 0.0f;   // reflectivity: 0 matt
     uint8_t slot = 0; // of the pattern table, from 1: 0 plain
     float ior = 0.0f; // index of refraction: 0 a mirror (if k > 0)
+    rtx_finish finish = rtxfinish::default_finish(); // ambient, diffuse and specular weight, shininess: the reference's constants
 };
+
+// Does a value count (n_reflective, n_patterned, n_refractive, n_finished)?
+inline bool counts(float v) { return v > 0.0f; }
+inline bool counts(uint8_t v) { return v != 0; }
+inline bool counts(const rtx_finish& f) { return !rtxfinish::is_default(f); }
 
 // The book.  Every set_* returns NULL for a good call, else what is wrong with it, and is all or nothing: a refused call has changed
 // nothing.  A change sets the flag (the device copies are stale until uploaded()) and moves the generation of what changed; a good
@@ -45,6 +53,7 @@ public:
     uint32_t n_reflective() const { return n_k_; }   // k > 0: while not 0 (or under RTX_OPT_REFLECT_CHECK 2) a frame takes the mirror path
     uint32_t n_patterned() const { return n_slot_; } // slot != 0: while not 0 a frame that would be direct takes the light / shadow path
     uint32_t n_refractive() const { return n_ior_; } // ior > 0: while not 0 the mirror path's launches get the ior arrays
+    uint32_t n_finished() const { return n_fin_; }   // finish not the default's bytes: while not 0 a frame that would be direct takes the light / shadow path
     bool stale() const { return stale_; }            // the device copies do not hold these values, this table or this sorted order yet
     const Generations& generations() const { return gen_; }
     template <class T>
@@ -83,6 +92,15 @@ public:
         return store(&Surface::ior, n_ior_, gen_.refraction, first, n, [&](size_t i) { return ior[i] > 0.0f ? ior[i] : 0.0f; }); // (-0 is stored as 0)
     }
 
+    // (*bad, if given: the first finish of the call that is refused, or n)
+    const char* set_finish(size_t first, size_t n, const rtx_finish* finishes, size_t* bad = nullptr)
+    {
+        if (bad) *bad = n;
+        if (const char* f = range_fault(size(), first, n)) return f;
+        if (const char* f = rtxfinish::values_fault(n, finishes, bad)) return f;
+        return store(&Surface::finish, n_fin_, gen_.finish, first, n, [&](size_t i) { return rtxfinish::stored(finishes[i]); }); // (-0 is stored as 0)
+    }
+
     const char* set_slot(size_t first, size_t n, size_t slot, size_t table_count)
     {
         if (const char* f = range_fault(size(), first, n)) return f;
@@ -106,7 +124,7 @@ private:
         for (size_t i = 0; i < n; i++) {
             T& v = edit()[first + i].*field;
             const T to = value_at(i);
-            count = count - (v > 0 ? 1u : 0u) + (to > 0 ? 1u : 0u);
+            count = count - (counts(v) ? 1u : 0u) + (counts(to) ? 1u : 0u);
             v = to;
         }
         if (n != 0) gen++;
@@ -119,13 +137,15 @@ private:
         n_k_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return s.k > 0.0f; });
         n_slot_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return s.slot != 0; });
         n_ior_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return s.ior > 0.0f; });
+        n_fin_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return counts(s.finish); });
         gen_.reflectivity++;
         gen_.pattern++;
         gen_.refraction++;
+        gen_.finish++;
     }
 
     std::vector<Surface> v_;
-    uint32_t n_k_ = 0, n_slot_ = 0, n_ior_ = 0;
+    uint32_t n_k_ = 0, n_slot_ = 0, n_ior_ = 0, n_fin_ = 0;
     bool stale_ = true;
     Generations gen_;
 };
@@ -142,7 +162,7 @@ template <class T>
 inline Orders<std::vector<T>> layout_of(const std::vector<T>& per_object, const std::vector<uint8_t>& kind_of, const std::vector<uint32_t>& local_of, size_t ns, size_t np,
                                         const std::vector<uint32_t>& sorted_idx)
 {
-    Orders<std::vector<T>> l{std::vector<T>(ns > 0 ? ns : 1, T(0)), std::vector<T>(ns > 0 ? ns : 1, T(0)), std::vector<T>(np > 0 ? np : 1, T(0))};
+    Orders<std::vector<T>> l{std::vector<T>(ns > 0 ? ns : 1, T()), std::vector<T>(ns > 0 ? ns : 1, T()), std::vector<T>(np > 0 ? np : 1, T())};
     for (size_t g = 0; g < per_object.size(); g++) (kind_of[g] == 2 ? l.sph : l.pl)[local_of[g]] = per_object[g];
     for (size_t p = 0; sorted_idx.size() == ns && p < ns; p++) l.sph_sorted[p] = l.sph[sorted_idx[p]];
     return l;

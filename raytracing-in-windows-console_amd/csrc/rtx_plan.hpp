@@ -1048,6 +1048,7 @@ inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n,
 //   mirror, RTX_OPT_REFLECT_GRID in effect: the secondary pass of either row is rtx_grid_reflect; nothing else of the row changes
 //   checker patterns (n_patterned != 0): a frame that would be direct takes the `shaded` row; nothing of any row changes -- the
 //   shade launches read the slots and the table (PatternArgs, rtx_kernels.h)
+//   surface finishes (n_finished != 0): the same -- the shade launches read the finishes (PatternArgs::fin_sph, fin_pl)
 //
 // The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
 // deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
@@ -1089,6 +1090,7 @@ struct ShadingRequest { // what the decision reads of the call, the options and 
     uint32_t ns = 0;
     bool grid_usable = false;        // the world grid was built and can be walked; known only after its build (shading_wants_grid)
     uint32_t n_patterned = 0;        // objects with a pattern slot above 0 (rtx_scene_set_object_pattern)
+    uint32_t n_finished = 0;         // objects whose finish is not the default (rtx_scene_set_finish)
 };
 
 struct ShadingPlan {
@@ -1115,6 +1117,7 @@ inline ShadePath shading_path(const ShadingRequest& q)
     if (q.n_reflective != 0 || q.reflect_check == 2) return kPathMirror; // (takes precedence, and runs the shadow test itself)
     if (q.shadows || q.n_lights != 1 || q.lights_check || !q.light0_is_reference) return kPathShaded;
     if (q.n_patterned != 0) return kPathShaded; // (a pattern is read by the shade launches alone: it adds no pass and no bytes)
+    if (q.n_finished != 0) return kPathShaded;  // (and so is a finish)
     return kPathDirect; // the state the reference has: every launch is the reference's
 }
 

@@ -66,6 +66,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.reflect_grid = ctx->opt_reflect_grid != 0;
     q.ns = ctx->ns;
     q.n_patterned = ctx->materials.n_patterned();
+    q.n_finished = ctx->materials.n_finished();
     return q;
 }
 
@@ -605,7 +606,7 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     return la;
 }
 
-// The device copies of the book after a change, a scene edit or a new sort (rtx_materials.hpp: the three attributes in their three
+// The device copies of the book after a change, a scene edit or a new sort (rtx_materials.hpp: the four attributes in their three
 // orders), the packed pattern table and, valid for the same generation, rtx_grid_reflect's map.  Waits for the frames in flight first.
 int upload_materials(rtx_ctx* ctx)
 {
@@ -625,6 +626,7 @@ int upload_materials(rtx_ctx* ctx)
     RTX_HIP(ctx, upload_orders(ctx->d_mat.k, &rtxmat::Surface::k));
     RTX_HIP(ctx, upload_orders(ctx->d_mat.ior, &rtxmat::Surface::ior));
     RTX_HIP(ctx, upload_orders(ctx->d_mat.slot, &rtxmat::Surface::slot));
+    RTX_HIP(ctx, upload_orders(ctx->d_mat.finish, &rtxmat::Surface::finish));
     RTX_HIP(ctx, upload(ctx->d_mat.table, table));
     RTX_HIP(ctx, upload(ctx->d_mat.pos, rtxmat::position_map(ctx->kind_of, ctx->local_of, ctx->ns, ctx->h_sorted_idx)));
     ctx->materials.uploaded();
@@ -641,10 +643,12 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     const bool mirror = shading_path(req) == kPathMirror;
     if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
     const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
-    if ((mirror || patterned) && ctx->materials.stale()) {
+    const bool finished = req.n_finished != 0 && shading_path(req) != kPathDirect; // (the same)
+    if ((mirror || patterned || finished) && ctx->materials.stale()) {
         if (capturing) {
-            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
-                                                                  : "graph capture: the pattern slots are not uploaded yet (render once before capturing)");
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror      ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
+                                                           : patterned ? "graph capture: the pattern slots are not uploaded yet (render once before capturing)"
+                                                                       : "graph capture: the finishes are not uploaded yet (render once before capturing)");
         }
         if ((rc = upload_materials(ctx)) != RTX_OK) return rc;
     }
@@ -707,6 +711,10 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         pa.slot_pl = ctx->d_mat.slot.pl.get();
         pa.table = ctx->d_mat.table.get();
         pa.n = (uint32_t)ctx->n_patterns;
+    }
+    if (finished) { // (else both stay nullptr: the shade launches run the code they ran before there were finishes)
+        pa.fin_sph = ctx->d_mat.finish.spheres(sorted_staging).get();
+        pa.fin_pl = ctx->d_mat.finish.pl.get();
     }
     if (shade_takes_light_set(plan.family)) {
         la = lights_args(ctx, hits);
@@ -782,6 +790,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     if (patterned) ctx->stat_pattern_frames++;
+    if (finished) ctx->stat_finish_frames++;
     if (mirror && ctx->materials.n_refractive() != 0) ctx->stat_refract_frames++;
     return RTX_OK;
 }

@@ -13,7 +13,19 @@
 
 // With REFLECT (the mirror path's third launch) each reflective pixel's secondary hit (ra.hits2) is shaded and blended into the
 // colour before it is encoded (reflect_blend); without, nothing of it is compiled.
-template <int MODE, int OUT, bool REFLECT>
+// FIN (rtx_scene_set_finish: the forms launched while some object has a finish of its own): every shade_light takes the finish of
+// the object it shades; without, nothing of it is compiled and the code is what it was before there were finishes.
+template <bool FIN>
+__device__ __forceinline__ V3 shade_light_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const KLight& L, float dpow, float spow)
+{
+    if constexpr (FIN) {
+        return shade_light(r, distance, normal, od, L, dpow, spow, finish_of(pa, id));
+    } else {
+        return shade_light(r, distance, normal, od, L, dpow, spow);
+    }
+}
+
+template <int MODE, int OUT, bool REFLECT, bool FIN>
 __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa, const ReflectArgs& ra, const PatternArgs& pa)
 {
     __shared__ float4 s_occ[kTileList];
@@ -84,11 +96,11 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
 
     // ---- shade with the light (both powers 0 in shadow) and encode
     if (any_hit) {
-        colour = shade_light(ray, distance, normal, od, sa.light, shadowed ? 0.0f : sa.light.dpow, shadowed ? 0.0f : sa.light.spow);
+        colour = shade_light_of<FIN>(pa, id, ray, distance, normal, od, sa.light, shadowed ? 0.0f : sa.light.dpow, shadowed ? 0.0f : sa.light.spow);
         if constexpr (REFLECT) {
             if (distance <= cam.far) {
-                colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a), [&](const Ray& r2, float t2, V3 n2, V3 od2) {
-                    return shade_light(r2, t2, n2, od2, sa.light, sa.light.dpow, sa.light.spow);
+                colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a), [&](const Ray& r2, float t2, V3 n2, V3 od2, uint32_t id2) {
+                    return shade_light_of<FIN>(pa, id2, r2, t2, n2, od2, sa.light, sa.light.dpow, sa.light.spow);
                 });
             }
         }
@@ -96,16 +108,16 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
     encode_and_store<MODE, OUT>(a, cam, s_digits, s_ramp, px.in_frame, px.newline_col, px.row, px.col, distance, normal, colour, shadingValue);
 }
 
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, const ShadowArgs sa, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
-    shade_body<MODE, OUT, false>(a, sa, ra, pa);
+    shade_body<MODE, OUT, false, FIN>(a, sa, ra, pa);
 }
 
 // The mirror path's third launch: rtx_shadow_shade's shading, then the blend.
-template <int MODE, int OUT>
+template <int MODE, int OUT, bool FIN = false>
 __global__ __launch_bounds__(kThreads) void rtx_reflect_shade(const KArgs a, const ShadowArgs sa, const ReflectArgs ra, const PatternArgs pa)
 {
-    shade_body<MODE, OUT, true>(a, sa, ra, pa);
+    shade_body<MODE, OUT, true, FIN>(a, sa, ra, pa);
 }

@@ -98,6 +98,15 @@ __device__ __forceinline__ Surface surface_of(const KArgs& a, const PatternArgs&
     return s;
 }
 
+// The finish of object `id` (rtx_scene_set_finish), for the FIN forms of the shade launches (launched only while pa.fin_sph and
+// pa.fin_pl are set): one 16-byte load by the index the od load used.  It is loaded where a level is shaded, not in surface_of:
+// level 0's shading comes after the shadow walk, and nothing more is held across that walk.
+__device__ __forceinline__ rtx_finish finish_of(const PatternArgs& pa, uint32_t id)
+{
+    const float4 f = (id & 0x80000000u) ? reinterpret_cast<const float4*>(pa.fin_pl)[id & 0x7fffffffu] : reinterpret_cast<const float4*>(pa.fin_sph)[id];
+    return rtx_finish{f.x, f.y, f.z, __float_as_uint(f.w)};
+}
+
 // ---------------------------------------------------------------- the walk over the scene's spheres
 
 // The scene is walked 512 spheres a step: two coalesced loads per thread, the next step's requested ahead.  keep(in0, c0, in1,
@@ -569,7 +578,7 @@ struct MayMeetBundles {
 };
 
 // Steps 4-6 for one pixel of the mirror path's shading launch: the secondary hit (ra.hits2[at]) shaded by shade(r2, t2, normal,
-// od) -- the light or lights at full powers, no shadow test there (the chain's launches have one: RTX_OPT_REFLECT_SHADOWS), no
+// od, object) -- the light or lights at full powers, no shadow test there (the chain's launches have one: RTX_OPT_REFLECT_SHADOWS), no
 // further bounce; black without a hit -- and blended with the local colour cl.  Pixels whose winner does not reflect keep cl.
 template <class Shade>
 __device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& ra, const PatternArgs& pa, const Ray& ray, float distance, V3 normal, uint32_t id,
@@ -583,7 +592,7 @@ __device__ __forceinline__ V3 reflect_blend(const KArgs& a, const ReflectArgs& r
     if (h.y != 0xffffffffu) {
         const float t2 = __uint_as_float(h.x);
         const Surface s2 = surface_of(a, pa, h.y, add(r2.o, mulf(r2.d, t2)));
-        cr = shade(r2, t2, s2.normal, s2.od);
+        cr = shade(r2, t2, s2.normal, s2.od, h.y);
     }
     const float w = 1.0f - k;
     return v3(minf(255.0f, cl.x * w + cr.x * k), minf(255.0f, cl.y * w + cr.y * k), minf(255.0f, cl.z * w + cr.z * k));
