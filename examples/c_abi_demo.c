@@ -31,6 +31,14 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    {
+        /* the cone of the one light, here none (dir (0,0,0): a point light, as the reference's is): the frame stays the reference's */
+        const rtx_spot spot = {{0.0f, 0.0f, 0.0f}, 0.0f, 0.0f};
+        if (rtx_scene_set_spots(ctx, 1, &spot) != RTX_OK) {
+            fprintf(stderr, "rtx_scene_set_spots: %s\n", rtx_last_error(ctx));
+            return 1;
+        }
+    }
 
     rtx_params params;
     if (rtx_camera_params(W, H, NULL, NULL, &params) != RTX_OK) {

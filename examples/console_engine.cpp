@@ -16,6 +16,8 @@
 // (Scene3D::SetRefraction, rtx_scene_set_refraction; no reference counterpart): glass balls over the floor.
 // --finish: the spheres cycle through four finishes as they are created -- matt, the default, glossy (exponent 2^7), glowing (0.8 of
 // their own colour under no light) -- and the floor is matt (Scene3D::SetFinish, rtx_scene_set_finish; no reference counterpart).
+// --spot: the light becomes a cone aimed at the scene's centre on the floor, full inside 18 degrees of its axis and gone beyond 26
+// (RayTracingManager::SetSpots, rtx_scene_set_spots; no reference counterpart): a lit disc with a soft edge.
 // --samples N: N x N rays per console cell, N in 1 .. 4, folded on the GPU (RayTracingManager::SetSupersampling, RTX_OPT_SUPERSAMPLE;
 // no reference counterpart): sphere rims get partial coverage instead of crawling cell by cell.
 //
@@ -157,7 +159,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false, finish = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false, finish = false, spot = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -174,13 +176,14 @@ int main(int argc, char** argv)
         else if (a == "--checker") checker = true; // a two-axis checker on the floor plane (Scene3D::SetPatterns, SetPlanePattern)
         else if (a == "--glass") glass = true; // the mirror key also turns every other sphere into glass (Scene3D::SetRefraction)
         else if (a == "--finish") finish = true; // matt, default, glossy and glowing spheres over a matt floor (Scene3D::SetFinish)
+        else if (a == "--spot") spot = true; // the light a cone aimed at the scene's centre (RayTracingManager::SetSpots)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
         else if (a == "--keys-only") keys_only = true; // input check without a GPU: raw mode on, print each decoded key, quit on x / Esc / end of input
         else if (a == "--trace" && i + 1 < argc) trace_path = argv[++i];
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--finish] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--finish] [--spot] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -226,6 +229,11 @@ int main(int argc, char** argv)
             if (half) rayTracingManager->SetHalfBlocks(true);
         }
         if (samples != 1) rayTracingManager->SetSupersampling(samples);
+        if (spot) {
+            // from the reference's light (1, 50, 0) down to the floor under the spheres, (5, -3, 28): cos 26 and cos 18 degrees
+            const rtx_spot cone = {{4.0f, -53.0f, 28.0f}, 0.898794f, 0.951057f};
+            rayTracingManager->SetSpots(&cone, 1);
+        }
         if (checker) {
             // dark cells of four world units across x and z; y does not count, so the pattern lies flat on the floor
             const rtx_pattern floor_checker = {{0.0f, 0.0f, 0.0f}, {0.25f, 0.0f, 0.25f}, {30.0f, 30.0f, 30.0f}};

@@ -420,6 +420,10 @@ enum rtx_stat {
                                      * other counters: 91 .. 154 are taken.)  No reference counterpart (RayTracing.cu:143-157) */
     RTX_STAT_FINISH_FRAMES = 89,    /* launch sets queued while that count is not 0: counted as RTX_STAT_PATTERN_FRAMES counts.  No
                                      * reference counterpart (RayTracing.cu:143-157) */
+    RTX_STAT_SPOT_LIGHTS = 88,      /* lights of the set that have a cone (rtx_scene_set_spots: a dir that is not (0,0,0)).  (Numbered below
+                                     * the other counters: 89 .. 154 are taken.)  No reference counterpart (RayTracing.cu:132) */
+    RTX_STAT_SPOT_FRAMES = 87,      /* launch sets queued while that count is not 0: counted as RTX_STAT_PATTERN_FRAMES counts.  No
+                                     * reference counterpart (RayTracing.cu:132) */
     RTX_STAT_CELL_CAPACITY_FLOOR = 107 /* entries per cell list the current grid is planned with at least (0: the default capacity has
                                      * sufficed); grown from the longest list the binning passes report */
 };
@@ -550,6 +554,49 @@ int rtx_scene_set_lights(rtx_ctx* ctx, size_t n, const rtx_light* lights);
 /* The set in use: writes min(capacity, n) lights to out (which may be NULL when capacity is 0) and always *n_out = n.
  * No reference counterpart (RayTracing.cu:132,143-157). */
 int rtx_scene_get_lights(const rtx_ctx* ctx, size_t capacity, rtx_light* out, size_t* n_out);
+/* Spot lights: a cone and a soft edge per light of the set.  rtx_scene_set_spots(ctx, n, spots) takes n = the number of lights in
+ * the set (RTX_STAT_LIGHTS; spots[i] belongs to light i) or n = 0 (spots may be NULL: every light is a point light again).  A dir
+ * of (0, 0, 0) leaves that light a point light, and its cosines are ignored.  All or nothing: a refused call changes nothing, returns
+ * RTX_ERR_INVALID_ARGUMENT and names the first offending light in rtx_last_error (on a device group: validated before any rank is
+ * touched, then applied to every rank).  Refused: any other n; spots == NULL with n > 0; a non-zero dir with a component that is
+ * not finite, or whose squared length, formed in double, lies outside [2^-40, 2^40]; a cosine that is not finite; cos_outer < -1;
+ * cos_inner > 1; cos_inner - cos_outer (one fp32 subtraction) below 2^-10 -- a hard edge is a narrow band.
+ * Stored, returned by rtx_scene_get_spots and read by the kernels: the axis a_q = (float)((double)dir_q / sqrt(dx^2 + dy^2 + dz^2)),
+ * formed in double, the two cosines, and inv = 1.0f / (cos_inner - cos_outer), one IEEE fp32 division on the host (at most 1024).
+ * A point light is stored as five zeros.
+ * THE RULE (as code, once: csrc/rtx_spot.hpp).  It applies to a visible pixel in the character modes; RGB_NORMALS and SDL are
+ * unaffected.  Wherever the rule of rtx_scene_set_lights enters the powers of light i at a point P -- level 0, and every level j
+ * of a mirror or glass chain at P_j -- they are replaced by dpow_i * w and spow_i * w.  With ld the shading's own lightDir after its
+ * normalise (normalize_gpu(L_i - P)):
+ *     m = (a_x * ld_x + a_y * ld_y) + a_z * ld_z
+ *     c = -m
+ *     x = (c - cos_outer) * inv
+ *     s = x > 0.0f ? (x < 1.0f ? x : 1.0f) : 0.0f        (a NaN x gives 0)
+ *     w = (s * s) * (3.0f - 2.0f * s)
+ * every operation rounded to fp32, nothing reassociated or contracted.  A point light has w = 1, and x * 1.0f is exact: a set
+ * without cones gives the bytes it gave before, operation for operation, from the kernels it launched before.  The finish weights,
+ * patterns, shadow tests and the chain's fold are unchanged, and so are distance, glyph and normal.  A light that is dark at a point
+ * still enters with both powers 0 -- the same float as dpow * 0.0f for a validated power.  So a light whose s at P is not above 0 is
+ * treated as dark at P without a segment test: with RTX_OPT_SHADOWS such a pixel is not pending for that light, adds nothing to the
+ * light's tile cone, and has no grid segment (neither walked nor counted in RTX_STAT_SHADOW_GRID_FALLBACK_POINTS).  With every cone
+ * missing the frame, RTX_STAT_SHADOW_LONGEST_LIST reads 0.
+ * The cones belong to the light set: rtx_scene_set_lights and rtx_scene_set_light (NULL included) replace the set, and every light
+ * is a point light afterwards -- set the lights first, then the cones.  rtx_scene_clear leaves the cones alone, as it leaves the
+ * lights.  The cones travel to the launches by value, as the light set does: a recorded graph keeps the cones it was recorded with,
+ * nothing is uploaded, no graph goes stale.  A cone on the reference's light alone, with shadows off, makes a frame that would be
+ * one launch the closest-hit launch and rtx_shadow_shade.  While a cone is set, the shade launch is the form of its family that
+ * also reads the finishes (default finishes where none was set): if no launch has uploaded the finishes yet, the first frame with a
+ * cone does, as the first frame with a finish would -- a graph capture cannot, so render once before capturing.  No reference
+ * counterpart (RayTracing.cu:132). */
+typedef struct rtx_spot {
+    float dir[3];     /* where the light points, any length; (0,0,0): a point light, the cosines are then ignored */
+    float cos_outer;  /* cosine of the angle from dir beyond which the light gives nothing */
+    float cos_inner;  /* cosine of the angle within which it gives its full powers */
+} rtx_spot;           /* 20 bytes */
+int rtx_scene_set_spots(rtx_ctx* ctx, size_t n, const rtx_spot* spots);
+/* The cones in use, as stored: writes min(capacity, n) entries to out (which may be NULL when capacity is 0) and always *n_out = the
+ * number of lights, as rtx_scene_get_lights does.  No reference counterpart (RayTracing.cu:132). */
+int rtx_scene_get_spots(const rtx_ctx* ctx, size_t capacity, rtx_spot* out, size_t* n_out);
 /* The most levels of secondary rays RTX_OPT_REFLECT_DEPTH takes.  No reference counterpart (RayTracing.cu:635). */
 #define RTX_MAX_REFLECT_DEPTH 4
 /* Mirror reflections: the reflectivity k in [0, 1] of objects first .. first+n-1 (creation indices, spheres and planes

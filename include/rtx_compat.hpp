@@ -741,6 +741,9 @@ public:
     // reference's) and hard shadows (RTX_OPT_SHADOWS).
     void SetLight(const rtx_light* light) { rtx_compat::check(m_ctx, rtx_scene_set_light(m_ctx, light), "rtx_scene_set_light"); }
     void SetLights(const rtx_light* lights, const size_t n) { rtx_compat::check(m_ctx, rtx_scene_set_lights(m_ctx, n, lights), "rtx_scene_set_lights"); }
+    // Extension, no reference counterpart (RayTracing.cu:132): a cone and a soft edge per light of the set (rtx_scene_set_spots: n the
+    // number of lights, or 0 for point lights again).  SetLight and SetLights clear the cones: set the lights first.
+    void SetSpots(const rtx_spot* spots, const size_t n) { rtx_compat::check(m_ctx, rtx_scene_set_spots(m_ctx, n, spots), "rtx_scene_set_spots"); }
     void SetShadows(const bool on) { rtx_compat::check(m_ctx, rtx_set_option(m_ctx, RTX_OPT_SHADOWS, on ? 1 : 0), "rtx_set_option(RTX_OPT_SHADOWS)"); }
     // Extension, no reference counterpart (RayTracing.cu:12-17 traces one ray per console cell): n x n rays per cell, n in 1 .. 4, folded
     // on the GPU (RTX_OPT_SUPERSAMPLE); Update then hands over the folded cells.  1 by default, and then nothing changes.

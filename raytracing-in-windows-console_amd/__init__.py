@@ -60,6 +60,7 @@ STAT_HALF_DELTA_FRAMES, STAT_HALF_DELTA_KEYFRAMES = 96, 95  # frames rtx_update_
 STAT_PATTERNED_OBJECTS, STAT_PATTERN_FRAMES = 94, 93  # objects with a pattern slot, and launch sets queued while there are some
 MAX_PATTERNS = 16
 STAT_REFRACTIVE_OBJECTS, STAT_REFRACT_FRAMES = 92, 91  # objects with ior > 0, and launch sets queued on the mirror path while there are some
+STAT_SPOT_LIGHTS, STAT_SPOT_FRAMES = 88, 87  # lights of the set that have a cone (rtx_scene_set_spots), and launch sets queued while there are some
 STAT_FINISHED_OBJECTS, STAT_FINISH_FRAMES = 90, 89  # objects whose finish is not the default, and launch sets queued while there are some
 STAT_SCENE_EDITS, STAT_SCENE_EDIT_MOVE = 148, 149
 STAT_SCENE_REMOVED = 150
@@ -115,6 +116,12 @@ class Finish(C.Structure):
     _fields_ = [("ambient", C.c_float), ("diffuse", C.c_float), ("specular", C.c_float), ("shininess_log2", C.c_uint32)]
 
 
+class Spot(C.Structure):
+    """struct rtx_spot: the cone of one light of the set (include/rtx.h, rtx_scene_set_spots): where it points, and the cosines of
+    the outer and the inner angle.  dir (0, 0, 0): a point light.  20 bytes."""
+    _fields_ = [("dir", C.c_float * 3), ("cos_outer", C.c_float), ("cos_inner", C.c_float)]
+
+
 # struct rtx_ray (32 bytes) and struct rtx_ray_hit (8 bytes) as numpy structured types: what Context.query_rays takes and returns
 RAY_DTYPE = np.dtype([("o", np.float32, 3), ("tmax", np.float32), ("d", np.float32, 3), ("skip", np.uint32)])
 RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("index", np.uint32)])
@@ -151,6 +158,11 @@ def make_finish(ambient=0.2, diffuse=1.0, specular=1.0, shininess_log2=5):
     return Finish(ambient, diffuse, specular, shininess_log2)
 
 
+def make_spot(dir=(0.0, 0.0, 0.0), cos_outer=0.0, cos_inner=0.0):
+    """A Spot; the defaults are a point light."""
+    return Spot((C.c_float * 3)(*dir), cos_outer, cos_inner)
+
+
 # every symbol include/rtx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _SIGNATURES = [
@@ -185,6 +197,8 @@ _SIGNATURES = [
     ("rtx_scene_get_reflectivity", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
     ("rtx_scene_set_refraction", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_float)]),
     ("rtx_scene_get_refraction", C.c_int, [_P, C.c_uint, C.POINTER(C.c_float)]),
+    ("rtx_scene_set_spots", C.c_int, [_P, C.c_size_t, C.POINTER(Spot)]),
+    ("rtx_scene_get_spots", C.c_int, [_P, C.c_size_t, C.POINTER(Spot), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_finish", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(Finish)]),
     ("rtx_scene_get_finish", C.c_int, [_P, C.c_uint, C.POINTER(Finish)]),
     ("rtx_scene_set_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern)]),
@@ -523,6 +537,28 @@ class Context:
             l = Light()
             C.memmove(C.byref(l), C.byref(arr[i]), C.sizeof(Light))
             out.append(l)
+        return out
+
+    def set_spots(self, spots):
+        """rtx_scene_set_spots: one Spot (or (dir, cos_outer, cos_inner) tuple) per light of the set, in the set's order, or an empty
+        sequence: every light a point light again.  Set the lights first: rtx_scene_set_lights clears the cones."""
+        spots = list(spots)
+        arr = (Spot * max(len(spots), 1))()
+        for i, sp in enumerate(spots):
+            sp = sp if isinstance(sp, Spot) else make_spot(*sp)
+            C.memmove(C.byref(arr[i]), C.byref(sp), C.sizeof(Spot))
+        self._check(lib().rtx_scene_set_spots(self._h, len(spots), arr if spots else None))
+
+    def get_spots(self):
+        """rtx_scene_get_spots: the cones in use as they are stored (unit axis, the two cosines), one Spot per light."""
+        arr = (Spot * MAX_LIGHTS)()
+        n = C.c_size_t()
+        self._check(lib().rtx_scene_get_spots(self._h, MAX_LIGHTS, arr, C.byref(n)))
+        out = []
+        for i in range(n.value):
+            sp = Spot()
+            C.memmove(C.byref(sp), C.byref(arr[i]), C.sizeof(Spot))
+            out.append(sp)
         return out
 
     def set_reflectivity(self, first, k):

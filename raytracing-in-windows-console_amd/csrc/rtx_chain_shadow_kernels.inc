@@ -1,6 +1,6 @@
 // rtx_chain_shadow_kernels.inc -- shadows seen in mirrors (RTX_OPT_REFLECT_SHADOWS): the launch between rtx_reflect_chain and the
 // chain's shade launch, included into namespace rtx of rtx_kernels.hip after rtx_tile_pass.inc, which holds every device function
-// it calls.  One instantiation: nothing is shaded or encoded here.
+// it calls.  Two instantiations (SPOT, below): nothing is shaded or encoded here.
 //
 // Level j (1 .. depth) of a pixel's chain that hit an object o_j has the hit point P_j = r_j.o + r_j.d * t_j (as shade_lights
 // forms `point`) and the normal n_j = surface_of(o_j, P_j).  Every thread walks its pixel's chain forward from the hits
@@ -32,7 +32,12 @@ struct ChainShadowShared {
 #ifndef RTX_CHAIN_SHADOW_WAVES
 #define RTX_CHAIN_SHADOW_WAVES 6 // (an experiment build may ask for another figure: make variant DEFS=-DRTX_CHAIN_SHADOW_WAVES=1)
 #endif
-__global__ __launch_bounds__(kThreads, RTX_CHAIN_SHADOW_WAVES) void rtx_chain_shadow(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const ChainShadowArgs cs)
+// SPOT (rtx_scene_set_spots: the form launched while some light of the set has a cone, its arguments the set with the cones behind
+// it): a level's point outside a light's cone is not pending for that light (lights_dark_set) -- it adds nothing to the light's tile
+// cone and tests no segment.  Without SPOT the code is what it was.
+template <bool SPOT>
+__global__ __launch_bounds__(kThreads, RTX_CHAIN_SHADOW_WAVES) void rtx_chain_shadow(const KArgs a, const LightsArgsOf<SPOT> la, const ReflectArgs ra, const ChainArgs ca,
+                                                                                     const ChainShadowArgs cs)
 {
     __shared__ ChainShadowShared s;
 

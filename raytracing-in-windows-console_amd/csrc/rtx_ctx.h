@@ -266,6 +266,8 @@ struct rtx_ctx {
     // more (or RTX_OPT_LIGHTS_CHECK 1) shade with rtx_lights_shade / rtx_lights_reflect_shade, which get the set by value.
     rtx_light lights[RTX_MAX_LIGHTS] = {rtx_reference_light()};
     size_t n_lights = 1;
+    rtxspot::Block spots = {}; // the cones of the set (rtx_scene_set_spots), as stored: all zero while every light is a point light
+    uint64_t stat_spot_frames = 0;
     int64_t opt_lights_check = 0;
     int64_t opt_shadows = 0;
     int64_t opt_shadow_check = 0;

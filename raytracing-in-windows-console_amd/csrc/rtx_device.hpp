@@ -7,6 +7,7 @@
 #pragma once
 
 #include "rtx_finish.hpp"
+#include "rtx_spot.hpp"
 #include "rtx_unit.hpp"
 
 #include <hip/hip_runtime.h>
@@ -383,9 +384,11 @@ __device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 norma
 
 // shade_light() for an object with a finish (rtx_scene_set_finish; the rule: rtx_finish.hpp): the object's ka, kd and ks where
 // shade_light() has 0.2f, no factor and 1.0f, and the 2^m-th power where it has pow32.  With the default finish the result is
-// shade_light()'s bit for bit.
+// shade_light()'s bit for bit.  The light's cone (rtx_scene_set_spots; the rule: rtx_spot.hpp): both powers times w, which is
+// exactly 1 for a point light.
 template <class LightT>
-__device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 normal, V3 od, const LightT& L, float dpow, float spow, const rtx_finish& f)
+__device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 normal, V3 od, const LightT& L, float dpow, float spow, const rtx_finish& f,
+                                          const rtxspot::Packed& sp)
 {
     const V3 point = add(r.o, mulf(r.d, distance));
     const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
@@ -395,6 +398,9 @@ __device__ __forceinline__ V3 shade_light(const Ray& r, float distance, V3 norma
     dist = dist * dist;
     const float divDistance = rcp_cr(dist);
     lightDir = normalize_gpu(lightDir);
+    const float w = rtxspot::weight(sp, lightDir.x, lightDir.y, lightDir.z);
+    dpow = dpow * w;
+    spow = spow * w;
 
     const V3 nn = normalize_gpu(normal);
     const V3 nv = normalize_gpu(viewDir);

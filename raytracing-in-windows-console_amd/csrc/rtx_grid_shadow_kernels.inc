@@ -2,12 +2,12 @@
 // rtx_kernels.hip after rtx_tile_pass.inc, which holds every device function of the test, and after the lights' kernel files, whose
 // lights_shade_body the shade family below instantiates.
 //
-// rtx_grid_shadow: one instantiation, nothing shaded or encoded.  A 256-thread workgroup owns a 16 x 16 tile as the other tile
+// rtx_grid_shadow: two instantiations (SPOT, below), nothing shaded or encoded.  A 256-thread workgroup owns a 16 x 16 tile as the other tile
 // passes do, so that neighbouring pixels walk neighbouring cells, but there is no list in LDS and no barrier: every pixel is on
 // its own.  Each thread rebuilds its pixel exactly as lights_shade_body and rtx_chain_shadow do (tile_pixel, surface_of, the
 // forward walk of the chain with reflectivity_of / secondary_ray: the same operations on the same bits, so P_j, n_j, o_j are theirs)
 // and decides for level 0 -- and for the levels 1 .. depth when gs.deep is set (RTX_OPT_REFLECT_SHADOWS in effect) -- and every
-// light of the set whether the point is dark: shadowed_before_spheres unchanged (self-shadow and planes), then segment_hits_sphere
+// light of the set whether the point is dark: shadowed_before_spheres unchanged (the light's cone, self-shadow and planes), then segment_hits_sphere
 // against the spheres of the grid's large list, then against the lists of the cells the segment's walk visits (rtx_grid.hpp:
 // walk_start / walk_step with d = toL and tmax = 1), leaving at the first hit.  The test is the brute path's; only which spheres a
 // segment is tested against changes, and rtx_grid.hpp (step 4) shows that no sphere the test would report is left out.  The lists
@@ -22,7 +22,8 @@
 
 // The lights (bit i) the point P -- normal `normal`, on object `id` -- is shadowed from: lights_dark_set's answer, per pixel.
 // Called by every lane of the wave (shadowed_before_spheres and the loops above vote).
-__device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LightsArgs& la, const GridShadowArgs& gs, V3 P, V3 normal, uint32_t id, bool testable,
+template <class LA>
+__device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LA& la, const GridShadowArgs& gs, V3 P, V3 normal, uint32_t id, bool testable,
                                                   uint32_t& n_fallback)
 {
     const bool on_plane = (id & 0x80000000u) != 0u;
@@ -36,7 +37,7 @@ __device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LightsAr
         const V3 L = v3(Lt.px, Lt.py, Lt.pz);
         const V3 toL = sub(L, P);
         bool pending = testable;
-        if (shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending)) dark |= 1u << i;
+        if (shadowed_before_spheres(a, la, i, P, normal, L, toL, own_plane, pending)) dark |= 1u << i;
         if (grid_segment_dark(a, gs, P, toL, own_gidx, own_pos, pending, n_fallback)) dark |= 1u << i;
     }
     return dark;
@@ -53,7 +54,11 @@ __device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LightsAr
 #else
 #define RTX_GRID_SHADOW_BOUNDS __launch_bounds__(kThreads)
 #endif
-__global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const ChainShadowArgs cs,
+// SPOT (rtx_scene_set_spots: the form launched while some light of the set has a cone, its arguments the set with the cones behind
+// it): a point outside a light's cone is not pending for that light -- no plane test, no segment, walked or counted -- and not dark
+// either: the shade launch weighs that light with 0 there.  The same launch bounds.  Without SPOT the code is what it was.
+template <bool SPOT>
+__global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const LightsArgsOf<SPOT> la, const ReflectArgs ra, const ChainArgs ca, const ChainShadowArgs cs,
                                                             const GridShadowArgs gs)
 {
     const uint32_t tid = threadIdx.x;
@@ -120,7 +125,7 @@ __global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const Ligh
 // no walk of the scene, no list in LDS -- for any set of 1 .. 8 lights.  REFLECT as there: 0 rtx_grid_shade, 1
 // rtx_grid_reflect_shade (one bounce), 2 rtx_grid_chain_shade, 3 rtx_grid_chain_shadow_shade (the deeper levels' words).
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_grid_shade(const KArgs a, const LightsArgs la, const uint32_t* dark0, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_grid_shade(const KArgs a, const LightsArgsOf<FIN> la, const uint32_t* dark0, const PatternArgs pa)
 {
     const ReflectArgs ra = {};
     const ChainArgs ca = {};
@@ -128,21 +133,21 @@ __global__ __launch_bounds__(kThreads) void rtx_grid_shade(const KArgs a, const 
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_grid_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const uint32_t* dark0, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_grid_reflect_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const uint32_t* dark0, const PatternArgs pa)
 {
     const ChainArgs ca = {};
     lights_shade_body<MODE, OUT, 1, true, FIN>(a, la, ra, ca, pa, nullptr, dark0);
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_grid_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const uint32_t* dark0,
+__global__ __launch_bounds__(kThreads) void rtx_grid_chain_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const ChainArgs ca, const uint32_t* dark0,
                                                                  const PatternArgs pa)
 {
     lights_shade_body<MODE, OUT, 2, true, FIN>(a, la, ra, ca, pa, nullptr, dark0);
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_grid_chain_shadow_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca,
+__global__ __launch_bounds__(kThreads) void rtx_grid_chain_shadow_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const ChainArgs ca,
                                                                         const ChainShadowArgs cs, const uint32_t* dark0, const PatternArgs pa)
 {
     lights_shade_body<MODE, OUT, 3, true, FIN>(a, la, ra, ca, pa, cs.dark, dark0);

@@ -523,6 +523,11 @@ int scene_set_finish(rtx_ctx* root, unsigned first, size_t n, const rtx_finish* 
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_finish(m, first, n, finishes); });
 }
 
+int scene_set_spots(rtx_ctx* root, size_t n, const rtx_spot* spots)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_spots(m, n, spots); });
+}
+
 int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns)
 {
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_patterns(m, n, patterns); });

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "rtx_finish.hpp"
 #include "rtx_grid.hpp"
 #include "rtx_lights.hpp"
@@ -146,6 +148,21 @@ struct LightsArgs {
     uint32_t brute;          // 1: no culling, every sphere a candidate for every live light (RTX_OPT_SHADOW_CHECK 1)
     uint32_t* longest;       // atomicMax of the most list entries a workgroup held, or nullptr
 };
+
+// Spot lights (rtx_scene_set_spots): the same arguments with the cones behind them, by value as the lights are.  Only the launches
+// that read cones take these -- the FIN forms of the shade families (which then read finishes and cones: launched while an object
+// has a finish or a light has a cone) and the SPOT forms of the two shadow passes; every other kernel's argument block is what it
+// was before there were cones.
+struct SpotShadowArgs : ShadowArgs {
+    rtxspot::Packed spot;    // light 0's
+};
+struct SpotLightsArgs : LightsArgs {
+    rtxspot::Block spots;    // spot[i] belongs to lights.light[i]
+};
+template <bool SPOT>
+using ShadowArgsOf = std::conditional_t<SPOT, SpotShadowArgs, ShadowArgs>;
+template <bool SPOT>
+using LightsArgsOf = std::conditional_t<SPOT, SpotLightsArgs, LightsArgs>;
 
 // The mirror path (rtx_scene_set_reflectivity): its second launch (rtx_reflect_hit) traces one secondary ray per reflective pixel
 // from the first launch's closest hits and writes its closest hit; its third (rtx_reflect_shade) shades as rtx_shadow_shade and
@@ -299,6 +316,7 @@ struct TileArgs {
     const KArgs* a;
     const ShadowArgs* shadow;      // rtx_shadow_shade, rtx_reflect_shade
     const LightsArgs* lights;      // every other family; rtx_chain_shadow, rtx_grid_shadow
+    const rtxspot::Block* spots;   // the cones of the set (rtx_scene_set_spots), or NULL while no light has one: the forms that read cones
     const ReflectArgs* reflect;    // the mirror path
     const ChainArgs* chain;        // ... through the chain kernels
     const ChainShadowArgs* deep;   // ... with the deeper levels shadow-tested

@@ -700,6 +700,32 @@ static bool tile_args_ok(const TileArgs* t, unsigned takes)
     return true;
 }
 
+// The arguments of the forms that read cones (rtx_scene_set_spots): the light set with the cones behind it, the one light with its
+// own.  No cones given (a FIN form launched for the finishes alone): every light a point light.
+static SpotLightsArgs spot_lights_args(const TileArgs* t)
+{
+    SpotLightsArgs la;
+    memset(&la, 0, sizeof la);
+    static_cast<LightsArgs&>(la) = *t->lights;
+    if (t->spots != nullptr) la.spots = *t->spots;
+    return la;
+}
+
+static SpotShadowArgs spot_shadow_args(const TileArgs* t)
+{
+    SpotShadowArgs sa;
+    memset(&sa, 0, sizeof sa);
+    static_cast<ShadowArgs&>(sa) = *t->shadow;
+    if (t->spots != nullptr) sa.spot = t->spots->spot[0];
+    return sa;
+}
+
+// The largest argument block of any launch is rtx_grid_chain_shadow_shade's in its FIN form: it must fit the 4 KB a kernel may take.
+static_assert(sizeof(KArgs) + sizeof(SpotLightsArgs) + sizeof(ReflectArgs) + sizeof(ChainArgs) + sizeof(ChainShadowArgs) + sizeof(const uint32_t*) + sizeof(PatternArgs) + 7 * 8 <= 4096,
+              "rtx_grid_chain_shadow_shade's arguments, each aligned to 8, exceed the kernel-argument limit");
+static_assert(sizeof(KArgs) + sizeof(SpotLightsArgs) + sizeof(ReflectArgs) + sizeof(ChainArgs) + sizeof(ChainShadowArgs) + sizeof(GridShadowArgs) + 6 * 8 <= 4096,
+              "the arguments of rtx_grid_shadow's SPOT form, each aligned to 8, exceed the kernel-argument limit");
+
 extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs* t, void* stream_v, int* hip_error)
 {
     using namespace rtx;
@@ -718,13 +744,24 @@ extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs
         hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, st, *t->a, *t->reflect, *t->chain);
         name = "rtx_reflect_chain";
         break;
+    // (the two shadow passes: their SPOT form while some light of the set has a cone -- rtx_scene_set_spots -- else the kernel they were)
     case rtxplan::kPassChainShadow:
-        hipLaunchKernelGGL(rtx_chain_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
-        name = "rtx_chain_shadow";
+        if (t->spots != nullptr) {
+            hipLaunchKernelGGL(rtx_chain_shadow<true>, grid, block, 0, st, *t->a, spot_lights_args(t), *t->reflect, *t->chain, *t->deep);
+            name = "rtx_chain_shadow<spot>";
+        } else {
+            hipLaunchKernelGGL(rtx_chain_shadow<false>, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep);
+            name = "rtx_chain_shadow";
+        }
         break;
     case rtxplan::kPassGridShadow:
-        hipLaunchKernelGGL(rtx_grid_shadow, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, *t->grid);
-        name = "rtx_grid_shadow";
+        if (t->spots != nullptr) {
+            hipLaunchKernelGGL(rtx_grid_shadow<true>, grid, block, 0, st, *t->a, spot_lights_args(t), *t->reflect, *t->chain, *t->deep, *t->grid);
+            name = "rtx_grid_shadow<spot>";
+        } else {
+            hipLaunchKernelGGL(rtx_grid_shadow<false>, grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, *t->grid);
+            name = "rtx_grid_shadow";
+        }
         break;
     default:
         hipLaunchKernelGGL(rtx_grid_reflect, grid, block, 0, st, *t->a, *t->reflect, *t->chain, *t->grid_reflect);
@@ -750,24 +787,43 @@ extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const Til
     // the family's FIN form while some object has a finish of its own (rtx_scene_set_finish), else the form without: two kernels, not
     // one with a uniform test -- a kernel's registers are those of its hungrier path, and with both paths in one the chain's grid
     // families lost an occupancy step for every frame, finished or not (profiles/r36_finish_resource_usage.txt)
+    // The FIN form also reads the cones of rtx_scene_set_spots, which travel behind the light set in its arguments (SpotLightsArgs,
+    // SpotShadowArgs): one rich form per family, not a SPOT form beside FIN -- the render path hands it the finishes (the default
+    // ones where no object has its own) whenever a light has a cone, so cones without finishes are refused here.
+    if (t->spots != nullptr && pa.fin_sph == nullptr) return nullptr;
     const auto launch = [&](auto m, auto o, auto fin, dim3 grid, dim3 block) {
         constexpr int M = decltype(m)::value, O = decltype(o)::value;
         constexpr bool F = decltype(fin)::value;
         hipStream_t st = (hipStream_t)stream_v;
+        // the light or the set as the form takes it: with the cones behind it (FIN), or as it is
+        const auto one = [&]() -> ShadowArgsOf<F> {
+            if constexpr (F) {
+                return spot_shadow_args(t);
+            } else {
+                return *t->shadow;
+            }
+        };
+        const auto set = [&]() -> LightsArgsOf<F> {
+            if constexpr (F) {
+                return spot_lights_args(t);
+            } else {
+                return *t->lights;
+            }
+        };
         switch (family) {
-        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->shadow, pa); break;
-        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, pa); break;
-        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->shadow, *t->reflect, pa); break;
-        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, pa); break;
-        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, pa); break;
+        case kShadowShade: hipLaunchKernelGGL((rtx::rtx_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, one(), pa); break;
+        case kLightsShade: hipLaunchKernelGGL((rtx::rtx_lights_shade<M, O, F>), grid, block, 0, st, *t->a, set(), pa); break;
+        case kReflectShade: hipLaunchKernelGGL((rtx::rtx_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, one(), *t->reflect, pa); break;
+        case kLightsReflectShade: hipLaunchKernelGGL((rtx::rtx_lights_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, pa); break;
+        case kLightsChainShade: hipLaunchKernelGGL((rtx::rtx_lights_chain_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, *t->chain, pa); break;
         case kLightsChainShadowShade:
-            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, pa);
+            hipLaunchKernelGGL((rtx::rtx_lights_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, *t->chain, *t->deep, pa);
             break;
-        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, t->dark0, pa); break;
-        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, t->dark0, pa); break;
-        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, t->dark0, pa); break;
+        case kGridShade: hipLaunchKernelGGL((rtx::rtx_grid_shade<M, O, F>), grid, block, 0, st, *t->a, set(), t->dark0, pa); break;
+        case kGridReflectShade: hipLaunchKernelGGL((rtx::rtx_grid_reflect_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, t->dark0, pa); break;
+        case kGridChainShade: hipLaunchKernelGGL((rtx::rtx_grid_chain_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, *t->chain, t->dark0, pa); break;
         default:
-            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, *t->lights, *t->reflect, *t->chain, *t->deep, t->dark0, pa);
+            hipLaunchKernelGGL((rtx::rtx_grid_chain_shadow_shade<M, O, F>), grid, block, 0, st, *t->a, set(), *t->reflect, *t->chain, *t->deep, t->dark0, pa);
             break;
         }
     };

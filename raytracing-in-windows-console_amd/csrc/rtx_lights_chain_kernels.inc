@@ -19,7 +19,7 @@
 // the same body with the pixel's word.
 
 template <bool FIN>
-__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgsOf<FIN>& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                       const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark)
 {
     V3 local[kMaxReflectDepth + 1];
@@ -49,7 +49,7 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
                     o = h.y;
                     const Surface sf = surface_of(a, pa, h.y, add(r.o, mulf(r.d, t)));
                     n = sf.normal;
-                    local[j + 1] = shade_lights_of<FIN>(pa, h.y, r, t, n, sf.od, la.lights, (deep_dark >> (8 * j)) & 0xffu);
+                    local[j + 1] = shade_lights_of<FIN>(pa, h.y, r, t, n, sf.od, la, (deep_dark >> (8 * j)) & 0xffu);
                 }
             }
         }
@@ -69,21 +69,21 @@ __device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const Ligh
 }
 
 template <bool FIN>
-__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgsOf<FIN>& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                  const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at)
 {
     return lights_chain_blend_dark<FIN>(a, la, ra, ca, pa, ray, distance, normal, id, cl, at, 0u);
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const ChainArgs ca, const PatternArgs pa)
 {
     lights_shade_body<MODE, OUT, 2, false, FIN>(a, la, ra, ca, pa);
 }
 
 // The chain's shade launch under RTX_OPT_REFLECT_SHADOWS: rtx_lights_chain_shade with the deeper levels' dark lights (cs.dark).
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shadow_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const ChainArgs ca,
+__global__ __launch_bounds__(kThreads) void rtx_lights_chain_shadow_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const ChainArgs ca,
                                                                           const ChainShadowArgs cs, const PatternArgs pa)
 {
     lights_shade_body<MODE, OUT, 3, false, FIN>(a, la, ra, ca, pa, cs.dark);

@@ -60,14 +60,19 @@ __device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 norm
 }
 
 // add_light for an object with a finish (rtx_scene_set_finish; the rule: rtx_finish.hpp): kd and ks where add_light has no factor
-// and 1.0f, the 2^m-th power where it has pow32.
-__device__ __forceinline__ void add_light(V3& res, V3 point, V3 nn, V3 nv, V3 od, const rtxlights::PackedLight& L, float dpow, float spow, const rtx_finish& f)
+// and 1.0f, the 2^m-th power where it has pow32.  The light's cone (rtx_scene_set_spots; the rule: rtx_spot.hpp): both powers
+// times w, which is exactly 1 for a point light.
+__device__ __forceinline__ void add_light(V3& res, V3 point, V3 nn, V3 nv, V3 od, const rtxlights::PackedLight& L, float dpow, float spow, const rtx_finish& f,
+                                          const rtxspot::Packed& sp)
 {
     V3 lightDir = sub(v3(L.px, L.py, L.pz), point);
     float dist = sqrt_cr(lightDir.x * lightDir.x + lightDir.y * lightDir.y + lightDir.z * lightDir.z);
     dist = dist * dist;
     const float divDistance = rcp_cr(dist);
     lightDir = normalize_gpu(lightDir);
+    const float w = rtxspot::weight(sp, lightDir.x, lightDir.y, lightDir.z);
+    dpow = dpow * w;
+    spow = spow * w;
 
     const float diffuseIntensity = clampf(dot(nn, lightDir), 0.0f, 1.0f);
     const V3 diffuse = v3(((L.dr * diffuseIntensity) * dpow) * divDistance, ((L.dg * diffuseIntensity) * dpow) * divDistance,
@@ -83,8 +88,9 @@ __device__ __forceinline__ void add_light(V3& res, V3 point, V3 nn, V3 nv, V3 od
     res.z = rtxfinish::add_terms(res.z, diffuse.z, f.diffuse, od.z, specular.z, f.specular);
 }
 
-// shade_lights for an object with a finish.
-__device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 normal, V3 od, const rtxlights::Block& ls, uint32_t shadowed, const rtx_finish& f)
+// shade_lights for an object with a finish, under lights with cones.
+__device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 normal, V3 od, const rtxlights::Block& ls, uint32_t shadowed, const rtx_finish& f,
+                                           const rtxspot::Block& sp)
 {
     const V3 point = add(r.o, mulf(r.d, distance));
     const V3 viewDir = normalize_gpu(mulf(r.d, -1.0f));
@@ -93,32 +99,32 @@ __device__ __forceinline__ V3 shade_lights(const Ray& r, float distance, V3 norm
     V3 res = v3(rtxfinish::ambient(f.ambient, od.x), rtxfinish::ambient(f.ambient, od.y), rtxfinish::ambient(f.ambient, od.z));
     for (uint32_t i = 0; i < ls.n; i++) {
         const bool dark = ((shadowed >> i) & 1u) != 0u;
-        add_light(res, point, nn, nv, od, ls.light[i], dark ? 0.0f : ls.light[i].dpow, dark ? 0.0f : ls.light[i].spow, f);
+        add_light(res, point, nn, nv, od, ls.light[i], dark ? 0.0f : ls.light[i].dpow, dark ? 0.0f : ls.light[i].spow, f, sp.spot[i]);
     }
     res = mulf(res, 255.0f);
     return v3(minf(255.0f, res.x), minf(255.0f, res.y), minf(255.0f, res.z));
 }
 
-// FIN (rtx_scene_set_finish: the forms launched while some object has a finish of its own): every shade_lights takes the finish of
-// the object it shades; without, nothing of it is compiled and the code is what it was before there were finishes.
-template <bool FIN>
-__device__ __forceinline__ V3 shade_lights_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const rtxlights::Block& ls,
-                                              uint32_t shadowed)
+// FIN (rtx_scene_set_finish, rtx_scene_set_spots: the forms launched while some object has a finish of its own or some light a
+// cone): every shade_lights takes the finish of the object it shades and the cones of the set (la is a SpotLightsArgs); without,
+// nothing of either is compiled and the code is what it was before there were finishes and cones.
+template <bool FIN, class LA>
+__device__ __forceinline__ V3 shade_lights_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const LA& la, uint32_t shadowed)
 {
     if constexpr (FIN) {
-        return shade_lights(r, distance, normal, od, ls, shadowed, finish_of(pa, id));
+        return shade_lights(r, distance, normal, od, la.lights, shadowed, finish_of(pa, id), la.spots);
     } else {
-        return shade_lights(r, distance, normal, od, ls, shadowed);
+        return shade_lights(r, distance, normal, od, la.lights, shadowed);
     }
 }
 
 // (rtx_lights_chain_kernels.inc: the blend over a chain of up to RTX_MAX_REFLECT_DEPTH levels; deep_dark: byte j - 1 the lights
 // level j is shadowed from)
 template <bool FIN>
-__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+__device__ __forceinline__ V3 lights_chain_blend_dark(const KArgs& a, const LightsArgsOf<FIN>& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                       const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at, uint32_t deep_dark);
 template <bool FIN>
-__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+__device__ __forceinline__ V3 lights_chain_blend(const KArgs& a, const LightsArgsOf<FIN>& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                  const Ray& ray, float distance, V3 normal, uint32_t id, V3 cl, size_t at);
 
 // What the shade family of the grid path keeps of LightsShared (RTX_OPT_SHADOW_GRID, rtx_grid_shadow_kernels.inc): the encoder's tables.
@@ -133,7 +139,7 @@ struct ShadeTablesShared {
 // hits: rtx_grid_shadow's output) instead of computed here -- no cone, no walk, no list in LDS.  What a value does not use is not
 // compiled.  FIN: the objects' finishes are read (shade_lights_of).
 template <int MODE, int OUT, int REFLECT, bool DARK0 = false, bool FIN = false>
-__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgs& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
+__device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsArgsOf<FIN>& la, const ReflectArgs& ra, const ChainArgs& ca, const PatternArgs& pa,
                                                   const uint32_t* deep_dark = nullptr, const uint32_t* dark0 = nullptr)
 {
     __shared__ std::conditional_t<DARK0, ShadeTablesShared, LightsShared> s;
@@ -179,11 +185,11 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
 
     // ---- shade with every light (both powers 0 for the lights the pixel is shadowed from) and encode
     if (any_hit) {
-        colour = shade_lights_of<FIN>(pa, id, ray, distance, normal, od, la.lights, dark);
+        colour = shade_lights_of<FIN>(pa, id, ray, distance, normal, od, la, dark);
         if constexpr (REFLECT == 1) {
             if (distance <= cam.far) {
                 colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a),
-                                       [&](const Ray& r2, float t2, V3 n2, V3 od2, uint32_t id2) { return shade_lights_of<FIN>(pa, id2, r2, t2, n2, od2, la.lights, 0u); });
+                                       [&](const Ray& r2, float t2, V3 n2, V3 od2, uint32_t id2) { return shade_lights_of<FIN>(pa, id2, r2, t2, n2, od2, la, 0u); });
             }
         } else if constexpr (REFLECT == 2) {
             if (distance <= cam.far) colour = lights_chain_blend<FIN>(a, la, ra, ca, pa, ray, distance, normal, id, colour, px.at(a));
@@ -195,7 +201,7 @@ __device__ __forceinline__ void lights_shade_body(const KArgs& a, const LightsAr
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgs la, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, const LightsArgsOf<FIN> la, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
     const ChainArgs ca = {};
@@ -204,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void rtx_lights_shade(const KArgs a, cons
 
 // The mirror path's third launch for a set of several lights: rtx_lights_shade's shading, then the blend.
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgs la, const ReflectArgs ra, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_lights_reflect_shade(const KArgs a, const LightsArgsOf<FIN> la, const ReflectArgs ra, const PatternArgs pa)
 {
     const ChainArgs ca = {}; // (read only by the chain's blend, which is not compiled here)
     lights_shade_body<MODE, OUT, 1, false, FIN>(a, la, ra, ca, pa);

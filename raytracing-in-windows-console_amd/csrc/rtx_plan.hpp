@@ -1049,6 +1049,8 @@ inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n,
 //   checker patterns (n_patterned != 0): a frame that would be direct takes the `shaded` row; nothing of any row changes -- the
 //   shade launches read the slots and the table (PatternArgs, rtx_kernels.h)
 //   surface finishes (n_finished != 0): the same -- the shade launches read the finishes (PatternArgs::fin_sph, fin_pl)
+//   spot lights (n_spots != 0): the same -- a cone on the reference's light is not the reference's light; the shade launches and the
+//   two shadow passes read the cones (SpotLightsArgs, SpotShadowArgs) in the forms that take them; nothing of any row changes
 //
 // The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
 // deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
@@ -1091,6 +1093,7 @@ struct ShadingRequest { // what the decision reads of the call, the options and 
     bool grid_usable = false;        // the world grid was built and can be walked; known only after its build (shading_wants_grid)
     uint32_t n_patterned = 0;        // objects with a pattern slot above 0 (rtx_scene_set_object_pattern)
     uint32_t n_finished = 0;         // objects whose finish is not the default (rtx_scene_set_finish)
+    uint32_t n_spots = 0;            // lights of the set that have a cone (rtx_scene_set_spots)
 };
 
 struct ShadingPlan {
@@ -1115,7 +1118,7 @@ inline ShadePath shading_path(const ShadingRequest& q)
 {
     if (q.mode < kShadedModeLo || q.mode > kShadedModeHi) return kPathDirect;
     if (q.n_reflective != 0 || q.reflect_check == 2) return kPathMirror; // (takes precedence, and runs the shadow test itself)
-    if (q.shadows || q.n_lights != 1 || q.lights_check || !q.light0_is_reference) return kPathShaded;
+    if (q.shadows || q.n_lights != 1 || q.lights_check || !q.light0_is_reference || q.n_spots != 0) return kPathShaded; // (the reference's light has no cone)
     if (q.n_patterned != 0) return kPathShaded; // (a pattern is read by the shade launches alone: it adds no pass and no bytes)
     if (q.n_finished != 0) return kPathShaded;  // (and so is a finish)
     return kPathDirect; // the state the reference has: every launch is the reference's

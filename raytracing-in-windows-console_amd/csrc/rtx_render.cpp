@@ -67,6 +67,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.ns = ctx->ns;
     q.n_patterned = ctx->materials.n_patterned();
     q.n_finished = ctx->materials.n_finished();
+    q.n_spots = rtxlights::spot_count(ctx->spots);
     return q;
 }
 
@@ -643,7 +644,9 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     const bool mirror = shading_path(req) == kPathMirror;
     if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
     const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
-    const bool finished = req.n_finished != 0 && shading_path(req) != kPathDirect; // (the same)
+    const bool spotted = req.n_spots != 0 && shading_path(req) != kPathDirect; // (the same)
+    // the forms of the shade families that read cones read finishes too: with a cone in the set they get the finishes, default or not
+    const bool finished = (req.n_finished != 0 || spotted) && shading_path(req) != kPathDirect; // (the same)
     if ((mirror || patterned || finished) && ctx->materials.stale()) {
         if (capturing) {
             return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror      ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
@@ -716,6 +719,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         pa.fin_sph = ctx->d_mat.finish.spheres(sorted_staging).get();
         pa.fin_pl = ctx->d_mat.finish.pl.get();
     }
+    if (spotted) t.spots = &ctx->spots; // (by value into the launches that read cones, as the lights: nothing is uploaded)
     if (shade_takes_light_set(plan.family)) {
         la = lights_args(ctx, hits);
         t.lights = &la;
@@ -790,7 +794,8 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ctx->last_kernel = name;
     (mirror ? ctx->stat_reflect_frames : ctx->stat_shadow_frames)++;
     if (patterned) ctx->stat_pattern_frames++;
-    if (finished) ctx->stat_finish_frames++;
+    if (req.n_finished != 0 && finished) ctx->stat_finish_frames++;
+    if (spotted) ctx->stat_spot_frames++;
     if (mirror && ctx->materials.n_refractive() != 0) ctx->stat_refract_frames++;
     return RTX_OK;
 }

@@ -15,18 +15,21 @@
 // colour before it is encoded (reflect_blend); without, nothing of it is compiled.
 // FIN (rtx_scene_set_finish: the forms launched while some object has a finish of its own): every shade_light takes the finish of
 // the object it shades; without, nothing of it is compiled and the code is what it was before there were finishes.
+// The FIN forms also read the light's cone (rtx_scene_set_spots: sa is a SpotShadowArgs): they are launched while some object has
+// a finish or the light a cone.
 template <bool FIN>
-__device__ __forceinline__ V3 shade_light_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const KLight& L, float dpow, float spow)
+__device__ __forceinline__ V3 shade_light_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const ShadowArgsOf<FIN>& sa, float dpow,
+                                             float spow)
 {
     if constexpr (FIN) {
-        return shade_light(r, distance, normal, od, L, dpow, spow, finish_of(pa, id));
+        return shade_light(r, distance, normal, od, sa.light, dpow, spow, finish_of(pa, id), sa.spot);
     } else {
-        return shade_light(r, distance, normal, od, L, dpow, spow);
+        return shade_light(r, distance, normal, od, sa.light, dpow, spow);
     }
 }
 
 template <int MODE, int OUT, bool REFLECT, bool FIN>
-__device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa, const ReflectArgs& ra, const PatternArgs& pa)
+__device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgsOf<FIN>& sa, const ReflectArgs& ra, const PatternArgs& pa)
 {
     __shared__ float4 s_occ[kTileList];
     __shared__ uint32_t s_occ_pos[kTileList];
@@ -67,7 +70,7 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
     const V3 toL = sub(L, P);
     bool pending = sa.test != 0u && any_hit && distance <= cam.far;
     const uint32_t own_plane = (id & 0x80000000u) ? (id & 0x7fffffffu) : 0xffffffffu;
-    bool shadowed = shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending);
+    bool shadowed = shadowed_before_spheres(a, sa, P, normal, L, toL, own_plane, pending);
 
     // spheres: the workgroup's cone from the light over its open hit points, unless every sphere is tested
     const float Lf[3] = {L.x, L.y, L.z};
@@ -96,11 +99,11 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
 
     // ---- shade with the light (both powers 0 in shadow) and encode
     if (any_hit) {
-        colour = shade_light_of<FIN>(pa, id, ray, distance, normal, od, sa.light, shadowed ? 0.0f : sa.light.dpow, shadowed ? 0.0f : sa.light.spow);
+        colour = shade_light_of<FIN>(pa, id, ray, distance, normal, od, sa, shadowed ? 0.0f : sa.light.dpow, shadowed ? 0.0f : sa.light.spow);
         if constexpr (REFLECT) {
             if (distance <= cam.far) {
                 colour = reflect_blend(a, ra, pa, ray, distance, normal, id, colour, px.at(a), [&](const Ray& r2, float t2, V3 n2, V3 od2, uint32_t id2) {
-                    return shade_light_of<FIN>(pa, id2, r2, t2, n2, od2, sa.light, sa.light.dpow, sa.light.spow);
+                    return shade_light_of<FIN>(pa, id2, r2, t2, n2, od2, sa, sa.light.dpow, sa.light.spow);
                 });
             }
         }
@@ -109,7 +112,7 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgs& sa,
 }
 
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, const ShadowArgs sa, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, const ShadowArgsOf<FIN> sa, const PatternArgs pa)
 {
     const ReflectArgs ra = {}; // (read only by the REFLECT parts, which are not compiled here)
     shade_body<MODE, OUT, false, FIN>(a, sa, ra, pa);
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(kThreads) void rtx_shadow_shade(const KArgs a, cons
 
 // The mirror path's third launch: rtx_shadow_shade's shading, then the blend.
 template <int MODE, int OUT, bool FIN = false>
-__global__ __launch_bounds__(kThreads) void rtx_reflect_shade(const KArgs a, const ShadowArgs sa, const ReflectArgs ra, const PatternArgs pa)
+__global__ __launch_bounds__(kThreads) void rtx_reflect_shade(const KArgs a, const ShadowArgsOf<FIN> sa, const ReflectArgs ra, const PatternArgs pa)
 {
     shade_body<MODE, OUT, true, FIN>(a, sa, ra, pa);
 }

@@ -198,6 +198,35 @@ __device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, V3 P, V3
     return shadowed;
 }
 
+// The same under a light set that may carry cones (rtx_scene_set_spots): with a SpotLightsArgs, a point outside light i's cone --
+// rtx_spot.hpp's own s, from the lightDir the shading forms at P, is not above 0 -- leaves `pending` first, and is not shadowed: the
+// shade launch weighs the light with 0 there, which is the float a dark light enters with.  With a LightsArgs nothing is added.
+template <class LA>
+__device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, const LA& la, uint32_t i, V3 P, V3 normal, V3 L, V3 toL, uint32_t own_plane, bool& pending)
+{
+    if constexpr (std::is_same_v<LA, SpotLightsArgs>) {
+        const rtxspot::Packed& sp = la.spots.spot[i];
+        if (pending && rtxspot::has_cone(sp)) {
+            const V3 ld = normalize_gpu(toL);
+            if (rtxspot::outside(sp, ld.x, ld.y, ld.z)) pending = false;
+        }
+    }
+    return shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending);
+}
+
+// ... and under the one light of rtx_shadow_shade / rtx_reflect_shade (SpotShadowArgs: its cone).
+template <class SA>
+__device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, const SA& sa, V3 P, V3 normal, V3 L, V3 toL, uint32_t own_plane, bool& pending)
+{
+    if constexpr (std::is_same_v<SA, SpotShadowArgs>) {
+        if (pending && rtxspot::has_cone(sa.spot)) {
+            const V3 ld = normalize_gpu(toL);
+            if (rtxspot::outside(sa.spot, ld.x, ld.y, ld.z)) pending = false;
+        }
+    }
+    return shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending);
+}
+
 // The workgroup's cone from light Lf over its pending hit points Pf (rtx_shadow.hpp).  false: no pixel of the workgroup is
 // pending, or the scene has no sphere -- there is no cone and nothing to walk (workgroup-uniform, as everything derived from
 // the sums); true: `cone` holds it, in every thread (brute: a cone that keeps every sphere).  Every wave meets the first
@@ -278,15 +307,15 @@ struct LightsShared {
 };
 
 // The lights (bit i: light i of la.lights) that the point P -- normal `normal`, on object `id` (sphere position, or plane index |
-// bit 31) -- is shadowed from; 0 for a pixel that is not `testable`.  Per light: self-shadow and the planes per pixel
+// bit 31) -- is shadowed from; 0 for a pixel that is not `testable`.  Per light: its cone (la a SpotLightsArgs), self-shadow and the planes per pixel
 // (shadowed_before_spheres) and the workgroup's cone from that light over its open points (light_cone), kept in s.cone; a light
 // with no open pixel in the workgroup has no cone.  Then ONE walk of the scene for all lights (walk_spheres): each staged sphere is
 // tested against every live cone and listed once with the 8-bit mask of the lights it was kept for; at a flush every wave goes
 // through the lights some lane of it is still open for, the segment (toL, 1 / len2) formed once per light.  Called by every
 // thread of the workgroup (the trip counts are workgroup-uniform; every wave meets the same barriers, at least one per light).
 // `s` holds occ, occ_pos, occ_mask (one byte per entry), red, cone and cnt, which is 0 on entry and 0 again on return.
-template <class Shared>
-__device__ __forceinline__ uint32_t lights_dark_set(const KArgs& a, const LightsArgs& la, Shared& s, uint32_t tid, uint32_t lane, uint32_t wave, V3 P, V3 normal,
+template <class Shared, class LA>
+__device__ __forceinline__ uint32_t lights_dark_set(const KArgs& a, const LA& la, Shared& s, uint32_t tid, uint32_t lane, uint32_t wave, V3 P, V3 normal,
                                                     uint32_t id, bool testable)
 {
     const uint32_t nl = la.lights.n;
@@ -299,7 +328,7 @@ __device__ __forceinline__ uint32_t lights_dark_set(const KArgs& a, const Lights
         const rtxlights::PackedLight& Lt = la.lights.light[i];
         const V3 L = v3(Lt.px, Lt.py, Lt.pz);
         bool pending = testable;
-        if (shadowed_before_spheres(a, P, normal, L, sub(L, P), own_plane, pending)) dark |= 1u << i;
+        if (shadowed_before_spheres(a, la, i, P, normal, L, sub(L, P), own_plane, pending)) dark |= 1u << i;
         if (pending) open |= 1u << i;
 
         const float Lf[3] = {L.x, L.y, L.z};
