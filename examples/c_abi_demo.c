@@ -39,6 +39,14 @@ int main(int argc, char** argv)
             return 1;
         }
     }
+    {
+        /* sphere 0 casts shadows, as every new object does (0: seen, lit and shadowed, but no obstacle to light): the frame stays the reference's */
+        const uint8_t cast = 1u;
+        if (rtx_scene_set_shadow_casting(ctx, 0, 1, &cast) != RTX_OK) {
+            fprintf(stderr, "rtx_scene_set_shadow_casting: %s\n", rtx_last_error(ctx));
+            return 1;
+        }
+    }
 
     rtx_params params;
     if (rtx_camera_params(W, H, NULL, NULL, &params) != RTX_OK) {

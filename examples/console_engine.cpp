@@ -14,6 +14,8 @@
 // cursor escape (RayTracingManager::SetHalfDeltaFrames, rtx_update_half_delta; no reference counterpart).
 // --glass: the mirror key (see below) then also gives every other sphere k = 0.85 and an index of refraction of 1.5
 // (Scene3D::SetRefraction, rtx_scene_set_refraction; no reference counterpart): glass balls over the floor.
+// --clear-glass: --glass, with shadows on from the start and the glass spheres casting no shadow (Scene3D::SetCastsShadow,
+// rtx_scene_set_shadow_casting; no reference counterpart): the balls bend the view and leave the floor behind them lit.
 // --finish: the spheres cycle through four finishes as they are created -- matt, the default, glossy (exponent 2^7), glowing (0.8 of
 // their own colour under no light) -- and the floor is matt (Scene3D::SetFinish, rtx_scene_set_finish; no reference counterpart).
 // --spot: the light becomes a cone aimed at the scene's centre on the floor, full inside 18 degrees of its axis and gone beyond 26
@@ -159,7 +161,7 @@ int main(int argc, char** argv)
     size_t W = 160, H = 50;
     int mode0 = BIT_ASCII, max_frames = -1; // the reference starts in BIT_ASCII (RayTracingManager.h:53)
     double fixed_dt = -1.0;
-    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false, finish = false, spot = false;
+    bool lockstep = false, spawn = true, status = true, keys_only = false, delta = false, half = false, checker = false, glass = false, clear_glass = false, finish = false, spot = false;
     int samples = 1;
     const char* trace_path = nullptr;
     int positional = 0;
@@ -175,6 +177,7 @@ int main(int argc, char** argv)
         else if (a == "--half") half = true; // W x 2H pixels as half blocks (RayTracingManager::SetHalfBlocks)
         else if (a == "--checker") checker = true; // a two-axis checker on the floor plane (Scene3D::SetPatterns, SetPlanePattern)
         else if (a == "--glass") glass = true; // the mirror key also turns every other sphere into glass (Scene3D::SetRefraction)
+        else if (a == "--clear-glass") glass = clear_glass = true; // ... which then casts no shadow, with shadows on (Scene3D::SetCastsShadow)
         else if (a == "--finish") finish = true; // matt, default, glossy and glowing spheres over a matt floor (Scene3D::SetFinish)
         else if (a == "--spot") spot = true; // the light a cone aimed at the scene's centre (RayTracingManager::SetSpots)
         else if (a == "--samples" && i + 1 < argc) samples = std::atoi(argv[++i]); // N x N rays per cell (RayTracingManager::SetSupersampling)
@@ -183,7 +186,7 @@ int main(int argc, char** argv)
         else if (a[0] != '-' && positional == 0) { W = std::strtoul(argv[i], nullptr, 10); positional++; }
         else if (a[0] != '-' && positional == 1) { H = std::strtoul(argv[i], nullptr, 10); positional++; }
         else {
-            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--finish] [--spot] [--samples 1..4] [--trace FILE]\n", argv[0]);
+            std::fprintf(stderr, "usage: %s [W H] [--mode 0..4] [--frames N] [--dt s] [--lockstep] [--no-spawn] [--no-status] [--delta] [--half] [--checker] [--glass] [--clear-glass] [--finish] [--spot] [--samples 1..4] [--trace FILE]\n", argv[0]);
             return 2;
         }
     }
@@ -262,6 +265,10 @@ int main(int argc, char** argv)
         if (finish) finish_new_objects();
         int mode = mode0;
         bool shadows = false, mirrors = false, pick = false;
+        if (clear_glass) { // (what a non-casting sphere is seen by: the shadows it does not throw)
+            shadows = true;
+            rayTracingManager->SetShadows(shadows);
+        }
         int bounces = 1;
         const char hide[] = "\x1b[?25l\x1b[2J"; // hide the cursor, clear (PrintMachine.cpp:120)
         if (write(STDOUT_FILENO, hide, sizeof hide - 1) < 0) return 1;
@@ -315,6 +322,7 @@ int main(int argc, char** argv)
                             if (rtx_scene_get_object(c, i, &type, row) != RTX_OK || type != 2 || nth++ % 2u != 0u) continue;
                             scene->SetReflectivity(i, mirrors ? 0.85f : 0.0f);
                             scene->SetRefraction(i, mirrors ? 1.5f : 0.0f);
+                            if (clear_glass) scene->SetCastsShadow(i, !mirrors); // (glass that leaves the floor lit)
                         }
                     }
                     break;

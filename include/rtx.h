@@ -663,7 +663,8 @@ int rtx_scene_get_reflectivity(const rtx_ctx* ctx, unsigned index, float* k);
  * o_j, exactly as the mirror ray is.  Everything else is unchanged: the existence rule k(o_j) > 0, the fold, the shadow tests at
  * P_j, distance, glyph and normal of the pixel.  As code, once: csrc/rtx_refract.hpp.
  * Out of scope: Fresnel weighting; an object that both mirrors and transmits (a ray tree); anything inside a glass sphere (the
- * interior is treated as empty); attenuated or coloured shadows (glass occludes like any object); a slab of finite thickness;
+ * interior is treated as empty); attenuated or coloured shadows (glass occludes like any object, unless it is told to cast no shadow at
+ * all: rtx_scene_set_shadow_casting); a slab of finite thickness;
  * ior < 1.  No reference counterpart (RayTracing.cu:635 plans a recursive RayTrace). */
 int rtx_scene_set_refraction(rtx_ctx* ctx, unsigned first, size_t n, const float* ior);
 /* The index of refraction of object `index` (0: a mirror).  No reference counterpart. */
@@ -712,6 +713,43 @@ typedef struct rtx_finish {
 int rtx_scene_set_finish(rtx_ctx* ctx, unsigned first, size_t n, const rtx_finish* finishes);
 /* The finish of object `index`.  No reference counterpart. */
 int rtx_scene_get_finish(const rtx_ctx* ctx, unsigned index, rtx_finish* out);
+/* Objects that cast no shadow: glass, light fittings, helper geometry, sky domes -- seen, lit and shadowed, but no obstacle to light.
+ * The flag `cast` (0 or 1) of objects first .. first+n-1 (creation indices, spheres and planes alike).  It belongs to an object as k,
+ * ior and the finish do: every new object has 1; rtx_scene_clear forgets the values, rtx_scene_set_spheres and rtx_scene_set_plane
+ * keep them, and after rtx_scene_remove_objects the survivors keep theirs under the renumbering rule.  All or nothing: a value other
+ * than 0 or 1, a range past rtx_scene_count or casts == NULL with n > 0 changes nothing and returns RTX_ERR_INVALID_ARGUMENT, and
+ * rtx_last_error names the first offending object (on a device group: validated before any rank is touched, then applied to every
+ * rank).
+ * The rule.  The shadow test of RTX_OPT_SHADOWS and RTX_OPT_REFLECT_SHADOWS at a point P with normal n on object o, for light i --
+ * at level 0 and at every level j of a chain, under every light set and every cone -- changes in one thing: which objects count as
+ * occluders.  A plane counts only if it is not o and its cast is 1; a sphere counts only if it is not o and its cast is 1.  Light i
+ * is dark at P iff
+ *   dot(n, L_i - P) <= 0, or
+ *   the open segment (P, L_i) crosses such a plane inside its bounds, or
+ *   the segment comes closer than r to the centre of such a sphere,
+ * with the expressions of rtx_scene_set_light, operation for operation.  Nothing else changes.  A non-casting object is still hit by
+ * primary rays, mirror rays, glass rays and queries; it still receives shadows and still shadows itself (the dot <= 0 test stays);
+ * its distance, glyph, normal, pattern and finish, the chain's fold, the cones' rule for which points are tested and rtx_query_rays
+ * (RTX_QUERY_ANY included) do not read the flag.
+ * What follows from it:
+ *   - while every object casts, every launch is what it is without this call, byte for byte and kernel for kernel;
+ *   - while some object does not cast but no shadow test runs (RTX_OPT_SHADOWS 0, or RTX_OPT_SHADOW_CHECK 2), the same: nobody
+ *     reads the flags;
+ *   - a flag never changes the path or the launch sequence of a frame, only which form of a kernel runs: while a shadow test runs
+ *     and some object casts no shadow, the launches that make the test are the forms that also read finishes and cones;
+ *   - RTX_OPT_SHADOW_CHECK 1 stays the brute reference of the culled path and honours the flags;
+ *   - a non-casting sphere is never listed as a candidate: RTX_STAT_SHADOW_LONGEST_LIST counts casting spheres only (under check 1
+ *     the number of casting spheres wherever a pixel is pending, 0 when no sphere casts);
+ *   - geometry is unchanged, so sorted copies, cell lists and the world grid stay valid (RTX_STAT_QUERY_GRID_BUILDS does not move on
+ *     a flag change, and RTX_OPT_SHADOW_GRID keeps walking the shared grid, which holds every sphere).
+ * A graph recorded before a change is refused by rtx_graph_launch (re-capture).  The device copies are uploaded with the
+ * reflectivities', in the same three orders and once more by creation index, at the cost of the one device wait stated at
+ * rtx_scene_set_reflectivity; recording right after a change fails with RTX_ERR_INVALID_ARGUMENT ("render once before capturing").
+ * Out of scope: attenuated or coloured shadows (a transmittance per object), a "receives no shadow" flag, objects invisible to
+ * primary or mirror rays.  No reference counterpart (the reference casts no shadows). */
+int rtx_scene_set_shadow_casting(rtx_ctx* ctx, unsigned first, size_t n, const uint8_t* casts);
+/* The flag of object `index` (1: it casts shadows).  No reference counterpart. */
+int rtx_scene_get_shadow_casting(const rtx_ctx* ctx, unsigned index, uint8_t* cast);
 /* Checker patterns: a second colour per object, chosen by the parity of the lattice cell the hit point lies in.  The table holds
  * up to RTX_MAX_PATTERNS entries, slots 1 .. n; an object carries a slot (0: none, what every new object has).  36 bytes. */
 #define RTX_MAX_PATTERNS 16

@@ -472,6 +472,13 @@ public:
         const rtx_finish f = {ambient, diffuse, specular, shininess_log2};
         check(rtx_scene_set_finish(ctx(), index, 1, &f), "rtx_scene_set_finish");
     }
+    // Extension, no reference counterpart (the reference casts no shadows): whether the object of creation index `index` counts as an
+    // occluder in the shadow tests (rtx_scene_set_shadow_casting; every new object does).  It is seen, lit and shadowed either way.
+    void SetCastsShadow(const unsigned index, const bool casts)
+    {
+        const uint8_t cast = casts ? 1u : 0u;
+        check(rtx_scene_set_shadow_casting(ctx(), index, 1, &cast), "rtx_scene_set_shadow_casting");
+    }
     // Extensions, no reference counterpart (RayTracing.cu:144 reads the one colour an object has): checker patterns.  The table of
     // up to RTX_MAX_PATTERNS entries (rtx_scene_set_patterns; entry i serves slot i + 1), the slot of the object of creation index
     // `index` (0: none), or of every plane this scene created (rtx_scene_set_object_pattern, a call per plane: the objects between

@@ -201,6 +201,8 @@ _SIGNATURES = [
     ("rtx_scene_get_spots", C.c_int, [_P, C.c_size_t, C.POINTER(Spot), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_finish", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(Finish)]),
     ("rtx_scene_get_finish", C.c_int, [_P, C.c_uint, C.POINTER(Finish)]),
+    ("rtx_scene_set_shadow_casting", C.c_int, [_P, C.c_uint, C.c_size_t, C.POINTER(C.c_uint8)]),
+    ("rtx_scene_get_shadow_casting", C.c_int, [_P, C.c_uint, C.POINTER(C.c_uint8)]),
     ("rtx_scene_set_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern)]),
     ("rtx_scene_get_patterns", C.c_int, [_P, C.c_size_t, C.POINTER(Pattern), C.POINTER(C.c_size_t)]),
     ("rtx_scene_set_object_pattern", C.c_int, [_P, C.c_uint, C.c_size_t, C.c_uint]),
@@ -596,6 +598,23 @@ class Context:
         out = Finish()
         self._check(lib().rtx_scene_get_finish(self._h, index, C.byref(out)))
         return out
+
+    def set_shadow_casting(self, first, casts):
+        """rtx_scene_set_shadow_casting: 0 (casts no shadow) or 1 for objects first, first+1, ... (creation indices); a sequence or
+        one value."""
+        casts = [casts] if np.isscalar(casts) else [int(v) for v in casts]
+        arr = (C.c_uint8 * max(len(casts), 1))()
+        for i, v in enumerate(casts):
+            if not 0 <= int(v) <= 255:
+                raise ValueError("a shadow-casting flag is a byte")
+            arr[i] = int(v)
+        self._check(lib().rtx_scene_set_shadow_casting(self._h, first, len(casts), arr if casts else None))
+
+    def get_shadow_casting(self, index):
+        """rtx_scene_get_shadow_casting: 1 if object `index` casts shadows, else 0."""
+        out = C.c_uint8(0)
+        self._check(lib().rtx_scene_get_shadow_casting(self._h, index, C.byref(out)))
+        return int(out.value)
 
     def set_patterns(self, patterns):
         """rtx_scene_set_patterns: the whole table, 0 .. MAX_PATTERNS Pattern values; entry i serves slot i + 1."""

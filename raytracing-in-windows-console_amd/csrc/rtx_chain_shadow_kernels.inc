@@ -34,7 +34,8 @@ struct ChainShadowShared {
 #endif
 // SPOT (rtx_scene_set_spots: the form launched while some light of the set has a cone, its arguments the set with the cones behind
 // it): a level's point outside a light's cone is not pending for that light (lights_dark_set) -- it adds nothing to the light's tile
-// cone and tests no segment.  Without SPOT the code is what it was.
+// cone and tests no segment.  Without SPOT the code is what it was.  The SPOT form also reads the shadow-casting flags
+// (rtx_scene_set_shadow_casting: la.cast, in lights_dark_set), so it is launched too while some object casts no shadow.
 template <bool SPOT>
 __global__ __launch_bounds__(kThreads, RTX_CHAIN_SHADOW_WAVES) void rtx_chain_shadow(const KArgs a, const LightsArgsOf<SPOT> la, const ReflectArgs ra, const ChainArgs ca,
                                                                                      const ChainShadowArgs cs)

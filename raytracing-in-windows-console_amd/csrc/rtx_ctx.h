@@ -283,7 +283,7 @@ struct rtx_ctx {
     std::vector<DeviceBuf<uint8_t>> hit_retired; // outgrown buffers that a recorded graph may still read
 
     // surface attributes by creation index (rtx_materials.hpp): the reflectivity k, the slot in the pattern table, the index of
-    // refraction and the finish, with their counts, the upload flag and the generations that tell recorded graphs they are stale.  While an object
+    // refraction, the finish and the shadow-casting flag, with their counts, the upload flag and the generations that tell recorded graphs they are stale.  While an object
     // has k > 0 (or under RTX_OPT_REFLECT_CHECK 2) rtx_render_rows traces the closest hits, rtx_reflect_hit the secondary hits of the
     // reflective pixels and rtx_reflect_shade shades and blends: 16 bytes per pixel of the stream's hit buffer.
     rtxmat::Book materials;
@@ -294,6 +294,8 @@ struct rtx_ctx {
         rtxmat::Orders<DeviceBuf<float>> k, ior;
         rtxmat::Orders<DeviceBuf<uint8_t>> slot;
         rtxmat::Orders<DeviceBuf<rtx_finish>> finish;
+        rtxmat::Orders<DeviceBuf<uint8_t>> cast;
+        DeviceBuf<uint8_t> cast_gidx; // the same flags by creation index, for the grid's lists (GridShadowArgs::list_gidx)
         DeviceBuf<rtxpattern::Entry> table;
         DeviceBuf<uint32_t> pos; // rtxmat::position_map, for rtx_grid_reflect (RTX_OPT_REFLECT_GRID)
     } d_mat;

@@ -5,9 +5,17 @@
 // Is the open segment from P to L (toL = L - P) within r of the centre of a sphere other than the one of creation index own_gidx
 // (own_pos: its position in a.sph_geom; 0xffffffff for both: none)?  `open`: the lanes that ask.  Adds the lanes that could not
 // walk their segment to n_fallback.
-__device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShadowArgs& gs, V3 P, V3 toL, uint32_t own_gidx, uint32_t own_pos, bool open,
-                                                  uint32_t& n_fallback)
+//
+// CAST (the rich form of rtx_grid_shadow, rtx_scene_set_shadow_casting): a sphere whose flag is 0 is no occluder.  The large list and
+// the cell lists know spheres by creation index (cast.gidx), the loop over the scene array by position (cast.sph); all nullptr (kernel
+// arguments: the test is uniform) while every object casts.  Which cells are walked and which segments fall back does not depend on
+// the flags.  Without CAST nothing of this is compiled.
+template <bool CAST>
+__device__ __forceinline__ bool grid_segment_dark_casting(const KArgs& a, const GridShadowArgs& gs, const CastArgs& cast, V3 P, V3 toL, uint32_t own_gidx,
+                                                          uint32_t own_pos, bool open, uint32_t& n_fallback)
 {
+    bool flags = false; // (CAST) are there flags to read?
+    if constexpr (CAST) flags = cast.gidx != nullptr;
     const float len2 = dot(toL, toL);
     const float inv_len2 = len2 > 0.0f ? 1.0f / len2 : 0.0f; // (as lights_dark_set forms it)
     const float Pf[3] = {P.x, P.y, P.z}, Df[3] = {toL.x, toL.y, toL.z};
@@ -20,6 +28,9 @@ __device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShad
             const uint32_t i = gs.large[j];
             const float4 sp = gs.scene_geom[i];
             const uint32_t gidx = __float_as_uint(gs.scene_od[i].w);
+            if constexpr (CAST) {
+                if (flags && cast.gidx[gidx] == 0u) continue; // (uniform)
+            }
             if (go && gidx != own_gidx && segment_hits_sphere(P, toL, inv_len2, sp)) {
                 hit = true;
                 go = false;
@@ -35,6 +46,9 @@ __device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShad
             const uint32_t b = gs.cell_start[c], e = gs.cell_start[c + 1u];
             for (uint32_t j = b; j < e; j++) {
                 if (segment_hits_sphere(P, toL, inv_len2, gs.list_geom[j]) && gs.list_gidx[j] != own_gidx) {
+                    if constexpr (CAST) {
+                        if (flags && cast.gidx[gs.list_gidx[j]] == 0u) continue; // (met, but no occluder)
+                    }
                     hit = true;
                     break;
                 }
@@ -49,6 +63,9 @@ __device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShad
         bool pending = fb;
         for (uint32_t j = 0; j < a.ns && __ballot(pending) != 0ull; j++) {
             const float4 sp = a.sph_geom[j];
+            if constexpr (CAST) {
+                if (flags && cast.sph[j] == 0u) continue; // (uniform)
+            }
             if (pending && j != own_pos && segment_hits_sphere(P, toL, inv_len2, sp)) {
                 hit = true;
                 pending = false;
@@ -56,4 +73,11 @@ __device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShad
         }
     }
     return hit;
+}
+
+__device__ __forceinline__ bool grid_segment_dark(const KArgs& a, const GridShadowArgs& gs, V3 P, V3 toL, uint32_t own_gidx, uint32_t own_pos, bool open,
+                                                  uint32_t& n_fallback)
+{
+    const CastArgs none = {nullptr, nullptr, nullptr};
+    return grid_segment_dark_casting<false>(a, gs, none, P, toL, own_gidx, own_pos, open, n_fallback);
 }

@@ -38,7 +38,11 @@ __device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LA& la, 
         const V3 toL = sub(L, P);
         bool pending = testable;
         if (shadowed_before_spheres(a, la, i, P, normal, L, toL, own_plane, pending)) dark |= 1u << i;
-        if (grid_segment_dark(a, gs, P, toL, own_gidx, own_pos, pending, n_fallback)) dark |= 1u << i;
+        if constexpr (std::is_same_v<LA, SpotLightsArgs>) { // (the rich form: the spheres that cast -- rtx_scene_set_shadow_casting)
+            if (grid_segment_dark_casting<true>(a, gs, la.cast, P, toL, own_gidx, own_pos, pending, n_fallback)) dark |= 1u << i;
+        } else {
+            if (grid_segment_dark(a, gs, P, toL, own_gidx, own_pos, pending, n_fallback)) dark |= 1u << i;
+        }
     }
     return dark;
 }
@@ -57,6 +61,8 @@ __device__ __forceinline__ uint32_t grid_dark_set(const KArgs& a, const LA& la, 
 // SPOT (rtx_scene_set_spots: the form launched while some light of the set has a cone, its arguments the set with the cones behind
 // it): a point outside a light's cone is not pending for that light -- no plane test, no segment, walked or counted -- and not dark
 // either: the shade launch weighs that light with 0 there.  The same launch bounds.  Without SPOT the code is what it was.
+// The SPOT form also reads the shadow-casting flags (rtx_scene_set_shadow_casting: la.cast), so it is launched too while some object
+// casts no shadow: a plane or a sphere whose flag is 0 is no occluder (shadowed_before_spheres, grid_segment_dark_casting).
 template <bool SPOT>
 __global__ RTX_GRID_SHADOW_BOUNDS void rtx_grid_shadow(const KArgs a, const LightsArgsOf<SPOT> la, const ReflectArgs ra, const ChainArgs ca, const ChainShadowArgs cs,
                                                             const GridShadowArgs gs)

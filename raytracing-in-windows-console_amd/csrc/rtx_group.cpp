@@ -528,6 +528,11 @@ int scene_set_spots(rtx_ctx* root, size_t n, const rtx_spot* spots)
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_spots(m, n, spots); });
 }
 
+int scene_set_shadow_casting(rtx_ctx* root, unsigned first, size_t n, const uint8_t* casts)
+{
+    return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_shadow_casting(m, first, n, casts); });
+}
+
 int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns)
 {
     return on_members(root, [&](rtx_ctx* m) { return rtx_scene_set_patterns(m, n, patterns); });

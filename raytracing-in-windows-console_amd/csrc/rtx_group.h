@@ -32,6 +32,7 @@ int scene_set_patterns(rtx_ctx* root, size_t n, const rtx_pattern* patterns);   
 int scene_set_object_pattern(rtx_ctx* root, unsigned first, size_t n, unsigned slot);
 int scene_set_refraction(rtx_ctx* root, unsigned first, size_t n, const float* ior);
 int scene_set_finish(rtx_ctx* root, unsigned first, size_t n, const rtx_finish* finishes);
+int scene_set_shadow_casting(rtx_ctx* root, unsigned first, size_t n, const uint8_t* casts);
 int scene_set_spots(rtx_ctx* root, size_t n, const rtx_spot* spots);
 // edits in place (the root has validated the range and applied the edit to itself): the host form calls every member; the device
 // form copies the rows from the root's device into every other member's scratch, behind `after` (an event on the caller's stream),

@@ -153,11 +153,22 @@ struct LightsArgs {
 // that read cones take these -- the FIN forms of the shade families (which then read finishes and cones: launched while an object
 // has a finish or a light has a cone) and the SPOT forms of the two shadow passes; every other kernel's argument block is what it
 // was before there were cones.
+// Objects that cast no shadow (rtx_scene_set_shadow_casting): one byte per object, 0 for an object the shadow tests do not count as
+// an occluder.  All nullptr while every object casts, or while the launch runs no shadow test: then nothing is loaded.  The flags
+// travel with the cones, to the same launches -- the rich forms, which are then launched while an object has a finish, a light has a
+// cone or an object casts no shadow under a running shadow test.  The device copies travel with the reflectivities'.
+struct CastArgs {
+    const uint8_t* sph;   // the spheres' flags, by the position the trace kernels index them by (KArgs::sph_geom's order): the walks
+    const uint8_t* pl;    // the planes', by plane index
+    const uint8_t* gidx;  // every object's, by creation index: the grid's lists know spheres by GridShadowArgs::list_gidx
+};
 struct SpotShadowArgs : ShadowArgs {
     rtxspot::Packed spot;    // light 0's
+    CastArgs cast;
 };
 struct SpotLightsArgs : LightsArgs {
     rtxspot::Block spots;    // spot[i] belongs to lights.light[i]
+    CastArgs cast;
 };
 template <bool SPOT>
 using ShadowArgsOf = std::conditional_t<SPOT, SpotShadowArgs, ShadowArgs>;
@@ -317,6 +328,7 @@ struct TileArgs {
     const ShadowArgs* shadow;      // rtx_shadow_shade, rtx_reflect_shade
     const LightsArgs* lights;      // every other family; rtx_chain_shadow, rtx_grid_shadow
     const rtxspot::Block* spots;   // the cones of the set (rtx_scene_set_spots), or NULL while no light has one: the forms that read cones
+    const CastArgs* cast;          // the shadow-casting flags (rtx_scene_set_shadow_casting), or NULL while no launch reads them: the same forms
     const ReflectArgs* reflect;    // the mirror path
     const ChainArgs* chain;        // ... through the chain kernels
     const ChainShadowArgs* deep;   // ... with the deeper levels shadow-tested

@@ -678,6 +678,7 @@ static const unsigned kFamilyTakes[rtxplan::kShadeFamilies] = {
 static bool tile_args_ok(const TileArgs* t, unsigned takes)
 {
     const KArgs* a = t->a;
+    if (t->cast != nullptr && (t->cast->sph == nullptr || t->cast->pl == nullptr || t->cast->gidx == nullptr)) return false; // (the flags: all three views or none)
     if ((takes & kTakesShadow) && t->shadow == nullptr) return false;
     if ((takes & kTakesLights) && (t->lights == nullptr || t->lights->lights.n == 0u || t->lights->lights.n > (uint32_t)rtxlights::kMaxLights)) return false;
     if ((takes & kTakesReflect) && t->reflect == nullptr) return false;
@@ -701,13 +702,15 @@ static bool tile_args_ok(const TileArgs* t, unsigned takes)
 }
 
 // The arguments of the forms that read cones (rtx_scene_set_spots): the light set with the cones behind it, the one light with its
-// own.  No cones given (a FIN form launched for the finishes alone): every light a point light.
+// own.  No cones given (a FIN form launched for the finishes alone): every light a point light.  Behind the cones the shadow-casting
+// flags (rtx_scene_set_shadow_casting); none given: every object casts.
 static SpotLightsArgs spot_lights_args(const TileArgs* t)
 {
     SpotLightsArgs la;
     memset(&la, 0, sizeof la);
     static_cast<LightsArgs&>(la) = *t->lights;
     if (t->spots != nullptr) la.spots = *t->spots;
+    if (t->cast != nullptr) la.cast = *t->cast; // (else nullptr: every object casts)
     return la;
 }
 
@@ -717,6 +720,7 @@ static SpotShadowArgs spot_shadow_args(const TileArgs* t)
     memset(&sa, 0, sizeof sa);
     static_cast<ShadowArgs&>(sa) = *t->shadow;
     if (t->spots != nullptr) sa.spot = t->spots->spot[0];
+    if (t->cast != nullptr) sa.cast = *t->cast;
     return sa;
 }
 
@@ -744,9 +748,10 @@ extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs
         hipLaunchKernelGGL(rtx_reflect_chain, grid, block, 0, st, *t->a, *t->reflect, *t->chain);
         name = "rtx_reflect_chain";
         break;
-    // (the two shadow passes: their SPOT form while some light of the set has a cone -- rtx_scene_set_spots -- else the kernel they were)
+    // (the two shadow passes: their SPOT form while some light of the set has a cone -- rtx_scene_set_spots -- or some object casts no
+    // shadow -- rtx_scene_set_shadow_casting -- else the kernel they were)
     case rtxplan::kPassChainShadow:
-        if (t->spots != nullptr) {
+        if (t->spots != nullptr || t->cast != nullptr) {
             hipLaunchKernelGGL(rtx_chain_shadow<true>, grid, block, 0, st, *t->a, spot_lights_args(t), *t->reflect, *t->chain, *t->deep);
             name = "rtx_chain_shadow<spot>";
         } else {
@@ -755,7 +760,7 @@ extern "C" const char* rtx_k_launch_pass(rtxplan::ShadePass pass, const TileArgs
         }
         break;
     case rtxplan::kPassGridShadow:
-        if (t->spots != nullptr) {
+        if (t->spots != nullptr || t->cast != nullptr) {
             hipLaunchKernelGGL(rtx_grid_shadow<true>, grid, block, 0, st, *t->a, spot_lights_args(t), *t->reflect, *t->chain, *t->deep, *t->grid);
             name = "rtx_grid_shadow<spot>";
         } else {
@@ -790,7 +795,8 @@ extern "C" const char* rtx_k_launch_shade(rtxplan::ShadeFamily family, const Til
     // The FIN form also reads the cones of rtx_scene_set_spots, which travel behind the light set in its arguments (SpotLightsArgs,
     // SpotShadowArgs): one rich form per family, not a SPOT form beside FIN -- the render path hands it the finishes (the default
     // ones where no object has its own) whenever a light has a cone, so cones without finishes are refused here.
-    if (t->spots != nullptr && pa.fin_sph == nullptr) return nullptr;
+    // The shadow-casting flags (rtx_scene_set_shadow_casting) travel behind the cones, to the same form, under the same rule.
+    if ((t->spots != nullptr || t->cast != nullptr) && pa.fin_sph == nullptr) return nullptr;
     const auto launch = [&](auto m, auto o, auto fin, dim3 grid, dim3 block) {
         constexpr int M = decltype(m)::value, O = decltype(o)::value;
         constexpr bool F = decltype(fin)::value;

@@ -1,5 +1,5 @@
 // rtx_materials.hpp -- the surface attributes every object carries by creation index (reflectivity, pattern slot, index of
-// refraction, finish), stated once for the host: the book that holds them with their counts, the one upload flag and the generations
+// refraction, finish, shadow casting), stated once for the host: the book that holds them with their counts, the one upload flag and the generations
 // recorded graphs are checked against, and the layout of their device copies.  The book's operations are the only way the library
 // changes any of it.  Host only, no HIP header: g++ compiles it on its own (tests/host/test_materials.cpp).
 #pragma once
@@ -15,16 +15,17 @@ namespace rtxmat {
 
 // What a recorded graph is stale against, beside the scene generation: a change alters which launches make a frame and what they read.
 struct Generations {
-    uint64_t reflectivity = 0, pattern = 0, refraction = 0, finish = 0;
+    uint64_t reflectivity = 0, pattern = 0, refraction = 0, finish = 0, cast = 0;
 };
 
-// NULL, or why a graph recorded at `then` must not be replayed `now`: the first of the four that moved, in this order.
+// NULL, or why a graph recorded at `then` must not be replayed `now`: the first of the five that moved, in this order.
 inline const char* stale_fault(const Generations& then, const Generations& now)
 {
     if (then.reflectivity != now.reflectivity) return "the reflectivities changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     if (then.pattern != now.pattern) return "the pattern table or the objects' slots changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     if (then.refraction != now.refraction) return "the indices of refraction changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     if (then.finish != now.finish) return "the finishes changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
+    if (then.cast != now.cast) return "the shadow-casting flags changed after this graph was recorded (its launches read the device copies, which the next launch replaces): re-capture";
     return nullptr;
 }
 
@@ -36,12 +37,15 @@ struct Surface {
     uint8_t slot = 0; // of the pattern table, from 1: 0 plain
     float ior = 0.0f; // index of refraction: 0 a mirror (if k > 0)
     rtx_finish finish = rtxfinish::default_finish(); // ambient, diffuse and specular weight, shininess: the reference's constants
+    uint8_t cast = 1; // does the object occlude light in the shadow tests (rtx_scene_set_shadow_casting)?  1: as every object did
 };
 
 // Does a value count (n_reflective, n_patterned, n_refractive, n_finished)?
 inline bool counts(float v) { return v > 0.0f; }
 inline bool counts(uint8_t v) { return v != 0; }
 inline bool counts(const rtx_finish& f) { return !rtxfinish::is_default(f); }
+// ... and for n_shadowless: the flags that are not the default
+inline bool casts_no_shadow(uint8_t cast) { return cast == 0; }
 
 // The book.  Every set_* returns NULL for a good call, else what is wrong with it, and is all or nothing: a refused call has changed
 // nothing.  A change sets the flag (the device copies are stale until uploaded()) and moves the generation of what changed; a good
@@ -54,6 +58,7 @@ public:
     uint32_t n_patterned() const { return n_slot_; } // slot != 0: while not 0 a frame that would be direct takes the light / shadow path
     uint32_t n_refractive() const { return n_ior_; } // ior > 0: while not 0 the mirror path's launches get the ior arrays
     uint32_t n_finished() const { return n_fin_; }   // finish not the default's bytes: while not 0 a frame that would be direct takes the light / shadow path
+    uint32_t n_shadowless() const { return n_nocast_; } // cast == 0: while not 0 the launches that run a shadow test get the flags
     bool stale() const { return stale_; }            // the device copies do not hold these values, this table or this sorted order yet
     const Generations& generations() const { return gen_; }
     template <class T>
@@ -101,6 +106,21 @@ public:
         return store(&Surface::finish, n_fin_, gen_.finish, first, n, [&](size_t i) { return rtxfinish::stored(finishes[i]); }); // (-0 is stored as 0)
     }
 
+    // (*bad, if given: the first flag of the call that is refused, or n)
+    const char* set_shadow_casting(size_t first, size_t n, const uint8_t* casts, size_t* bad = nullptr)
+    {
+        if (bad) *bad = n;
+        if (const char* f = range_fault(size(), first, n)) return f;
+        if (n != 0 && casts == nullptr) return "casts is NULL";
+        for (size_t i = 0; i < n; i++) {
+            if (casts[i] > 1) {
+                if (bad) *bad = i;
+                return "cast must be 0 or 1";
+            }
+        }
+        return store(&Surface::cast, n_nocast_, gen_.cast, first, n, [&](size_t i) { return casts[i]; }, casts_no_shadow);
+    }
+
     const char* set_slot(size_t first, size_t n, size_t slot, size_t table_count)
     {
         if (const char* f = range_fault(size(), first, n)) return f;
@@ -118,17 +138,23 @@ private:
         return v_;
     }
 
-    template <class T, class At>
-    const char* store(T Surface::*field, uint32_t& count, uint64_t& gen, size_t first, size_t n, At value_at)
+    template <class T, class At, class Counts>
+    const char* store(T Surface::*field, uint32_t& count, uint64_t& gen, size_t first, size_t n, At value_at, Counts counted)
     {
         for (size_t i = 0; i < n; i++) {
             T& v = edit()[first + i].*field;
             const T to = value_at(i);
-            count = count - (counts(v) ? 1u : 0u) + (counts(to) ? 1u : 0u);
+            count = count - (counted(v) ? 1u : 0u) + (counted(to) ? 1u : 0u);
             v = to;
         }
         if (n != 0) gen++;
         return nullptr;
+    }
+
+    template <class T, class At>
+    const char* store(T Surface::*field, uint32_t& count, uint64_t& gen, size_t first, size_t n, At value_at)
+    {
+        return store(field, count, gen, first, n, value_at, [](const T& v) { return counts(v); });
     }
 
     void keep(std::vector<Surface> kept) // (every count afresh, every generation moves)
@@ -138,14 +164,16 @@ private:
         n_slot_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return s.slot != 0; });
         n_ior_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return s.ior > 0.0f; });
         n_fin_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return counts(s.finish); });
+        n_nocast_ = (uint32_t)std::count_if(v_.begin(), v_.end(), [](const Surface& s) { return casts_no_shadow(s.cast); });
         gen_.reflectivity++;
         gen_.pattern++;
         gen_.refraction++;
         gen_.finish++;
+        gen_.cast++;
     }
 
     std::vector<Surface> v_;
-    uint32_t n_k_ = 0, n_slot_ = 0, n_ior_ = 0, n_fin_ = 0;
+    uint32_t n_k_ = 0, n_slot_ = 0, n_ior_ = 0, n_fin_ = 0, n_nocast_ = 0;
     bool stale_ = true;
     Generations gen_;
 };

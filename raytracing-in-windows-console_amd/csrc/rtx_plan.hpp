@@ -1051,6 +1051,8 @@ inline size_t frames_per_chunk(uint64_t W, uint64_t H, uint64_t px_bytes, int n,
 //   surface finishes (n_finished != 0): the same -- the shade launches read the finishes (PatternArgs::fin_sph, fin_pl)
 //   spot lights (n_spots != 0): the same -- a cone on the reference's light is not the reference's light; the shade launches and the
 //   two shadow passes read the cones (SpotLightsArgs, SpotShadowArgs) in the forms that take them; nothing of any row changes
+//   objects that cast no shadow (n_shadowless != 0): no path and no row changes, whatever the count -- while a shadow test runs
+//   (shadow_tests_run) the launches that make it take the form that reads the flags (CastArgs, behind the cones)
 //
 // The hit buffer holds, per pixel of the launch, `levels` hit arrays (level j at byte 8 j px), then with `deep` a word of the
 // deeper levels' dark lights, then with `grid` a word of level 0's (dark0): 8 levels + 4 [deep] + 4 [grid] bytes.
@@ -1094,6 +1096,7 @@ struct ShadingRequest { // what the decision reads of the call, the options and 
     uint32_t n_patterned = 0;        // objects with a pattern slot above 0 (rtx_scene_set_object_pattern)
     uint32_t n_finished = 0;         // objects whose finish is not the default (rtx_scene_set_finish)
     uint32_t n_spots = 0;            // lights of the set that have a cone (rtx_scene_set_spots)
+    uint32_t n_shadowless = 0;       // objects that cast no shadow (rtx_scene_set_shadow_casting): read by no row of the plan
 };
 
 struct ShadingPlan {
@@ -1123,6 +1126,10 @@ inline ShadePath shading_path(const ShadingRequest& q)
     if (q.n_finished != 0) return kPathShaded;  // (and so is a finish)
     return kPathDirect; // the state the reference has: every launch is the reference's
 }
+
+// Do the frame's launches run shadow tests -- RTX_OPT_SHADOWS on and RTX_OPT_SHADOW_CHECK not 2, on a path that shades?  Then, and
+// only then, somebody reads the shadow-casting flags (rtx_scene_set_shadow_casting).
+inline bool shadow_tests_run(const ShadingRequest& q) { return q.shadows && q.shadow_check != 2 && shading_path(q) != kPathDirect; }
 
 // Does the frame ask for shadow tests (RTX_OPT_SHADOW_GRID) or for its mirror rays (RTX_OPT_REFLECT_GRID) through the world grid?
 // By the options and the scene alone: the caller then brings the grid up to date, once for both (a build blocks, so a capturing

@@ -68,6 +68,7 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     q.n_patterned = ctx->materials.n_patterned();
     q.n_finished = ctx->materials.n_finished();
     q.n_spots = rtxlights::spot_count(ctx->spots);
+    q.n_shadowless = ctx->materials.n_shadowless();
     return q;
 }
 
@@ -607,8 +608,8 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     return la;
 }
 
-// The device copies of the book after a change, a scene edit or a new sort (rtx_materials.hpp: the four attributes in their three
-// orders), the packed pattern table and, valid for the same generation, rtx_grid_reflect's map.  Waits for the frames in flight first.
+// The device copies of the book after a change, a scene edit or a new sort (rtx_materials.hpp: the five attributes in their three
+// orders, the shadow-casting flags by creation index too), the packed pattern table and, valid for the same generation, rtx_grid_reflect's map.  Waits for the frames in flight first.
 int upload_materials(rtx_ctx* ctx)
 {
     std::vector<rtxpattern::Entry> table(rtxpattern::kMaxPatterns); // (always all of them, zeros past the table's count)
@@ -628,6 +629,12 @@ int upload_materials(rtx_ctx* ctx)
     RTX_HIP(ctx, upload_orders(ctx->d_mat.ior, &rtxmat::Surface::ior));
     RTX_HIP(ctx, upload_orders(ctx->d_mat.slot, &rtxmat::Surface::slot));
     RTX_HIP(ctx, upload_orders(ctx->d_mat.finish, &rtxmat::Surface::finish));
+    RTX_HIP(ctx, upload_orders(ctx->d_mat.cast, &rtxmat::Surface::cast));
+    {
+        std::vector<uint8_t> by_gidx = ctx->materials.column(&rtxmat::Surface::cast);
+        if (by_gidx.empty()) by_gidx.push_back(1); // (never fewer than one entry, as the orders)
+        RTX_HIP(ctx, upload(ctx->d_mat.cast_gidx, by_gidx));
+    }
     RTX_HIP(ctx, upload(ctx->d_mat.table, table));
     RTX_HIP(ctx, upload(ctx->d_mat.pos, rtxmat::position_map(ctx->kind_of, ctx->local_of, ctx->ns, ctx->h_sorted_idx)));
     ctx->materials.uploaded();
@@ -646,12 +653,15 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
     const bool spotted = req.n_spots != 0 && shading_path(req) != kPathDirect; // (the same)
     // the forms of the shade families that read cones read finishes too: with a cone in the set they get the finishes, default or not
-    const bool finished = (req.n_finished != 0 || spotted) && shading_path(req) != kPathDirect; // (the same)
+    // ... and the shadow-casting flags (rtx_scene_set_shadow_casting), which somebody reads only while a shadow test runs
+    const bool shadowless = req.n_shadowless != 0 && shadow_tests_run(req);
+    const bool finished = (req.n_finished != 0 || spotted || shadowless) && shading_path(req) != kPathDirect; // (the same)
     if ((mirror || patterned || finished) && ctx->materials.stale()) {
         if (capturing) {
-            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror      ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
-                                                           : patterned ? "graph capture: the pattern slots are not uploaded yet (render once before capturing)"
-                                                                       : "graph capture: the finishes are not uploaded yet (render once before capturing)");
+            return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, mirror       ? "graph capture: the reflectivities are not uploaded yet (render once before capturing)"
+                                                           : patterned  ? "graph capture: the pattern slots are not uploaded yet (render once before capturing)"
+                                                           : shadowless ? "graph capture: the shadow-casting flags are not uploaded yet (render once before capturing)"
+                                                                        : "graph capture: the finishes are not uploaded yet (render once before capturing)");
         }
         if ((rc = upload_materials(ctx)) != RTX_OK) return rc;
     }
@@ -697,6 +707,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     ChainShadowArgs cs;
     GridReflectArgs gr;
     PatternArgs pa;
+    CastArgs cast;
     TileArgs t;
     std::memset(&pa, 0, sizeof pa);
     std::memset(&ra, 0, sizeof ra);
@@ -720,6 +731,12 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         pa.fin_pl = ctx->d_mat.finish.pl.get();
     }
     if (spotted) t.spots = &ctx->spots; // (by value into the launches that read cones, as the lights: nothing is uploaded)
+    if (shadowless) { // (else NULL: every launch is the one it is without flags)
+        cast.sph = ctx->d_mat.cast.spheres(sorted_staging).get();
+        cast.pl = ctx->d_mat.cast.pl.get();
+        cast.gidx = ctx->d_mat.cast_gidx.get();
+        t.cast = &cast;
+    }
     if (shade_takes_light_set(plan.family)) {
         la = lights_args(ctx, hits);
         t.lights = &la;

@@ -15,8 +15,9 @@
 // colour before it is encoded (reflect_blend); without, nothing of it is compiled.
 // FIN (rtx_scene_set_finish: the forms launched while some object has a finish of its own): every shade_light takes the finish of
 // the object it shades; without, nothing of it is compiled and the code is what it was before there were finishes.
-// The FIN forms also read the light's cone (rtx_scene_set_spots: sa is a SpotShadowArgs): they are launched while some object has
-// a finish or the light a cone.
+// The FIN forms also read the light's cone (rtx_scene_set_spots: sa is a SpotShadowArgs) and the shadow-casting flags
+// (rtx_scene_set_shadow_casting: sa.cast): they are launched while some object has a finish, the light a cone, or some object casts
+// no shadow while the shadow test runs.
 template <bool FIN>
 __device__ __forceinline__ V3 shade_light_of(const PatternArgs& pa, uint32_t id, const Ray& r, float distance, V3 normal, V3 od, const ShadowArgsOf<FIN>& sa, float dpow,
                                              float spow)
@@ -80,8 +81,11 @@ __device__ __forceinline__ void shade_body(const KArgs& a, const ShadowArgsOf<FI
         const float len2 = dot(toL, toL);
         const float inv_len2 = len2 > 0.0f ? 1.0f / len2 : 0.0f;
         const uint32_t own_sphere = (id & 0x80000000u) ? 0xffffffffu : id;
-        walk_spheres<kTileList>(
-            a, tid, lane, s_occ, s_occ_pos, nullptr, &s_cnt, sa.longest,
+        // (FIN, the rich form: the spheres that cast -- rtx_scene_set_shadow_casting; else the walk as it was)
+        const uint8_t* cast_sph = nullptr;
+        if constexpr (FIN) cast_sph = sa.cast.sph;
+        walk_spheres_casting<kTileList, FIN>(
+            a, cast_sph, tid, lane, s_occ, s_occ_pos, nullptr, &s_cnt, sa.longest,
             [&](bool in0, float4 c0, bool in1, float4 c1, uint32_t& k0, uint32_t& k1) {
                 k0 = in0 && rtxshadow::may_occlude(cone, Lf, c0.x, c0.y, c0.z, c0.w) ? 1u : 0u;
                 k1 = in1 && rtxshadow::may_occlude(cone, Lf, c1.x, c1.y, c1.z, c1.w) ? 1u : 0u;

@@ -116,9 +116,17 @@ __device__ __forceinline__ rtx_finish finish_of(const PatternArgs& pa, uint32_t 
 // the list is nearly full, and after the last step, flush(cnt) runs the threads' exact tests over its cnt entries; it must not
 // contain a barrier, and nothing here may leave the loop by a condition that is not workgroup-uniform.  `longest` (or nullptr)
 // gets the entries the workgroup listed over all fillings.
-template <int CAP, class Keep, class Flush>
-__device__ __forceinline__ void walk_spheres(const KArgs& a, uint32_t tid, uint32_t lane, float4* s_list, uint32_t* s_pos, uint8_t* s_payload, uint32_t* s_cnt,
-                                             uint32_t* longest, Keep keep, Flush flush)
+//
+// CAST (the shadow walks of the rich forms, rtx_scene_set_shadow_casting): `cast` holds a byte per sphere in a.sph_geom's order, or
+// is nullptr (a kernel argument: the test is uniform) while every sphere casts.  A sphere whose byte is 0 is dropped where it would be
+// kept -- whatever keep() says of it -- so it is never listed, no flush meets it and the lists are shorter.  The byte is loaded by
+// staged position (coalesced), requested with the next step's geometry and in front of it, ahead of this step's tests, and read
+// behind them: the tests hide its way, the geometry's request need not have landed when it is read, and no register holds it across
+// a flush (held from step to step as the geometry is, it cost the chain's families and rtx_reflect_shade an occupancy step and
+// rtx_chain_shadow scratch: profiles/r39_cast_resource_usage.txt).  Without CAST nothing of this is compiled: the code is what it was.
+template <int CAP, bool CAST, class Keep, class Flush>
+__device__ __forceinline__ void walk_spheres_casting(const KArgs& a, const uint8_t* cast, uint32_t tid, uint32_t lane, float4* s_list, uint32_t* s_pos,
+                                                     uint8_t* s_payload, uint32_t* s_cnt, uint32_t* longest, Keep keep, Flush flush)
 {
     const uint32_t ns = a.ns;
     uint32_t listed = 0u; // candidates this workgroup kept after culling, over all fillings of the list
@@ -128,11 +136,22 @@ __device__ __forceinline__ void walk_spheres(const KArgs& a, uint32_t tid, uint3
     for (uint32_t base = 0; base < ns; base += (uint32_t)kChunk) {
         const float4 c0 = g0, c1 = g1;
         const uint32_t i0 = base + tid, i1 = base + (uint32_t)kThreads + tid;
+        uint32_t f0 = 1u, f1 = 1u; // (CAST) do this step's two spheres cast a shadow?
+        if constexpr (CAST) {
+            if (cast != nullptr) {
+                if (i0 < ns) f0 = cast[i0];
+                if (i1 < ns) f1 = cast[i1];
+            }
+        }
         // the next step's loads go out before this step's tests
         if (i0 + (uint32_t)kChunk < ns) g0 = a.sph_geom[i0 + kChunk];
         if (i1 + (uint32_t)kChunk < ns) g1 = a.sph_geom[i1 + kChunk];
         uint32_t p0 = 0u, p1 = 0u;
         keep(i0 < ns, c0, i1 < ns, c1, p0, p1);
+        if constexpr (CAST) {
+            p0 = f0 != 0u ? p0 : 0u;
+            p1 = f1 != 0u ? p1 : 0u;
+        }
         const bool k0 = p0 != 0u, k1 = p1 != 0u;
         const unsigned long long m0 = __ballot(k0), m1 = __ballot(k1);
         const uint32_t n0 = (uint32_t)__popcll(m0), n1 = (uint32_t)__popcll(m1);
@@ -168,11 +187,21 @@ __device__ __forceinline__ void walk_spheres(const KArgs& a, uint32_t tid, uint3
     if (longest != nullptr && tid == 0u) atomicMax(longest, listed);
 }
 
+template <int CAP, class Keep, class Flush>
+__device__ __forceinline__ void walk_spheres(const KArgs& a, uint32_t tid, uint32_t lane, float4* s_list, uint32_t* s_pos, uint8_t* s_payload, uint32_t* s_cnt,
+                                             uint32_t* longest, Keep keep, Flush flush)
+{
+    walk_spheres_casting<CAP, false>(a, nullptr, tid, lane, s_list, s_pos, s_payload, s_cnt, longest, keep, flush);
+}
+
 // ---------------------------------------------------------------- the shadow test of one light
 
 // Self-shadow and the planes, per pixel: is the visible point P (normal `normal`, on plane own_plane or 0xffffffff) cut off from
 // the light L (toL = L - P)?  A pixel that is leaves `pending`; one that stays pending has its segment tested against the spheres.
-__device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, V3 P, V3 normal, V3 L, V3 toL, uint32_t own_plane, bool& pending)
+// CAST (rtx_scene_set_shadow_casting): cast_pl holds a byte per plane, or is nullptr while every plane casts; a plane whose byte is 0
+// is no occluder -- one wave-uniform read per plane.  Self-shadow stays: a non-casting object still shadows itself.
+template <bool CAST>
+__device__ __forceinline__ bool shadowed_before_spheres_casting(const KArgs& a, const uint8_t* cast_pl, V3 P, V3 normal, V3 L, V3 toL, uint32_t own_plane, bool& pending)
 {
     bool shadowed = false;
     if (pending && dot(normal, toL) <= 0.0f) {
@@ -182,6 +211,9 @@ __device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, V3 P, V3
     // planes: few, wave-uniform index (scalar loads)
     if (__ballot(pending) != 0ull) {
         for (uint32_t q = 0; q < a.np; q++) {
+            if constexpr (CAST) {
+                if (cast_pl != nullptr && cast_pl[q] == 0u) continue; // (uniform)
+            }
             const float4 pa = a.pl_a[q], pb = a.pl_b[q];
             const V3 pp = v3(pa.x, pa.y, pa.z), pn = v3(pb.x, pb.y, pb.z);
             const float sP = dot(sub(P, pp), pn), sL = dot(sub(L, pp), pn);
@@ -198,6 +230,11 @@ __device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, V3 P, V3
     return shadowed;
 }
 
+__device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, V3 P, V3 normal, V3 L, V3 toL, uint32_t own_plane, bool& pending)
+{
+    return shadowed_before_spheres_casting<false>(a, nullptr, P, normal, L, toL, own_plane, pending);
+}
+
 // The same under a light set that may carry cones (rtx_scene_set_spots): with a SpotLightsArgs, a point outside light i's cone --
 // rtx_spot.hpp's own s, from the lightDir the shading forms at P, is not above 0 -- leaves `pending` first, and is not shadowed: the
 // shade launch weighs the light with 0 there, which is the float a dark light enters with.  With a LightsArgs nothing is added.
@@ -210,6 +247,7 @@ __device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, const LA
             const V3 ld = normalize_gpu(toL);
             if (rtxspot::outside(sp, ld.x, ld.y, ld.z)) pending = false;
         }
+        return shadowed_before_spheres_casting<true>(a, la.cast.pl, P, normal, L, toL, own_plane, pending); // (the planes that cast)
     }
     return shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending);
 }
@@ -223,6 +261,7 @@ __device__ __forceinline__ bool shadowed_before_spheres(const KArgs& a, const SA
             const V3 ld = normalize_gpu(toL);
             if (rtxspot::outside(sa.spot, ld.x, ld.y, ld.z)) pending = false;
         }
+        return shadowed_before_spheres_casting<true>(a, sa.cast.pl, P, normal, L, toL, own_plane, pending); // (the planes that cast)
     }
     return shadowed_before_spheres(a, P, normal, L, toL, own_plane, pending);
 }
@@ -344,8 +383,12 @@ __device__ __forceinline__ uint32_t lights_dark_set(const KArgs& a, const LA& la
     // ---- spheres: one walk of the scene for all lights
     if (live != 0u) {
         const uint32_t own_sphere = (id & 0x80000000u) ? 0xffffffffu : id;
-        walk_spheres<kTileList>(
-            a, tid, lane, s.occ, s.occ_pos, reinterpret_cast<uint8_t*>(s.occ_mask), &s.cnt, la.longest,
+        // (the rich form: the spheres that cast -- rtx_scene_set_shadow_casting; else the walk as it was)
+        constexpr bool kCast = std::is_same_v<LA, SpotLightsArgs>;
+        const uint8_t* cast_sph = nullptr;
+        if constexpr (kCast) cast_sph = la.cast.sph;
+        walk_spheres_casting<kTileList, kCast>(
+            a, cast_sph, tid, lane, s.occ, s.occ_pos, reinterpret_cast<uint8_t*>(s.occ_mask), &s.cnt, la.longest,
             [&](bool in0, float4 c0, bool in1, float4 c1, uint32_t& km0, uint32_t& km1) { // the lights each of the two spheres may occlude
                 for (uint32_t m = live; m != 0u; m &= m - 1u) {
                     const uint32_t i = (uint32_t)__builtin_ctz(m);
