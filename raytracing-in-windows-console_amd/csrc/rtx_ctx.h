@@ -5,6 +5,7 @@
 #include "rtx_kernels.h"
 #include "rtx_materials.hpp"
 #include "rtx_mem.hpp"
+#include "rtx_options.hpp"
 #include "rtx_plan.hpp"
 #include "rtx_sync.hpp"
 
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+using rtxmem::Counter;
 using rtxmem::DeviceBuf;
 using rtxmem::Event;
 using rtxmem::PinnedBuf;
@@ -97,18 +99,16 @@ struct rtx_ctx {
     Stream stream;                  // (declared first: destroyed after everything that was queued on it is gone)
     Event ev_start, ev_stop;        // (with timing: rtx_timer_*)
     size_t max_w = 0, max_h = 0, capacity = 0;
+    rtxopt::Options opt;            // what rtx_set_option stores (rtx_options.hpp; a group's own four: rtx_group.cpp)
     DeviceBuf<uint8_t> d_frame;
     DeviceBuf<uint8_t> d_min;       // minimise output (allocated on first use)
     DeviceBuf<uint8_t> d_scan;      // minimise scratch (bytes)
     DeviceBuf<uint32_t> d_words;    // rtx_update's pixel words (W * H; allocated on first use)
-    int64_t opt_update_words = -1;  // -1 auto (on), 0 off: rtx_update traces pixel words and minimises from them
-    int64_t opt_update_host_write = -1; // RTX_OPT_UPDATE_HOST_WRITE: -1 auto (frames up to 2^17 slots), 0 off, 1 on
     uint64_t stat_host_writes = 0;
     PinnedBuf<uint64_t> h_pair;     // two pinned words: a rank's stream length and failure word (rtx_update on a group, RTX_OPT_GROUP_UPDATE)
     DeviceBuf<uint64_t> d_look;     // rtx_min_fused's look-back tables (agg, grp: rtx_post.hip), zeroed when allocated
     size_t look_blocks() const { return d_look.capacity() / 2; } // ... sized for this many blocks
     uint32_t look_epoch = 0;        // of the last fused launch (0: none yet; never used as a tag)
-    int64_t opt_min_fused = -1;     // RTX_OPT_MINIMIZE_FUSED: -1 auto (on), 0 three launches, 1 on, 2 on with blocks that give up (tests)
     uint64_t stat_min_fallbacks = 0; // fused minimise launches that gave up and were redone as three launches
     DeviceBuf<uint8_t> d_grey;
     size_t dirty_hi = 0;            // bytes of d_frame that may be non-zero
@@ -126,16 +126,9 @@ struct rtx_ctx {
     DeviceBuf<uint32_t> d_sorted_idx, d_pos_of;
     std::vector<float4> h_centres;  // cx cy cz r as created, by sphere index (the sort's input; the device copy moves under physics)
     uint64_t sorted_gen = 0;
-    int64_t opt_sorted_store = -1;  // -1 auto (on), 0 off
     std::vector<uint8_t> kind_of;   // per creation index: 1 plane, 2 sphere (Object3D.h:14)
     std::vector<uint32_t> local_of; // per creation index: index within its kind
 
-    int64_t opt_kernel = RTX_KERNEL_AUTO;
-    int64_t opt_tile_log2w = 0;
-    int64_t opt_subtiles = 0;
-    int64_t opt_two_level = -1;     // -1 auto, 0 off, 1 on
-    int64_t opt_refine = -1;        // -1 auto, 0 off, 1 on
-    int64_t opt_cell_capacity = 0;  // entries per coarse cell list; 0 = 4 ns / cells + 1024
     // two-level culling scratch, one set per stream that renders (launches on one stream are ordered, so a
     // set is never shared by frames in flight on different streams)
     struct CellScratch {
@@ -196,8 +189,6 @@ struct rtx_ctx {
         uint64_t last_use = 0;
     };
     XcdOrder xcd_orders[4];                     // the grids seen last (least recently used is replaced)
-    int64_t opt_cell_reuse = -1;                // -1 auto (on), 0 off: bin per frame as before round 3
-    int64_t opt_xcd_order = -1;                 // -1 auto (on for two-level grids), 0 off
     // view-density feedback (rtxplan::ViewDensity): the longest candidate list the trace workgroups of an epoch (8 culling
     // launches) report, copied to the pinned word when the epoch ends and taken as an observation once that copy has landed
     DeviceBuf<uint32_t> d_longest;              // three words in rotation: the epoch being filled, the next one (zeroed), the one before (being copied)
@@ -206,7 +197,6 @@ struct rtx_ctx {
     bool longest_copy_pending = false;
     uint32_t longest_epoch = 0, longest_launches = 0;
     rtxplan::ViewDensity view_density;
-    int64_t opt_view_adapt = -1;                // -1 auto (on), 0 off
     uint64_t stat_density_switches = 0;
     hipStream_t recent_streams[16] = {nullptr}; // the render streams of the last two-level launches
     unsigned recent_pos = 0, render_streams_seen = 0;
@@ -223,10 +213,7 @@ struct rtx_ctx {
                                      // |dt| x the largest |speed x mover|; rtx_scene_set_spheres: the largest move; other scene edits and removals add 1e3):
                                      // dispatch orders go stale with it
     float max_speed = 0.0f;          // largest |speed * mover| any sphere was given: what a physics step moves it by per unit of dt
-    int64_t opt_batch = -1;         // -1 auto (on), 0 off: rtx_submit_slabs renders consecutive slabs of one stream with one launch
     uint64_t stat_batched_launches = 0;
-    int64_t opt_tile_order = -1;    // -1 = auto (grids of one dispatch round, period 16), 0 = off, k = on: re-derive the order after
-                                    // the 1st and 2nd frame of a grid, then every k-th
     int n_cu = 0;                   // compute units of the device
 
     // events of rtx_submit_slabs' fork/join: one for `after`, one per distinct render stream seen
@@ -268,11 +255,7 @@ struct rtx_ctx {
     size_t n_lights = 1;
     rtxspot::Block spots = {}; // the cones of the set (rtx_scene_set_spots), as stored: all zero while every light is a point light
     uint64_t stat_spot_frames = 0;
-    int64_t opt_lights_check = 0;
-    int64_t opt_shadows = 0;
-    int64_t opt_shadow_check = 0;
     uint64_t stat_shadow_frames = 0;
-    DeviceBuf<uint32_t> d_shadow_longest; // the longest occluder list of the last two-pass launch (one word)
     static constexpr int kMaxHitStreams = 64;
     struct HitScratch {
         hipStream_t stream = nullptr;
@@ -300,21 +283,30 @@ struct rtx_ctx {
         DeviceBuf<uint32_t> pos; // rtxmat::position_map, for rtx_grid_reflect (RTX_OPT_REFLECT_GRID)
     } d_mat;
     std::vector<uint32_t> h_sorted_idx; // sorted position -> sphere index of the sorted copy (valid while sorted_gen == scene_gen)
-    int64_t opt_reflect_check = 0;
     uint64_t stat_reflect_frames = 0;
-    DeviceBuf<uint32_t> d_reflect_longest; // the longest candidate list of the last launch set on the path (one word)
     // mirrors that see mirrors (RTX_OPT_REFLECT_DEPTH): at depth 1 with the check option 0 every launch is the one-bounce path's;
     // otherwise rtx_reflect_chain traces every level in one launch and rtx_lights_chain_shade folds the chain, through 8 (depth + 1)
     // bytes per pixel of the stream's hit buffer.  The depth travels in the kernel arguments.
-    int64_t opt_reflect_depth = 1;
-    int64_t opt_reflect_depth_check = 0;
-    DeviceBuf<uint32_t> d_reflect_rays; // secondary rays per level of the last launch set on the chain kernels (RTX_MAX_REFLECT_DEPTH words)
-    bool reflect_rays_valid = false;    // the launch set queued last took the chain kernels (else RTX_STAT_REFLECT_RAYS reads 0)
     // shadows seen in mirrors (RTX_OPT_REFLECT_SHADOWS): in effect while RTX_OPT_SHADOWS is 1 and the mirror path is taken; then the
     // chain kernels at any depth, rtx_chain_shadow between them, and 4 more bytes per pixel of the hit buffer (the dark words)
-    int64_t opt_reflect_shadows = 0;
-    DeviceBuf<uint32_t> d_reflect_shadow_points; // hit points tested per level by the last launch set (RTX_MAX_REFLECT_DEPTH words)
-    bool reflect_shadow_points_valid = false;    // the launch set queued last ran rtx_chain_shadow (else the counters read 0)
+
+    // The counters kernels write and rtx_get_option reads back (rtxmem::Counter): one word or one array per context, which the
+    // launch set queued last has zeroed on its stream, behind its closest-hit launch.  When each reads its words and when 0:
+    //  - the two longest lists and the two fallback counters: whenever the buffer exists (it keeps the last launch set's words
+    //    that wrote it);
+    //  - reflect_rays: on the mirror path launch_frame sets valid to whether the plan counts rays (the chain kernels or
+    //    rtx_grid_reflect; else RTX_STAT_REFLECT_RAYS reads 0).  The shaded path without a mirror and the direct path leave flag
+    //    and buffer alone: the words of the last mirror frame stay readable;
+    //  - reflect_shadow_points: cleared at the top of launch_frame by every frame off the mirror path, the direct path included,
+    //    and by every batched launch (never the mirror path's); on the mirror path valid is whether rtx_chain_shadow runs (plan.deep);
+    //  - delta_counts (changed cells, runs): valid from the first delta launch queued on (rtx_delta_counters, below).
+    Counter<uint32_t, 1> shadow_longest;          // the longest occluder list of the last two-pass launch
+    Counter<uint32_t, 1> reflect_longest;         // the longest candidate list of the last launch set on the mirror path
+    Counter<uint32_t, RTX_MAX_REFLECT_DEPTH> reflect_rays{false};          // secondary rays per level
+    Counter<uint32_t, RTX_MAX_REFLECT_DEPTH> reflect_shadow_points{false}; // hit points shadow-tested per level
+    Counter<uint32_t, 1> shadow_grid_fallback;    // segments of the last launch set through the grid that tested every sphere
+    Counter<uint32_t, 1> reflect_grid_fallback;   // rays of the last launch set through the grid that tested every sphere
+    Counter<unsigned long long, 2> delta_counts{false};
 
     // ray queries (rtx_query_rays, rtx_pick; rtx_query.cpp): the world grid over the scene arrays in creation order, rebuilt on the
     // context's stream by the first query after a scene edit or a physics step (qgrid.dirty).  The build is the writer of `sync`
@@ -333,28 +325,21 @@ struct rtx_ctx {
         rtxsync::Shared sync;
     };
     QueryGrid qgrid;
-    int64_t opt_query_check = 0;
-    int64_t opt_query_load = 0;       // RTX_OPT_QUERY_LOAD: spheres per cell the grid aims at, in 1/16 (0: rtxgrid::kDefaultLoad)
     uint64_t stat_query_builds = 0;
 
     // shadow tests through that grid (RTX_OPT_SHADOW_GRID): in effect while RTX_OPT_SHADOWS is 1, RTX_OPT_SHADOW_CHECK 0, the scene has
     // a sphere and the build found a usable grid; then rtx_grid_shadow decides every level's dark lights per pixel and the
     // rtx_grid_*shade family shades from its words: 4 more bytes per pixel of the stream's hit buffer
-    int64_t opt_shadow_grid = 0;
     uint64_t stat_shadow_grid_frames = 0;
-    DeviceBuf<uint32_t> d_shadow_grid_fallback; // segments of the last launch set on the path that tested every sphere (one word)
 
     // mirror rays through that grid (RTX_OPT_REFLECT_GRID): in effect on the mirror path while RTX_OPT_REFLECT_CHECK is 0, the scene has a
     // sphere and the build found a usable grid; then rtx_grid_reflect writes the hit arrays in place of rtx_reflect_hit /
     // rtx_reflect_chain, finding spheres through d_mat.pos.
-    int64_t opt_reflect_grid = 0;
     uint64_t stat_reflect_grid_frames = 0;
-    DeviceBuf<uint32_t> d_reflect_grid_fallback; // rays of the last launch set on the path that tested every sphere (one word)
 
     // supersampling (RTX_OPT_SUPERSAMPLE): with S > 1 rtx_render_rows runs its launches for the S W x S H sample frame in values form
     // into the render stream's sample buffer (32 S^2 W rows bytes; one per render stream as the hit buffers, for at most
     // kMaxHitStreams streams; it grows on demand, never shrinks and goes with the context) and rtx_resolve folds it into the target
-    int64_t opt_supersample = 1;
     uint64_t stat_supersample_frames = 0;
     struct SampleScratch {
         hipStream_t stream = nullptr;
@@ -391,8 +376,6 @@ struct rtx_ctx {
     size_t delta_w = 0, delta_h = 0;
     int delta_mode = -1;
     DeviceBuf<uint8_t> d_delta_out;
-    DeviceBuf<unsigned long long> d_delta_counts;
-    bool delta_counts_valid = false;    // a delta launch has run (else the two counters read 0)
     uint64_t stat_delta_frames = 0, stat_delta_keyframes = 0;
     uint64_t stat_half_delta_frames = 0, stat_half_delta_keyframes = 0; // RTX_STAT_HALF_DELTA_FRAMES, _KEYFRAMES
 
@@ -409,6 +392,14 @@ struct rtx_ctx {
 // rtx_api.cpp
 int rtx_fail(rtx_ctx* ctx, int status, const std::string& msg);
 int rtx_hip_fail(rtx_ctx* ctx, hipError_t e, const char* what);
+// the two counters for a delta launch about to be queued: from now on RTX_STAT_DELTA_CELLS and _RUNS read them
+inline int rtx_delta_counters(rtx_ctx* ctx, unsigned long long** out)
+{
+    if (ctx->delta_counts.ensure() != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
+    ctx->delta_counts.valid = true;
+    *out = ctx->delta_counts.get();
+    return RTX_OK;
+}
 int rtx_sync_scene(rtx_ctx* ctx);
 void rtx_scene_edited(rtx_ctx* ctx);
 int rtx_sort_scene(rtx_ctx* ctx, const float origin[3]); // rtx_post.hip

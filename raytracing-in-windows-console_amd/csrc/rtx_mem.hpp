@@ -1,6 +1,6 @@
 // rtx_mem.hpp -- the owners of everything the library allocates on a device: memory (DeviceBuf), pinned host memory (PinnedBuf),
-// events and streams.  Move-only; a destructor releases.  Nothing else in csrc/ allocates or frees (rtx_host_alloc / rtx_host_free
-// apart: that memory is the caller's).  DESIGN.md, "Ownership".
+// the counters kernels write and the host reads back (Counter), events and streams.  Move-only; a destructor releases.  Nothing else in
+// csrc/ allocates or frees (rtx_host_alloc / rtx_host_free apart: that memory is the caller's).  DESIGN.md, "Ownership".
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -105,6 +105,36 @@ template <class T>
 using DeviceBuf = Buf<T, false>;
 template <class T>
 using PinnedBuf = Buf<T, true>;
+
+// n words of device memory -> the host, after everything queued on the device: the one place the library reads counters back.
+template <class T>
+hipError_t read_words(int device, const T* d_src, size_t n, T* out)
+{
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e != hipSuccess ? e : hipMemcpy(out, d_src, n * sizeof(T), hipMemcpyDeviceToHost);
+}
+
+// N words that kernels count into, allocated on first use.  `valid` says whether the words belong to the launch set queued last:
+// whoever queues launches sets it, and a counter that is not valid, or has never been allocated, reads 0 without touching the device.
+template <class T, size_t N>
+class Counter {
+public:
+    explicit Counter(bool valid_ = true) : valid(valid_) {}
+    bool valid;
+
+    hipError_t ensure() { return buf_.reserve(N, nothing()); }
+    hipError_t zero(hipStream_t s) const { return hipMemsetAsync(buf_.get(), 0, N * sizeof(T), s); }
+    T* get() const { return buf_.get(); }
+    hipError_t read(int device, T (&out)[N]) const
+    {
+        for (T& w : out) w = 0;
+        return buf_.get() && valid ? read_words(device, buf_.get(), N, out) : hipSuccess;
+    }
+
+private:
+    DeviceBuf<T> buf_;
+};
 
 // An event, created on first use.  Converts to its handle (nullptr until ensure has succeeded).
 class Event {

@@ -139,7 +139,7 @@ int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_o
     *run = MinRun{in, d_out, d_scan, (uint64_t*)d_scan, 0u};
     const uint64_t n_slots = (uint64_t)in.w * in.h;
     const uint64_t n_blocks = min_blocks(n_slots);
-    if (ctx->opt_min_fused == 0 || n_blocks > (1u << 24)) return launch_minimize_chain(ctx, *run);
+    if (ctx->opt.min_fused == 0 || n_blocks > (1u << 24)) return launch_minimize_chain(ctx, *run);
     int rc = ensure_look_tables(ctx, (size_t)n_blocks);
     if (rc != RTX_OK) return rc;
     if (++ctx->look_epoch == 0u) {
@@ -152,7 +152,7 @@ int launch_minimize(rtx_ctx* ctx, void* d_scan, const MinInput& in, uint8_t* d_o
     uint64_t* agg = ctx->d_look.get();
     uint64_t* grp = agg + ctx->look_blocks();
     const uint32_t ng = (uint32_t)(ctx->look_blocks() / rtx::kLookGroup);
-    const uint32_t polls = ctx->opt_min_fused == 2 ? 0u : rtx::kLookPolls;
+    const uint32_t polls = ctx->opt.min_fused == 2 ? 0u : rtx::kLookPolls;
     if (in.counts) RTX_HIP(ctx, hipMemsetAsync(in.counts, 0, 2 * sizeof(unsigned long long), ctx->stream));
     rc = with_source(ctx, in, [&](auto src) {
         using Src = decltype(src);
@@ -598,11 +598,10 @@ int rtx_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void* d_cu
     }
     if (out_capacity < rtx_delta_bound(mode, w, h)) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_delta_words: the output holds less than rtx_delta_bound");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
-    }
-    ctx->delta_counts_valid = true;
-    return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts.get()), d_out, out_bytes);
+    unsigned long long* counts = nullptr;
+    const int rc = rtx_delta_counters(ctx, &counts);
+    if (rc != RTX_OK) return rc;
+    return minimize_and_wait(ctx, delta_input(mode, w, h, d_cur, d_prev, counts), d_out, out_bytes);
 }
 
 size_t rtx_half_bound(int mode, size_t w, size_t h)
@@ -642,11 +641,10 @@ int rtx_half_delta_words(rtx_ctx* ctx, int mode, size_t w, size_t h, const void*
     }
     if (out_capacity < bound) return rtx_fail(ctx, RTX_ERR_TOO_LARGE, "rtx_half_delta_words: the output holds less than rtx_half_delta_bound");
     RTX_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) {
-        return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
-    }
-    ctx->delta_counts_valid = true;
-    return minimize_and_wait(ctx, half_delta_input(mode, w, h, d_cur, d_prev, ctx->d_delta_counts.get()), d_out, out_bytes);
+    unsigned long long* counts = nullptr;
+    const int rc = rtx_delta_counters(ctx, &counts);
+    if (rc != RTX_OK) return rc;
+    return minimize_and_wait(ctx, half_delta_input(mode, w, h, d_cur, d_prev, counts), d_out, out_bytes);
 }
 
 } // extern "C"

@@ -49,7 +49,7 @@ int fill_grid(rtx_ctx* ctx)
     RTX_HIP(ctx, hipMemcpyAsync(box, b.bounds, sizeof box, hipMemcpyDeviceToHost, st));
     RTX_HIP(ctx, hipStreamSynchronize(st));
     const uint32_t n_finite = float_to_bits(box[6]);
-    const float load = ctx->opt_query_load > 0 ? (float)ctx->opt_query_load / 16.0f : rtxgrid::kDefaultLoad;
+    const float load = ctx->opt.query_load > 0 ? (float)ctx->opt.query_load / 16.0f : rtxgrid::kDefaultLoad;
     q.plan = rtxgrid::plan_grid(box, box + 3, n_finite, load);
     if (!q.plan.ok) {
         q.brute = true; // no usable grid: nothing to walk
@@ -119,7 +119,7 @@ int query_device(rtx_ctx* ctx, size_t n, const void* d_rays, void* d_hits, unsig
     int rc = rtx_sync_scene(ctx);
     if (rc != RTX_OK) return rc;
     rtx_ctx::QueryGrid& g = ctx->qgrid;
-    const bool brute = ctx->opt_query_check == 1;
+    const bool brute = ctx->opt.query_check == 1;
     if ((rc = rtx_grid_ensure(ctx, stream)) != RTX_OK) return rc;
     QueryArgs a;
     std::memset(&a, 0, sizeof a);
@@ -179,8 +179,6 @@ bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status)
 {
     *status = RTX_OK;
     switch (option) {
-    case RTX_OPT_QUERY_CHECK: *value = ctx->opt_query_check; return true;
-    case RTX_OPT_QUERY_LOAD: *value = ctx->opt_query_load; return true;
     case RTX_STAT_QUERY_GRID_BUILDS: *value = (int64_t)ctx->stat_query_builds; return true;
     case RTX_STAT_QUERY_LARGE_SPHERES: *value = (int64_t)ctx->qgrid.n_large; return true;
     case RTX_STAT_QUERY_GRID_CELLS: *value = (int64_t)ctx->qgrid.n_cells; return true;
@@ -188,12 +186,7 @@ bool rtx_query_stat(const rtx_ctx* ctx, int option, int64_t* value, int* status)
     case RTX_STAT_QUERY_BRUTE: *value = ctx->qgrid.brute ? 1 : 0; return true;
     case RTX_STAT_QUERY_FALLBACK_RAYS: {
         uint32_t w = 0;
-        if (ctx->qgrid.d_words.get()) {
-            if (hipSetDevice(ctx->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-                hipMemcpy(&w, ctx->qgrid.d_words.get() + 2, sizeof w, hipMemcpyDeviceToHost) != hipSuccess) {
-                *status = RTX_ERR_HIP;
-            }
-        }
+        if (ctx->qgrid.d_words.get() && rtxmem::read_words(ctx->device, ctx->qgrid.d_words.get() + 2, 1, &w) != hipSuccess) *status = RTX_ERR_HIP;
         *value = (int64_t)w;
         return true;
     }

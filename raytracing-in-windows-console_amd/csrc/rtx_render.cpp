@@ -31,7 +31,7 @@ double pixel_aspect(const rtx_params* p)
 
 bool uses_culling_kernel(const rtx_ctx* ctx)
 {
-    switch (ctx->opt_kernel) {
+    switch (ctx->opt.kernel) {
     case RTX_KERNEL_BRUTE: return false;
     case RTX_KERNEL_BINNED: return true;
     default: return ctx->ns > 64; // below that the frustum set-up costs more than it saves
@@ -42,7 +42,7 @@ bool uses_culling_kernel(const rtx_ctx* ctx)
 bool uses_two_level(const rtx_ctx* ctx, bool view_dense = false)
 {
     const uint32_t from = view_dense ? 256u : 2048u;
-    return uses_culling_kernel(ctx) && ctx->ns > 0 && (ctx->opt_two_level >= 1 || (ctx->opt_two_level < 0 && ctx->ns >= from));
+    return uses_culling_kernel(ctx) && ctx->ns > 0 && (ctx->opt.two_level >= 1 || (ctx->opt.two_level < 0 && ctx->ns >= from));
 }
 
 // What rtxplan::plan_shading reads of the call, the options and the scene (grid_usable: not known yet).
@@ -52,18 +52,18 @@ rtxplan::ShadingRequest shading_request(const rtx_ctx* ctx, int mode)
     const rtx_light ref = rtx_reference_light();
     rtxplan::ShadingRequest q;
     q.mode = mode;
-    q.shadows = ctx->opt_shadows != 0;
-    q.shadow_check = (int)ctx->opt_shadow_check;
-    q.lights_check = ctx->opt_lights_check != 0;
+    q.shadows = ctx->opt.shadows != 0;
+    q.shadow_check = (int)ctx->opt.shadow_check;
+    q.lights_check = ctx->opt.lights_check != 0;
     q.n_lights = ctx->n_lights;
     q.light0_is_reference = std::memcmp(&ctx->lights[0], &ref, sizeof ref) == 0;
     q.n_reflective = ctx->materials.n_reflective();
-    q.reflect_check = (int)ctx->opt_reflect_check;
-    q.reflect_depth = (uint32_t)ctx->opt_reflect_depth;
-    q.reflect_depth_check = ctx->opt_reflect_depth_check != 0;
-    q.reflect_shadows = ctx->opt_reflect_shadows != 0;
-    q.shadow_grid = ctx->opt_shadow_grid != 0;
-    q.reflect_grid = ctx->opt_reflect_grid != 0;
+    q.reflect_check = (int)ctx->opt.reflect_check;
+    q.reflect_depth = (uint32_t)ctx->opt.reflect_depth;
+    q.reflect_depth_check = ctx->opt.reflect_depth_check != 0;
+    q.reflect_shadows = ctx->opt.reflect_shadows != 0;
+    q.shadow_grid = ctx->opt.shadow_grid != 0;
+    q.reflect_grid = ctx->opt.reflect_grid != 0;
     q.ns = ctx->ns;
     q.n_patterned = ctx->materials.n_patterned();
     q.n_finished = ctx->materials.n_finished();
@@ -80,7 +80,7 @@ int check_recordable(rtx_ctx* ctx, hipStream_t stream, int mode, bool* capturing
     RTX_HIP(ctx, hipStreamIsCapturing(stream, &st));
     *capturing = st == hipStreamCaptureStatusActive;
     if (!*capturing) return RTX_OK;
-    if (ctx->opt_supersample > 1 && mode != RTX_SDL) {
+    if (ctx->opt.supersample > 1 && mode != RTX_SDL) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "graph capture: supersampled launches cannot be recorded (RTX_OPT_SUPERSAMPLE: the sample buffer may grow)");
     }
     if (ctx->ns > ctx->ns_uploaded || ctx->np > ctx->np_uploaded) {
@@ -102,7 +102,7 @@ int scene_up_to_date(rtx_ctx* ctx, const float cam_pos[3])
 {
     int rc;
     if ((rc = rtx_sync_scene(ctx)) != RTX_OK) return rc;
-    if (ctx->opt_sorted_store != 0 && ctx->sorted_gen != ctx->scene_gen && ctx->ns >= 256u) {
+    if (ctx->opt.sorted_store != 0 && ctx->sorted_gen != ctx->scene_gen && ctx->ns >= 256u) {
         if ((rc = rtx_sort_scene(ctx, cam_pos)) != RTX_OK) return rc;
         ctx->lists_gen++; // (cell lists hold positions in those arrays)
         ctx->cell_policy.invalidate();
@@ -144,9 +144,9 @@ rtxplan::TileRequest tile_request(const rtx_ctx* ctx, const RenderCall& c, doubl
     q.aspect = aspect;
     q.n_cu = ctx->n_cu;
     q.cull = cull;
-    q.opt_subtiles = (int)ctx->opt_subtiles;
-    q.opt_tile_log2w = (int)ctx->opt_tile_log2w;
-    q.opt_refine = (int)ctx->opt_refine;
+    q.opt_subtiles = (int)ctx->opt.subtiles;
+    q.opt_tile_log2w = (int)ctx->opt.tile_log2w;
+    q.opt_refine = (int)ctx->opt.refine;
     return q;
 }
 
@@ -338,7 +338,7 @@ const uint32_t* xcd_tile_order(rtx_ctx* ctx, const rtxplan::TileShape& t, const 
     // (grids of several dispatch rounds only, unless asked for: where every workgroup is resident at once the tiles that share
     // a CU decide the launch's length, and those are dealt by measured work, not by neighbourhood -- C2 with two-level
     // culling: 30.4 us alone under this order, 24.7 under the balanced one)
-    if (ctx->opt_xcd_order == 0 || (ctx->opt_xcd_order < 0 && n <= rtxplan::resident_slots(ctx->n_cu)) || n < 64 || n > (1u << 22) ||
+    if (ctx->opt.xcd_order == 0 || (ctx->opt.xcd_order < 0 && n <= rtxplan::resident_slots(ctx->n_cu)) || n < 64 || n > (1u << 22) ||
         t.grid_x > 0xffffu || t.grid_y > 0xffffu) {
         return nullptr;
     }
@@ -399,7 +399,7 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
             RTX_HIP(ctx, hipMemsetAsync(ctx->d_cell_max.get(), 0, sizeof(uint32_t), stream));
         }
     }
-    rtxplan::CellGrid g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt_cell_capacity, 0);
+    rtxplan::CellGrid g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt.cell_capacity, 0);
     {
         const uint64_t id[3] = {(p->x << 32) | p->y, ((uint64_t)row0 << 32) | rows,
                                 ((uint64_t)g.gx << 56) ^ ((uint64_t)g.gy << 48) ^ ((uint64_t)shape.grid_x << 24) ^ (uint64_t)shape.grid_y ^ (ctx->lists_gen << 8)};
@@ -414,10 +414,10 @@ int prepare_cells(rtx_ctx* ctx, const rtx_params* p, hipStream_t stream, const r
             }
         }
         if (ctx->h_cell_max.get()) ctx->cell_cap_floor = rtxplan::cell_capacity_wanted(*ctx->h_cell_max.get(), g.cap > ctx->cell_cap_floor ? g.cap : ctx->cell_cap_floor, ctx->cell_cap_floor);
-        if (ctx->cell_cap_floor) g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt_cell_capacity, ctx->cell_cap_floor);
+        if (ctx->cell_cap_floor) g = rtxplan::plan_cells(shape, ctx->ns, aspect, ctx->opt.cell_capacity, ctx->cell_cap_floor);
     }
     *static_order = still_only ? nullptr : xcd_tile_order(ctx, shape, g);
-    if (ctx->opt_cell_reuse == 0) return still_only ? RTX_OK : cells_per_frame(ctx, stream, a, g);
+    if (ctx->opt.cell_reuse == 0) return still_only ? RTX_OK : cells_per_frame(ctx, stream, a, g);
     rtxplan::CellKey key;
     key.W = p->x;
     key.H = p->y;
@@ -531,8 +531,8 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
         rtx_grid_read(ctx, stream); // (nothing of this frame reads the lists: a rebuild need not wait for it)
         return RTX_OK;
     }
-    RTX_HIP(ctx, ctx->d_shadow_grid_fallback.reserve(1, rtxmem::nothing()));
-    RTX_HIP(ctx, ctx->d_reflect_grid_fallback.reserve(1, rtxmem::nothing()));
+    RTX_HIP(ctx, ctx->shadow_grid_fallback.ensure());
+    RTX_HIP(ctx, ctx->reflect_grid_fallback.ensure());
     gs->grid = g.plan;
     gs->cell_start = g.cell_count.get();
     gs->list_geom = g.list_geom.get();
@@ -541,7 +541,7 @@ int grid_shadow_args(rtx_ctx* ctx, hipStream_t stream, GridShadowArgs* gs, bool*
     gs->scene_od = ctx->d_sph_od.get();
     gs->large = g.d_large.get();
     gs->n_large = g.n_large;
-    gs->fallback = ctx->d_shadow_grid_fallback.get();
+    gs->fallback = ctx->shadow_grid_fallback.get();
     *in_effect = true;
     return RTX_OK;
 }
@@ -589,9 +589,9 @@ ShadowArgs shadow_args(const rtx_ctx* ctx, const void* hits)
     const rtx_light& l = ctx->lights[0];
     sa.light = KLight{l.pos[0], l.pos[1], l.pos[2], l.diffuse_rgb[0], l.diffuse_rgb[1], l.diffuse_rgb[2], l.diffuse_power,
                       l.specular_rgb[0], l.specular_rgb[1], l.specular_rgb[2], l.specular_power};
-    sa.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
-    sa.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
-    sa.longest = ctx->d_shadow_longest.get();
+    sa.test = (ctx->opt.shadows != 0 && ctx->opt.shadow_check != 2) ? 1u : 0u;
+    sa.brute = ctx->opt.shadow_check == 1 ? 1u : 0u;
+    sa.longest = ctx->shadow_longest.get();
     return sa;
 }
 
@@ -602,9 +602,9 @@ LightsArgs lights_args(const rtx_ctx* ctx, const void* hits)
     std::memset(&la, 0, sizeof la);
     la.hits = (const uint2*)hits;
     rtxlights::pack(ctx->n_lights, ctx->lights, &la.lights); // (the set was validated when it was stored)
-    la.test = (ctx->opt_shadows != 0 && ctx->opt_shadow_check != 2) ? 1u : 0u;
-    la.brute = ctx->opt_shadow_check == 1 ? 1u : 0u;
-    la.longest = ctx->d_shadow_longest.get();
+    la.test = (ctx->opt.shadows != 0 && ctx->opt.shadow_check != 2) ? 1u : 0u;
+    la.brute = ctx->opt.shadow_check == 1 ? 1u : 0u;
+    la.longest = ctx->shadow_longest.get();
     return la;
 }
 
@@ -649,7 +649,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     int rc, herr = 0;
     ShadingRequest req = shading_request(ctx, mode);
     const bool mirror = shading_path(req) == kPathMirror;
-    if (!mirror) ctx->reflect_shadow_points_valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
+    if (!mirror) ctx->reflect_shadow_points.valid = false; // (RTX_STAT_REFLECT_SHADOW_POINTS reads 0)
     const bool patterned = req.n_patterned != 0 && shading_path(req) != kPathDirect; // (direct with patterns: RGB_NORMALS, SDL)
     const bool spotted = req.n_spots != 0 && shading_path(req) != kPathDirect; // (the same)
     // the forms of the shade families that read cones read finishes too: with a cone in the set they get the finishes, default or not
@@ -678,25 +678,24 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
 
     // the hit buffer, the counters this plan's kernels write, the closest hits
     const size_t px = (size_t)a.W * (a.row_end - a.row0);
-    const size_t per_level = RTX_MAX_REFLECT_DEPTH * sizeof(uint32_t);
     void* hit_base = nullptr;
     if ((rc = hit_buffer(ctx, stream, px * plan.bytes_per_px, capturing, &hit_base)) != RTX_OK) return rc;
     char* const hits = (char*)hit_base;
-    RTX_HIP(ctx, ctx->d_shadow_longest.reserve(1, rtxmem::nothing()));
-    if (mirror) RTX_HIP(ctx, ctx->d_reflect_longest.reserve(1, rtxmem::nothing()));
+    RTX_HIP(ctx, ctx->shadow_longest.ensure());
+    if (mirror) RTX_HIP(ctx, ctx->reflect_longest.ensure());
     const bool counts_rays = plan.chain() || plan.grid_reflect(); // (RTX_STAT_REFLECT_RAYS)
-    if (counts_rays) RTX_HIP(ctx, ctx->d_reflect_rays.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
-    if (plan.deep) RTX_HIP(ctx, ctx->d_reflect_shadow_points.reserve(RTX_MAX_REFLECT_DEPTH, rtxmem::nothing()));
+    if (counts_rays) RTX_HIP(ctx, ctx->reflect_rays.ensure());
+    if (plan.deep) RTX_HIP(ctx, ctx->reflect_shadow_points.ensure());
     if ((rc = trace_hits(ctx, a, mode, cull, stream, hits)) != RTX_OK) return rc;
-    if (mirror) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_longest.get(), 0, sizeof(uint32_t), stream));
-    RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_longest.get(), 0, sizeof(uint32_t), stream));
-    if (counts_rays) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_rays.get(), 0, per_level, stream));
-    if (plan.deep) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_shadow_points.get(), 0, per_level, stream));
-    if (plan.dark0) RTX_HIP(ctx, hipMemsetAsync(ctx->d_shadow_grid_fallback.get(), 0, sizeof(uint32_t), stream));
-    if (plan.grid_reflect()) RTX_HIP(ctx, hipMemsetAsync(ctx->d_reflect_grid_fallback.get(), 0, sizeof(uint32_t), stream));
-    if (mirror) { // (the other paths leave reflect_rays_valid as it is)
-        ctx->reflect_rays_valid = counts_rays;
-        ctx->reflect_shadow_points_valid = plan.deep;
+    if (mirror) RTX_HIP(ctx, ctx->reflect_longest.zero(stream));
+    RTX_HIP(ctx, ctx->shadow_longest.zero(stream));
+    if (counts_rays) RTX_HIP(ctx, ctx->reflect_rays.zero(stream));
+    if (plan.deep) RTX_HIP(ctx, ctx->reflect_shadow_points.zero(stream));
+    if (plan.dark0) RTX_HIP(ctx, ctx->shadow_grid_fallback.zero(stream));
+    if (plan.grid_reflect()) RTX_HIP(ctx, ctx->reflect_grid_fallback.zero(stream));
+    if (mirror) { // (the other paths leave reflect_rays.valid as it is)
+        ctx->reflect_rays.valid = counts_rays;
+        ctx->reflect_shadow_points.valid = plan.deep;
     }
 
     // every argument struct once, from the plan's offsets; what the plan has none of stays zero
@@ -749,8 +748,8 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         ra.hits2 = (uint2*)(hits + 8u * px); // level 1's
         ra.k_sph = ctx->d_mat.k.spheres(sorted_staging).get();
         ra.k_pl = ctx->d_mat.k.pl.get();
-        ra.brute = ctx->opt_reflect_check == 1 ? 1u : 0u;
-        ra.longest = ctx->d_reflect_longest.get();
+        ra.brute = ctx->opt.reflect_check == 1 ? 1u : 0u;
+        ra.longest = ctx->reflect_longest.get();
         if (ctx->materials.n_refractive() != 0) { // (else both stay nullptr: every secondary ray is the mirror's)
             ra.ior_sph = ctx->d_mat.ior.spheres(sorted_staging).get();
             ra.ior_pl = ctx->d_mat.ior.pl.get();
@@ -759,11 +758,11 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
     if (counts_rays) { // (rtx_grid_reflect at depth 1: one level into the two-level buffer)
         ca.depth = plan.levels - 1u;
         ca.px = (uint32_t)px;
-        ca.rays = ctx->d_reflect_rays.get();
+        ca.rays = ctx->reflect_rays.get();
     }
     if (plan.deep) {
         cs.dark = (uint32_t*)(hits + plan.deep_off * px);
-        cs.points = ctx->d_reflect_shadow_points.get();
+        cs.points = ctx->reflect_shadow_points.get();
     }
     if (plan.dark0) {
         gs.dark0 = (uint32_t*)(hits + plan.dark0_off * px);
@@ -782,7 +781,7 @@ int launch_frame(rtx_ctx* ctx, const KArgs& a, int mode, int cull, hipStream_t s
         gr.large = gs.large;
         gr.n_large = gs.n_large;
         gr.pos_of_gidx = ctx->d_mat.pos.get() + (sorted_staging ? rtxmat::map_stride(ctx->materials.size()) : 0); // (the map's half for that order)
-        gr.fallback = ctx->d_reflect_grid_fallback.get();
+        gr.fallback = ctx->reflect_grid_fallback.get();
         t.grid_reflect = &gr;
     }
 
@@ -883,7 +882,7 @@ void fill_frame_args(const rtx_ctx* ctx, const rtx_params* p, const RenderCall& 
     a.np = ctx->np;
     a.sph_geom = a.sph_scene_geom = ctx->d_sph_geom.get();
     a.sph_od = ctx->d_sph_od.get();
-    if (ctx->opt_sorted_store != 0 && ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr) {
+    if (ctx->opt.sorted_store != 0 && ctx->sorted_gen == ctx->scene_gen && ctx->d_sorted_geom.get() != nullptr) {
         // the trace kernels read the direction-sorted copies, by position
         a.sph_geom = ctx->d_sorted_geom.get();
         a.sph_od = ctx->d_sorted_od.get();
@@ -908,14 +907,14 @@ void fill_frame_args(const rtx_ctx* ctx, const rtx_params* p, const RenderCall& 
 // the dense plan bought nothing alone and cost a turning camera 20 % with frames in flight (config 3: 82.6 -> 101.7 us).
 bool view_adaptation_applies(const rtx_ctx* ctx, const rtxplan::TileRequest& q, bool capturing)
 {
-    if (!q.cull || capturing || ctx->opt_view_adapt == 0 || ctx->opt_subtiles || ctx->ns < 256u ||
+    if (!q.cull || capturing || ctx->opt.view_adapt == 0 || ctx->opt.subtiles || ctx->ns < 256u ||
         !((double)ctx->ns / ((double)q.W * (double)q.H) < rtxplan::kDenseScene)) {
         return false;
     }
     rtxplan::TileRequest sparse_q = q;
     sparse_q.view_dense = false;
     const rtxplan::TileShape sparse = rtxplan::plan_tiles(sparse_q);
-    return (uint64_t)sparse.grid_x * sparse.grid_y <= rtxplan::resident_slots(ctx->n_cu) || ctx->opt_view_adapt > 0;
+    return (uint64_t)sparse.grid_x * sparse.grid_y <= rtxplan::resident_slots(ctx->n_cu) || ctx->opt.view_adapt > 0;
 }
 
 // ... the launch's side of it: where its workgroups report to.
@@ -926,7 +925,7 @@ int density_feedback_args(rtx_ctx* ctx, hipStream_t stream, bool view_dense, KAr
             (void)hipGetLastError();
             ctx->d_longest.release();
             ctx->h_longest.release();
-            ctx->opt_view_adapt = 0; // no feedback: the plan follows the scene's numbers alone
+            ctx->opt.view_adapt = 0; // no feedback: the plan follows the scene's numbers alone
             return RTX_OK;
         }
         *ctx->h_longest.get() = 0u;
@@ -975,7 +974,7 @@ int dispatch_order_args(rtx_ctx* ctx, hipStream_t stream, const rtx_params* p, c
 {
     *to_out = nullptr;
     const uint64_t nt = (uint64_t)shape.grid_x * shape.grid_y;
-    if (ctx->opt_tile_order != 0 && ctx->n_cu > 0) {
+    if (ctx->opt.tile_order != 0 && ctx->n_cu > 0) {
         // auto (-1): only grids that fit one dispatch round -- there the order balances the CUs; with several rounds the
         // hardware's refill does that, and ordering by cost would only separate tiles that share 128-byte lines
         const uint64_t slots = rtxplan::resident_slots(ctx->n_cu);
@@ -983,9 +982,9 @@ int dispatch_order_args(rtx_ctx* ctx, hipStream_t stream, const rtx_params* p, c
         // end of a launch, and what ends it is the lifetime of the workgroups dispatched last -- heaviest first, they are the
         // light ones (config 5 alone 44.6 -> 41.4 us, config 3 103.1 -> 97.2; with frames in flight on several streams the same
         // order costs 1-2 %, and from seven rounds on -- 8K -- it costs more than the tail is worth)
-        const bool lone_stream = batch_n == 0 && ctx->opt_tile_order == -1 && ctx->render_streams_seen == 1 && nt > slots && nt <= 6 * slots;
-        const int64_t opt_eff = (lone_stream || (batch_n != 0 && ctx->opt_tile_order < 0)) ? 16 : ctx->opt_tile_order;
-        const bool wanted = ctx->opt_tile_order > 0 || nt <= slots || lone_stream || batch_n != 0;
+        const bool lone_stream = batch_n == 0 && ctx->opt.tile_order == -1 && ctx->render_streams_seen == 1 && nt > slots && nt <= 6 * slots;
+        const int64_t opt_eff = (lone_stream || (batch_n != 0 && ctx->opt.tile_order < 0)) ? 16 : ctx->opt.tile_order;
+        const bool wanted = ctx->opt.tile_order > 0 || nt <= slots || lone_stream || batch_n != 0;
         const bool one_round = batch_n == 0 && nt <= slots && nt <= 2048u && ctx->n_cu <= 1024 && shape.tiles256 >= 2000u; // (from half a megapixel: a pass costs 10 us)
         if (wanted && shape.grid_x <= 0xffffu && shape.grid_y <= 0xffffu && nt * (batch_n ? batch_n : 1u) >= 2u * (uint64_t)ctx->n_cu && nt <= (1u << 22)) {
             const uint64_t key[3] = {(c.W << 32) | c.H, (c.row0 << 32) | c.rows,
@@ -1081,10 +1080,10 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
                  hipStream_t stream, unsigned flags, bool* done)
 {
     *done = false;
-    if (ctx->opt_supersample > 1) return RTX_OK; // (every slab has its own sample frame and fold)
+    if (ctx->opt.supersample > 1) return RTX_OK; // (every slab has its own sample frame and fold)
     if (rtxplan::shading_path(shading_request(ctx, mode)) != rtxplan::kPathDirect) return RTX_OK; // (several launches per slab)
     if (n < 2 || n > (size_t)kMaxBatch || mode < RTX_BIT_ASCII || mode >= RTX_SDL || (flags & ~(unsigned)RTX_RENDER_COMPACT) != 0u) return RTX_OK;
-    if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt_refine == 1) return RTX_OK;
+    if (!uses_culling_kernel(ctx) || uses_two_level(ctx, false) || ctx->opt.refine == 1) return RTX_OK;
     for (size_t i = 0; i < n; i++) {
         if (!d_outs[i] || !same_projection(params[0], params[i])) return RTX_OK;
     }
@@ -1106,9 +1105,9 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
     rtxplan::TileRequest q = tile_request(ctx, c, aspect, true);
     // the plan of the whole batch: as many 256-pixel tiles as all its frames have, so that the sub-tile count is chosen for
     // the grid the GPU really sees (one dispatch round where that is possible)
-    if (ctx->opt_subtiles == 0) q.rows = c.rows * n;
+    if (ctx->opt.subtiles == 0) q.rows = c.rows * n;
     rtxplan::TileShape shape = rtxplan::plan_tiles(q);
-    if (ctx->opt_subtiles == 0) {
+    if (ctx->opt.subtiles == 0) {
         q.opt_subtiles = (int)shape.nsub;
         q.opt_tile_log2w = (int)shape.lw;
         q.rows = c.rows;
@@ -1125,7 +1124,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
     bool identical = true;
     for (size_t i = 1; i < n; i++) identical = identical && same_camera(params[0], params[i]);
     const uint32_t* static_order = nullptr;
-    if (identical && !capturing && ctx->opt_two_level < 0 && ctx->opt_cell_reuse != 0 && ctx->ns >= 256u &&
+    if (identical && !capturing && ctx->opt.two_level < 0 && ctx->opt.cell_reuse != 0 && ctx->ns >= 256u &&
         (uint64_t)shape.grid_x * shape.grid_y <= rtxplan::resident_slots(ctx->n_cu)) {
         // exact cell lists while camera and scene rest, as for a plain launch; every frame of the batch is that one view
         if ((rc = prepare_cells(ctx, &params[0], stream, shape, c.row0, c.rows, aspect, a, &static_order, true)) != RTX_OK) return rc;
@@ -1150,7 +1149,7 @@ int render_batch(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode, siz
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_MODE, "invalid rendering mode or tile configuration");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "batched trace kernel launch");
     ctx->last_kernel = name;
-    ctx->reflect_shadow_points_valid = false; // (batched launches are never the mirror path's)
+    ctx->reflect_shadow_points.valid = false; // (batched launches are never the mirror path's)
     ctx->stat_batched_launches++;
     if (to && (rc = dispatch_order_derive(ctx, stream, shape, a, to, od)) != RTX_OK) return rc;
     *done = true;
@@ -1182,7 +1181,7 @@ int render_planned(rtx_ctx* ctx, const rtx_params* p, int mode, const RenderCall
     const uint32_t* static_order = nullptr;
     if (uses_two_level(ctx, q.view_dense)) {
         if ((rc = prepare_cells(ctx, p, stream, shape, c.row0, c.rows, aspect, a, &static_order, false)) != RTX_OK) return rc;
-    } else if (cull && !capturing && ctx->opt_two_level < 0 && ctx->opt_cell_reuse != 0 && ctx->ns >= 256u &&
+    } else if (cull && !capturing && ctx->opt.two_level < 0 && ctx->opt.cell_reuse != 0 && ctx->ns >= 256u &&
                (uint64_t)shape.grid_x * shape.grid_y <= rtxplan::resident_slots(ctx->n_cu)) {
         // under 2048 spheres a pre-pass per frame does not pay, lists that cost nothing do: exact ones, while everything rests.
         // (Grids of one dispatch round only: there every workgroup's staging sits on the launch's critical path -- config 2
@@ -1238,7 +1237,7 @@ int render_supersampled(rtx_ctx* ctx, const rtx_params* p, int mode, const Rende
     KArgs a;
     fill_frame_args(ctx, p, c, a);
     int herr = 0;
-    const char* name = rtx_k_launch_resolve(&a, samples, (int)ctx->opt_supersample, mode, stream, &herr);
+    const char* name = rtx_k_launch_resolve(&a, samples, (int)ctx->opt.supersample, mode, stream, &herr);
     if (!name) return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "supersampling: invalid rendering mode or frame geometry for the fold");
     if (herr != 0) return rtx_hip_fail(ctx, (hipError_t)herr, "fold kernel launch");
     ctx->last_kernel = name;
@@ -1261,9 +1260,9 @@ int rtx_render_rows(rtx_ctx* ctx, const rtx_params* p, int mode, size_t row0, si
     RenderCall c;
     int rc = validate_render_call(ctx, p, mode, row0, rows, d_out, out_row_base, flags, &c);
     if (rc != RTX_OK) return rc;
-    const bool supersampled = ctx->opt_supersample > 1 && mode != RTX_SDL; // (RTX_SDL writes nothing: as without the option)
+    const bool supersampled = ctx->opt.supersample > 1 && mode != RTX_SDL; // (RTX_SDL writes nothing: as without the option)
     rtxplan::SamplePlan sp;
-    if (supersampled && !(sp = rtxplan::plan_supersample(c.W, c.H, c.row0, c.rows, (int)ctx->opt_supersample)).ok) {
+    if (supersampled && !(sp = rtxplan::plan_supersample(c.W, c.H, c.row0, c.rows, (int)ctx->opt.supersample)).ok) {
         return rtx_fail(ctx, RTX_ERR_INVALID_ARGUMENT, "RTX_OPT_SUPERSAMPLE: S * params.x and S * params.y must be below 2^31");
     }
     RTX_HIP(ctx, hipSetDevice(ctx->device));
@@ -1344,7 +1343,7 @@ int rtx_submit_slabs(rtx_ctx* ctx, size_t n, const rtx_params* params, int mode,
         size_t run = 1;
         while (i + run < n && run < (size_t)kMaxBatch && streams[i + run] == streams[i]) run++;
         bool batched = false;
-        if (run >= 2 && ctx->opt_batch != 0) {
+        if (run >= 2 && ctx->opt.batch != 0) {
             hipStream_t s = streams[i] ? static_cast<hipStream_t>(streams[i]) : ctx->stream;
             const int rc = render_batch(ctx, run, &params[i], mode, row0, rows, &d_outs[i], out_row_base, s, flags, &batched);
             if (rc != RTX_OK) return rc;

@@ -22,7 +22,7 @@ using UpdateSlot = rtx_ctx::UpdateSlot;
 int enter(rtx_ctx* ctx, rtxplan::UpdateEntry entry, const rtx_params* p, int mode, const void* host_out, double dt, int run_physics, UpdatePlan* plan, bool unknown_flags = false)
 {
     const bool aligned = ((uintptr_t)host_out & 15u) == 0;
-    *plan = rtxplan::plan_update({entry, mode, p->x, p->y, ctx->capacity, unknown_flags, ctx->opt_update_words, ctx->opt_min_fused, ctx->opt_update_host_write, ctx->group != nullptr, rtxgroup::update_direct_wanted(ctx), aligned});
+    *plan = rtxplan::plan_update({entry, mode, p->x, p->y, ctx->capacity, unknown_flags, ctx->opt.update_words, ctx->opt.min_fused, ctx->opt.update_host_write, ctx->group != nullptr, rtxgroup::update_direct_wanted(ctx), aligned});
     int rc;
     if (plan->physics_first && run_physics && (rc = rtx_update_objects(ctx, dt)) != RTX_OK) return rc;
     if (plan->refusal != RTX_OK) return rtx_fail(ctx, plan->refusal, plan->message);
@@ -361,9 +361,9 @@ int rtx_update_delta(rtx_ctx* ctx, const rtx_params* params, int mode, double dt
     if ((rc = trace_words(ctx, params, mode, ctx->d_delta_words[at], true, &in)) != RTX_OK) return rc;
     if (!key) {
         if (ctx->d_delta_out.reserve(rtx_delta_bound(mode, W, H), rtxmem::after_stream(ctx->stream)) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta buffer");
-        if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
-        ctx->delta_counts_valid = true;
-        in = delta_input(mode, W, H, in.data, ctx->d_delta_words[at ^ 1u].get(), ctx->d_delta_counts.get());
+        unsigned long long* counts = nullptr;
+        if ((rc = rtx_delta_counters(ctx, &counts)) != RTX_OK) return rc;
+        in = delta_input(mode, W, H, in.data, ctx->d_delta_words[at ^ 1u].get(), counts);
         d_stream = ctx->d_delta_out.get();
     }
     if ((rc = encode_copy_wait(ctx, in, d_stream, host_out, host_capacity, "rtx_update_delta: the stream is longer than host_capacity (the next call gives a key frame)", out_bytes)) != RTX_OK) return rc;
@@ -421,9 +421,9 @@ int rtx_update_half_delta(rtx_ctx* ctx, const rtx_params* params, int mode, doub
     if (key) {
         in = half_input(mode, W, H, in.data);
     } else {
-        if (ctx->d_delta_counts.reserve(2, rtxmem::nothing()) != hipSuccess) return rtx_fail(ctx, RTX_ERR_OUT_OF_MEMORY, "hipMalloc failed for the delta counters");
-        ctx->delta_counts_valid = true;
-        in = half_delta_input(mode, W, H, in.data, ctx->d_delta_words[at ^ 1u].get(), ctx->d_delta_counts.get());
+        unsigned long long* counts = nullptr;
+        if ((rc = rtx_delta_counters(ctx, &counts)) != RTX_OK) return rc;
+        in = half_delta_input(mode, W, H, in.data, ctx->d_delta_words[at ^ 1u].get(), counts);
     }
     if ((rc = encode_copy_wait(ctx, in, ctx->d_half_out.get(), host_out, host_capacity, "rtx_update_half_delta: the stream is longer than host_capacity (the next call gives a key frame)", out_bytes)) != RTX_OK) return rc;
     ctx->delta_at = at;

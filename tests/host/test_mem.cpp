@@ -4,6 +4,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -86,6 +87,24 @@ hipError_t hipStreamSynchronize(hipStream_t s)
 hipError_t hipDeviceSynchronize(void)
 {
     g_log.push_back("hipDeviceSynchronize");
+    return hipSuccess;
+}
+hipError_t g_copy_result = hipSuccess; // what the next copies to the host return
+hipError_t hipSetDevice(int device)
+{
+    g_log.push_back("hipSetDevice " + std::to_string(device));
+    return hipSuccess;
+}
+hipError_t hipMemcpy(void* to, const void* from, size_t bytes, hipMemcpyKind kind)
+{
+    g_log.push_back(std::string(kind == hipMemcpyDeviceToHost ? "hipMemcpy(to host) " : "hipMemcpy ") + std::to_string(bytes));
+    if (g_copy_result == hipSuccess) std::memcpy(to, from, bytes);
+    return g_copy_result;
+}
+hipError_t hipMemsetAsync(void* p, int v, size_t bytes, hipStream_t s)
+{
+    g_log.push_back(std::string(s ? "hipMemsetAsync(s) " : "hipMemsetAsync(0) ") + std::to_string(bytes));
+    std::memset(p, v, bytes);
     return hipSuccess;
 }
 hipError_t hipGetLastError(void)
@@ -298,6 +317,64 @@ void test_adopt()
     g_log.clear();
 }
 
+// The counters kernels write (Counter): what the context's seven are made of -- one word, four words, two long words.
+template <class T, size_t N>
+void counter_case(const char* alloc, const char* zeroed, const char* copied)
+{
+    hipStream_t s = (hipStream_t)(uintptr_t)0x10;
+    {
+        Counter<T, N> c;
+        T out[N];
+        CHECK(c.valid && c.get() == nullptr);
+        // no buffer: zeros, and no call
+        for (T& w : out) w = 7;
+        CHECK(c.read(3, out) == hipSuccess && log_is({}));
+        for (const T w : out) CHECK(w == 0);
+        // ensure allocates once
+        CHECK(c.ensure() == hipSuccess && log_is({alloc}) && c.get() != nullptr && g_live == 1);
+        T* first = c.get();
+        CHECK(c.ensure() == hipSuccess && c.ensure() == hipSuccess && log_is({}) && c.get() == first);
+        // zero: one memset of the whole counter on the stream given
+        for (size_t i = 0; i < N; i++) c.get()[i] = (T)(i + 1);
+        CHECK(c.zero(s) == hipSuccess && log_is({zeroed}));
+        for (size_t i = 0; i < N; i++) CHECK(c.get()[i] == 0);
+        // a buffer, valid: set the device, wait for it, copy -- in that order, nothing else
+        for (size_t i = 0; i < N; i++) c.get()[i] = (T)(40 + i);
+        CHECK(c.read(3, out) == hipSuccess && log_is({"hipSetDevice 3", "hipDeviceSynchronize", copied}));
+        for (size_t i = 0; i < N; i++) CHECK(out[i] == (T)(40 + i));
+        // not valid: zeros, and no call; valid again: the words are still there
+        c.valid = false;
+        CHECK(c.read(3, out) == hipSuccess && log_is({}));
+        for (const T w : out) CHECK(w == 0);
+        c.valid = true;
+        CHECK(c.read(0, out) == hipSuccess && log_is({"hipSetDevice 0", "hipDeviceSynchronize", copied}) && out[N - 1] == (T)(40 + N - 1));
+        // the copy's error is the read's
+        g_copy_result = hipErrorInvalidValue;
+        CHECK(c.read(3, out) == hipErrorInvalidValue && log_is({"hipSetDevice 3", "hipDeviceSynchronize", copied}));
+        g_copy_result = hipSuccess;
+        const Counter<T, N> off(false); // (the context's flagged counters start like this)
+        CHECK(!off.valid && off.read(3, out) == hipSuccess && log_is({}));
+    }
+    CHECK(log_is({"hipFree"}) && g_live == 0);
+}
+
+void test_counters()
+{
+    counter_case<uint32_t, 1>("hipMalloc 4", "hipMemsetAsync(s) 4", "hipMemcpy(to host) 4");
+    counter_case<uint32_t, 4>("hipMalloc 16", "hipMemsetAsync(s) 16", "hipMemcpy(to host) 16");
+    counter_case<unsigned long long, 2>("hipMalloc 16", "hipMemsetAsync(s) 16", "hipMemcpy(to host) 16");
+    // a word inside a larger buffer (the query grid's fallback word): the same three calls
+    DeviceBuf<uint32_t> words;
+    CHECK(words.reserve(12, nothing()) == hipSuccess);
+    words.get()[2] = 9u;
+    g_log.clear();
+    uint32_t w = 0;
+    CHECK(read_words(1, words.get() + 2, 1, &w) == hipSuccess && w == 9u);
+    CHECK(log_is({"hipSetDevice 1", "hipDeviceSynchronize", "hipMemcpy(to host) 4"}));
+    words.release();
+    g_log.clear();
+}
+
 } // namespace
 
 int main()
@@ -307,6 +384,7 @@ int main()
     test_failed_grow();
     test_moves();
     test_adopt();
+    test_counters();
     CHECK(g_live == 0);
     if (g_failed) {
         std::printf("%d checks failed\n", g_failed);

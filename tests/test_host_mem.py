@@ -1,4 +1,4 @@
-"""The owning types of csrc/rtx_mem.hpp (DeviceBuf, PinnedBuf, Event, Stream) without a GPU: tests/host/test_mem.cpp defines the HIP
+"""The owning types of csrc/rtx_mem.hpp (DeviceBuf, PinnedBuf, Counter, Event, Stream) without a GPU: tests/host/test_mem.cpp defines the HIP
 entry points the header calls itself -- malloc behind them, a log of calls, a live count, an allocation that fails on request -- so no
 HIP library is linked; compiled with the g++ line of tests/test_host_delta.py plus the HIP API header's include path, and run directly
 under AddressSanitizer + UndefinedBehaviorSanitizer."""
